@@ -18,7 +18,9 @@ each network (2 global views per sample: the reference has no multi-crop, SURVEY
 out_dim 8192, bf16 MFMA operands with fp32 accumulation / residual stream / losses / optimiser.
 Inputs are resident in HBM before the timed region.  Weak scaling: per-GPU batch fixed.
 
-Output: ONE JSON line on rank 0 (see the contract in the task description), with
+Output: ONE JSON line on rank 0 with the headline figure: metric, value (samples/s), unit, higher_is_better, dtype, ms_per_step
+(milliseconds of one timed step), the workload's config and the last timed step's loss / grad-norm.  A plain run does only that: set-up,
+--warmup steps, --steps timed steps, the --dump-outputs files, the line.  With --full the line also carries
   roofline       the dominant kernel (the bf16 MFMA GEMM family that takes most of the step): algorithmic bytes / FLOPs of its
                  launches / their summed duration, measured live with HIP events on the launch stream over the timed
                  region; "step" adds the whole-step figure of BASELINE.md section 2;
@@ -31,7 +33,11 @@ Output: ONE JSON line on rank 0 (see the contract in the task description), with
                  has two views), vit_large_bs128 (the per-GPU shape of configs[4]);
   cpu_baseline   the CPU oracle's same training step timed on this box's host cores (rank 0, N=1 only);
   framework_baseline  the same oracle step with every tensor on this GPU under torch.autocast(bfloat16): what the reference's
-                 own loop does on this MI355X through plain PyTorch-ROCm, at the headline batch size (+ "speedup" = value / it).
+                 own loop does on this MI355X through plain PyTorch-ROCm, at the headline batch size (+ "speedup" = value / it);
+  config         host_enqueue_ms_per_step (a few extra steps on an empty launch queue) and, with N > 1, what the collectives ran on.
+
+--dump-outputs DIR writes what the last timed step hands its caller as DIR/<name>.npy (see dump_outputs); the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -51,6 +57,7 @@ for _p in (ROOT, os.path.join(ROOT, "dino-x_amd")):
 PEAK_BF16_DENSE_TFLOPS = 2500.0   # MI355X_MICROARCH.md: ~2.5 PFLOP/s dense bf16 MFMA
 PEAK_HBM_GBS = 8000.0             # MI355X_MICROARCH.md: HBM3E ~8 TB/s
 PMC_FILES = ("r03_pmc_traffic.json", "r02_pmc_traffic.json")  # profiles/: per-kernel HBM bytes from the rocprofv3 --pmc passes of this same command, newest first
+DUMP_SAMPLE = 1 << 20             # --dump-outputs: elements kept of each flat state array (a fixed, seeded sample; 5 arrays x 4 MiB)
 
 
 def fwd_flops_per_image(img=224, patch=16, dim=384, depth=12, out_dim=8192, regs=4, gram=True):
@@ -141,7 +148,14 @@ def parse_args(argv=None):
     ap.add_argument("--no-kernel-timing", action="store_true", help="do not bracket GEMM launches with HIP events")
     ap.add_argument("--time-every", type=int, default=16, help="bracket one GEMM launch in this many with HIP events (1: all, which costs the timed region ~2.3 %%)")
     ap.add_argument("--no-step-split", action="store_true", help="skip the extra steps that time the phases of the step (profiler runs)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: roofline (GEMM kernel timing), host enqueue, step split, secondary "
+                         "configs, cpu_baseline, framework_baseline (the --no-* options above trim this)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def launch_ranks(args) -> int:
@@ -254,6 +268,26 @@ def host_enqueue_ms(wl, n=5) -> float:
     return 1e3 * sorted(ts)[len(ts) // 2]
 
 
+def dump_outputs(eng, out_dir) -> None:
+    """What a caller of TrainEngine.step holds after the last timed step, as out_dir/<name>.npy: the step's scalars (float64: loss, dino,
+    gram, koleo, grad_norm, lr), the DINO centre, and the flat fp32 arenas -- student and teacher weights, the step's gradient, the AdamW
+    moments -- as the same fixed, seeded sample of DUMP_SAMPLE elements each (float32, ~20 MB in all)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in eng.scalars().items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.asarray([v], dtype=np.float64))
+    n = eng.flat_p.numel()
+    idx = None
+    if n > DUMP_SAMPLE:
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+    np.save(os.path.join(out_dir, "center.npy"), eng.center.detach().float().cpu().reshape(-1).numpy())
+    for name, a in (("student_params", eng.flat_p), ("teacher_params", eng.flat_t), ("grad", eng.flat_g), ("adam_m", eng.adam_m),
+                    ("adam_v", eng.adam_v)):
+        a = a.detach().float().cpu().reshape(-1)
+        np.save(os.path.join(out_dir, f"{name}.npy"), (a if idx is None else a[idx]).numpy())
+
+
 def secondary(dev, note) -> dict:
     """Short (3 warm-up + 2 x 8 timed steps) measurements of the other single-GPU BASELINE configs, so that the driver's record -- not a
     builder log -- holds them.  `value` / `ms_per_step` are the MEAN of the two rounds (the protocol the headline and the baselines can be
@@ -269,7 +303,7 @@ def secondary(dev, note) -> dict:
             ("bs256_koleo_accum4", dict(B=256, koleo=0.1, accum=4),
              "the headline workload the way the reference's production runs use it (docs/EXPERIMENTS.md): --koleo-weight 0.1, --accumulation-steps 4 (samples/s counts micro-batches)"),
             ("bs64_fp32", dict(B=64, fp32=True),
-             "the headline model without --amp: fp32 on the exact-fp32 matrix instructions, bs 64 (python bench.py --fp32 --batch-size 64 adds the plain-PyTorch fp32 figure)"),
+             "the headline model without --amp: fp32 on the exact-fp32 matrix instructions, bs 64 (python bench.py --full --fp32 --batch-size 64 adds the plain-PyTorch fp32 figure)"),
             ("bs64_scale_off", dict(B=64, scale_aware=False), "BASELINE configs[1]: ViT-S/16 224, bs 64, scale-aware off, 2 views/sample"),
             ("bs64_scale_off_graph", dict(B=64, scale_aware=False, graph=True), "configs[1] with the step replayed as one captured hipGraph"),
             ("multicrop_2g8l", dict(B=256, L=8), "configs[2] read literally: 2 global + 8 local 96px views/sample (extension: the reference has 2 views)"),
@@ -344,7 +378,7 @@ def main() -> None:
     wl = Workload(dev, rank, model=args.model, B=B, scale_aware=not args.no_scale_aware, L=L, local_size=args.local_size, fp32=args.fp32,
                   steps_hint=args.steps + args.warmup + 8 + (16 if world > 1 else 0), graph=args.graph)
     note(f"model + data resident (world {world}, B {B}/GPU, {'fp32' if args.fp32 else 'bf16'})")
-    timer = None if (args.no_kernel_timing or args.graph) else ops.GemmTimer(every=args.time_every)
+    timer = None if (not args.full or args.no_kernel_timing or args.graph) else ops.GemmTimer(every=args.time_every)
     # Data parallel: should the gradient buckets be exchanged FROM backward (overlapped: RCCL's channel workgroups then hold CUs beside the
     # persistent GEMM / attention kernels, which cost them +35..55 % while they do) or AFTER it (one exposed burst)?  Which is cheaper is a
     # property of the node, so a few extra warm-up steps time both and every rank keeps the faster -- unless
@@ -378,14 +412,17 @@ def main() -> None:
     scal = wl.eng.scalars()
     if not (scal["loss"] == scal["loss"]):
         raise SystemExit("non-finite loss in the timed region")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl.eng, args.dump_outputs)
+        note(f"outputs of the last timed step written to {args.dump_outputs}")
     kernels = timer.summary() if timer else {}
-    host_ms = host_enqueue_ms(wl)                     # (every rank: the step holds collectives)
-    split = wl.step_split() if not (args.graph or args.no_step_split) else None     # (every rank: the step holds collectives)
+    host_ms = host_enqueue_ms(wl) if args.full else None                                    # (every rank: the step holds collectives)
+    split = wl.step_split() if args.full and not (args.graph or args.no_step_split) else None     # (every rank: the step holds collectives)
     overlapped = getattr(wl.eng.bucketer, "fired_in_backward", None)
     # what the collectives really ran on: the backend of the process group, the number of ranks an all-reduce of ones sees, and the
     # slowest rank's exposed communication (the `comm_exposed` phase of step_ms_split: what did not fit under backward)
     dist_info = None
-    if world > 1:
+    if world > 1 and args.full:
         ones = torch.ones(1, device=dev)
         dist.all_reduce(ones)
         exposed = torch.tensor([split["comm_exposed"] if split else -1.0], dtype=torch.float64, device=dev)
@@ -397,54 +434,56 @@ def main() -> None:
 
     if rank == 0:
         samples_s = world * B * args.steps / dt
-        gf_sample = wl.gflop_per_sample()
-        step_tflops = samples_s * gf_sample / 1e3 / world          # per GPU
-        roof = {"bound": "mfma", "achieved": None, "peak": PEAK_BF16_DENSE_TFLOPS, "unit": "TFLOP/s", "frac": None, "traffic": None}
-        if kernels:
-            dom = max(kernels, key=lambda k: kernels[k]["ms"])
-            d = kernels[dom]
-            sec = d["ms"] * 1e-3
-            tf, gbs = d["flops"] / sec / 1e12, d["bytes"] / sec / 1e9
-            # Which roof bounds the dominant kernel is decided from its own launches: the time the MFMA pipe needs for their
-            # algorithmic FLOPs at the dense bf16 peak against the time HBM needs for their algorithmic bytes at its peak.
-            # With K = 384..1536 and M ~ 1e5 the products of this path sit at or under the ridge (2.5 PF / 8 TB/s = 312 FLOP/B;
-            # qkv 288, fc1 with its GELU' side tensor 171, proj 77): the larger floor is the HBM one.
-            t_mfma, t_hbm = d["flops"] / (PEAK_BF16_DENSE_TFLOPS * 1e12), d["bytes"] / (PEAK_HBM_GBS * 1e9)
-            mfma = {"achieved": round(tf, 2), "peak": PEAK_BF16_DENSE_TFLOPS, "unit": "TFLOP/s", "frac": round(tf / PEAK_BF16_DENSE_TFLOPS, 4),
-                    "floor_ms_per_step": round(1e3 * t_mfma / args.steps, 3)}
-            hbm = {"achieved": round(gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": round(gbs / PEAK_HBM_GBS, 4),
-                   "floor_ms_per_step": round(1e3 * t_hbm / args.steps, 3), "algorithmic_bytes_per_launch": round(d["bytes"] / d["launches"])}
-            if t_hbm >= t_mfma:
-                roof.update(bound="hbm", achieved=hbm["achieved"], peak=PEAK_HBM_GBS, unit="GB/s", frac=hbm["frac"], mfma=mfma, hbm=hbm)
-            else:
-                roof.update(bound="mfma", achieved=mfma["achieved"], frac=mfma["frac"], mfma=mfma, hbm=hbm)
-            roof.update(kernel=dom, launches_per_step=d["launches"] // args.steps, timed_launches=d["timed"], avg_launch_us=round(1e3 * d["ms"] / d["launches"], 2),
-                        kernel_share_of_step=round(d["ms"] / (dt * 1e3), 4),
-                        all_gemm_kernels={k: {"launches": v["launches"], "ms": round(v["ms"], 3),
-                                              "tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2),
-                                              "gbs": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1)} for k, v in kernels.items()})
-        # HBM bytes per launch of the dominant kernel from the committed PMC passes (rocprofv3 --pmc FETCH_SIZE and, in a
-        # separate run, WRITE_SIZE of this same command; FETCH doubled per the gfx950 correction) -- bench.py cannot run the
-        # profiler on itself, so the figure is read from profiles/.  It is reported only while the kernel sources are the ones the
-        # profile was taken on (its "_source_fingerprint" stamp, dinox.hostinfo.source_fingerprint): a stale profile gives null.
-        if args.model == "vit-small" and B == 256 and not L and not args.no_scale_aware:
-            from dinox.hostinfo import source_fingerprint
-            fp_now = source_fingerprint()
-            for pmc_file in PMC_FILES:
-                try:
-                    pmc = json.load(open(os.path.join(ROOT, "profiles", pmc_file)))
-                except (OSError, ValueError):
-                    continue
-                fam = "dinox::" + roof.get("kernel", "")
-                if pmc.get("_source_fingerprint") != fp_now:
-                    roof["traffic_note"] = (f"profiles/{pmc_file} was taken on other kernel sources (stamp {pmc.get('_source_fingerprint')}, now {fp_now}): "
-                                            "traffic withheld until tools/refresh_profiles.sh is re-run")
-                elif fam in pmc:
-                    roof["traffic"] = pmc[fam]["hbm_bytes_per_launch"]
-                    roof["traffic_note"] = f"measured avg HBM bytes/launch (PMC, profiles/{pmc_file}, same kernel sources) beside hbm.algorithmic_bytes_per_launch"
-                break
-        roof["step"] = {"gflop_per_sample": round(gf_sample, 2), "achieved": round(step_tflops, 2),
-                        "frac": round(step_tflops / PEAK_BF16_DENSE_TFLOPS, 4)}
+        roof = None
+        if args.full:
+            gf_sample = wl.gflop_per_sample()
+            step_tflops = samples_s * gf_sample / 1e3 / world          # per GPU
+            roof = {"bound": "mfma", "achieved": None, "peak": PEAK_BF16_DENSE_TFLOPS, "unit": "TFLOP/s", "frac": None, "traffic": None}
+            if kernels:
+                dom = max(kernels, key=lambda k: kernels[k]["ms"])
+                d = kernels[dom]
+                sec = d["ms"] * 1e-3
+                tf, gbs = d["flops"] / sec / 1e12, d["bytes"] / sec / 1e9
+                # Which roof bounds the dominant kernel is decided from its own launches: the time the MFMA pipe needs for their
+                # algorithmic FLOPs at the dense bf16 peak against the time HBM needs for their algorithmic bytes at its peak.
+                # With K = 384..1536 and M ~ 1e5 the products of this path sit at or under the ridge (2.5 PF / 8 TB/s = 312 FLOP/B;
+                # qkv 288, fc1 with its GELU' side tensor 171, proj 77): the larger floor is the HBM one.
+                t_mfma, t_hbm = d["flops"] / (PEAK_BF16_DENSE_TFLOPS * 1e12), d["bytes"] / (PEAK_HBM_GBS * 1e9)
+                mfma = {"achieved": round(tf, 2), "peak": PEAK_BF16_DENSE_TFLOPS, "unit": "TFLOP/s", "frac": round(tf / PEAK_BF16_DENSE_TFLOPS, 4),
+                        "floor_ms_per_step": round(1e3 * t_mfma / args.steps, 3)}
+                hbm = {"achieved": round(gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": round(gbs / PEAK_HBM_GBS, 4),
+                       "floor_ms_per_step": round(1e3 * t_hbm / args.steps, 3), "algorithmic_bytes_per_launch": round(d["bytes"] / d["launches"])}
+                if t_hbm >= t_mfma:
+                    roof.update(bound="hbm", achieved=hbm["achieved"], peak=PEAK_HBM_GBS, unit="GB/s", frac=hbm["frac"], mfma=mfma, hbm=hbm)
+                else:
+                    roof.update(bound="mfma", achieved=mfma["achieved"], frac=mfma["frac"], mfma=mfma, hbm=hbm)
+                roof.update(kernel=dom, launches_per_step=d["launches"] // args.steps, timed_launches=d["timed"], avg_launch_us=round(1e3 * d["ms"] / d["launches"], 2),
+                            kernel_share_of_step=round(d["ms"] / (dt * 1e3), 4),
+                            all_gemm_kernels={k: {"launches": v["launches"], "ms": round(v["ms"], 3),
+                                                  "tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2),
+                                                  "gbs": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1)} for k, v in kernels.items()})
+            # HBM bytes per launch of the dominant kernel from the committed PMC passes (rocprofv3 --pmc FETCH_SIZE and, in a
+            # separate run, WRITE_SIZE of this same command; FETCH doubled per the gfx950 correction) -- bench.py cannot run the
+            # profiler on itself, so the figure is read from profiles/.  It is reported only while the kernel sources are the ones the
+            # profile was taken on (its "_source_fingerprint" stamp, dinox.hostinfo.source_fingerprint): a stale profile gives null.
+            if args.model == "vit-small" and B == 256 and not L and not args.no_scale_aware:
+                from dinox.hostinfo import source_fingerprint
+                fp_now = source_fingerprint()
+                for pmc_file in PMC_FILES:
+                    try:
+                        pmc = json.load(open(os.path.join(ROOT, "profiles", pmc_file)))
+                    except (OSError, ValueError):
+                        continue
+                    fam = "dinox::" + roof.get("kernel", "")
+                    if pmc.get("_source_fingerprint") != fp_now:
+                        roof["traffic_note"] = (f"profiles/{pmc_file} was taken on other kernel sources (stamp {pmc.get('_source_fingerprint')}, now {fp_now}): "
+                                                "traffic withheld until tools/refresh_profiles.sh is re-run")
+                    elif fam in pmc:
+                        roof["traffic"] = pmc[fam]["hbm_bytes_per_launch"]
+                        roof["traffic_note"] = f"measured avg HBM bytes/launch (PMC, profiles/{pmc_file}, same kernel sources) beside hbm.algorithmic_bytes_per_launch"
+                    break
+            roof["step"] = {"gflop_per_sample": round(gf_sample, 2), "achieved": round(step_tflops, 2),
+                            "frac": round(step_tflops / PEAK_BF16_DENSE_TFLOPS, 4)}
         views = "2 views/sample" if not L else f"2 global + {L} local {args.local_size}px views/sample"
         if args.model == "vit-small":
             metric = (f"training images/sec (source samples; 2 global + {L} local {args.local_size}px views each; multi-crop extension, the reference has 2 global views) ViT-S/16 224px bs{B}/GPU"
@@ -458,13 +497,16 @@ def main() -> None:
             "config": {"workload": ("ViT-S" if args.model == "vit-small" else "ViT-L") + f"/16 224x224x3 2.5D slice stacks, "
                                    f"{'scale-aware' if not args.no_scale_aware else 'scale-aware off'}, {views}, DINO+Gram loss, AdamW+EMA",
                        "per_gpu_batch": B, "global_batch": B * world, "views_per_step": (2 + L) * B * world, "local_crops": L, "tokens": 201, "out_dim": wl.out_dim,
-                       "parallelism": f"dp{world}", "views_per_s": round((2 + L) * samples_s, 2), "hipgraph": bool(args.graph), "host_enqueue_ms_per_step": round(host_ms, 2),
-                       "host_enqueue_note": "median host time to issue one step on an empty launch queue; host_enqueue_ms_in_flight = the same call inside the timed region, where it also waits for queue room",
+                       "parallelism": f"dp{world}", "views_per_s": round((2 + L) * samples_s, 2), "hipgraph": bool(args.graph),
                        "host_enqueue_ms_in_flight": round(timed.host_enqueue_in_flight_ms, 2),
                        "loss": round(scal["loss"], 5), "grad_norm": round(scal["grad_norm"], 5)},
-            "roofline": roof,
-            "step_ms_split": split,
         }
+        if args.full:
+            line["config"]["host_enqueue_ms_per_step"] = round(host_ms, 2)
+            line["config"]["host_enqueue_note"] = ("median host time to issue one step on an empty launch queue; host_enqueue_ms_in_flight = the same "
+                                                   "call inside the timed region, where it also waits for queue room")
+            line["roofline"] = roof
+            line["step_ms_split"] = split
         if world > 1 and overlapped is not None:
             line["config"]["grad_buckets_launched_during_backward"] = f"{overlapped}/{len(wl.eng.bucketer.buckets)}"
         if dist_info is not None:
@@ -472,13 +514,13 @@ def main() -> None:
         if dp_probe is not None:
             line["config"]["grad_exchange_probe"] = dp_probe
         default_cfg = args.model == "vit-small" and B == 256 and not L and not args.no_scale_aware and not args.fp32
-        if world == 1 and not args.no_secondary and default_cfg:
+        if args.full and world == 1 and not args.no_secondary and default_cfg:
             wl = None
             import gc
             gc.collect()
             torch.cuda.empty_cache()
             line["secondary"] = secondary(dev, note)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             note("timing the CPU oracle (cpu_baseline) ...")
             vit_s = dict(img_size=224, patch=16, dim=384, depth=12, heads=6, num_registers=4, scale_aware=True)
             line["cpu_baseline"] = cpu_baseline(vit_s, 8192) if args.model == "vit-small" else None

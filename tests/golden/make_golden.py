@@ -30,6 +30,9 @@ Fixtures
   ckpt_tiny.npz       the batches of those steps, the state the checkpoint must restore, and step 4 as the reference runs it after
                       its own load_checkpoint (:1128-1193) into fresh modules + a fresh torch.optim.AdamW
   get_lr.npz          get_lr at a grid of (step,total)
+  ckpt_xref.npz       the other direction: engine_checkpoint_00000003.pth (written by the engine, tests/test_gpu_parity.py::
+                      test_engine_written_checkpoint_payload) restored by the reference's load_checkpoint into fresh modules + a
+                      stock torch.optim.AdamW -- the state it restores and the step 4 it then takes in its loop order
 """
 from __future__ import annotations
 
@@ -343,6 +346,43 @@ def ckpt_tiny():
     print(f"ckpt_tiny.npz + {path.name} ({path.stat().st_size / 1024:.1f} KiB): losses={out['losses']}")
 
 
+def ckpt_xref():
+    """SURVEY 8f-1, direction engine -> reference: the reference's own load_checkpoint (:1128-1193) restores the engine-written
+    engine_checkpoint_00000003.pth, then takes step 4 (ckpt_tiny's batch 3) in its loop order (:1692-1802)."""
+    from pathlib import Path
+    g = np.load(os.path.join(HERE, "ckpt_tiny.npz"))
+    lr, min_lr, warm, max_steps, wd, ema, ts, tt, cm, gw = [float(v) for v in g["hp"]]
+    kw = dict(img_size=28, patch=14, dim=32, depth=2, heads=2, mlp_ratio=4.0, use_grad_checkpoint=False, scale_aware=True)
+    student = P.DinoStudentTeacher(P.PatchViT(**kw), out_dim=64)
+    teacher = P.DinoStudentTeacher(P.PatchViT(**kw), out_dim=64)
+    for p in teacher.parameters():
+        p.requires_grad_(False)
+    opt = torch.optim.AdamW(student.parameters(), lr=lr, weight_decay=wd)
+    scaler = torch.amp.GradScaler("cpu", enabled=False)
+    L = P.DINOLoss(64, center_momentum=cm)
+    step, cfg = P.load_checkpoint(Path(HERE) / "engine_checkpoint_00000003.pth", student, teacher, opt, scaler, L, torch.device("cpu"),
+                                  scale_aware=True)
+    assert step == 3 and cfg.model.dim == 32 and cfg.scale_aware
+    out = sd_arrays("student3", student.state_dict())
+    out.update(sd_arrays("teacher3", teacher.state_dict()))
+    out["center3"] = L.center.clone()
+    out["adam_step3"] = np.array([float(opt.state_dict()["state"][0]["step"])], dtype=np.float64)
+    cur_lr = P.get_lr(3, int(max_steps), int(warm), lr, min_lr)
+    for pg in opt.param_groups:
+        pg["lr"] = cur_lr
+    batch, sp2 = torch.from_numpy(g["batch3"]), torch.from_numpy(g["spacing3"])
+    s_feats = student.backbone(batch, spacing=sp2)
+    with torch.no_grad():
+        t_feats = teacher.backbone(batch, spacing=sp2)
+    loss = L(student.head(s_feats[:, 0]), teacher.head(t_feats[:, 0]), ts, tt) + gw * P.compute_gram_anchoring_loss(s_feats, t_feats)
+    loss.backward()
+    gn = sum(p.grad.norm(2).item() ** 2 for p in student.parameters() if p.grad is not None) ** 0.5
+    opt.step()
+    out.update(sd_arrays("student4", student.state_dict()))
+    out["step4"] = np.array([loss.item(), gn, cur_lr], dtype=np.float64)          # loss, grad-norm, lr of step 4
+    save("ckpt_xref.npz", **out)
+
+
 def vit_plain():
     g = torch.Generator().manual_seed(32)
     torch.manual_seed(1)
@@ -458,3 +498,4 @@ if __name__ == "__main__":
     get_lr_grid()
     vit_tiny_autocast()
     ckpt_tiny()
+    ckpt_xref()

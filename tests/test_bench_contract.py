@@ -1,4 +1,4 @@
-"""The bench.py output contract, checked on the line recorded in profiles/ (the last `python bench.py` run on an MI355X):
+"""The bench.py output contract, checked on the line recorded in profiles/ (the last `python bench.py --full` run on an MI355X):
 one JSON object with the driver's keys, the roofline and cpu_baseline objects, and internally consistent numbers."""
 import json
 import os
@@ -53,3 +53,37 @@ def test_recorded_bench_line_meets_the_contract():
         assert f["speedup"] == pytest.approx(d["value"] / f["value"], rel=1e-2)
     c = d["cpu_baseline"]
     assert c["kind"] in ("port", "reference") and c["cores"] >= 1 and c["value"] > 0 and c["unit"] == d["unit"] and c["sample"]
+
+
+def test_bench_options_and_dump_outputs(tmp_path, monkeypatch):
+    """--full is off by default, --steps below 1 is refused, and dump_outputs writes the step's scalars (float64) and the same seeded
+    sample of every flat state array (float32), identically from run to run."""
+    from types import SimpleNamespace
+
+    import numpy as np
+    import torch
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert a.steps == 3 and a.warmup == 1 and not a.full and a.dump_outputs == str(tmp_path)
+    assert bench.parse_args(["--full"]).full and bench.parse_args([]).dump_outputs is None
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1000)
+    p = torch.randn(5000, generator=torch.Generator().manual_seed(0))
+    scal = {"loss": 8.25, "dino": 8.0, "gram": 0.25, "koleo": 0.0, "grad_norm": 2.5, "lr": 1e-4}
+    eng = SimpleNamespace(flat_p=p, flat_t=2 * p, flat_g=3 * p, adam_m=4 * p, adam_v=5 * p, center=torch.randn(1, 64), scalars=lambda: scal)
+    for d in ("a", "b"):
+        bench.dump_outputs(eng, str(tmp_path / d))
+    names = {f[:-4] for f in os.listdir(tmp_path / "a")}
+    assert names == set(scal) | {"center", "student_params", "teacher_params", "grad", "adam_m", "adam_v"}
+    for n in names:
+        x, y = np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), n
+    for k, v in scal.items():
+        assert np.load(tmp_path / "a" / f"{k}.npy").tolist() == [v]
+    s = np.load(tmp_path / "a" / "student_params.npy")
+    idx = np.nonzero(np.isin(p.numpy(), s))[0]                   # the sampled positions, in arena order
+    assert s.shape == (1000,) and len(idx) == 1000 and np.array_equal(s, p.numpy()[idx])
+    for i, n in enumerate(("teacher_params", "grad", "adam_m", "adam_v"), 2):        # the same elements of every arena
+        assert np.array_equal(np.load(tmp_path / "a" / f"{n}.npy"), (i * p).numpy()[idx]), n
+    assert np.array_equal(np.load(tmp_path / "a" / "center.npy"), eng.center.reshape(-1).numpy())

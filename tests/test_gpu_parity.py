@@ -1559,8 +1559,8 @@ def test_engine_written_checkpoint_payload(dx, tmp_path):
     """Direction engine -> reference: three engine steps from ckpt_tiny's initial state, the CLI's save_checkpoint, then step 4.
     Here the payload is checked to be what the reference's load_checkpoint consumes (keys, AdamW state_dict format accepted by a
     stock torch.optim.AdamW, centre under dino_loss.center) and to equal the reference's state after the same three steps; the
-    file + the engine's step 4 are left in gpurun_out/engine_ckpt/ so that tests/test_checkpoint_xref.py (build container, real
-    reference) can resume it with the reference's own load_checkpoint and compare step 4."""
+    file + the engine's step 4 are written out beside the tree as the source of tests/golden/engine_*, which
+    tests/test_checkpoint_xref.py compares with the reference's resume of the same file (tests/golden/ckpt_xref.npz)."""
     import json, os
     from conftest import ROOT
     cli = _cli()
@@ -2078,7 +2078,7 @@ def test_bench_launches_its_own_ranks(dx):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch-size", "16",
-                        "--no-cpu-baseline", "--no-secondary"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=400)
+                        "--full", "--no-cpu-baseline", "--no-secondary"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=400)
     assert r.returncode == 0, r.stderr.decode(errors="replace")[-2000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
     assert len(lines) == 1, lines
@@ -2096,6 +2096,29 @@ def test_bench_launches_its_own_ranks(dx):
     c = d["config"]
     assert c["dist_backend"] == "gloo" and c["rccl_ranks_seen"] == 2 and c["comm_exposed_ms_max_over_ranks"] >= 0.0
     assert len(c["grad_bucket_bytes"]) == total and sum(c["grad_bucket_bytes"]) == c["grad_bytes_per_step"] and c["centre_allreduce_bytes"] == 4 * 8192
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(dx, tmp_path):
+    """A plain `python bench.py` times exactly --steps steps and prints the headline line without the --full measurements; --dump-outputs
+    leaves the last timed step's scalars and a float sample of its state (<= 64 MB in all), and the dumped loss is the line's loss."""
+    import json, os, subprocess, sys
+    import numpy as np
+    from conftest import ROOT
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch-size", "16",
+                        "--dump-outputs", str(out)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=400)
+    assert r.returncode == 0, r.stderr.decode(errors="replace")[-2000:]
+    lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["unit"] == "samples/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "bf16" and d["value"] == pytest.approx(16 / (d["ms_per_step"] * 1e-3), rel=1e-3)
+    assert not {"roofline", "step_ms_split", "secondary", "cpu_baseline", "framework_baseline"} & set(d)
+    files = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert {"loss", "grad_norm", "center", "student_params", "teacher_params", "grad"} <= set(files)
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in files.values())
+    assert sum(os.path.getsize(out / f) for f in os.listdir(out)) <= 64 << 20
+    assert float(files["loss"][0]) == pytest.approx(d["config"]["loss"], abs=1e-5)
 
 
 def test_gemm_timer_samples_launches_and_prices_families(dx):

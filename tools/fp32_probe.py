@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""fp32 (no --amp) step of this engine at a given batch size.  The comparison with plain PyTorch fp32 on the same GPU is `python bench.py --fp32
+"""fp32 (no --amp) step of this engine at a given batch size.  The comparison with plain PyTorch fp32 on the same GPU is `python bench.py --full --fp32
 --batch-size B` (its framework_baseline leg runs the restated reference loop without autocast)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
