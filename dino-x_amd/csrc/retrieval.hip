@@ -1,0 +1,324 @@
+// retrieval.hip -- label-free view-retrieval score: per query, the RANK of its positive key in a similarity sweep, without ever
+// holding the similarity matrix.  Replaces the host block of the reference's scripts/phase5_view_retrieval_eval.py:214-227
+// (S = Q K^T as an N x N numpy array, argmax / argpartition over its rows: 64 MB at N = 4096, 17 GB at N = 65 536).
+//
+//   s(i,j)     = sum_d q[i,d] k[j,d]              exact-fp32 MFMA (v_mfma_f32_32x32x2_f32): per score a d-ordered fp32 fma chain
+//   pos_val[i] = s(i, target[i])
+//   rank[i]    = #{j : s(i,j) > pos_val[i]} + #{j < target[i] : s(i,j) == pos_val[i]}      (place in a stable descending sort)
+//   best_val[i], best_idx[i] = max_j s(i,j) and its lowest index                           (np.argmax: first maximum)
+//
+// Three launches on the caller's stream:
+//   1. retrieval_pos:    pos_val.  A wave multiplies 32 key rows GATHERED by target against its 32 query rows on the same MFMA, in the
+//                        same d order and with the same operand roles as the sweep, and keeps the diagonal: the value is bitwise the
+//                        score the sweep finds in column target[i], which is what gives the tie term a meaning.
+//   2. retrieval_sweep:  128 keys x 128 queries per tile, the loop structure of gemm_f32_big (gemm_f32.hip) with the KEYS on the MFMA's
+//                        row side: a lane then owns one query per 32-wide column block and its 16 accumulators of a block are 16 keys,
+//                        so the compare / count / running maximum of the epilogue needs five registers per query column instead of
+//                        five per accumulator.  grid = (query strips, key splits); a workgroup walks the key tiles of its split
+//                        and stores one (count, max, argmax) triple per query into the workspace.
+//   3. retrieval_finish: one thread per query adds the counts and merges the maxima of the splits in ascending split order.
+// Plain stores only, no atomics: two runs give identical bits.
+#include "common.h"
+
+namespace dinox {
+
+constexpr int RR_TQ = 128, RR_TK = 128, RR_BK = 16, RR_THREADS = 256;
+constexpr int RR_LD = RR_TK + 4;               // LDS row pitch (floats): the four k-quads of a staging store land 16 banks apart
+// Key splits, a pure function of (Nq, Nk) so that dinox_retrieval_ws_bytes and the launch always agree (measured on MI355X,
+// tools/retrieval_bench.py, DESIGN.md "Retrieval"): the sweep holds three workgroups per CU, 768 on the
+// chip.  Many small workgroups balance the tail of a long sweep (N = 16 384: 2048 workgroups of 8 tiles beat 1024 of 16 by 7 %); but a grid
+// just above 768 one-tile workgroups ends with one workgroup per CU and nothing to hide its barriers behind (N = 4096: 1024 x 1 tile
+// 204 us, 512 x 2 tiles 177 us), so a grid that cannot be resident at once gives every workgroup at least two tiles.
+constexpr int64_t RR_TARGET_GROUPS = 2048, RR_RESIDENT_GROUPS = 768;
+
+struct RrSplit {
+  int64_t strips, tiles_per_split, splits;
+};
+
+static RrSplit rr_split(int64_t Nq, int64_t Nk) {
+  RrSplit s;
+  s.strips = ceil_div(Nq, (int64_t)RR_TQ);
+  const int64_t tiles = ceil_div(Nk, (int64_t)RR_TK);
+  int64_t want = ceil_div(RR_TARGET_GROUPS, s.strips);
+  if (want > tiles) want = tiles;
+  if (want > 65535) want = 65535;              // grid.y
+  s.tiles_per_split = ceil_div(tiles, want);
+  if (s.tiles_per_split < 2 && tiles >= 2 && s.strips * tiles > RR_RESIDENT_GROUPS) s.tiles_per_split = 2;
+  s.splits = ceil_div(tiles, s.tiles_per_split);   // no empty split
+  return s;
+}
+
+__device__ __forceinline__ int rr_target(const int32_t* __restrict__ target, int64_t i, int64_t Nk) {
+  int64_t t = target ? (int64_t)target[i] : i;
+  t = t < 0 ? 0 : (t >= Nk ? Nk - 1 : t);      // a bad index must not become a bad address (documented in dinox.h: the caller's contract)
+  return (int)t;
+}
+
+// (value, index) maximum with the lowest index on equal values
+__device__ __forceinline__ void rr_max(float& bv, int& bi, float v, int i) {
+  if (v > bv || (v == bv && i < bi)) {
+    bv = v;
+    bi = i;
+  }
+}
+
+// ------------------------------------------------------------------------------------------ 1. pos_val
+// One wave per 32 queries.  MFMA operands straight from global memory (this pass is 1/128 of the sweep's work per key tile):
+// lane l feeds row (l & 31), k = k0 + 2 j + (l >> 5) of its key row (A side) and of its query row (B side).  The zero fill of a ragged
+// D is harmless to the chain: fma(0, 0, c) = c.
+__global__ __launch_bounds__(RR_THREADS) void retrieval_pos(const float* __restrict__ q, int64_t ldq, const float* __restrict__ k, int64_t ldk,
+                                                           const int32_t* __restrict__ target, int64_t Nq, int64_t Nk, int64_t D,
+                                                           float* __restrict__ pos_val) {
+  const int lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
+  const int64_t i = ((int64_t)blockIdx.x * (RR_THREADS / 64) + (threadIdx.x >> 6)) * 32 + c;
+  const int64_t ic = i < Nq ? i : Nq - 1;      // clamped: lanes past the end compute a row nobody stores
+  const float* qr = q + ic * ldq;
+  const float* kr = k + (int64_t)rr_target(target, ic, Nk) * ldk;
+  f32x16 acc;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+  float a[RR_BK / 2], b[RR_BK / 2], an[RR_BK / 2], bn[RR_BK / 2];
+  auto fetch = [&](int64_t k0, float (&x)[RR_BK / 2], float (&y)[RR_BK / 2]) {
+#pragma unroll
+    for (int j = 0; j < RR_BK / 2; ++j) {
+      const int64_t kk = k0 + 2 * j + h;
+      const bool ok = kk < D;
+      x[j] = ok ? kr[kk] : 0.f;
+      y[j] = ok ? qr[kk] : 0.f;
+    }
+  };
+  fetch(0, an, bn);
+  for (int64_t k0 = 0; k0 < D; k0 += RR_BK) {
+#pragma unroll
+    for (int j = 0; j < RR_BK / 2; ++j) {
+      a[j] = an[j];
+      b[j] = bn[j];
+    }
+    if (k0 + RR_BK < D) fetch(k0 + RR_BK, an, bn);           // next slab: in flight under the products below
+#pragma unroll
+    for (int j = 0; j < RR_BK / 2; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j], b[j], acc, 0, 0, 0);
+  }
+  // C(row r, column c) sits in lane (c, h) at register e with r = (e & 3) + 8 (e >> 2) + 4 h: the diagonal r = c
+  const int e_diag = (c & 3) + 4 * (c >> 3);
+  float v = 0.f;
+#pragma unroll
+  for (int e = 0; e < 16; ++e)
+    if (e == e_diag) v = acc[e];
+  if (h == ((c >> 2) & 1) && i < Nq) pos_val[i] = v;
+}
+
+// ------------------------------------------------------------------------------------------ 2. sweep
+// 128 rows x 16 k of a row-major operand: 512 quads, two per thread; four neighbouring threads read 64 contiguous bytes of a row.
+// VEC: every quad is 16-byte aligned and whole (pointer, leading dimension and D multiples of four floats) -- one dwordx4 load per quad;
+// otherwise element loads.  Rows past the end and k past D read as zero (no load is issued for them).
+template <bool VEC>
+__device__ __forceinline__ void rr_fetch(const float* __restrict__ base, int64_t ld, int64_t row0, int64_t rows, int64_t k0, int64_t D,
+                                         f32x4 (&v)[2]) {
+  const int t = threadIdx.x;
+  const int64_t gk = k0 + 4 * (t & 3);
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int64_t gr = row0 + (t >> 2) + 64 * i;
+    f32x4 x = {0.f, 0.f, 0.f, 0.f};
+    if (gr < rows) {
+      const float* p = base + gr * ld + gk;
+      if constexpr (VEC) {
+        if (gk < D) x = *reinterpret_cast<const f32x4*>(p);
+      } else {
+#pragma unroll
+        for (int cc = 0; cc < 4; ++cc)
+          if (gk + cc < D) x[cc] = p[cc];
+      }
+    }
+    v[i] = x;
+  }
+}
+
+__device__ __forceinline__ void rr_put(const f32x4 (&v)[2], float (*dst)[RR_LD]) {
+  const int t = threadIdx.x, kq = 4 * (t & 3);
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int cc = 0; cc < 4; ++cc) dst[kq + cc][(t >> 2) + 64 * i] = v[i][cc];
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(RR_THREADS, 3) void retrieval_sweep(const float* __restrict__ q, int64_t ldq, const float* __restrict__ k, int64_t ldk,
+                                                             const int32_t* __restrict__ target, int64_t Nq, int64_t Nk, int64_t D,
+                                                             const float* __restrict__ pos_val, int64_t tiles_per_split,
+                                                             int32_t* __restrict__ ws_cnt, float* __restrict__ ws_val,
+                                                             int32_t* __restrict__ ws_idx) {
+  __shared__ float Ks[RR_BK][RR_LD];
+  __shared__ float Qs[RR_BK][RR_LD];
+  __shared__ int red_cnt[2][RR_TQ];
+  __shared__ float red_val[2][RR_TQ];
+  __shared__ int red_idx[2][RR_TQ];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, c = lane & 31, h = lane >> 5;
+  const int wr = wv >> 1, wc = wv & 1;           // wr: which 64 keys of the tile, wc: which 64 queries of the strip
+  const int64_t q0 = (int64_t)blockIdx.x * RR_TQ;
+  const int64_t tiles = ceil_div(Nk, (int64_t)RR_TK);
+  const int64_t tile_lo = (int64_t)blockIdx.y * tiles_per_split;
+  const int64_t tile_hi = tile_lo + tiles_per_split < tiles ? tile_lo + tiles_per_split : tiles;
+
+  // this lane's two queries (one per 32-wide column block), their positive score and positive index
+  float pos[2], bv[2];
+  int tgt[2], bi[2], cnt[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int64_t qi = q0 + wc * 64 + j * 32 + c;
+    const bool ok = qi < Nq;
+    pos[j] = ok ? pos_val[qi] : 0.f;
+    tgt[j] = ok ? rr_target(target, qi, Nk) : 0;
+    bv[j] = -INFINITY;
+    bi[j] = 0x7fffffff;
+    cnt[j] = 0;
+  }
+
+  for (int64_t tile = tile_lo; tile < tile_hi; ++tile) {
+    const int64_t k0row = tile * RR_TK;
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    f32x4 vk[2], vq[2];
+    rr_fetch<VEC>(k, ldk, k0row, Nk, 0, D, vk);
+    rr_fetch<VEC>(q, ldq, q0, Nq, 0, D, vq);
+    for (int64_t d0 = 0; d0 < D; d0 += RR_BK) {
+      rr_put(vk, Ks);
+      rr_put(vq, Qs);
+      __syncthreads();
+      if (d0 + RR_BK < D) {                                  // next slab: in flight under the products below
+        rr_fetch<VEC>(k, ldk, k0row, Nk, d0 + RR_BK, D, vk);
+        rr_fetch<VEC>(q, ldq, q0, Nq, d0 + RR_BK, D, vq);
+      }
+#pragma unroll
+      for (int kk = 0; kk < RR_BK; kk += 2) {
+        const int kr = kk + h;
+        const float a0 = Ks[kr][wr * 64 + c], a1 = Ks[kr][wr * 64 + 32 + c];
+        const float b0 = Qs[kr][wc * 64 + c], b1 = Qs[kr][wc * 64 + 32 + c];
+        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+      }
+      __syncthreads();
+    }
+    // epilogue on the accumulators: acc[i][j][e] = s(query j-block column c, key k0row + wr 64 + i 32 + (e & 3) + 8 (e >> 2) + 4 h).
+    // Keys past Nk were multiplied as zero rows: they are neither counted nor allowed to win the maximum.
+    const int nk = (int)Nk, key0 = (int)k0row + wr * 64 + 4 * h;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        __builtin_amdgcn_sched_barrier(0);                   // one 32 x 32 block at a time: 16 accumulator reads live, not 64
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int key = key0 + i * 32 + (e & 3) + 8 * (e >> 2);
+          const float s = acc[i][j][e];
+          if (key < nk) {
+            cnt[j] += (s > pos[j] || (s == pos[j] && key < tgt[j])) ? 1 : 0;
+            rr_max(bv[j], bi[j], s, key);
+          }
+        }
+      }
+  }
+
+  // the two half-waves hold different keys of the same query; then the two key-side waves meet in LDS
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    cnt[j] += __shfl_xor(cnt[j], 32, 64);
+    const float ov = __shfl_xor(bv[j], 32, 64);
+    const int oi = __shfl_xor(bi[j], 32, 64);
+    rr_max(bv[j], bi[j], ov, oi);
+    if (h == 0) {
+      const int col = wc * 64 + j * 32 + c;
+      red_cnt[wr][col] = cnt[j];
+      red_val[wr][col] = bv[j];
+      red_idx[wr][col] = bi[j];
+    }
+  }
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < RR_TQ && q0 + t < Nq) {
+    float v = red_val[0][t];
+    int ix = red_idx[0][t];
+    rr_max(v, ix, red_val[1][t], red_idx[1][t]);
+    const int64_t o = (int64_t)blockIdx.y * Nq + q0 + t;
+    ws_cnt[o] = red_cnt[0][t] + red_cnt[1][t];
+    ws_val[o] = v;
+    ws_idx[o] = ix;
+  }
+}
+
+// ------------------------------------------------------------------------------------------ 3. merge of the key splits
+__global__ __launch_bounds__(RR_THREADS) void retrieval_finish(const int32_t* __restrict__ ws_cnt, const float* __restrict__ ws_val,
+                                                              const int32_t* __restrict__ ws_idx, int64_t Nq, int splits,
+                                                              int32_t* __restrict__ rank, int32_t* __restrict__ best_idx,
+                                                              float* __restrict__ best_val) {
+  const int64_t i = (int64_t)blockIdx.x * RR_THREADS + threadIdx.x;
+  if (i >= Nq) return;
+  int n = 0, bi = 0x7fffffff;
+  float bv = -INFINITY;
+  for (int s0 = 0; s0 < splits; s0 += 8) {        // ascending split = ascending key range: a fixed order; eight splits' loads in flight
+    int c[8], ix[8];
+    float v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const bool ok = s0 + u < splits;
+      const int64_t o = (int64_t)(ok ? s0 + u : s0) * Nq + i;
+      c[u] = ok ? ws_cnt[o] : 0;
+      v[u] = ok ? ws_val[o] : -INFINITY;
+      ix[u] = ok ? ws_idx[o] : 0x7fffffff;
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      n += c[u];
+      rr_max(bv, bi, v[u], ix[u]);
+    }
+  }
+  rank[i] = n;
+  best_idx[i] = bi;
+  best_val[i] = bv;
+}
+
+}  // namespace dinox
+
+using namespace dinox;
+
+extern "C" int64_t dinox_retrieval_ws_bytes(int64_t Nq, int64_t Nk, int64_t D) {
+  if (Nq <= 0 || Nk <= 0 || D <= 0) return 0;
+  return rr_split(Nq, Nk).splits * Nq * 12;      // (count, maximum, its index) per query and key split
+}
+
+extern "C" int dinox_retrieval_rank(const float* q, int64_t ldq, const float* k, int64_t ldk, const int32_t* target, int64_t Nq, int64_t Nk,
+                                    int64_t D, int32_t* rank, int32_t* best_idx, float* best_val, float* pos_val, void* ws, void* stream) {
+  DX_REQUIRE(q && k && rank && best_idx && best_val && pos_val && ws, DINOX_EINVAL, "retrieval_rank: null pointer");
+  DX_REQUIRE(Nq > 0 && Nk > 0 && D > 0 && Nq <= 0x7fffffff - RR_TQ && Nk <= 0x7fffffff - RR_TK && ldq >= D && ldk >= D, DINOX_EINVAL,   // (padded indices of the last tile stay in int)
+             "retrieval_rank: Nq=%lld Nk=%lld D=%lld ldq=%lld ldk=%lld", (long long)Nq, (long long)Nk, (long long)D, (long long)ldq,
+             (long long)ldk);
+  DX_REQUIRE(target || Nq == Nk, DINOX_EINVAL, "retrieval_rank: a null target means target[i] = i and needs Nq == Nk (%lld, %lld)",
+             (long long)Nq, (long long)Nk);
+  const RrSplit sp = rr_split(Nq, Nk);
+  DX_REQUIRE(sp.strips <= 0x7fffffff, DINOX_EINVAL, "retrieval_rank: Nq=%lld", (long long)Nq);
+  const bool vec = (uintptr_t)q % 16 == 0 && (uintptr_t)k % 16 == 0 && ldq % 4 == 0 && ldk % 4 == 0 && D % 4 == 0;
+  int32_t* ws_cnt = (int32_t*)ws;
+  float* ws_val = (float*)(ws_cnt + sp.splits * Nq);
+  int32_t* ws_idx = (int32_t*)(ws_val + sp.splits * Nq);
+  hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL(retrieval_pos, dim3((unsigned)ceil_div(Nq, (int64_t)(32 * RR_THREADS / 64))), dim3(RR_THREADS), 0, st, q, ldq, k, ldk,
+                     target, Nq, Nk, D, pos_val);
+  if (int rc = check_launch("retrieval_pos")) return rc;
+  const dim3 grid((unsigned)sp.strips, (unsigned)sp.splits);
+#define RR_SWEEP(V) \
+  hipLaunchKernelGGL(retrieval_sweep<V>, grid, dim3(RR_THREADS), 0, st, q, ldq, k, ldk, target, Nq, Nk, D, (const float*)pos_val, \
+                     sp.tiles_per_split, ws_cnt, ws_val, ws_idx)
+  if (vec) RR_SWEEP(true); else RR_SWEEP(false);
+#undef RR_SWEEP
+  if (int rc = check_launch("retrieval_sweep")) return rc;
+  hipLaunchKernelGGL(retrieval_finish, dim3((unsigned)ceil_div(Nq, (int64_t)RR_THREADS)), dim3(RR_THREADS), 0, st, (const int32_t*)ws_cnt,
+                     (const float*)ws_val, (const int32_t*)ws_idx, Nq, (int)sp.splits, rank, best_idx, best_val);
+  return check_launch("retrieval_finish");
+}

@@ -1906,3 +1906,56 @@ class GeluFn(torch.autograd.Function):
         dx = torch.empty_like(xf)
         check(lib.dinox_gelu_bwd(_p(dyf), _p(xf), _p(dx), xf.numel(), _stream()), "dinox_gelu_bwd")
         return dx.to(ctx.xdtype)
+
+
+# ------------------------------------------------------------------------------------------
+# view retrieval (csrc/retrieval.hip)
+# ------------------------------------------------------------------------------------------
+def normalize_rows(x: Tensor):
+    """F.normalize(x, dim=-1) of fp32 rows [V, D] (x / max(||x||, 1e-12)) on dinox_koleo_normalize; returns (unit rows, norms [V])."""
+    _need_cuda(x)
+    x = _c(x.float())
+    V, D = x.shape
+    f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=x.device)
+    xh, norm, sq = f(V, D), f(V), f(V)
+    check(lib.dinox_koleo_normalize(_p(x), _p(xh), _p(norm), _p(sq), V, D, 1e-12, _stream()), "dinox_koleo_normalize")
+    return xh, norm
+
+
+def retrieval_rank(q: Tensor, k: Tensor, target: Optional[Tensor] = None):
+    """For each fp32 query row of q [Nq, D] against the fp32 key rows of k [Nk, D]: (rank, best_idx, best_val, pos_val), each [Nq] --
+    rank[i] is the place of key target[i] (default: i) in a stable descending sort of the scores q_i . k_j, best_* the row maximum and
+    its first index, pos_val the positive's score.  The scores exist only in the accumulators of the exact-fp32 MFMA: no Nq x Nk
+    tensor is allocated.  The rows are used as given (normalise them first: normalize_rows); target indices are checked against
+    [0, Nk) here (the kernel itself clamps them).  Rows of NaNs compare false with everything: see include/dinox.h."""
+    _need_cuda(q, k, target)
+    if q.dtype != torch.float32 or k.dtype != torch.float32 or q.dim() != 2 or k.dim() != 2 or q.shape[1] != k.shape[1]:
+        raise ValueError(f"retrieval_rank: fp32 [Nq, D] and [Nk, D] rows expected, got {q.dtype}{tuple(q.shape)} and {k.dtype}{tuple(k.shape)}")
+    if q.stride(1) != 1 or q.stride(0) < q.shape[1]:
+        q = q.contiguous()
+    if k.stride(1) != 1 or k.stride(0) < k.shape[1]:
+        k = k.contiguous()
+    (Nq, D), Nk = q.shape, k.shape[0]
+    if min(Nq, Nk, D) < 1:
+        raise ValueError(f"retrieval_rank: empty operand (Nq={Nq}, Nk={Nk}, D={D})")
+    if target is None:
+        if Nq != Nk:
+            raise ValueError(f"retrieval_rank: without target, query i is matched to key i and Nq must equal Nk ({Nq}, {Nk})")
+    else:
+        if target.shape != (Nq,):
+            raise ValueError(f"retrieval_rank: target must have shape ({Nq},), got {tuple(target.shape)}")
+        if target.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"retrieval_rank: target must be int32 or int64 indices, got {target.dtype}")
+        lo, hi = int(target.min()), int(target.max())          # one host sync on an evaluation path: the kernel clamps, it cannot refuse
+        if lo < 0 or hi >= Nk:
+            raise ValueError(f"retrieval_rank: target indices must lie in [0, {Nk}), got [{lo}, {hi}]")
+        target = _c(target.to(torch.int32))
+    dev = q.device
+    rank = torch.empty(Nq, dtype=torch.int32, device=dev)
+    best_idx = torch.empty(Nq, dtype=torch.int32, device=dev)
+    best_val = torch.empty(Nq, dtype=torch.float32, device=dev)
+    pos_val = torch.empty(Nq, dtype=torch.float32, device=dev)
+    ws = torch.empty(int(lib.dinox_retrieval_ws_bytes(Nq, Nk, D)), dtype=torch.uint8, device=dev)
+    check(lib.dinox_retrieval_rank(_p(q), q.stride(0), _p(k), k.stride(0), _p(target), Nq, Nk, D, _p(rank), _p(best_idx), _p(best_val),
+                                   _p(pos_val), _p(ws), _stream()), "dinox_retrieval_rank")
+    return rank, best_idx, best_val, pos_val

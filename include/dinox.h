@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define DINOX_ABI_VERSION 3   /* 3: + dinox_block_forward / _backward, dinox_gemm_timer_* (additive) */
+#define DINOX_ABI_VERSION 3   /* 3: + dinox_block_forward / _backward, dinox_gemm_timer_*, dinox_retrieval_* (additive) */
 
 /* dtype codes */
 #define DINOX_F32 0
@@ -404,6 +404,28 @@ typedef struct dinox_block_bwd_args {
 
 int dinox_block_forward(const dinox_block_fwd_args* args, void* stream);
 int dinox_block_backward(const dinox_block_bwd_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * View-retrieval rank -- replaces the host block of scripts/phase5_view_retrieval_eval.py:214-227 (S = Q K^T as an N x N numpy array,
+ * np.argmax / np.argpartition over its rows).  No Nq x Nk array exists: the similarity tiles live in the accumulators of the exact-fp32
+ * MFMA and leave them as counts.  q [Nq][D] (ldq >= D) and k [Nk][D] (ldk >= D) are fp32 rows, used as given (pass unit rows:
+ * dinox_koleo_normalize with eps = 1e-12 is F.normalize); target[i] is the index of query i's positive key (NULL: target[i] = i,
+ * needs Nq == Nk).  With s(i,j) = sum_d q[i][d] k[j][d], fp32, ascending d:
+ *   pos_val[i]  = s(i, target[i]), bitwise the value the sweep computes for that column;
+ *   rank[i]     = #{j : s(i,j) > pos_val[i]} + #{j < target[i] : s(i,j) == pos_val[i]}  -- the positive's place in a stable descending
+ *                 sort; rank == 0 is exactly np.argmax(S[i]) == target[i], rank < k is "among the k nearest";
+ *   best_val[i] = max_j s(i,j), best_idx[i] = its lowest index.
+ * ws: dinox_retrieval_ws_bytes(Nq, Nk, D) bytes (12 bytes per query and key split, a pure function of the three sizes; contents need not be
+ * initialised).  Any Nq, Nk, D >= 1 (Nq, Nk <= 2^31 - 129).
+ * Caller's contract: 0 <= target[i] < Nk.  An index outside that range is CLAMPED into it (it never becomes an address), so the outputs
+ * of that query then describe key 0 or key Nk - 1; dinox.ops.retrieval_rank checks the range before the call.
+ * Non-finite scores: every comparison with a NaN is false, so a query row of NaNs gets rank 0, best_idx = 0x7fffffff, best_val = -inf and a
+ * NaN pos_val; test pos_val (dinox.retrieval.view_retrieval does) before reading a score from such rows.
+ * Three launches on the stream, no atomics: results are bit-reproducible.
+ * ------------------------------------------------------------------------------------------ */
+int64_t dinox_retrieval_ws_bytes(int64_t Nq, int64_t Nk, int64_t D);
+int dinox_retrieval_rank(const float* q, int64_t ldq, const float* k, int64_t ldk, const int32_t* target, int64_t Nq, int64_t Nk, int64_t D,
+                         int32_t* rank, int32_t* best_idx, float* best_val, float* pos_val, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Per-launch timing of dinox_gemm (diagnostic; bench.py's roofline object).  Between start and stop every dinox_gemm launch -- also
