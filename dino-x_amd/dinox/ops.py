@@ -14,6 +14,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import math
+import operator
 import os
 import weakref
 from typing import Optional
@@ -1959,3 +1960,61 @@ def retrieval_rank(q: Tensor, k: Tensor, target: Optional[Tensor] = None):
     check(lib.dinox_retrieval_rank(_p(q), q.stride(0), _p(k), k.stride(0), _p(target), Nq, Nk, D, _p(rank), _p(best_idx), _p(best_val),
                                    _p(pos_val), _p(ws), _stream()), "dinox_retrieval_rank")
     return rank, best_idx, best_val, pos_val
+
+
+KNN_MAX_K = 32
+
+
+def knn_topk(q: Tensor, k: Tensor, K: int, exclude=None):
+    """(idx int32 [Nq, K], val fp32 [Nq, K]): for each fp32 query row of q [Nq, D], the K keys of k [Nk, D] with the highest scores q_i . k_j,
+    ordered by (score descending, index ascending); key ``exclude[i]`` is left out of row i (``exclude="self"`` = arange(Nq), needs
+    Nq == Nk: the self-exclusion of a set searched against itself; -1 or any index outside [0, Nk) leaves nothing out).  With fewer than K
+    eligible keys the remaining slots hold index -1 and value -inf.  1 <= K <= 32.  The scores are the ones ``retrieval_rank`` sees (same
+    sweep, csrc/knn.hip): column 0 is bitwise its best_idx / best_val.  No Nq x Nk tensor is allocated; the workspace is 8 K bytes per query
+    and key split.  Rows are used as given (normalise them first: normalize_rows); rows that meet NaN scores: see include/dinox.h.
+    Arguments are checked before the device is: a wrong call raises ValueError anywhere."""
+    if not (isinstance(q, Tensor) and isinstance(k, Tensor)) or q.dtype != torch.float32 or k.dtype != torch.float32 or q.dim() != 2 \
+            or k.dim() != 2 or q.shape[1] != k.shape[1]:
+        raise ValueError("knn_topk: fp32 [Nq, D] and [Nk, D] rows expected, got "
+                         + " and ".join(f"{t.dtype}{tuple(t.shape)}" if isinstance(t, Tensor) else type(t).__name__ for t in (q, k)))
+    (Nq, D), Nk = q.shape, k.shape[0]
+    if min(Nq, Nk, D) < 1:
+        raise ValueError(f"knn_topk: empty operand (Nq={Nq}, Nk={Nk}, D={D})")
+    if q.device != k.device:
+        raise ValueError(f"knn_topk: queries on {q.device}, keys on {k.device}")
+    K_given = K
+    try:
+        K = None if isinstance(K, bool) else operator.index(K)                 # Python and NumPy integers; not bool, not float
+    except TypeError:
+        K = None
+    if K is None or not 1 <= K <= KNN_MAX_K:
+        raise ValueError(f"knn_topk: K must be an integer in [1, {KNN_MAX_K}], got {K_given!r} (q {tuple(q.shape)}, k {tuple(k.shape)})")
+    if isinstance(exclude, str):
+        if exclude != "self":
+            raise ValueError(f"knn_topk: exclude must be None, 'self' or an index tensor of shape ({Nq},), got {exclude!r}")
+        if Nq != Nk:
+            raise ValueError(f"knn_topk: exclude='self' leaves key i out of row i and needs Nq == Nk ({Nq}, {Nk})")
+        exclude = torch.arange(Nq, dtype=torch.int32, device=q.device)
+    elif exclude is not None:
+        if not isinstance(exclude, Tensor) or exclude.shape != (Nq,):
+            raise ValueError(f"knn_topk: exclude must have shape ({Nq},), got {tuple(getattr(exclude, 'shape', ()))}")
+        if exclude.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"knn_topk: exclude must be int32 or int64 indices, got {exclude.dtype}")
+        if exclude.device != q.device:
+            raise ValueError(f"knn_topk: queries on {q.device}, exclude on {exclude.device}")
+    _need_cuda(q, k, exclude)
+    if exclude is not None and exclude.dtype != torch.int32:
+        exclude = torch.where((exclude >= 0) & (exclude < Nk), exclude, torch.full_like(exclude, -1)).to(torch.int32)   # (no wrap-around into range)
+    if exclude is not None:
+        exclude = _c(exclude)
+    if q.stride(1) != 1 or q.stride(0) < D:
+        q = q.contiguous()
+    if k.stride(1) != 1 or k.stride(0) < D:
+        k = k.contiguous()
+    dev = q.device
+    idx = torch.empty((Nq, K), dtype=torch.int32, device=dev)
+    val = torch.empty((Nq, K), dtype=torch.float32, device=dev)
+    ws = torch.empty(int(lib.dinox_knn_ws_bytes(Nq, Nk, D, K)), dtype=torch.uint8, device=dev)
+    check(lib.dinox_knn_topk(_p(q), q.stride(0), _p(k), k.stride(0), _p(exclude), Nq, Nk, D, K, _p(idx), _p(val), _p(ws), _stream()),
+          "dinox_knn_topk")
+    return idx, val

@@ -116,3 +116,55 @@ def view_retrieval(student, dataset, idxs: Sequence[int], batch_size: int = 64, 
     if not bool(torch.isfinite(pos_val).all()) or not bool(torch.isfinite(K).all()):
         raise FloatingPointError("view_retrieval: non-finite embeddings (diverged checkpoint?); no score can be given")
     return {**metrics_from_ranks(rank.cpu().numpy(), topk, ratio), **stats}
+
+
+# ------------------------------------------------------------------------------------------ deterministic evaluation inputs
+EVAL_WINDOW = (40.0, 400.0)             # the reference's fixed soft-tissue window (level, width): scripts/evaluate_panorgan.py:105-106
+
+
+def eval_view(H: int, W: int):
+    """The one deterministic view of an (H, W) slice stack: fixed window level 40 / width 400, the centred square crop of side
+    min(H, W), no flip -- the reference's ``EvalDataset`` (scripts/evaluate_panorgan.py:91-168: Resize(img_size, bicubic) of the shorter
+    side, CenterCrop(img_size), normalise) restated on the device view kernel: resizing the shorter side to S and cutting the centre
+    S x S is cutting the centred min(H, W) square and resizing it to S x S (up to the rounding of the longer side).  Resize parity
+    with torchvision is NOT pinned: torchvision is not a dependency; the view kernel is pinned to torch's bicubic antialias kernel
+    (DESIGN.md section 8f-2)."""
+    from .views import ViewParams
+    side = min(H, W)
+    return ViewParams(EVAL_WINDOW[0], EVAL_WINDOW[1], (H - side) // 2, (W - side) // 2, side, side, False)
+
+
+def embed_eval_slices(student, dataset, idxs: Sequence[int], img_size: int, batch_size: int = 64, scale_aware: bool = False, *,
+                      amp_dtype: Optional[torch.dtype] = None):
+    """(E, spacing): the unit CLS row of the deterministic view (``eval_view``) of ``dataset[i]``, i in ``idxs``, fp32 [N, D] on the
+    student's device, and the (N, 3) spacings on the host.  Items follow the raw-stack protocol of the training script's datasets
+    (``raw_views = True``): ``(u16 stack (3, H, W) or its three slices, <ignored view draws>, spacing (3,))``.  The stacks go through
+    ``dinox.views.make_views`` (one kernel: window, crop, bicubic resize, normalise); every slice is embedded once."""
+    from .views import collate_stacks, make_views
+    bb = _backbone(student)
+    anchor = next(bb.parameters())
+    ops._need_cuda(anchor)
+    n = len(idxs)
+    if n <= 0:
+        raise ValueError("embed_eval_slices: no samples")
+    E, spacings, at = None, [], 0
+    was_training = bb.training
+    bb.eval()
+    try:
+        with ops.compute_dtype(amp_dtype or torch.float32):
+            for lo in range(0, n, batch_size):
+                items = []
+                for i in idxs[lo:lo + batch_size]:
+                    stack, _, sp = dataset[i]
+                    H, W = (stack.shape[1], stack.shape[2]) if isinstance(stack, np.ndarray) else stack[0].shape
+                    items.append((stack, [eval_view(H, W)], sp))
+                batch = collate_stacks(items).to(anchor.device)
+                e = embed_cls(bb, make_views(batch, img_size), batch.spacing if scale_aware else None)
+                if E is None:
+                    E = e.new_empty(n, e.shape[1])
+                E[at:at + len(e)] = e
+                at += len(e)
+                spacings.append(batch.spacing.cpu())
+    finally:
+        bb.train(was_training)
+    return E, torch.cat(spacings, 0)

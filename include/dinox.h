@@ -29,7 +29,9 @@
 extern "C" {
 #endif
 
-#define DINOX_ABI_VERSION 3   /* 3: + dinox_block_forward / _backward, dinox_gemm_timer_*, dinox_retrieval_* (additive) */
+#define DINOX_ABI_VERSION 3   /* 3: + dinox_block_forward / _backward, dinox_gemm_timer_*, dinox_retrieval_*, dinox_knn_* (all additive: no entry
+                               * of an earlier library changed, so the number callers test, dinox_version() == 3, stays; probe the symbol
+                               * to learn whether a given build has the later additions) */
 
 /* dtype codes */
 #define DINOX_F32 0
@@ -426,6 +428,26 @@ int dinox_block_backward(const dinox_block_bwd_args* args, void* stream);
 int64_t dinox_retrieval_ws_bytes(int64_t Nq, int64_t Nk, int64_t D);
 int dinox_retrieval_rank(const float* q, int64_t ldq, const float* k, int64_t ldk, const int32_t* target, int64_t Nq, int64_t Nk, int64_t D,
                          int32_t* rank, int32_t* best_idx, float* best_val, float* pos_val, void* ws, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K nearest keys -- replaces the host block of scripts/evaluate_panorgan.py:526-529 (S = E E^T as an N x N numpy array, fill_diagonal(-inf),
+ * np.argpartition over its rows) and feeds the weighted k-NN probe.  Same operands, same score as dinox_retrieval_rank (exact-fp32 MFMA, one
+ * d-ordered fp32 fma chain per score; the two entries share the tile loop): for equal operands out_val[i][0], out_idx[i][0] are BITWISE
+ * best_val[i], best_idx[i] of dinox_retrieval_rank.
+ *   row i of out_idx / out_val [Nq][K] = the first K keys in the order (score descending, index ascending) -- a total order, the result is
+ *   unique -- with key exclude[i] left out (exclude = NULL or exclude[i] = -1: nothing left out; exclude[i] = i is the reference's
+ *   fill_diagonal(-inf)).  exclude[i] is only ever COMPARED with key indices: a value outside [0, Nk) leaves nothing out and never becomes an
+ *   address.  1 <= K <= 32, anything else returns DINOX_EINVAL.  Fewer than K eligible keys: the remaining slots hold index -1 and value -inf.
+ * ws: dinox_knn_ws_bytes(Nq, Nk, D, K) bytes (8 K bytes per query and key split; the splits are a pure function of Nq and Nk, never more
+ * than dinox_retrieval_rank uses; 0 for every Nq, Nk, D, K the call refuses; contents need not be initialised).  Any Nq, Nk, D >= 1 (Nq, Nk <= 2^31 - 129), ldq, ldk >= D.
+ * Non-finite scores: a NaN score compares false with everything and never enters a row, so a query row of NaNs returns K times (-1, -inf) and
+ * a NaN key is never a neighbour; no ordering promise is made for rows that meet NaNs, but no address depends on a score and no loop on a
+ * comparison: such rows neither fault nor hang.
+ * Two launches on the stream, plain stores, no atomics: results are bit-reproducible.
+ * ------------------------------------------------------------------------------------------ */
+int64_t dinox_knn_ws_bytes(int64_t Nq, int64_t Nk, int64_t D, int K);
+int dinox_knn_topk(const float* q, int64_t ldq, const float* k, int64_t ldk, const int32_t* exclude, int64_t Nq, int64_t Nk, int64_t D, int K,
+                   int32_t* out_idx, float* out_val, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Per-launch timing of dinox_gemm (diagnostic; bench.py's roofline object).  Between start and stop every dinox_gemm launch -- also
