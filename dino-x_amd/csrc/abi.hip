@@ -44,6 +44,15 @@ int reserve_lds(const void* kern, size_t bytes, const char* what) {
   return 0;
 }
 
+int device_cu_count() {
+  static const int ncu = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) (void)hipGetLastError();
+    return n > 0 ? n : 256;
+  }();
+  return ncu;
+}
+
 int check_launch(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {

@@ -1,19 +1,7 @@
 // attention.hip -- dinox_attention_{fwd,bwd} dispatch: MFMA flash kernels for bf16 when the shape is
 // inside their envelope, otherwise the fp32-math reference kernels (attention_ref.hip).
-#include <cstdlib>
-
 #include "common.h"
-
-namespace dinox {
-int launch_attention_ref_fwd(const void*, void*, float*, int, int, int, int, int, hipStream_t);
-int launch_attention_ref_bwd(const void*, const void*, const void*, const float*, void*, int, int, int, int, int, hipStream_t);
-int launch_attention_bf16_fwd(const void*, void*, float*, int, int, int, int, hipStream_t);   // EUNSUPPORTED if outside envelope
-int launch_attention_bf16_bwd(const void*, const void*, const void*, const float*, void*, float*, int, int, int, int, hipStream_t);
-int launch_attention_flash_fwd(const void*, void*, float*, int, int, int, int, hipStream_t);  // attention_flash.hip: any N, d <= 128 (d % 8 == 0)
-int launch_attention_flash_bwd(const void*, const void*, const void*, const float*, void*, float*, int, int, int, int, hipStream_t);
-bool attention_qkv_fused_ok(int B, int N, int heads, int d, int D);
-int launch_attention_qkv_fused_fwd(const void*, const void*, const float*, void*, void*, float*, int, int, int, int, int, hipStream_t);
-}  // namespace dinox
+#include "kernels.h"
 
 using namespace dinox;
 
@@ -30,7 +18,7 @@ extern "C" int dinox_attention_fwd(const void* qkv, void* o, float* lse, int B, 
   hipStream_t st = as_stream(stream);
   if (dtype == DINOX_BF16) {
     int rc = launch_attention_bf16_fwd(qkv, o, lse, B, N, heads, d, st);              // head size 64, whole score strips in registers
-    if (rc == DINOX_EUNSUPPORTED && !getenv("DINOX_ATTN_NO_FLASH"))                    // (A/B and tests: the per-lane reference kernels instead)
+    if (rc == DINOX_EUNSUPPORTED && !knob_set("DINOX_ATTN_NO_FLASH"))                    // (A/B and tests: the per-lane reference kernels instead)
       rc = launch_attention_flash_fwd(qkv, o, lse, B, N, heads, d, st);                // the tiled form: long sequences, other head sizes
     if (rc != DINOX_EUNSUPPORTED) return rc;
   }
@@ -49,7 +37,7 @@ extern "C" int dinox_attention_bwd(const void* d_o, const void* qkv, const void*
   hipStream_t st = as_stream(stream);
   if (dtype == DINOX_BF16) {
     int rc = launch_attention_bf16_bwd(d_o, qkv, o, lse, dqkv, (float*)ws, B, N, heads, d, st);
-    if (rc == DINOX_EUNSUPPORTED && !getenv("DINOX_ATTN_NO_FLASH")) rc = launch_attention_flash_bwd(d_o, qkv, o, lse, dqkv, (float*)ws, B, N, heads, d, st);
+    if (rc == DINOX_EUNSUPPORTED && !knob_set("DINOX_ATTN_NO_FLASH")) rc = launch_attention_flash_bwd(d_o, qkv, o, lse, dqkv, (float*)ws, B, N, heads, d, st);
     if (rc != DINOX_EUNSUPPORTED) return rc;
   }
   return launch_attention_ref_bwd(d_o, qkv, o, lse, dqkv, B, N, heads, d, dtype, st);

@@ -23,9 +23,9 @@
 //           dP = dO . V^T -> dV += P^T dO, dK += dS^T Q.
 // (two backward kernels recompute S/dP once more than a single fused pass would: 7 instead of 5 tile
 //  products, traded for no cross-wave reduction of dQ; attention is ~8 % of the block's FLOPs.)
-#include <cstdlib>
 
 #include "common.h"
+#include "kernels.h"
 #include <type_traits>
 
 namespace dinox {
@@ -1152,7 +1152,7 @@ int launch_attention_bf16_fwd(const void* qkv, void* o, float* lse, int B, int N
   {
     const int nw = nblk < 8 ? nblk : 8;
     const size_t lds = (size_t)4 * nblk * 32 * 128 + 8 * 32 * sizeof(float) + (size_t)nw * ST_BYTES;    // images, 1/rowsum, output staging (per wave)
-    static const bool off = getenv("DINOX_ATTN_NO_PERSIST") != nullptr;
+    static const bool off = knob_set("DINOX_ATTN_NO_PERSIST");
     if (lds <= 160 * 1024 && !off && nblk <= nw) {          // one query block per wave (the kernel relies on it)
       const int npairs = B * heads;
       // resident workgroups: one per CU at 7 blocks (201 tokens); short sequences (the 41-token local crops: two waves, 41 KiB) get as many as
@@ -1210,7 +1210,7 @@ int launch_attention_bf16_bwd(const void* d_o, const void* qkv, const void* o, c
   {
     // one persistent kernel (N <= 224): every tensor moves once, loads run under the other phase's arithmetic
     const size_t ldsf = (size_t)4 * nblk * 32 * 128 + 2 * (size_t)nblk * 32 * sizeof(float) + (size_t)nblk * ST_BYTES;
-    static const bool split = getenv("DINOX_ATTN_BWD_SPLIT") != nullptr;
+    static const bool split = knob_set("DINOX_ATTN_BWD_SPLIT");
     if (nblk <= 7 && ldsf <= 160 * 1024 && !split) {
       const int npairs = B * heads;
       const int per_cu = persist_wgs_per_cu(ldsf, nblk);

@@ -13,9 +13,9 @@
 //   * the forward keeps the running row maximum and sum of online softmax (per 32-key tile; the output block is rescaled only when
 //     some row's maximum really moved -- after the first few tiles it rarely does).
 // Replaces F.scaled_dot_product_attention (reference zoo/arch.py:51) and its backward.
-#include <cstdlib>
 
 #include "common.h"
+#include "kernels.h"
 
 namespace dinox {
 
@@ -378,7 +378,6 @@ __global__ __launch_bounds__(256, 2) void attn_flash_bwd_dkv(const bf16_t* __res
 // ------------------------------------------------------------------------------------------ launchers
 static int fl_dh(int d) { return d <= 64 ? 64 : d <= 96 ? 96 : 128; }
 static bool fl_ok(const void* a, const void* b, int d) { return d >= 8 && d <= 128 && (d & 7) == 0 && !((uintptr_t)a & 15) && !((uintptr_t)b & 15); }
-int reserve_lds(const void* kern, size_t bytes, const char* what);
 
 int launch_attention_flash_fwd(const void* qkv, void* o, float* lse, int B, int N, int heads, int d, hipStream_t st) {
   if (!fl_ok(qkv, o, d)) return DINOX_EUNSUPPORTED;

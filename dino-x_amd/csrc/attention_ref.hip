@@ -4,6 +4,7 @@
 // Replaces reshape/permute/unbind + F.scaled_dot_product_attention + transpose/reshape of the
 // reference (zoo/arch.py:45-52): softmax(Q K^T / sqrt(d)) V, no mask, no dropout.
 #include "common.h"
+#include "kernels.h"
 
 namespace dinox {
 

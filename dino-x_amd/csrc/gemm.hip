@@ -2,7 +2,7 @@
 #include <cstring>
 
 #include "common.h"
-#include "gemm_common.h"
+#include "kernels.h"
 
 namespace dinox {
 
@@ -98,7 +98,7 @@ extern "C" const char* dinox_gemm_kernel_name(const dinox_gemm_args* a) {
   if (!a) return "";
   GemmParams p;
   to_params(a, p);
-  const char* v = gemm_bf16_variant(p);
+  const char* v = gemm_variant_name(gemm_bf16_variant(p));
   return v ? v : "gemm_f32";
 }
 
@@ -127,7 +127,7 @@ extern "C" int dinox_gemm(const dinox_gemm_args* a, void* stream) {
   if (g_timer_on) {
     std::lock_guard<std::mutex> lk(g_timer_mu);
     if (g_timer_on) {
-      const char* v = gemm_bf16_variant(p);
+      const char* v = gemm_variant_name(gemm_bf16_variant(p));
       TimerRec& r = g_timer[TimerKey(v ? v : "gemm_f32", p.M, p.N, p.K, p.batch, p.epilogue, p.in_dtype, p.out_dtype,
                                      (p.aux && (p.epilogue & (DINOX_EPI_GELU | DINOX_EPI_DGELU))) ? 1 : 0, (p.batch > 1 && p.strideB == 0) ? 1 : 0)];
       r.launches++;

@@ -15,12 +15,8 @@
 // K-step ahead into registers and written to the other LDS stage after the MFMAs (one barrier per step).
 // Workgroup ids are remapped so that each XCD walks a contiguous run of tiles: the N-tiles that share an
 // A row-panel hit that XCD's private L2 (cdna_hip_programming.md T1, bijective form).
-#include <cstdlib>
-
-#include <cstring>
-
 #include "common.h"
-#include "gemm_common.h"
+#include "kernels.h"
 
 namespace dinox {
 
@@ -542,47 +538,33 @@ static void tn_split_plan(const GemmParams& p, int& splits, int64_t& kps) {
 }
 
 static bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-int tn_big_plan(const GemmParams& p, int& tiles_m, int& tiles_n, int& splits, int64_t& kps);     // gemm_bf16_tnbig.hip
-int64_t tn_big_ws_bytes(const GemmParams& p);
-int launch_gemm_bf16_tn_big(const GemmParams& p, hipStream_t st, int& splits_out, int& tiles_n_out);
-bool gemm_bf16_nt_glds_ok(const GemmParams& p);
-int launch_gemm_bf16_nt_glds(const GemmParams& p, hipStream_t st);
-bool gemm_bf16_nt_areg_ok(const GemmParams& p);
-int launch_gemm_bf16_nt_areg(const GemmParams& p, hipStream_t st);
-bool gemm_bf16_nt_pp_ok(const GemmParams& p);                                                   // gemm_bf16_pp.hip
-int launch_gemm_bf16_nt_pp(const GemmParams& p, hipStream_t st);
-bool gemm_bf16_nt_pp128_ok(const GemmParams& p);                                                // gemm_bf16_pp128.hip
-int launch_gemm_bf16_nt_pp128(const GemmParams& p, hipStream_t st);
-bool gemm_bf16_nt_pp384_ok(const GemmParams& p);                                                // gemm_bf16_pp384.hip
-int launch_gemm_bf16_nt_pp384(const GemmParams& p, hipStream_t st);
 
 // Which NT products take the persistent ping-pong kernels (gemm_bf16_pp.hip: 256 x 256 tiles, gemm_bf16_pp128.hip: 256 x 128), and which
 // of the two.  DINOX_NT_PP (read per call, so one process can A/B and the tests can force small shapes onto them): 0 = never; 1 = every
 // product inside the envelope, tile width by shape; 2 / 3 = every product on the 128-wide / 256-wide tiles; unset = the measured policy.
-static const char* nt_pp_choice(const GemmParams& p) {
-  if (p.transA || p.transB) return nullptr;
-  const char* e = getenv("DINOX_NT_PP");
-  const int mode = e ? atoi(e) : -1;
-  if (mode == 0) return nullptr;
+static GemmVariant nt_pp_choice(const GemmParams& p) {
+  using V = GemmVariant;
+  if (p.transA || p.transB) return V::None;
+  const int mode = knob_int("DINOX_NT_PP", -1);
+  if (mode == 0) return V::None;
   const bool ok256 = gemm_bf16_nt_pp_ok(p), ok128 = gemm_bf16_nt_pp128_ok(p);
   {
     // The full-row tile for N = 384 (gemm_bf16_pp384.hip; DINOX_NT_PP384 read per call: 0 = never, 1 = every product in its envelope,
     // unset = the measured policy).  tools/pp384_check.py, M = 102 912, interleaved with the 256 x 128 kernel on one box: dX K 1536
     // 139 -> 118 us, dX K 1152 95 -> 86 (M = 25 728: 46 -> 43, 37 -> 34); K = 384 a tie (43 vs 45); with the fp32 residual epilogue a tie
     // too (fc2 175 vs 175: its two rounds of tiles run in lockstep, so the 316 MB of residual traffic are not hidden behind K loops).
-    const char* e3 = getenv("DINOX_NT_PP384");
-    const int m3 = e3 ? atoi(e3) : -1;
+    const int m3 = knob_int("DINOX_NT_PP384", -1);
     if (m3 != 0 && mode != 2 && mode != 3 && gemm_bf16_nt_pp384_ok(p) &&
         (m3 > 0 || (p.out_dtype == DINOX_BF16 && !(p.epilogue & DINOX_EPI_RESIDUAL) && p.K >= 768 && p.M >= 8192)))
-      return "gemm_bf16_nt_pp384";
+      return V::NtPp384;
   }
-  if (mode == 2) return ok128 ? "gemm_bf16_nt_pp128" : nullptr;
-  if (mode == 3) return ok256 ? "gemm_bf16_nt_pp" : nullptr;
+  if (mode == 2) return ok128 ? V::NtPp128 : V::None;
+  if (mode == 3) return ok256 ? V::NtPp : V::None;
   // a narrow last column tile wastes matrix work on the 256-wide form: N = 384 is 1.5 tiles (and 804 tiles = 3.14 rounds on 256 CUs)
   const int64_t rem = p.N % 256;
   const bool narrow = p.N < 1024 && rem != 0 && rem <= 128;
-  const char* pick = narrow ? (ok128 ? "gemm_bf16_nt_pp128" : nullptr) : (ok256 ? "gemm_bf16_nt_pp" : nullptr);
-  if (mode >= 1 || !pick) return pick;
+  const V pick = narrow ? (ok128 ? V::NtPp128 : V::None) : (ok256 ? V::NtPp : V::None);
+  if (mode >= 1 || pick == V::None) return pick;
   // Measured policy (tools/pp_check.py, MI355X, old = gemm_bf16_nt_areg / _glds; M = 102 912 / 51 456 / 25 728 tokens):
   //   256-wide: qkv 140 -> 104-112 us, plain K 384 N 1536 164 -> 125-131, GELU' product 186 -> 172-176 (x0.9 at every M); ViT-L qkv 425 -> 291,
   //             fc1 651 -> 480, fc2 525 -> 452 us.  The GELU epilogue at K = 384 is bound by its ~50 VALU cycles per element either way
@@ -592,57 +574,56 @@ static const char* nt_pp_choice(const GemmParams& p) {
   // Small problems (less than one round of tiles) keep the 128 x 128 kernels, whose tiles are four times as many.
   const int64_t units = ceil_div(p.M, (int64_t)256) * ceil_div(p.N, (int64_t)(narrow ? 128 : 256));
   if (narrow) {
-    if (p.K >= 768) return units >= 192 ? pick : nullptr;
-    return (units >= 1024 && !(p.epilogue & DINOX_EPI_RESIDUAL)) ? pick : nullptr;
+    if (p.K >= 768) return units >= 192 ? pick : V::None;
+    return (units >= 1024 && !(p.epilogue & DINOX_EPI_RESIDUAL)) ? pick : V::None;
   }
   // (Until the last day of round 3 the GELU epilogue at K < 768 stayed on the register-prefetch kernel -- a tie in the micro-benchmark, where
   //  the token operand sits in the memory-side cache from the previous iteration.  In the step it does not: behind the LayerNorm-fused
   //  proj the 128 x 128 kernel takes 230 us; on the 256 x 256 tiles the step is 0.25 ms shorter.  DINOX_FC1_AREG=1 restores the old choice.)
   if ((p.epilogue & DINOX_EPI_GELU) && p.K < 768) {
-    const char* ea = getenv("DINOX_FC1_AREG");
-    if ((ea && atoi(ea) != 0) || units < 1024) return nullptr;   // (bs 64, 606 tiles: 12.46 ms per step on the 128 x 128 kernel, 12.50 here)
+    if (knob_int("DINOX_FC1_AREG", 0) != 0 || units < 1024) return V::None;   // (bs 64, 606 tiles: 12.46 ms per step on the 128 x 128 kernel, 12.50 here)
   }
-  return units >= 192 ? pick : nullptr;
+  return units >= 192 ? pick : V::None;
 }
 
-const char* gemm_bf16_variant(const GemmParams& p) {
-  if (p.in_dtype != DINOX_BF16) return nullptr;
-  if (!aligned16(p.A) || !aligned16(p.B) || (p.lda & 7) || (p.ldb & 7) || (p.strideA & 7) || (p.strideB & 7)) return nullptr;
-  if (const char* pp = nt_pp_choice(p)) return pp;
+GemmVariant gemm_bf16_variant(const GemmParams& p) {
+  using V = GemmVariant;
+  if (p.in_dtype != DINOX_BF16) return V::None;
+  if (!aligned16(p.A) || !aligned16(p.B) || (p.lda & 7) || (p.ldb & 7) || (p.strideA & 7) || (p.strideB & 7)) return V::None;
+  if (const V pp = nt_pp_choice(p); pp != V::None) return pp;
   if (gemm_bf16_nt_glds_ok(p)) {
     // Short reductions (K = 384: qkv, proj, fc1, GELU' products of ViT-S) take the form that prefetches the token operand through
     // registers (gemm_bf16_areg.hip): -7 .. -12 % per launch, where the first loads' latency is a large part of a 12-step tile.
     // Measured against this kernel at bs256: K = 768 equal, K = 1152 / 1536 +7 .. +10 % (the extra LDS writes cost more than the
     // deeper prefetch gains once the ring is in steady state), so longer reductions stay here.  DINOX_NT_AREG_MAXK moves the
     // boundary (0 switches the register form off, 1 << 30 sends every K % 192 == 0 product to it) for A/B runs and tests.
-    const char* e = getenv("DINOX_NT_AREG_MAXK");
-    const int64_t maxk = e ? atoll(e) : 576;
-    static const bool no_areg = getenv("DINOX_NT_NO_AREG") != nullptr;
-    return !no_areg && p.K <= maxk && gemm_bf16_nt_areg_ok(p) ? "gemm_bf16_nt_areg" : "gemm_bf16_nt_glds";
+    const int64_t maxk = knob_int("DINOX_NT_AREG_MAXK", 576);
+    static const bool no_areg = knob_set("DINOX_NT_NO_AREG");
+    return !no_areg && p.K <= maxk && gemm_bf16_nt_areg_ok(p) ? V::NtAreg : V::NtGlds;
   }
-  if (p.transA == 0 && p.transB == 0 && (p.K & 7) == 0) return "gemm_bf16_nt";
+  if (p.transA == 0 && p.transB == 0 && (p.K & 7) == 0) return V::Nt;
   if (p.transA == 1 && p.transB == 1 && (p.M & 7) == 0 && (p.N & 7) == 0) {
     if (p.ws) {                                     // with a workspace the long-K dW products run on big tiles (gemm_bf16_tnbig.hip)
       int a, b, c;
       int64_t d;
-      if (tn_big_plan(p, a, b, c, d)) return "gemm_bf16_tn_big";
+      if (tn_big_plan(p, a, b, c, d)) return V::TnBig;
     }
     const bool small = p.K * p.lda * 2 < (int64_t)0x7fffffff && p.K * p.ldb * 2 < (int64_t)0x7fffffff && p.M >= 8 && p.N >= 8;
-    return small ? "gemm_bf16_tn_dma" : "gemm_bf16_tn";
+    return small ? V::TnDma : V::Tn;
   }
-  return nullptr;
+  return V::None;
 }
 
 // The deterministic reduction needs one contiguous [M][N] fp32 result of one problem, written by the DMA form of the TN kernel.
-static bool tn_det_ok(const GemmParams& p, const char* variant, int splits) {
-  return variant && !strcmp(variant, "gemm_bf16_tn_dma") && splits > 1 && p.batch == 1 && p.ldc == p.N && p.out_dtype == DINOX_F32 &&
+static bool tn_det_ok(const GemmParams& p, GemmVariant variant, int splits) {
+  return variant == GemmVariant::TnDma && splits > 1 && p.batch == 1 && p.ldc == p.N && p.out_dtype == DINOX_F32 &&
          (p.epilogue & ~DINOX_EPI_ACCUM) == 0;
 }
 
 int64_t gemm_bf16_ws_bytes(const GemmParams& p) {
   if (const int64_t big = tn_big_ws_bytes(p)) return big;
-  const char* v = gemm_bf16_variant(p);
-  if (!v || strncmp(v, "gemm_bf16_tn", 12)) return 0;
+  const GemmVariant v = gemm_bf16_variant(p);
+  if (v != GemmVariant::TnBig && v != GemmVariant::TnDma && v != GemmVariant::Tn) return 0;
   int splits;
   int64_t kps;
   tn_split_plan(p, splits, kps);
@@ -652,22 +633,28 @@ int64_t gemm_bf16_ws_bytes(const GemmParams& p) {
 }
 
 int launch_gemm_bf16(const GemmParams& p, hipStream_t st) {
-  const char* v = gemm_bf16_variant(p);
-  if (!v) return DINOX_EUNSUPPORTED;
-  if (v[10] == 'n' && v[12] == '_') return v[13] == 'p' ? (v[15] == '1' ? launch_gemm_bf16_nt_pp128(p, st) : v[15] == '3' ? launch_gemm_bf16_nt_pp384(p, st) : launch_gemm_bf16_nt_pp(p, st)) : v[13] == 'a' ? launch_gemm_bf16_nt_areg(p, st) : launch_gemm_bf16_nt_glds(p, st);
+  using V = GemmVariant;
+  const V v = gemm_bf16_variant(p);
+  switch (v) {
+    case V::None: return DINOX_EUNSUPPORTED;
+    case V::NtPp: return launch_gemm_bf16_nt_pp(p, st);
+    case V::NtPp128: return launch_gemm_bf16_nt_pp128(p, st);
+    case V::NtPp384: return launch_gemm_bf16_nt_pp384(p, st);
+    case V::NtAreg: return launch_gemm_bf16_nt_areg(p, st);
+    case V::NtGlds: return launch_gemm_bf16_nt_glds(p, st);
+    case V::Nt: case V::TnBig: case V::TnDma: case V::Tn: break;      // the kernels of this file, below
+  }
   const int tiles_m = (int)ceil_div(p.M, GB_BM), tiles_n = (int)ceil_div(p.N, GB_BN);
   const int64_t ntile = (int64_t)tiles_m * tiles_n;
   if (ntile > 0x7fffffff || p.batch > 65535) return DINOX_EUNSUPPORTED;
   const size_t lds = 4 * GB_TILE_BYTES;
-  if (v[10] == 'n') {  // "gemm_bf16_nt"
+  const bool f32 = p.out_dtype == DINOX_F32;
+  if (v == V::Nt) {
     dim3 grid((unsigned)ntile, (unsigned)p.batch);
-    if (p.out_dtype == DINOX_F32)
-      hipLaunchKernelGGL((gemm_bf16_nt<DINOX_F32>), grid, dim3(GB_THREADS), lds, st, p, tiles_m, tiles_n);
-    else
-      hipLaunchKernelGGL((gemm_bf16_nt<DINOX_BF16>), grid, dim3(GB_THREADS), lds, st, p, tiles_m, tiles_n);
+    hipLaunchKernelGGL((f32 ? gemm_bf16_nt<DINOX_F32> : gemm_bf16_nt<DINOX_BF16>), grid, dim3(GB_THREADS), lds, st, p, tiles_m, tiles_n);
     return check_launch("gemm_bf16_nt");
   }
-  if (!strcmp(v, "gemm_bf16_tn_big")) {
+  if (v == V::TnBig) {
     int sp = 1, tn_ = 1;
     if (int rc = launch_gemm_bf16_tn_big(p, st, sp, tn_)) return rc;
     return launch_tn_reduce(p, sp, tn_, st);
@@ -677,7 +664,6 @@ int launch_gemm_bf16(const GemmParams& p, hipStream_t st) {
   int splits;
   int64_t kps;
   tn_split_plan(p, splits, kps);
-  if (p.batch > 65535) return DINOX_EUNSUPPORTED;
   GemmParams q = p;
   const bool det = q.ws != nullptr && tn_det_ok(p, v, splits);
   if (!det) q.ws = nullptr;
@@ -697,19 +683,9 @@ int launch_gemm_bf16(const GemmParams& p, hipStream_t st) {
   }
   if (ntile * splits > 0x7fffffff) return DINOX_EUNSUPPORTED;
   dim3 grid((unsigned)(ntile * splits), (unsigned)p.batch);
-  const char* what = "gemm_bf16_tn";
-  if (v[12] == '_') {  // "gemm_bf16_tn_dma"
-    what = "gemm_bf16_tn_dma";
-    if (p.out_dtype == DINOX_F32)
-      hipLaunchKernelGGL((gemm_bf16_tn_dma<DINOX_F32>), grid, dim3(GB_THREADS), lds, st, q, tiles_m, tiles_n, splits, kps);
-    else
-      hipLaunchKernelGGL((gemm_bf16_tn_dma<DINOX_BF16>), grid, dim3(GB_THREADS), lds, st, q, tiles_m, tiles_n, splits, kps);
-  } else if (p.out_dtype == DINOX_F32) {
-    hipLaunchKernelGGL((gemm_bf16_tn<DINOX_F32>), grid, dim3(GB_THREADS), lds, st, q, tiles_m, tiles_n, splits, kps);
-  } else {
-    hipLaunchKernelGGL((gemm_bf16_tn<DINOX_BF16>), grid, dim3(GB_THREADS), lds, st, q, tiles_m, tiles_n, splits, kps);
-  }
-  if (int rc = check_launch(what)) return rc;
+  const auto kern = v == V::TnDma ? (f32 ? gemm_bf16_tn_dma<DINOX_F32> : gemm_bf16_tn_dma<DINOX_BF16>) : (f32 ? gemm_bf16_tn<DINOX_F32> : gemm_bf16_tn<DINOX_BF16>);
+  hipLaunchKernelGGL(kern, grid, dim3(GB_THREADS), lds, st, q, tiles_m, tiles_n, splits, kps);
+  if (int rc = check_launch(gemm_variant_name(v))) return rc;
   if (det) return launch_tn_reduce(p, splits, tiles_n, st);
   return 0;
 }

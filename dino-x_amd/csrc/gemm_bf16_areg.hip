@@ -34,7 +34,7 @@
 //     5 % SLOWER: gfx950 has one in-order counter for loads and stores, so a tile's first counted wait also waits for the previous
 //     tile's stores to be acknowledged.
 #include "common.h"
-#include "gemm_common.h"
+#include "kernels.h"
 #include <type_traits>
 
 namespace dinox {
@@ -61,7 +61,7 @@ constexpr int AR_SETS = 6;                                             // regist
 constexpr int AR_ATILE = AR_BM * AR_BK * 2, AR_BTILE = AR_BN * AR_BK * 2, AR_SLOT = AR_ATILE + AR_BTILE;
 constexpr int AR_KBLOCK = 6 * AR_BK * 2;                               // bytes of K one block of six steps advances a row by
 
-enum { AR_PLAIN = 0, AR_GELU = 1, AR_DGELU = 2 };
+enum { AR_PLAIN = EPI_ACT_PLAIN, AR_GELU = EPI_ACT_GELU, AR_DGELU = EPI_ACT_DGELU };
 
 __device__ __forceinline__ int ar_xcd_remap(int bid, int nwg) {
   const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
@@ -409,7 +409,7 @@ static void ar_launch(const GemmParams& p, unsigned ntile, int tiles_n, size_t l
   // ordinary stores for A/B runs.
   // Only for bf16 outputs: the fp32 outputs are the residual stream, which the following LayerNorm reads straight back (neutral on
   // proj here, +9 % on the K = 1536 fc2 product when tried in gemm_bf16_nt_glds, whose bf16 products gain 1-2 %: not adopted there).
-  static const int knob = getenv("DINOX_NT_STORES") ? atoi(getenv("DINOX_NT_STORES")) : -1;      // read once per process
+  const int knob = knob_int("DINOX_NT_STORES", -1);             // (read per call: test_gemm_nt_store_policy_is_only_a_hint flips it)
   int nt = knob >= 0 ? knob : (OUT_DT == DINOX_BF16 ? 1 : 0);
   // (A/B values: 2 = only outputs of 10 or more column tiles, 3 = only narrower ones.  Whole step on one box: off 44.40 ms, 3: 44.05,
   //  2: 43.34, all bf16 outputs: 43.45.  LayerNorm outputs are the opposite case: stored non-temporally the step LOSES 1.1 ms, the
@@ -426,19 +426,11 @@ int launch_gemm_bf16_nt_areg(const GemmParams& p, hipStream_t st) {
   if (ntile64 > 0x7fffffff) return DINOX_EUNSUPPORTED;
   const unsigned ntile = (unsigned)ntile64;
   const size_t lds = 3 * (size_t)AR_SLOT + 4 * 256;
-  const int act = (p.epilogue & DINOX_EPI_GELU) ? AR_GELU : (p.epilogue & DINOX_EPI_DGELU) ? AR_DGELU : AR_PLAIN;
-  const bool res = (p.epilogue & DINOX_EPI_RESIDUAL) != 0;
-#define AR_L(OUT)                                                                                                         \
-  switch (act * 2 + (res ? 1 : 0)) {                                                                                      \
-    case 0: ar_launch<OUT, AR_PLAIN, false>(p, ntile, tiles_n, lds, st); break;                                           \
-    case 1: ar_launch<OUT, AR_PLAIN, true>(p, ntile, tiles_n, lds, st); break;                                            \
-    case 2: ar_launch<OUT, AR_GELU, false>(p, ntile, tiles_n, lds, st); break;                                            \
-    case 4: ar_launch<OUT, AR_DGELU, false>(p, ntile, tiles_n, lds, st); break;                                           \
-    default: return DINOX_EUNSUPPORTED;                                                                                   \
-  }
-  if (p.out_dtype == DINOX_BF16) { AR_L(DINOX_BF16) } else { AR_L(DINOX_F32) }
-#undef AR_L
-  return check_launch("gemm_bf16_nt_areg");
+  const int rc = with_epilogue_case(p, [&](auto out, auto act, auto res) {
+    ar_launch<decltype(out)::value, decltype(act)::value, decltype(res)::value>(p, ntile, tiles_n, lds, st);
+    return 0;
+  });
+  return rc ? rc : check_launch("gemm_bf16_nt_areg");
 }
 
 }  // namespace dinox

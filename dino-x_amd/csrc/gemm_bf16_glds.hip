@@ -16,10 +16,9 @@
 //   * epilogue variants are compile-time (no flag tests in the inner code) and GELU uses a 1.5e-7-accurate
 //     rational erf instead of erff.
 // Envelope: K % 64 == 0, N % 8 == 0, 16-B aligned operands/outputs; anything else takes gemm_bf16_nt.
-#include <cstdlib>
 
 #include "common.h"
-#include "gemm_common.h"
+#include "kernels.h"
 
 namespace dinox {
 
@@ -347,8 +346,7 @@ bool gemm_bf16_nt_glds_ok(const GemmParams& p) {
 }
 
 int launch_gemm_bf16_nt_glds(const GemmParams& p, hipStream_t st) {
-  static const int knob = getenv("DINOX_NT_BK") ? atoi(getenv("DINOX_NT_BK")) : 0;   // tuning knobs (A/B testing)
-  static const int knob_bm = getenv("DINOX_NT_BM") ? atoi(getenv("DINOX_NT_BM")) : 0;
+  static const int knob = knob_int("DINOX_NT_BK", 0), knob_bm = knob_int("DINOX_NT_BM", 0);   // tuning knobs (A/B testing), read once
   // measured (tools/gemm_bench.py): K <= 512 runs faster on the 3-stage BK=32 ring, longer K on the 2-stage BK=64 form
   // ... unless the tile count fills the 512 resident slots of the BK = 64 form so badly (bs 64: fc2 / dX are 603 tiles = 1.18 rounds) that the 768 slots
   // of the BK = 32 form win although it is ~10 % slower per tile (measured at bs 256: fc2 233 vs 210 us, dX 195 vs 175 us)
@@ -371,33 +369,22 @@ int launch_gemm_bf16_nt_glds(const GemmParams& p, hipStream_t st) {
   const size_t lds = (size_t)stages * (bm + GG_BN) * bk * 2;
   const int act = (p.epilogue & DINOX_EPI_GELU) ? GG_GELU : (p.epilogue & DINOX_EPI_DGELU) ? GG_DGELU : GG_PLAIN;
   const bool res = (p.epilogue & DINOX_EPI_RESIDUAL) != 0;
-#define GG_L(OUT, ACT, RES, BK, ST, BM)                                                                                  \
-  do {                                                                                                                    \
-    auto kern = gemm_bf16_nt_glds<OUT, ACT, RES, BK, ST, BM>;                                                             \
-    if (int rc = reserve_lds(reinterpret_cast<const void*>(kern), lds, "gemm_bf16_nt_glds")) return rc;                  \
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, p, tiles_m, tiles_n);                                           \
-  } while (0)
-#define GG(OUT, ACT, RES)                                                       \
-  do {                                                                          \
-    if (bm == 256) {                                                            \
-      if (bk == 32) GG_L(OUT, ACT, RES, 32, 3, 256); else GG_L(OUT, ACT, RES, 64, 2, 256); \
-    } else {                                                                    \
-      if (bk == 32) GG_L(OUT, ACT, RES, 32, 3, 128); else GG_L(OUT, ACT, RES, 64, 2, 128); \
-    }                                                                           \
-  } while (0)
-#define GG_ACT(OUT, RES)                                                                  \
-  do {                                                                                    \
-    if (act == GG_GELU) GG(OUT, GG_GELU, RES); else if (act == GG_DGELU) GG(OUT, GG_DGELU, RES); else GG(OUT, GG_PLAIN, RES); \
-  } while (0)
-  if (p.out_dtype == DINOX_BF16) {
-    if (res) GG_ACT(DINOX_BF16, true); else GG_ACT(DINOX_BF16, false);
-  } else {
-    if (res) GG_ACT(DINOX_F32, true); else GG_ACT(DINOX_F32, false);
-  }
+  auto launch = [&](auto kern) -> int {
+    if (int rc = reserve_lds(reinterpret_cast<const void*>(kern), lds, "gemm_bf16_nt_glds")) return rc;
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, p, tiles_m, tiles_n);
+    return check_launch("gemm_bf16_nt_glds");
+  };
+#define GG_K(OUT, ACT, RES, BK, ST, BM) launch(gemm_bf16_nt_glds<OUT, ACT, RES, BK, ST, BM>)
+#define GG(OUT, ACT, RES)                                                                               \
+  (bm == 256 ? (bk == 32 ? GG_K(OUT, ACT, RES, 32, 3, 256) : GG_K(OUT, ACT, RES, 64, 2, 256))           \
+             : (bk == 32 ? GG_K(OUT, ACT, RES, 32, 3, 128) : GG_K(OUT, ACT, RES, 64, 2, 128)))
+#define GG_ACT(OUT, RES) (act == GG_GELU ? GG(OUT, GG_GELU, RES) : act == GG_DGELU ? GG(OUT, GG_DGELU, RES) : GG(OUT, GG_PLAIN, RES))
+  const int rc = p.out_dtype == DINOX_BF16 ? (res ? GG_ACT(DINOX_BF16, true) : GG_ACT(DINOX_BF16, false))
+                                           : (res ? GG_ACT(DINOX_F32, true) : GG_ACT(DINOX_F32, false));
 #undef GG_ACT
 #undef GG
-#undef GG_L
-  return check_launch("gemm_bf16_nt_glds");
+#undef GG_K
+  return rc;
 }
 
 }  // namespace dinox

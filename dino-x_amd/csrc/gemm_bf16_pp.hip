@@ -23,7 +23,6 @@
 //     its derivative side tensor, x GELU', fp32 residual as in the other NT kernels; bf16 outputs leave by non-temporal stores.
 // Envelope: K % 64 == 0, K >= 128, N % 8 == 0, no batch, 16-byte aligned operands, leading dimensions < 2^21 (32-bit byte offsets
 // inside a tile).  Replaces nn.Linear forward / dX products (reference zoo/arch.py:46,53,75-76).
-#include <cstdlib>
 
 #include "common.h"
 #include "gemm_common.h"
@@ -289,44 +288,19 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp(GemmParams p, int tile
 bool gemm_bf16_nt_pp_ok(const GemmParams& p) { return pp_envelope_ok(p, PP_BK); }
 
 int launch_gemm_bf16_nt_pp(const GemmParams& p, hipStream_t st) {
-  const int64_t tiles_m = ceil_div(p.M, (int64_t)PP_BM), tiles_n = ceil_div(p.N, (int64_t)PP_BN);
-  const int64_t units = tiles_m * tiles_n;
-  if (units > 0x3fffffff) return DINOX_EUNSUPPORTED;
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return fail(DINOX_EINVAL, "gemm_bf16_nt_pp: no device");
-    ncu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  const char* eo = getenv("DINOX_PP_ORDER");
-  const int order = eo ? atoi(eo) : 1;
   // start delay of the workgroups that own one tile less than the busiest ones (up to about one tile period, cycles): pays where the
   // epilogue is long (GELU' product 184 -> 172 us, fc2 180 -> 176), costs where it is short (qkv 104 vs 112 us): off for plain / bias
-  const char* es = getenv("DINOX_PP_STAGGER");
   const bool heavy = (p.epilogue & (DINOX_EPI_GELU | DINOX_EPI_DGELU | DINOX_EPI_RESIDUAL)) != 0;
-  const int stagger = es ? atoi(es) : heavy ? (int)(p.K / PP_BK) * 2600 + ((p.epilogue & (DINOX_EPI_GELU | DINOX_EPI_DGELU)) ? 12000 : 4000) : 0;
-  const unsigned grid = (unsigned)(units < ncu ? units : ncu);
-  const int act = (p.epilogue & DINOX_EPI_GELU) ? PP_GELU : (p.epilogue & DINOX_EPI_DGELU) ? PP_DGELU : PP_PLAIN;
-  const bool res = (p.epilogue & DINOX_EPI_RESIDUAL) != 0;
-#define PP_L(OUT, ACT, RES)                                                                                               \
-  do {                                                                                                                    \
-    auto kern = gemm_bf16_nt_pp<OUT, ACT, RES>;                                                                           \
-    if (int rc = reserve_lds(reinterpret_cast<const void*>(kern), PP_LDS, "gemm_bf16_nt_pp")) return rc;                  \
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), PP_LDS, st, p, (int)tiles_n, (int)units, order, stagger);                    \
-  } while (0)
-#define PP_A(OUT)                                                                                                         \
-  switch (act * 2 + (res ? 1 : 0)) {                                                                                      \
-    case 0: PP_L(OUT, PP_PLAIN, false); break;                                                                            \
-    case 1: PP_L(OUT, PP_PLAIN, true); break;                                                                             \
-    case 2: PP_L(OUT, PP_GELU, false); break;                                                                             \
-    case 4: PP_L(OUT, PP_DGELU, false); break;                                                                            \
-    default: return DINOX_EUNSUPPORTED;                                                                                   \
-  }
-  if (p.out_dtype == DINOX_BF16) { PP_A(DINOX_BF16) } else { PP_A(DINOX_F32) }
-#undef PP_A
-#undef PP_L
-  return check_launch("gemm_bf16_nt_pp");
+  const int stagger = heavy ? (int)(p.K / PP_BK) * 2600 + ((p.epilogue & (DINOX_EPI_GELU | DINOX_EPI_DGELU)) ? 12000 : 4000) : 0;
+  PersistPlan pl;
+  if (!persist_plan(p, PP_BM, PP_BN, stagger, pl)) return DINOX_EUNSUPPORTED;
+  const int rc = with_epilogue_case(p, [&](auto out, auto act, auto res) {
+    auto kern = gemm_bf16_nt_pp<decltype(out)::value, decltype(act)::value, decltype(res)::value>;
+    if (int rc = reserve_lds(reinterpret_cast<const void*>(kern), PP_LDS, "gemm_bf16_nt_pp")) return rc;
+    hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(512), PP_LDS, st, p, pl.tiles_n, pl.units, pl.order, pl.stagger);
+    return 0;
+  });
+  return rc ? rc : check_launch("gemm_bf16_nt_pp");
 }
 
 }  // namespace dinox

@@ -17,7 +17,6 @@
 //   * epilogue staging in the K-tile buffer the tile's last K-tile has just freed (nothing is requested into it before the next tile's
 //     first L slot, and a workgroup barrier separates the two), 4 KiB per wave, then the shared fused epilogue (gemm_pp_common.h).
 // Envelope as gemm_bf16_pp.hip.  Replaces nn.Linear forward / dX products (reference zoo/arch.py:53,76 and their backward).
-#include <cstdlib>
 
 #include "common.h"
 #include "gemm_common.h"
@@ -251,44 +250,17 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp128(GemmParams p, int t
 bool gemm_bf16_nt_pp128_ok(const GemmParams& p) { return pp_envelope_ok(p, PQ_BK) && p.K >= 3 * PQ_BK; }
 
 int launch_gemm_bf16_nt_pp128(const GemmParams& p, hipStream_t st) {
-  const int64_t tiles_m = ceil_div(p.M, (int64_t)PQ_BM), tiles_n = ceil_div(p.N, (int64_t)PQ_BN);
-  const int64_t units = tiles_m * tiles_n;
-  if (units > 0x3fffffff) return DINOX_EUNSUPPORTED;
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return fail(DINOX_EINVAL, "gemm_bf16_nt_pp128: no device");
-    ncu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  const char* eo = getenv("DINOX_PP_ORDER");
-  const int order = eo ? atoi(eo) : 1;
-  // start delay of the workgroups that own one tile less than the busiest ones (up to about one tile period, cycles): pays where the
-  // epilogue is long (GELU' product 184 -> 172 us, fc2 180 -> 176), costs where it is short (qkv 104 vs 112 us): off for plain / bias
-  const char* es = getenv("DINOX_PP_STAGGER");
+  // start stagger as in gemm_bf16_pp.hip (heavy epilogues only), scaled to this tile's period
   const bool heavy = (p.epilogue & (DINOX_EPI_GELU | DINOX_EPI_DGELU | DINOX_EPI_RESIDUAL)) != 0;
-  const int stagger = es ? atoi(es) : heavy ? (int)(p.K / PQ_BK) * 1300 + 3000 : 0;
-  const unsigned grid = (unsigned)(units < ncu ? units : ncu);
-  const int act = (p.epilogue & DINOX_EPI_GELU) ? PP_GELU : (p.epilogue & DINOX_EPI_DGELU) ? PP_DGELU : PP_PLAIN;
-  const bool res = (p.epilogue & DINOX_EPI_RESIDUAL) != 0;
-#define PQ_L(OUT, ACT, RES)                                                                                               \
-  do {                                                                                                                    \
-    auto kern = gemm_bf16_nt_pp128<OUT, ACT, RES>;                                                                        \
-    if (int rc = reserve_lds(reinterpret_cast<const void*>(kern), PQ_LDS, "gemm_bf16_nt_pp128")) return rc;               \
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), PQ_LDS, st, p, (int)tiles_n, (int)units, order, stagger);             \
-  } while (0)
-#define PQ_A(OUT)                                                                                                         \
-  switch (act * 2 + (res ? 1 : 0)) {                                                                                      \
-    case 0: PQ_L(OUT, PP_PLAIN, false); break;                                                                            \
-    case 1: PQ_L(OUT, PP_PLAIN, true); break;                                                                             \
-    case 2: PQ_L(OUT, PP_GELU, false); break;                                                                             \
-    case 4: PQ_L(OUT, PP_DGELU, false); break;                                                                            \
-    default: return DINOX_EUNSUPPORTED;                                                                                   \
-  }
-  if (p.out_dtype == DINOX_BF16) { PQ_A(DINOX_BF16) } else { PQ_A(DINOX_F32) }
-#undef PQ_A
-#undef PQ_L
-  return check_launch("gemm_bf16_nt_pp128");
+  PersistPlan pl;
+  if (!persist_plan(p, PQ_BM, PQ_BN, heavy ? (int)(p.K / PQ_BK) * 1300 + 3000 : 0, pl)) return DINOX_EUNSUPPORTED;
+  const int rc = with_epilogue_case(p, [&](auto out, auto act, auto res) {
+    auto kern = gemm_bf16_nt_pp128<decltype(out)::value, decltype(act)::value, decltype(res)::value>;
+    if (int rc = reserve_lds(reinterpret_cast<const void*>(kern), PQ_LDS, "gemm_bf16_nt_pp128")) return rc;
+    hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(512), PQ_LDS, st, p, pl.tiles_n, pl.units, pl.order, pl.stagger);
+    return 0;
+  });
+  return rc ? rc : check_launch("gemm_bf16_nt_pp128");
 }
 
 }  // namespace dinox

@@ -25,7 +25,6 @@
 // takes three slabs of 80 / 64 / 64 rows through the same LDS, the residual pieces requested four at a time ahead of their use.
 // Envelope: N == 384, K % 32 == 0, K >= 128; plain / bias epilogues with bf16 or fp32 out, fp32 residual with fp32 out.
 // Replaces nn.Linear's input-gradient products and fc2 (reference zoo/arch.py:76 and the backward of :46,53,75,76).
-#include <cstdlib>
 #include <type_traits>
 
 #include "common.h"
@@ -448,20 +447,21 @@ bool gemm_bf16_nt_pp384_ok(const GemmParams& p) {
   return (p.M + PR_BM) * p.lda * 2 < ((int64_t)1 << 31) && (int64_t)PR_BN * p.ldb * 2 < ((int64_t)1 << 31);      // buffer descriptors, 32-bit offsets
 }
 
-int launch_gemm_bf16_nt_pp384(const GemmParams& p, hipStream_t st) {
+// One tile per workgroup: the grid is the row-tile count for all three forms of the kernel.
+template <typename Kern>
+static int pr_launch(Kern kern, const GemmParams& p, const PpLnExtra& ln, const char* what, hipStream_t st) {
   const int64_t units = ceil_div(p.M, (int64_t)PR_BM);
   if (units > 0x3fffffff) return DINOX_EUNSUPPORTED;
-#define PR_L(OUT, RES)                                                                                                    \
-  do {                                                                                                                    \
-    auto kern = gemm_bf16_nt_pp384<OUT, RES, false>;                                                                      \
-    if (int rc = reserve_lds(reinterpret_cast<const void*>(kern), PR_LDS, "gemm_bf16_nt_pp384")) return rc;               \
-    hipLaunchKernelGGL(kern, dim3((unsigned)units), dim3(512), PR_LDS, st, p, PpLnExtra{});                               \
-  } while (0)
-  if (p.out_dtype == DINOX_BF16) PR_L(DINOX_BF16, false);
-  else if (p.epilogue & DINOX_EPI_RESIDUAL) PR_L(DINOX_F32, true);
-  else PR_L(DINOX_F32, false);
-#undef PR_L
-  return check_launch("gemm_bf16_nt_pp384");
+  if (int rc = reserve_lds(reinterpret_cast<const void*>(kern), PR_LDS, "gemm_bf16_nt_pp384")) return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)units), dim3(512), PR_LDS, st, p, ln);
+  return check_launch(what);
+}
+
+int launch_gemm_bf16_nt_pp384(const GemmParams& p, hipStream_t st) {
+  const char* what = "gemm_bf16_nt_pp384";
+  if (p.out_dtype == DINOX_BF16) return pr_launch(gemm_bf16_nt_pp384<DINOX_BF16, false, false>, p, PpLnExtra{}, what, st);
+  if (p.epilogue & DINOX_EPI_RESIDUAL) return pr_launch(gemm_bf16_nt_pp384<DINOX_F32, true, false>, p, PpLnExtra{}, what, st);
+  return pr_launch(gemm_bf16_nt_pp384<DINOX_F32, false, false>, p, PpLnExtra{}, what, st);
 }
 
 // The product + LayerNorm form (called by dinox_linear_residual_ln, gemm_bf16_rowln.hip): y bf16, N = 384, the envelope above.
@@ -481,12 +481,7 @@ int launch_gemm_bf16_nt_pp384_ln(const void* a, const void* w, const float* bias
   p.alpha = 1.0f;
   p.bias = bias; p.residual = residual; p.ldr = PR_BN;
   const PpLnExtra ln{gamma, beta, y, mean, rstd, eps};
-  const int64_t units = ceil_div(M, (int64_t)PR_BM);
-  if (units > 0x3fffffff) return DINOX_EUNSUPPORTED;
-  auto kern = gemm_bf16_nt_pp384<DINOX_F32, true, true>;
-  if (int rc = reserve_lds(reinterpret_cast<const void*>(kern), PR_LDS, "gemm_bf16_nt_pp384")) return rc;
-  hipLaunchKernelGGL(kern, dim3((unsigned)units), dim3(512), PR_LDS, st, p, ln);
-  return check_launch("gemm_bf16_nt_pp384(ln)");
+  return pr_launch(gemm_bf16_nt_pp384<DINOX_F32, true, true>, p, ln, "gemm_bf16_nt_pp384(ln)", st);
 }
 
 // The product + LayerNorm-backward form (called by dinox_linear_ln_bwd, layernorm.hip).  ws: tiles x 2 x 384 floats.
@@ -504,12 +499,7 @@ int launch_gemm_bf16_nt_pp384_lnbwd(const void* a, const void* w, const float* x
   p.residual = dx_add; p.ldr = PR_BN;
   p.aux = ws;
   const PpLnExtra ln{gamma, x, dx_lowp, const_cast<float*>(mean), const_cast<float*>(rstd), 0.f};
-  const int64_t units = ceil_div(M, (int64_t)PR_BM);
-  if (units > 0x3fffffff) return DINOX_EUNSUPPORTED;
-  auto kern = gemm_bf16_nt_pp384<DINOX_BF16, false, false, true>;
-  if (int rc = reserve_lds(reinterpret_cast<const void*>(kern), PR_LDS, "gemm_bf16_nt_pp384")) return rc;
-  hipLaunchKernelGGL(kern, dim3((unsigned)units), dim3(512), PR_LDS, st, p, ln);
-  return check_launch("gemm_bf16_nt_pp384(ln_bwd)");
+  return pr_launch(gemm_bf16_nt_pp384<DINOX_BF16, false, false, true>, p, ln, "gemm_bf16_nt_pp384(ln_bwd)", st);
 }
 
 }  // namespace dinox

@@ -21,7 +21,7 @@
 #include <type_traits>
 
 #include "common.h"
-#include "gemm_common.h"
+#include "kernels.h"
 
 namespace dinox {
 
@@ -427,14 +427,13 @@ int tn_big_plan(const GemmParams& p, int& tiles_m, int& tiles_n, int& splits, in
   if ((((uintptr_t)p.A) | ((uintptr_t)p.B)) & 15) return 0;
   if (p.K * p.lda * 2 >= (int64_t)0x7fffffff || p.K * p.ldb * 2 >= (int64_t)0x7fffffff) return 0;
   if (p.K < 8192) return 0;
-  static const bool off = getenv("DINOX_TN_BIG_OFF") != nullptr;
+  static const bool off = knob_set("DINOX_TN_BIG_OFF");
   if (off) return 0;
   // Three tile shapes (1: 256 x 192, 2: 384 x 128, 3: 256 x 256); every workgroup of the ONE resident round does kps k-rows of a whole
   // tile (padding included), so the product's time goes with  kps x TM x TN  of the shape's own split plan -- ViT-L's 4096 x 1024
   // dW1 is 96 tiles of 256 x 192 (two splits: 192 of 256 CUs busy, 11 % of the tile area padding) but 64 tiles of 256 x 256 (four
   // splits, every CU, no padding).  Ties go to the shape that stages fewer bytes per k-row (TM + TN).  DINOX_TN_FORM=1|2|3 forces one (A/B).
-  const char* fenv = getenv("DINOX_TN_FORM");                 // (read per call: tools flip it between launches)
-  const int forced = fenv ? atoi(fenv) : 0;
+  const int forced = knob_int("DINOX_TN_FORM", 0);            // (read per call: tools flip it between launches)
   static const int TMs[4] = {0, 256, 384, 256}, TNs[4] = {0, 192, 128, 256};
   int form = 0;
   int64_t best = 0;
@@ -474,38 +473,18 @@ int launch_gemm_bf16_tn_big(const GemmParams& p, hipStream_t st, int& splits_out
   splits_out = splits;
   tiles_n_out = tiles_n;
   const unsigned grid = (unsigned)(tiles_m * tiles_n * splits);
-  const char* epp = getenv("DINOX_TN_PP");                    // (read per call: tools flip it between launches)  0 = every wave in step
-  const int mode = epp ? atoi(epp) : 2;
-  if (mode != 0) {
-    const size_t lds = (size_t)(TB_STAGES + 1) * (form == 1 ? 7 : 8) * TB_SUB;     // five stages: 140 / 160 KiB
-#define TB_L(IM_, JN_, MODE_)                                                                                            \
-  do {                                                                                                                   \
-    auto kern = gemm_bf16_tn_big<IM_, JN_, MODE_>;                                                                       \
-    if (int rc = reserve_lds(reinterpret_cast<const void*>(kern), lds, "gemm_bf16_tn_big")) return rc;                   \
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, p, tiles_m, tiles_n, splits, kps);                          \
-  } while (0)
-    if (mode == 1) {
-      if (form == 1) TB_L(2, 3, 1); else if (form == 2) TB_L(3, 2, 1); else TB_L(2, 4, 1);
-    } else {
-      if (form == 1) TB_L(2, 3, 2); else if (form == 2) TB_L(3, 2, 2); else TB_L(2, 4, 2);
-    }
-#undef TB_L
+  const int knob = knob_int("DINOX_TN_PP", 2);                // (read per call: tools flip it between launches)
+  const int mode = knob == 0 ? 0 : knob == 1 ? 1 : 2;         // 0 = every wave in step, 1 / 2 = two wave groups in anti-phase
+  // a stage is 7 sub-tiles (256 x 192) or 8; four stages in step (112 / 128 KiB), five in anti-phase (140 / 160 KiB)
+  const size_t lds = (size_t)(TB_STAGES + (mode ? 1 : 0)) * (form == 1 ? 7 : 8) * TB_SUB;
+  auto launch = [&](auto kern) -> int {
+    if (int rc = reserve_lds(reinterpret_cast<const void*>(kern), lds, "gemm_bf16_tn_big")) return rc;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, p, tiles_m, tiles_n, splits, kps);
     return check_launch("gemm_bf16_tn_big");
-  }
-  if (form == 1) {
-    constexpr size_t lds = (size_t)TB_STAGES * 7 * TB_SUB;
-    if (int rc = reserve_lds(reinterpret_cast<const void*>(gemm_bf16_tn_big<2, 3, 0>), lds, "gemm_bf16_tn_big")) return rc;
-    hipLaunchKernelGGL((gemm_bf16_tn_big<2, 3, 0>), dim3(grid), dim3(512), lds, st, p, tiles_m, tiles_n, splits, kps);
-  } else if (form == 2) {
-    constexpr size_t lds = (size_t)TB_STAGES * 8 * TB_SUB;
-    if (int rc = reserve_lds(reinterpret_cast<const void*>(gemm_bf16_tn_big<3, 2, 0>), lds, "gemm_bf16_tn_big")) return rc;
-    hipLaunchKernelGGL((gemm_bf16_tn_big<3, 2, 0>), dim3(grid), dim3(512), lds, st, p, tiles_m, tiles_n, splits, kps);
-  } else {
-    constexpr size_t lds = (size_t)TB_STAGES * 8 * TB_SUB;
-    if (int rc = reserve_lds(reinterpret_cast<const void*>(gemm_bf16_tn_big<2, 4, 0>), lds, "gemm_bf16_tn_big")) return rc;
-    hipLaunchKernelGGL((gemm_bf16_tn_big<2, 4, 0>), dim3(grid), dim3(512), lds, st, p, tiles_m, tiles_n, splits, kps);
-  }
-  return check_launch("gemm_bf16_tn_big");
+  };
+#define TB_FORMS(MODE_) (form == 1 ? launch(gemm_bf16_tn_big<2, 3, MODE_>) : form == 2 ? launch(gemm_bf16_tn_big<3, 2, MODE_>) : launch(gemm_bf16_tn_big<2, 4, MODE_>))
+  return mode == 0 ? TB_FORMS(0) : mode == 1 ? TB_FORMS(1) : TB_FORMS(2);
+#undef TB_FORMS
 }
 
 }  // namespace dinox

@@ -1,4 +1,4 @@
-// gemm_common.h -- kernel-side view of dinox_gemm_args and the shared scalar epilogue.
+// gemm_common.h -- kernel-side view of dinox_gemm_args and the shared scalar epilogue (host-side prototypes: kernels.h).
 #pragma once
 #include "common.h"
 
@@ -41,10 +41,5 @@ __device__ __forceinline__ void epilogue_store(const GemmParams& p, int64_t bz, 
   if (p.epilogue & DINOX_EPI_ACCUM) v += ((const float*)p.C)[ci];
   elem<OUT_DT>::st(p.C, ci, v);
 }
-
-int launch_gemm_f32(const GemmParams& p, hipStream_t st);
-const char* gemm_bf16_variant(const GemmParams& p);  // kernel the bf16 dispatcher would use, or nullptr
-int launch_gemm_bf16(const GemmParams& p, hipStream_t st);  // returns DINOX_EUNSUPPORTED when it cannot take the shape
-int64_t gemm_bf16_ws_bytes(const GemmParams& p);            // workspace of the deterministic split-K reduction (0: none)
 
 }  // namespace dinox

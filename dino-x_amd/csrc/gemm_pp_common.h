@@ -2,7 +2,7 @@
 // the fused epilogue of one wave's accumulator block and the workgroup -> tile assignment.
 #pragma once
 #include "common.h"
-#include "gemm_common.h"
+#include "kernels.h"
 
 namespace dinox {
 
@@ -13,7 +13,7 @@ typedef float pp_f32x4 __attribute__((ext_vector_type(4)));
 typedef float pp_f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 pp_bf16x2 __attribute__((ext_vector_type(2)));
 
-enum { PP_PLAIN = 0, PP_GELU = 1, PP_DGELU = 2 };
+enum { PP_PLAIN = EPI_ACT_PLAIN, PP_GELU = EPI_ACT_GELU, PP_DGELU = EPI_ACT_DGELU };
 
 // two floats -> one dword of two bf16 (ONE v_cvt_pk_bf16_f32; the scalar casts cost a convert each plus a v_or_b32_sdwa)
 __device__ __forceinline__ unsigned pp_pack2(float a, float b) {

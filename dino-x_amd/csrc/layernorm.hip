@@ -4,6 +4,7 @@
 // forward path.  Algorithmic bytes per row: fwd 4D read + (4|2)D write; bwd (4|2)D + 4D read, 4D
 // (+4D when accumulating, +2D for the bf16 copy) written.
 #include "common.h"
+#include "kernels.h"
 
 namespace dinox {
 
@@ -426,11 +427,10 @@ static int ln_parts(int64_t rows) {
   return (int)(p < LN_MAX_PARTS ? p : LN_MAX_PARTS);
 }
 
-// gemm_bf16_pp384.hip: the input-gradient product into width 384 with LayerNorm backward as its epilogue
-int pp384_lnbwd_tiles(int64_t M);
-bool gemm_bf16_nt_pp384_ln_ok(int64_t M, int K);
-int launch_gemm_bf16_nt_pp384_lnbwd(const void* a, const void* w, const float* x, const float* gamma, const float* mean, const float* rstd,
-                                    float* dx, const float* dx_add, void* dx_lowp, float* ws, int64_t M, int K, hipStream_t st);
+static bool ln_use384() {                             // the width-384 kernels unless DINOX_LN_NO384 is set (A/B knob, read once)
+  static const bool no384 = knob_set("DINOX_LN_NO384");
+  return !no384;
+}
 
 }  // namespace dinox
 
@@ -445,14 +445,10 @@ extern "C" int dinox_layernorm_fwd(const float* x, const float* w, const float* 
   if (blocks > 256 * 16) blocks = 256 * 16;
   hipStream_t st = as_stream(stream);
   const bool fast = (dim % 4 == 0) && dim <= 256 * LN_MAXV;
-  static const bool no384 = getenv("DINOX_LN_NO384") != nullptr;                     // A/B knob
-  if (dim == 384 && !no384 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)w | (uintptr_t)b) & 15) == 0) {
+  if (dim == 384 && ln_use384() && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)w | (uintptr_t)b) & 15) == 0) {
     int64_t blk = ceil_div(rows, (int64_t)(LN_THREADS / 64) * 2 * 2);             // two rows per half wave and iteration
     if (blk > 256 * 8) blk = 256 * 8;
-    if (out_dtype == DINOX_F32)
-      hipLaunchKernelGGL((ln_fwd_384<DINOX_F32>), dim3((unsigned)blk), dim3(LN_THREADS), 0, st, x, w, b, y, mean, rstd, rows, eps);
-    else
-      hipLaunchKernelGGL((ln_fwd_384<DINOX_BF16>), dim3((unsigned)blk), dim3(LN_THREADS), 0, st, x, w, b, y, mean, rstd, rows, eps);
+    hipLaunchKernelGGL((out_dtype == DINOX_F32 ? ln_fwd_384<DINOX_F32> : ln_fwd_384<DINOX_BF16>), dim3((unsigned)blk), dim3(LN_THREADS), 0, st, x, w, b, y, mean, rstd, rows, eps);
     return check_launch("layernorm_fwd");
   }
 #define LN_FWD(DT, NV) hipLaunchKernelGGL((ln_fwd_kernel<DT, NV>), dim3((unsigned)blocks), dim3(LN_THREADS), 0, st, x, w, b, y, mean, rstd, rows, dim, eps)
@@ -464,10 +460,7 @@ extern "C" int dinox_layernorm_fwd(const float* x, const float* w, const float* 
       if (nv <= 1) LN_FWD(DINOX_BF16, 1); else if (nv <= 2) LN_FWD(DINOX_BF16, 2); else if (nv <= 4) LN_FWD(DINOX_BF16, 4); else LN_FWD(DINOX_BF16, 8);
     }
   } else {
-    if (out_dtype == DINOX_F32)
-      hipLaunchKernelGGL((ln_fwd_generic<DINOX_F32>), dim3((unsigned)blocks), dim3(LN_THREADS), 0, st, x, w, b, y, mean, rstd, rows, dim, eps);
-    else
-      hipLaunchKernelGGL((ln_fwd_generic<DINOX_BF16>), dim3((unsigned)blocks), dim3(LN_THREADS), 0, st, x, w, b, y, mean, rstd, rows, dim, eps);
+    hipLaunchKernelGGL((out_dtype == DINOX_F32 ? ln_fwd_generic<DINOX_F32> : ln_fwd_generic<DINOX_BF16>), dim3((unsigned)blocks), dim3(LN_THREADS), 0, st, x, w, b, y, mean, rstd, rows, dim, eps);
   }
 #undef LN_FWD
   return check_launch("layernorm_fwd");
@@ -489,16 +482,12 @@ extern "C" int dinox_layernorm_bwd(const void* dy, const float* x, const float* 
   const size_t lds = (size_t)(LN_THREADS / 64) * 2 * dim * sizeof(float);
   const bool fast = (dim % 4 == 0) && dim <= 256 * LN_MAXV && lds <= 64 * 1024;
   float* wsf = (float*)ws;
-  static const bool no384 = getenv("DINOX_LN_NO384") != nullptr;                     // A/B knob
   const bool al16 = (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)dx_add | (uintptr_t)dx_lowp | (uintptr_t)w) & 15) == 0;
-  if (dim == 384 && !no384 && al16) {
+  if (dim == 384 && ln_use384() && al16) {
     // 167 registers = three waves per SIMD = three blocks per CU: 768 blocks are one resident round (the workspace holds `parts` >= that)
     const int64_t want = ceil_div(rows, (int64_t)(LN_THREADS / 64) * 2 * 2);
     const int nblk = (int)(want < parts ? want : (parts < 768 ? parts : 768));
-    if (dy_dtype == DINOX_F32)
-      hipLaunchKernelGGL((ln_bwd_384<DINOX_F32>), dim3(nblk), dim3(LN_THREADS), lds, st, dy, x, w, mean, rstd, dx, dx_lowp, wsf, rows, dx_add);
-    else
-      hipLaunchKernelGGL((ln_bwd_384<DINOX_BF16>), dim3(nblk), dim3(LN_THREADS), lds, st, dy, x, w, mean, rstd, dx, dx_lowp, wsf, rows, dx_add);
+    hipLaunchKernelGGL((dy_dtype == DINOX_F32 ? ln_bwd_384<DINOX_F32> : ln_bwd_384<DINOX_BF16>), dim3(nblk), dim3(LN_THREADS), lds, st, dy, x, w, mean, rstd, dx, dx_lowp, wsf, rows, dx_add);
     if (int rc = check_launch("layernorm_bwd")) return rc;
     hipLaunchKernelGGL(ln_bwd_reduce, dim3((unsigned)ceil_div(2 * dim, 4)), dim3(256), 0, st, wsf, dw, db, nblk, dim, accumulate ? 1 : 0);
     return check_launch("layernorm_bwd_reduce");
@@ -514,10 +503,7 @@ extern "C" int dinox_layernorm_bwd(const void* dy, const float* x, const float* 
   } else {
     const size_t l2 = (size_t)2 * dim * sizeof(float);
     DX_REQUIRE(l2 <= 64 * 1024, DINOX_EUNSUPPORTED, "layernorm_bwd: dim %d too large", dim);
-    if (dy_dtype == DINOX_F32)
-      hipLaunchKernelGGL((ln_bwd_generic<DINOX_F32>), dim3(parts), dim3(LN_THREADS), l2, st, dy, x, w, mean, rstd, dx, dx_lowp, wsf, rows, dim, dx_add);
-    else
-      hipLaunchKernelGGL((ln_bwd_generic<DINOX_BF16>), dim3(parts), dim3(LN_THREADS), l2, st, dy, x, w, mean, rstd, dx, dx_lowp, wsf, rows, dim, dx_add);
+    hipLaunchKernelGGL((dy_dtype == DINOX_F32 ? ln_bwd_generic<DINOX_F32> : ln_bwd_generic<DINOX_BF16>), dim3(parts), dim3(LN_THREADS), l2, st, dy, x, w, mean, rstd, dx, dx_lowp, wsf, rows, dim, dx_add);
   }
 #undef LN_BWD
   int rc = check_launch("layernorm_bwd");
