@@ -125,6 +125,10 @@ SIGNATURES = {
     "dinox_retrieval_rank": (i32, [vp, i64, vp, i64, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp]),
     "dinox_knn_ws_bytes": (i64, [i64, i64, i64, i32]),
     "dinox_knn_topk": (i32, [vp, i64, vp, i64, vp, i64, i64, i64, i32, vp, vp, vp, vp]),
+    "dinox_gram_ws_bytes": (i64, [i64, i64]),
+    "dinox_gram_f32": (i32, [vp, i64, i64, i64, vp, vp, vp, vp, vp]),
+    "dinox_softmax_probe_ws_bytes": (i64, [i64, i64, i32]),
+    "dinox_softmax_probe": (i32, [vp, i64, vp, i64, i64, i32, vp, vp, vp, vp, vp, vp]),
     "dinox_gemm_timer_start": (i32, [i32]),
     "dinox_gemm_timer_stop": (i64, [C.c_char_p, i64]),
 }

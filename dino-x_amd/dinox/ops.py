@@ -2018,3 +2018,84 @@ def knn_topk(q: Tensor, k: Tensor, K: int, exclude=None):
     check(lib.dinox_knn_topk(_p(q), q.stride(0), _p(k), k.stride(0), _p(exclude), Nq, Nk, D, K, _p(idx), _p(val), _p(ws), _stream()),
           "dinox_knn_topk")
     return idx, val
+
+
+# ------------------------------------------------------------------------------------------
+# probes (csrc/gram.hip, csrc/probe.hip)
+# ------------------------------------------------------------------------------------------
+GRAM_MAX_D = 1024
+PROBE_MAX_C = 32
+
+
+def _describe(*ts) -> str:
+    return " and ".join(f"{t.dtype}{tuple(t.shape)}" if isinstance(t, Tensor) else type(t).__name__ for t in ts)
+
+
+def _rows_operand(x: Tensor, D: int) -> Tensor:
+    return x if x.stride(1) == 1 and x.stride(0) >= D else x.contiguous()
+
+
+def gram(x: Tensor, shift: Optional[Tensor] = None):
+    """(gram float64 [D, D], colsum float64 [D]) of the fp32 rows x [N, D]: with z_i = x_i - shift (one fp32 subtraction per element;
+    ``shift`` fp32 [D] or None), gram = sum_i z_i z_i^T and colsum = sum_i z_i.  Exact-fp32 MFMA products over a deterministic split of
+    the rows, the splits summed in double (csrc/gram.hip): |error of gram[a, b]| <= N 2^-24 sum_i |z_ia z_ib|, bit-reproducible and
+    symmetric to the bit.  1 <= D <= 1024.  Append a target column to x to get X^T y and y^T y from the same pass.
+    Arguments are checked before the device is: a wrong call raises ValueError anywhere."""
+    if not isinstance(x, Tensor) or x.dtype != torch.float32 or x.dim() != 2:
+        raise ValueError(f"gram: fp32 [N, D] rows expected, got {_describe(x)}")
+    N, D = x.shape
+    if N < 1 or not 1 <= D <= GRAM_MAX_D:
+        raise ValueError(f"gram: needs N >= 1 and 1 <= D <= {GRAM_MAX_D}, got N={N}, D={D}")
+    if shift is not None:
+        if not isinstance(shift, Tensor) or shift.dtype != torch.float32 or shift.shape != (D,):
+            raise ValueError(f"gram: shift must be fp32 of shape ({D},), got {_describe(shift)}")
+        if shift.device != x.device:
+            raise ValueError(f"gram: rows on {x.device}, shift on {shift.device}")
+    _need_cuda(x, shift)
+    x = _rows_operand(x, D)
+    if shift is not None:
+        shift = _c(shift)
+    dev = x.device
+    g = torch.empty((D, D), dtype=torch.float64, device=dev)
+    cs = torch.empty(D, dtype=torch.float64, device=dev)
+    ws = torch.empty(int(lib.dinox_gram_ws_bytes(N, D)), dtype=torch.uint8, device=dev)
+    check(lib.dinox_gram_f32(_p(x), x.stride(0), N, D, _p(shift), _p(g), _p(cs), _p(ws), _stream()), "dinox_gram_f32")
+    return g, cs
+
+
+def softmax_probe(x: Tensor, label: Tensor, theta: Tensor, *, want_grad: bool = True, want_prob: bool = False):
+    """One evaluation of a softmax (multinomial logistic) probe on the fp32 rows x [N, D] with int labels [N] and fp32 parameters
+    theta [C, D + 1] (last column = intercept): returns (loss, grad, prob) with loss = sum_i (logsumexp(z_i) - z_i,label_i) as a float64
+    0-d tensor, grad = sum_i (p_i - onehot_i) [x_i, 1]^T float64 [C, D + 1] (both None without ``want_grad``) and prob = softmax(z) fp32
+    [N, C] (None without ``want_prob``).  ``want_grad=False, want_prob=True`` is the predict form; the probabilities are bitwise the same
+    in both forms.  A row whose label is outside [0, C) contributes nothing to loss and grad.  2 <= C <= 32, 1 <= D <= 1024.  One pass
+    over x on the exact-fp32 MFMA, deterministic reduction in double (csrc/probe.hip).
+    Arguments are checked before the device is: a wrong call raises ValueError anywhere."""
+    if not isinstance(x, Tensor) or x.dtype != torch.float32 or x.dim() != 2:
+        raise ValueError(f"softmax_probe: fp32 [N, D] rows expected, got {_describe(x)}")
+    N, D = x.shape
+    if N < 1 or not 1 <= D <= GRAM_MAX_D:
+        raise ValueError(f"softmax_probe: needs N >= 1 and 1 <= D <= {GRAM_MAX_D}, got N={N}, D={D}")
+    if not isinstance(theta, Tensor) or theta.dtype != torch.float32 or theta.dim() != 2 or theta.shape[1] != D + 1:
+        raise ValueError(f"softmax_probe: theta must be fp32 [C, {D + 1}] (last column = intercept), got {_describe(theta)}")
+    C = theta.shape[0]
+    if not 2 <= C <= PROBE_MAX_C:
+        raise ValueError(f"softmax_probe: C must lie in [2, {PROBE_MAX_C}], got {C}")
+    if not isinstance(label, Tensor) or label.shape != (N,) or label.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"softmax_probe: label must be int32 or int64 of shape ({N},), got {_describe(label)}")
+    if not (want_grad or want_prob):
+        raise ValueError("softmax_probe: nothing asked for (want_grad=False, want_prob=False)")
+    if label.device != x.device or theta.device != x.device:
+        raise ValueError(f"softmax_probe: rows on {x.device}, label on {label.device}, theta on {theta.device}")
+    _need_cuda(x, label, theta)
+    if label.dtype != torch.int32:
+        label = torch.where((label >= 0) & (label < C), label, torch.full_like(label, -1)).to(torch.int32)     # (no wrap-around into range)
+    x, label, theta = _rows_operand(x, D), _c(label), _c(theta)
+    dev = x.device
+    loss = torch.empty((), dtype=torch.float64, device=dev) if want_grad else None
+    grad = torch.empty((C, D + 1), dtype=torch.float64, device=dev) if want_grad else None
+    prob = torch.empty((N, C), dtype=torch.float32, device=dev) if want_prob else None
+    ws = torch.empty(int(lib.dinox_softmax_probe_ws_bytes(N, D, C)) // 8 + 1, dtype=torch.float64, device=dev)
+    check(lib.dinox_softmax_probe(_p(x), x.stride(0), _p(label), N, D, C, _p(theta), _p(loss), _p(grad), _p(prob), _p(ws), _stream()),
+          "dinox_softmax_probe")
+    return loss, grad, prob

@@ -17,8 +17,21 @@ What is here:
 What is kept from the reference is its interface: the flags that apply and their defaults, the seeding order, the result envelope
 (``kind``, ``version``, ``created_at``, ``checkpoint``, ``step``, ``scale_aware``, ``seed``, ``val_slices``, ``datasets``, ``model``,
 ``metrics``, ``seconds``), the output file (``panorgan_eval_step<step>.json`` next to the checkpoint unless ``--out``), ``ok=true`` as
-the last line and exit status 0.  The reference's other five metrics (per-dataset view retrieval, logistic probe, spacing counterfactual,
-ridge spacing prediction, embedding statistics) are not built yet and no key is written for them.
+the last line and exit status 0.
+
+With ``--probes`` three more of the reference's metrics are written, all linear algebra on the embedding matrix the script already holds on
+the device (``dinox.probes``; csrc/probe.hip, csrc/gram.hip):
+
+* ``metrics.dataset_discrimination_probe`` -- metric 2: multinomial logistic regression over the dataset labels, series-level split,
+  series bootstrap; every evaluation of the fit is one kernel pass over the train rows.
+* ``metrics.spacing_prediction`` -- metric 5: ridge regression of log(spacing_x) from the Gram matrix of [E | y].
+* ``metrics.embedding_stats`` -- metric 6: centroids, spread, first principal axis against spacing, cross-dataset centroid cosines.
+
+Same keys and the reference's stdout lines.  The probes are opt-in and their two flags (``--probes``, and ``--skip-probes``, the explicit
+form of the default, which wins when both are given) are added by ``build_parser(probe_flags=True)``, the parser ``main`` uses: the
+result file of a run without them, and the flag surface ``build_parser()`` returns, are what the nearest-neighbour tests pin.  The
+reference's remaining two metrics (1, per-dataset view retrieval, and 3, spacing counterfactual) need extra backbone passes; they are not
+built and no key is written for them.
 
 Extensions: ``--synthetic N`` (N seeded synthetic HU stacks, seed = ``--seed``, instead of a PNG index; the dataset of sample i is
 ``synthetic_label(i)``), ``--amp-dtype bf16`` (bf16 backbone; the similarity is fp32 either way), ``--dump-embeddings FILE`` (the
@@ -58,6 +71,12 @@ _FLAGS = (
     ("--dump-embeddings", dict(type=Path, default=None, metavar="FILE", help="extension: write the embeddings and labels as .npz")),
 )
 
+# the probe block (metrics 2, 5, 6): build_parser(probe_flags=True)
+_PROBE_FLAGS = (
+    ("--probes", dict(action="store_true", help="extension: also run the logistic probe, the spacing ridge and the embedding statistics")),
+    ("--skip-probes", dict(action="store_true", help="extension: do not run them (the default; wins over --probes)")),
+)
+
 _MODEL_KEYS = ("name", "patch", "dim", "depth", "heads")
 _SYNTHETIC_DATASETS = ("synthetic_a", "synthetic_b", "synthetic_c")
 DOMAIN_K, PROBE_K, PROBE_T = 10, 20, 0.07
@@ -69,11 +88,46 @@ def synthetic_label(i: int) -> str:
     return _SYNTHETIC_DATASETS[0 if r < 4 else (1 if r < 6 else 2)]
 
 
-def build_parser() -> argparse.ArgumentParser:
-    ap = argparse.ArgumentParser(description="Pan-organ evaluation: domain clustering and k-NN probe")
-    for flag, kw in _FLAGS:
+def build_parser(probe_flags: bool = False) -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(description="Pan-organ evaluation: domain clustering, k-NN probe, linear probes and embedding statistics")
+    for flag, kw in _FLAGS + (_PROBE_FLAGS if probe_flags else ()):
         ap.add_argument(flag, **kw)
     return ap
+
+
+def probe_series(rows, synthetic: bool) -> list:
+    """The series handed to the probes: the row's series_dir; in --synthetic mode ``series_dir:dataset``, because synthetic_label deals
+    the samples of one synthetic series to several datasets and a series of the split has one dataset."""
+    return [f"{r.series_dir}:{r.dataset}" if synthetic else str(r.series_dir) for r in rows]
+
+
+def run_probes(E, spacings, labels, series, seed: int, metrics: dict) -> None:
+    """Metrics 2, 5 and 6 into ``metrics``, with the reference's stdout lines (steps 3 to 5 of 5)."""
+    from dinox import probes
+    print("\n[3/5] Dataset discrimination linear probe...")
+    probe = probes.logistic_probe(E, labels, series, seed=seed)
+    metrics["dataset_discrimination_probe"] = probe
+    if "accuracy" in probe:
+        print(f"  Accuracy: {probe['accuracy']:.3f} (CI: {probe['accuracy_ci95']})")
+        print(f"  AUC: {probe['auc']:.3f}")
+    else:
+        print(f"  ⚠️  {probe.get('error', 'unknown error')}")
+    print("\n[4/5] Spacing prediction sanity check...")
+    ridge = probes.spacing_ridge(E, spacings, labels, series, seed=seed)
+    metrics["spacing_prediction"] = ridge
+    if "r2" in ridge:
+        print(f"  R²: {ridge['r2']:.3f}")
+        print(f"  MAE(log spacing): {ridge['mae_log_spacing']:.4f}")
+    else:
+        print(f"  ⚠️  {ridge.get('error', 'unknown error')}")
+    print("\n[5/5] Embedding statistics...")
+    stats = probes.embedding_stats(E, spacings, labels)
+    metrics["embedding_stats"] = stats
+    for name, d in stats["per_dataset"].items():
+        print(f"  {name}: std={d['embedding_std']:.4f} intra_cos={d['intra_cosine_to_centroid']:.3f} "
+              f"pca1_sp_corr={d['pca1_spacing_correlation']:.3f}")
+    for pair, cos in stats["cross_dataset_centroid_cosine"].items():
+        print(f"  Cross: {pair} = {cos:.3f}")
 
 
 def _check_args(args) -> None:
@@ -92,7 +146,7 @@ def _check_args(args) -> None:
 
 
 def main(argv=None) -> int:
-    args = build_parser().parse_args(argv)
+    args = build_parser(probe_flags=True).parse_args(argv)
     _check_args(args)
     for seed_fn in (random.seed, np.random.seed, torch.manual_seed):        # the reference's order
         seed_fn(args.seed)
@@ -128,7 +182,7 @@ def main(argv=None) -> int:
     }
 
     print("\n[embed] Embedding all val slices (deterministic)...")
-    E, _ = retrieval.embed_eval_slices(student, ds, list(range(n)), size, batch_size=args.batch_size, scale_aware=args.scale_aware,
+    E, spacings = retrieval.embed_eval_slices(student, ds, list(range(n)), size, batch_size=args.batch_size, scale_aware=args.scale_aware,
                                        amp_dtype=torch.bfloat16 if args.amp_dtype == "bf16" else None)
     if not bool(torch.isfinite(E).all()):
         raise SystemExit("ok=false\nnon-finite embeddings (diverged checkpoint?); no neighbours can be given")
@@ -154,12 +208,19 @@ def main(argv=None) -> int:
     print(f"  Accuracy: {probe['accuracy']:.3f}")
     t_neigh = time.time() - t0
 
+    t_probes = None
+    if args.probes and not args.skip_probes:
+        t0 = time.time()
+        run_probes(E, spacings, labels, probe_series(ds.rows, bool(args.synthetic)), args.seed, results["metrics"])
+        t_probes = time.time() - t0
+
     results["seconds"] = time.time() - started
     out = args.out or args.checkpoint.parent / f"panorgan_eval_step{step}.json"
     out.parent.mkdir(parents=True, exist_ok=True)
     out.write_text(json.dumps(results, indent=2) + "\n")
     print(f"\n{'─' * 60}")
-    print(f"Evaluation complete in {results['seconds']:.1f}s (embedding {t_embed:.2f}s, neighbours {t_neigh:.3f}s)")
+    print(f"Evaluation complete in {results['seconds']:.1f}s (embedding {t_embed:.2f}s, neighbours {t_neigh:.3f}s"
+          + (f", probes {t_probes:.3f}s)" if t_probes is not None else ")"))
     print(f"Results: {out}")
     print("ok=true")
     return 0

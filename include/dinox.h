@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define DINOX_ABI_VERSION 3   /* 3: + dinox_block_forward / _backward, dinox_gemm_timer_*, dinox_retrieval_*, dinox_knn_* (all additive: no entry
+#define DINOX_ABI_VERSION 3   /* 3: + dinox_block_forward / _backward, dinox_gemm_timer_*, dinox_retrieval_*, dinox_knn_*, dinox_gram_*, dinox_softmax_probe* (all additive: no entry
                                * of an earlier library changed, so the number callers test, dinox_version() == 3, stays; probe the symbol
                                * to learn whether a given build has the later additions) */
 
@@ -448,6 +448,40 @@ int dinox_retrieval_rank(const float* q, int64_t ldq, const float* k, int64_t ld
 int64_t dinox_knn_ws_bytes(int64_t Nq, int64_t Nk, int64_t D, int K);
 int dinox_knn_topk(const float* q, int64_t ldq, const float* k, int64_t ldk, const int32_t* exclude, int64_t Nq, int64_t Nk, int64_t D, int K,
                    int32_t* out_idx, float* out_val, void* ws, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Second moments of the columns of x [N][D] fp32 (ldx >= D) -- replaces the host NumPy / scikit-learn passes of the reference's ridge and
+ * embedding-statistics metrics (scripts/evaluate_panorgan.py:569-697).  With z_i = x_i - shift (ONE fp32 subtraction per element; shift
+ * NULL: z = x):   gram[a][b] = sum_i z_ia z_ib  (double [D][D], symmetric to the bit),   colsum[a] = sum_i z_ia  (double [D]).
+ * Append a target column to x to read X^T y and y^T y from the same pass.  1 <= D <= 1024, N >= 1; anything else returns DINOX_EINVAL.
+ * Exact-fp32 MFMA products summed in fp32 over a split of the rows (at most ceil(N / splits) + 15 terms, in row order), the splits then
+ * summed in ascending order in double: |error of gram[a][b]| <= N 2^-24 sum_i |z_ia z_ib|.  Rows past N and columns past D enter as
+ * exact zeros.  Non-finite inputs propagate into the sums they belong to and neither fault nor hang.
+ * ws: dinox_gram_ws_bytes(N, D) bytes (a pure function of the two sizes; 0 for sizes the call refuses; contents need not be
+ * initialised).  Two launches on the stream, plain stores, no atomics: results are bit-reproducible.
+ * ------------------------------------------------------------------------------------------ */
+int64_t dinox_gram_ws_bytes(int64_t N, int64_t D);
+int dinox_gram_f32(const float* x, int64_t ldx, int64_t N, int64_t D, const float* shift, double* gram, double* colsum, void* ws, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * One evaluation of a multinomial logistic (softmax) probe -- the inner step of the reference's dataset-discrimination metric
+ * (scripts/evaluate_panorgan.py:375-379, scikit-learn's LogisticRegression on the host).  x [N][D] fp32 rows (ldx >= D), label int32 [N],
+ * theta fp32 [C][D + 1] with the intercept in the last column:
+ *   z_ic = theta_c[:D] . x_i + theta_c[D],   p_i = softmax(z_i)  (log-sum-exp form: no overflow at any finite logit),
+ *   loss[0]  = sum_i (logsumexp(z_i) - z_i,label_i)                       double, or NULL
+ *   grad     = sum_i (p_ic - [label_i == c]) [x_i, 1]                     double [C][D + 1], or NULL
+ *   prob     = p                                                          fp32 [N][C], or NULL
+ * loss == NULL && grad == NULL is the predict form; the probabilities are bitwise the same in both forms.  2 <= C <= 32, 1 <= D <= 1024,
+ * N >= 1, at least one output; anything else returns DINOX_EINVAL.  A row whose label is outside [0, C) contributes nothing to loss and
+ * grad (its prob row is still written); a label is only ever COMPARED with class numbers and never becomes an address.
+ * Logits and R^T X on the exact-fp32 MFMA; the rows are read once.  Per-workgroup fp32 partial gradients (row order) and double partial
+ * losses are added in ascending workgroup order in double.  Non-finite inputs propagate and neither fault nor hang.
+ * ws: dinox_softmax_probe_ws_bytes(N, D, C) bytes, 8-byte aligned (a pure function of the sizes; 0 for sizes the call refuses; contents
+ * need not be initialised).  One launch (predict form) or two on the stream, plain stores, no atomics: results are bit-reproducible.
+ * ------------------------------------------------------------------------------------------ */
+int64_t dinox_softmax_probe_ws_bytes(int64_t N, int64_t D, int C);
+int dinox_softmax_probe(const float* x, int64_t ldx, const int32_t* label, int64_t N, int64_t D, int C, const float* theta, double* loss,
+                        double* grad, float* prob, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Per-launch timing of dinox_gemm (diagnostic; bench.py's roofline object).  Between start and stop every dinox_gemm launch -- also
