@@ -123,6 +123,9 @@ SIGNATURES = {
     "dinox_block_backward": (i32, [C.POINTER(BlockBwdArgs), vp]),
     "dinox_retrieval_ws_bytes": (i64, [i64, i64, i64]),
     "dinox_retrieval_rank": (i32, [vp, i64, vp, i64, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp]),
+    "dinox_retrieval_rank_windowed_ws_bytes": (i64, [i64, i64, i64]),
+    "dinox_retrieval_rank_windowed": (i32, [vp, i64, vp, i64, vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp]),
+    "dinox_row_dots": (i32, [vp, i64, vp, i64, i64, i64, vp, vp]),
     "dinox_knn_ws_bytes": (i64, [i64, i64, i64, i32]),
     "dinox_knn_topk": (i32, [vp, i64, vp, i64, vp, i64, i64, i64, i32, vp, vp, vp, vp]),
     "dinox_gram_ws_bytes": (i64, [i64, i64]),

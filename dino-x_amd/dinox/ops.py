@@ -1962,6 +1962,74 @@ def retrieval_rank(q: Tensor, k: Tensor, target: Optional[Tensor] = None):
     return rank, best_idx, best_val, pos_val
 
 
+def _rr_rows(name: str, q: Tensor, k: Tensor):
+    """The row checks of retrieval_rank for a sibling entry: fp32 [Nq, D] / [Nk, D], row-major views with a leading dimension kept."""
+    if q.dtype != torch.float32 or k.dtype != torch.float32 or q.dim() != 2 or k.dim() != 2 or q.shape[1] != k.shape[1]:
+        raise ValueError(f"{name}: fp32 [Nq, D] and [Nk, D] rows expected, got {q.dtype}{tuple(q.shape)} and {k.dtype}{tuple(k.shape)}")
+    if q.stride(1) != 1 or q.stride(0) < q.shape[1]:
+        q = q.contiguous()
+    if k.stride(1) != 1 or k.stride(0) < k.shape[1]:
+        k = k.contiguous()
+    if min(q.shape[0], k.shape[0], q.shape[1]) < 1:
+        raise ValueError(f"{name}: empty operand (Nq={q.shape[0]}, Nk={k.shape[0]}, D={q.shape[1]})")
+    return q, k
+
+
+def _rr_index(name: str, what: str, t: Tensor, Nq: int) -> Tensor:
+    if t.shape != (Nq,):
+        raise ValueError(f"{name}: {what} must have shape ({Nq},), got {tuple(t.shape)}")
+    if t.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{name}: {what} must be int32 or int64 indices, got {t.dtype}")
+    return t
+
+
+def retrieval_rank_windowed(q: Tensor, k: Tensor, key_lo: Tensor, key_hi: Tensor, target: Optional[Tensor] = None):
+    """retrieval_rank with a key window per query: (rank, best_idx, best_val, pos_val), each [Nq], where query i competes only with the keys
+    key_lo[i] <= j < key_hi[i] -- rank[i] is the place of key target[i] (default: i) among them, best_* the window's maximum and its first
+    (global) index, pos_val the positive's score.  The scores are bitwise those of retrieval_rank; a strip of queries sweeps only the key
+    tiles its windows touch, so rows sorted by group cost sum n_g^2 scores (csrc/retrieval.hip).  Window bounds outside [0, Nk] are clamped by
+    the kernel and are no error; an empty window gives rank 0, best_idx 0x7fffffff, best_val -inf; a target outside its window is allowed.
+    target indices are checked against [0, Nk) here.  See include/dinox.h."""
+    _need_cuda(q, k, key_lo, key_hi, target)
+    name = "retrieval_rank_windowed"
+    q, k = _rr_rows(name, q, k)
+    (Nq, D), Nk = q.shape, k.shape[0]
+    key_lo, key_hi = _rr_index(name, "key_lo", key_lo, Nq), _rr_index(name, "key_hi", key_hi, Nq)
+    # int64 bounds beyond int32 are clamped here the way the kernel clamps the rest
+    key_lo, key_hi = _c(key_lo.clamp(0, Nk).to(torch.int32)), _c(key_hi.clamp(0, Nk).to(torch.int32))
+    if target is None:
+        if Nq != Nk:
+            raise ValueError(f"{name}: without target, query i is matched to key i and Nq must equal Nk ({Nq}, {Nk})")
+    else:
+        target = _rr_index(name, "target", target, Nq)
+        lo, hi = int(target.min()), int(target.max())
+        if lo < 0 or hi >= Nk:
+            raise ValueError(f"{name}: target indices must lie in [0, {Nk}), got [{lo}, {hi}]")
+        target = _c(target.to(torch.int32))
+    dev = q.device
+    rank = torch.empty(Nq, dtype=torch.int32, device=dev)
+    best_idx = torch.empty(Nq, dtype=torch.int32, device=dev)
+    best_val = torch.empty(Nq, dtype=torch.float32, device=dev)
+    pos_val = torch.empty(Nq, dtype=torch.float32, device=dev)
+    ws = torch.empty(int(lib.dinox_retrieval_rank_windowed_ws_bytes(Nq, Nk, D)), dtype=torch.uint8, device=dev)
+    check(lib.dinox_retrieval_rank_windowed(_p(q), q.stride(0), _p(k), k.stride(0), _p(target), _p(key_lo), _p(key_hi), Nq, Nk, D, _p(rank),
+                                            _p(best_idx), _p(best_val), _p(pos_val), _p(ws), _stream()), "dinox_retrieval_rank_windowed")
+    return rank, best_idx, best_val, pos_val
+
+
+def row_dots(a: Tensor, b: Tensor) -> Tensor:
+    """out[i] = a_i . b_i of fp32 rows a, b [N, D], fp32 [N]: bitwise ``retrieval_rank(a, b)[3]`` (the positive's score of query a_i against
+    key b_i) from that entry's first launch alone -- no workspace, no sweep.  Row-major views with a leading dimension are accepted."""
+    _need_cuda(a, b)
+    a, b = _rr_rows("row_dots", a, b)
+    if a.shape != b.shape:
+        raise ValueError(f"row_dots: rows are paired and the shapes must be equal, got {tuple(a.shape)} and {tuple(b.shape)}")
+    N, D = a.shape
+    out = torch.empty(N, dtype=torch.float32, device=a.device)
+    check(lib.dinox_row_dots(_p(a), a.stride(0), _p(b), b.stride(0), N, D, _p(out), _stream()), "dinox_row_dots")
+    return out
+
+
 KNN_MAX_K = 32
 
 

@@ -29,9 +29,21 @@ the device (``dinox.probes``; csrc/probe.hip, csrc/gram.hip):
 
 Same keys and the reference's stdout lines.  The probes are opt-in and their two flags (``--probes``, and ``--skip-probes``, the explicit
 form of the default, which wins when both are given) are added by ``build_parser(probe_flags=True)``, the parser ``main`` uses: the
-result file of a run without them, and the flag surface ``build_parser()`` returns, are what the nearest-neighbour tests pin.  The
-reference's remaining two metrics (1, per-dataset view retrieval, and 3, spacing counterfactual) need extra backbone passes; they are not
-built and no key is written for them.
+result file of a run without them, and the flag surface ``build_parser()`` returns, are what the nearest-neighbour tests pin.
+
+With ``--view-metrics`` the reference's remaining two metrics are written, the ones that need backbone passes of their own
+(``dinox.retrieval``; csrc/retrieval.hip):
+
+* ``metrics.view_retrieval_per_dataset`` -- metric 1: per dataset, ``--n-retrieval`` (512) slices, two random views each, how often view
+  2 of a slice is the nearest of its dataset's keys to view 1.  The reference's sampling and RNG position (right after seeding, before the
+  deterministic embedding pass); one embedding pass over all datasets' picks and one windowed rank call instead of an S = Q K^T per
+  dataset.  ``--skip-view-retrieval`` leaves it out (no key, the reference's SKIPPED line).
+* ``metrics.spacing_counterfactual`` -- metric 3: ``--n-counterfactual`` (256) slices, the same pixels embedded with the real, the doubled
+  and the halved spacing; mean / std / median of the three cosine distances.  Without ``--scale-aware`` the reference's
+  ``{"skipped": true, ...}`` dict.
+
+Same keys and the reference's stdout lines; both keys come after the existing ones in ``metrics``.  The four flags are added by
+``build_parser(view_flags=True)``; a run without ``--view-metrics`` writes what it wrote before.
 
 Extensions: ``--synthetic N`` (N seeded synthetic HU stacks, seed = ``--seed``, instead of a PNG index; the dataset of sample i is
 ``synthetic_label(i)``), ``--amp-dtype bf16`` (bf16 backbone; the similarity is fp32 either way), ``--dump-embeddings FILE`` (the
@@ -77,6 +89,14 @@ _PROBE_FLAGS = (
     ("--skip-probes", dict(action="store_true", help="extension: do not run them (the default; wins over --probes)")),
 )
 
+# the view block (metrics 1, 3): build_parser(view_flags=True)
+_VIEW_FLAGS = (
+    ("--view-metrics", dict(action="store_true", help="extension: also run per-dataset view retrieval and the spacing counterfactual")),
+    ("--n-retrieval", dict(type=int, default=512, help="samples per dataset for view retrieval")),
+    ("--n-counterfactual", dict(type=int, default=256, help="samples for the spacing counterfactual")),
+    ("--skip-view-retrieval", dict(action="store_true", help="skip view retrieval")),
+)
+
 _MODEL_KEYS = ("name", "patch", "dim", "depth", "heads")
 _SYNTHETIC_DATASETS = ("synthetic_a", "synthetic_b", "synthetic_c")
 DOMAIN_K, PROBE_K, PROBE_T = 10, 20, 0.07
@@ -88,9 +108,9 @@ def synthetic_label(i: int) -> str:
     return _SYNTHETIC_DATASETS[0 if r < 4 else (1 if r < 6 else 2)]
 
 
-def build_parser(probe_flags: bool = False) -> argparse.ArgumentParser:
+def build_parser(probe_flags: bool = False, view_flags: bool = False) -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="Pan-organ evaluation: domain clustering, k-NN probe, linear probes and embedding statistics")
-    for flag, kw in _FLAGS + (_PROBE_FLAGS if probe_flags else ()):
+    for flag, kw in _FLAGS + (_PROBE_FLAGS if probe_flags else ()) + (_VIEW_FLAGS if view_flags else ()):
         ap.add_argument(flag, **kw)
     return ap
 
@@ -130,6 +150,39 @@ def run_probes(E, spacings, labels, series, seed: int, metrics: dict) -> None:
         print(f"  Cross: {pair} = {cos:.3f}")
 
 
+def run_view_retrieval(student, ds, labels, args, amp_dtype, metrics: dict) -> None:
+    """Metric 1 into ``metrics`` with the reference's stdout lines.  ``ds`` is in its random-view mode for the call."""
+    from dinox import retrieval
+    if args.skip_view_retrieval:
+        print("\n[views 1/2] Per-dataset view retrieval... SKIPPED (--skip-view-retrieval)")
+        return
+    print("\n[views 1/2] Per-dataset view retrieval...")
+    raw, ds.raw_views = ds.raw_views, False                 # items = ([view 1, view 2], spacing)
+    try:
+        res = retrieval.view_retrieval_per_dataset(student, ds, labels, n_per_dataset=args.n_retrieval, seed=args.seed,
+                                                   batch_size=args.batch_size, scale_aware=args.scale_aware, amp_dtype=amp_dtype)
+    finally:
+        ds.raw_views = raw
+    metrics["view_retrieval_per_dataset"] = res
+    for name, d in res.items():
+        print(f"  {name}: top1={d['top1']:.4f} ratio={d['ratio_vs_random']:.1f}×")
+
+
+def run_counterfactual(student, ds, size: int, args, amp_dtype, metrics: dict) -> None:
+    """Metric 3 into ``metrics`` with the reference's stdout lines."""
+    from dinox import retrieval
+    print("\n[views 2/2] Spacing counterfactual test...")
+    if not args.scale_aware:
+        print("  Skipped (baseline model has no scale embedding)")
+        metrics["spacing_counterfactual"] = dict(retrieval.COUNTERFACTUAL_SKIPPED)
+        return
+    cf = retrieval.spacing_counterfactual(student, ds, size, n=args.n_counterfactual, seed=args.seed, batch_size=args.batch_size,
+                                          amp_dtype=amp_dtype)
+    metrics["spacing_counterfactual"] = cf
+    print(f"  real→2x: dist={cf['cosine_distance_real_vs_2x']['mean']:.4f}")
+    print(f"  real→½x: dist={cf['cosine_distance_real_vs_half']['mean']:.4f}")
+
+
 def _check_args(args) -> None:
     need = [("Checkpoint", args.checkpoint)]
     if not args.synthetic:
@@ -143,10 +196,12 @@ def _check_args(args) -> None:
         raise SystemExit("--synthetic must be >= 0")
     if args.batch_size <= 0:
         raise SystemExit("--batch-size must be > 0")
+    if args.n_retrieval <= 0 or args.n_counterfactual <= 0:
+        raise SystemExit("--n-retrieval and --n-counterfactual must be > 0")
 
 
 def main(argv=None) -> int:
-    args = build_parser(probe_flags=True).parse_args(argv)
+    args = build_parser(probe_flags=True, view_flags=True).parse_args(argv)
     _check_args(args)
     for seed_fn in (random.seed, np.random.seed, torch.manual_seed):        # the reference's order
         seed_fn(args.seed)
@@ -181,13 +236,25 @@ def main(argv=None) -> int:
         "model": {f: getattr(mc, f) for f in _MODEL_KEYS}, "metrics": {},
     }
 
+    amp_dtype = torch.bfloat16 if args.amp_dtype == "bf16" else None
+    view_metrics, t_views = {}, None
+    if args.view_metrics:                                  # metric 1 first: the reference's position in the global RNG streams
+        t0 = time.time()
+        try:
+            run_view_retrieval(student, ds, labels, args, amp_dtype, view_metrics)
+        except FloatingPointError as e:
+            raise SystemExit(f"ok=false\n{e}")
+        torch.cuda.synchronize()
+        t_views = [time.time() - t0, 0.0]
+
     print("\n[embed] Embedding all val slices (deterministic)...")
+    t0 = time.time()
     E, spacings = retrieval.embed_eval_slices(student, ds, list(range(n)), size, batch_size=args.batch_size, scale_aware=args.scale_aware,
-                                       amp_dtype=torch.bfloat16 if args.amp_dtype == "bf16" else None)
+                                       amp_dtype=amp_dtype)
     if not bool(torch.isfinite(E).all()):
         raise SystemExit("ok=false\nnon-finite embeddings (diverged checkpoint?); no neighbours can be given")
     torch.cuda.synchronize()
-    t_embed = time.time() - started
+    t_embed = time.time() - t0
     print(f"  Embedded {E.shape[0]} slices → ({E.shape[1]}D) in {t_embed:.2f}s")
     if args.dump_embeddings is not None:
         args.dump_embeddings.parent.mkdir(parents=True, exist_ok=True)
@@ -214,13 +281,24 @@ def main(argv=None) -> int:
         run_probes(E, spacings, labels, probe_series(ds.rows, bool(args.synthetic)), args.seed, results["metrics"])
         t_probes = time.time() - t0
 
+    if args.view_metrics:
+        t0 = time.time()
+        try:
+            run_counterfactual(student, ds, size, args, amp_dtype, view_metrics)
+        except FloatingPointError as e:
+            raise SystemExit(f"ok=false\n{e}")
+        torch.cuda.synchronize()
+        t_views[1] = time.time() - t0
+        results["metrics"].update(view_metrics)            # after the existing keys, metric 1 before metric 3
+
     results["seconds"] = time.time() - started
     out = args.out or args.checkpoint.parent / f"panorgan_eval_step{step}.json"
     out.parent.mkdir(parents=True, exist_ok=True)
     out.write_text(json.dumps(results, indent=2) + "\n")
     print(f"\n{'─' * 60}")
     print(f"Evaluation complete in {results['seconds']:.1f}s (embedding {t_embed:.2f}s, neighbours {t_neigh:.3f}s"
-          + (f", probes {t_probes:.3f}s)" if t_probes is not None else ")"))
+          + (f", probes {t_probes:.3f}s" if t_probes is not None else "")
+          + (f", view retrieval {t_views[0]:.2f}s, counterfactual {t_views[1]:.2f}s)" if t_views is not None else ")"))
     print(f"Results: {out}")
     print("ok=true")
     return 0

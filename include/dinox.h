@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define DINOX_ABI_VERSION 3   /* 3: + dinox_block_forward / _backward, dinox_gemm_timer_*, dinox_retrieval_*, dinox_knn_*, dinox_gram_*, dinox_softmax_probe* (all additive: no entry
+#define DINOX_ABI_VERSION 3   /* 3: + dinox_block_forward / _backward, dinox_gemm_timer_*, dinox_retrieval_* (later also dinox_retrieval_rank_windowed*, dinox_row_dots), dinox_knn_*, dinox_gram_*, dinox_softmax_probe* (all additive: no entry
                                * of an earlier library changed, so the number callers test, dinox_version() == 3, stays; probe the symbol
                                * to learn whether a given build has the later additions) */
 
@@ -428,6 +428,36 @@ int dinox_block_backward(const dinox_block_bwd_args* args, void* stream);
 int64_t dinox_retrieval_ws_bytes(int64_t Nq, int64_t Nk, int64_t D);
 int dinox_retrieval_rank(const float* q, int64_t ldq, const float* k, int64_t ldk, const int32_t* target, int64_t Nq, int64_t Nk, int64_t D,
                          int32_t* rank, int32_t* best_idx, float* best_val, float* pos_val, void* ws, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Windowed view-retrieval rank -- the per-dataset view retrieval of scripts/evaluate_panorgan.py (metric 1: one Q K^T per dataset) as ONE
+ * call over the concatenated rows.  The semantics of dinox_retrieval_rank with every "over j" restricted to the window of query i,
+ * key_lo[i] <= j < key_hi[i]:
+ *   pos_val[i]  = s(i, target[i]);
+ *   rank[i]     = #{j in window : s(i,j) > pos_val[i]} + #{j in window, j < target[i] : s(i,j) == pos_val[i]};
+ *   best_val[i] = the maximum over the window, best_idx[i] = its lowest index, a GLOBAL key index.
+ * target == NULL means target[i] = i and needs Nq == Nk.  s(i,j) is BITWISE the score dinox_retrieval_rank computes for the same operands
+ * (same tile loop, key tiles at multiples of 128 of the global key index): a window of [0, Nk) for every query reproduces that entry bit
+ * for bit, and a window equal to a row range reproduces the call on that range (best_idx shifted by the range's start).
+ * Work: a strip of 128 queries sweeps only the key tiles one of its windows touches, so with rows sorted by group the cost is
+ * sum n_g^2 scores, not Nq Nk.  Windows may be arbitrary and unsorted (the cost is then the tiles each strip's windows touch).
+ * ws: dinox_retrieval_rank_windowed_ws_bytes(Nq, Nk, D) bytes (12 bytes per query and key split, a pure function of the sizes; contents
+ * need not be initialised).  Any Nq, Nk, D >= 1 (Nq, Nk <= 2^31 - 129), ldq, ldk >= D.
+ * Bad input never becomes an address or a loop bound: key_lo[i] and key_hi[i] are CLAMPED into [0, Nk] and target[i] into [0, Nk) as
+ * in dinox_retrieval_rank.  An empty window (lo >= hi after clamping) gives rank 0, best_idx = 0x7fffffff, best_val = -inf; pos_val is
+ * still written.  A target outside its window is allowed: rank is the place the target would take among the window's keys.
+ * Non-finite scores behave as documented for dinox_retrieval_rank (a NaN query row: rank 0, best_idx = 0x7fffffff, best_val = -inf, NaN
+ * pos_val; test pos_val).  Three launches on the stream, plain stores, no atomics: results are bit-reproducible.
+ * ------------------------------------------------------------------------------------------ */
+int64_t dinox_retrieval_rank_windowed_ws_bytes(int64_t Nq, int64_t Nk, int64_t D);
+int dinox_retrieval_rank_windowed(const float* q, int64_t ldq, const float* k, int64_t ldk, const int32_t* target, const int32_t* key_lo,
+                                  const int32_t* key_hi, int64_t Nq, int64_t Nk, int64_t D, int32_t* rank, int32_t* best_idx, float* best_val,
+                                  float* pos_val, void* ws, void* stream);
+
+/* Paired row dot products: out[i] = sum_d a[i][d] b[i][d] for fp32 rows a [N][D] (lda >= D), b [N][D] (ldb >= D) -- BITWISE pos_val[i] of
+ * dinox_retrieval_rank(q = a, k = b, target = NULL): the first of its launches on its own (same operand roles, same ascending-d fp32 chain
+ * on the exact-fp32 MFMA), no workspace, no sweep.  The cosine distance of the spacing counterfactual (metric 3) is 1 - out[i] of unit rows. */
+int dinox_row_dots(const float* a, int64_t lda, const float* b, int64_t ldb, int64_t N, int64_t D, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K nearest keys -- replaces the host block of scripts/evaluate_panorgan.py:526-529 (S = E E^T as an N x N numpy array, fill_diagonal(-inf),

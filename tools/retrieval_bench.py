@@ -9,7 +9,15 @@ fp32 matrix peak (the kernel is compute-bound: q and k are at most 100 MB), the 
 candidate, and whether the fused kernel is within the GEMM's own spread of the GEMM.  One JSON line at the end.
 
     python tools/retrieval_bench.py            [ROUNDS=5 MIN_S=0.2 SHAPES=4096x384,16384x384]
+
+``--groups G`` times the windowed entry instead (dinox_retrieval_rank_windowed, the per-dataset view retrieval of the pan-organ
+evaluation): G groups of GROUP_ROWS (512) rows at D = GROUP_D (384), rows sorted by group, ONE windowed call over all G x 512 rows against
+the loop of G dinox_retrieval_rank calls on the row slices -- what the evaluation would run without the windowed entry.  Same
+alternation, rounds and median; the two must agree bit for bit (checked).
+
+    python tools/retrieval_bench.py --groups 5     [ROUNDS=5 MIN_S=0.2 GROUP_ROWS=512 GROUP_D=384]
 """
+import argparse
 import json
 import os
 import statistics
@@ -47,8 +55,45 @@ def timed(fn, min_s):
     return a.elapsed_time(b) / reps
 
 
+def groups_main(G):
+    n, D = int(os.environ.get("GROUP_ROWS", 512)), int(os.environ.get("GROUP_D", 384))
+    N = G * n
+    g = torch.Generator(device=dev).manual_seed(0)
+    q = ops.normalize_rows(torch.randn(N, D, device=dev, generator=g))[0]
+    k = ops.normalize_rows(q + 0.5 * torch.randn(N, D, device=dev, generator=g))[0]
+    key_lo = (torch.arange(N, device=dev) // n * n).to(torch.int32)
+    key_hi = key_lo + n
+    slices = [(q[a:a + n], k[a:a + n]) for a in range(0, N, n)]
+    cands = {"windowed": lambda: ops.retrieval_rank_windowed(q, k, key_lo, key_hi),
+             "loop_of_rank_calls": lambda: [ops.retrieval_rank(a, b) for a, b in slices]}
+    for fn in cands.values():
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    one, many = cands["windowed"](), cands["loop_of_rank_calls"]()
+    same = all(torch.equal(one[o].view(torch.int32), torch.cat([m[o] for m in many]).view(torch.int32)) for o in (0, 2, 3)) and \
+        torch.equal(one[1], torch.cat([m[1] + i * n for i, m in enumerate(many)]))
+    times = {name: [] for name in cands}
+    for _ in range(ROUNDS):
+        for name, fn in cands.items():
+            times[name].append(timed(fn, MIN_S))
+    row = {"groups": G, "rows_per_group": n, "D": D, "bitwise_equal": bool(same)}
+    for name, ts in times.items():
+        med = statistics.median(ts)
+        row[name] = {"ms": round(med, 4), "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4), "spread": round((max(ts) - min(ts)) / med, 4)}
+        print(f"G={G:3d} n={n} D={D} {name:20s} {med:10.4f} ms  spread {100 * row[name]['spread']:.2f} %", flush=True)
+    row["windowed_over_loop"] = round(row["windowed"]["ms"] / row["loop_of_rank_calls"]["ms"], 4)
+    print(f"         windowed / loop = {row['windowed_over_loop']:.4f}  bitwise equal: {same}", flush=True)
+    print(json.dumps({"tool": "retrieval_bench", "mode": "groups", "rounds": ROUNDS, "min_s": MIN_S, "results": [row]}))
+
+
 def main():
     assert torch.cuda.is_available(), "retrieval_bench needs a GPU"
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--groups", type=int, default=0, metavar="G", help="time the windowed call against a loop of G per-group calls")
+    args = ap.parse_args()
+    if args.groups > 0:
+        return groups_main(args.groups)
     g = torch.Generator(device=dev).manual_seed(0)
     results = []
     for N, D in SHAPES:
