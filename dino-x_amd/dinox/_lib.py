@@ -16,7 +16,9 @@ import torch  # noqa: F401  (must precede the CDLL below)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DINOX_LIB") or os.path.join(_HERE, "libdinox_hip.so")     # DINOX_LIB: A/B another build of the same ABI
 
-F32, BF16 = 0, 1
+F32, BF16, U16, I16 = 0, 1, 2, 3
+FMT_HU_FLOAT, FMT_HU16_PNG, FMT_WINDOWED_FLOAT = 0, 1, 2
+EUNSUPPORTED = -2
 EPI_BIAS, EPI_GELU, EPI_DGELU, EPI_RESIDUAL, EPI_ACCUM, EPI_AUXGRAD = 1, 2, 4, 8, 16, 32
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
@@ -100,6 +102,8 @@ SIGNATURES = {
     "dinox_slice_views_lds_bytes": (i64, [i32, i32]),
     "dinox_slice_views": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
     "dinox_slice_views_patches": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "dinox_encode_preprocess_lds_bytes": (i64, [i32, i32]),
+    "dinox_encode_preprocess": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, C.c_double, C.c_double, i32, vp]),
     "dinox_softmax_rows": (i32, [vp, vp, i64, i32, i32, i64, vp]),
     "dinox_softmax_bwd_rows": (i32, [vp, vp, vp, f32, i64, i32, i32, i64, vp]),
     "dinox_koleo_normalize": (i32, [vp, vp, vp, vp, i64, i32, f32, vp]),

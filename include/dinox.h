@@ -36,6 +36,8 @@ extern "C" {
 /* dtype codes */
 #define DINOX_F32 0
 #define DINOX_BF16 1
+#define DINOX_U16 2   /* source planes of dinox_encode_preprocess only */
+#define DINOX_I16 3
 
 /* error codes (negative); positive returns are hipError_t values */
 #define DINOX_OK 0
@@ -276,6 +278,31 @@ int dinox_slice_views(const void* raw_u16, const int64_t* view_i, const float* v
  * makes of dinox_slice_views' output, without writing and re-reading the fp32 image batch (4 + 4 B per pixel). */
 int dinox_slice_views_patches(const void* raw_u16, const int64_t* view_i, const float* view_f, void* u, int V, int S, int max_crop,
                               int patch, int ld, int out_dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Inference-side preprocessing -- replaces the host code of zoo.encode (reference zoo/encode.py:34-72,129-157): source
+ * element -> fp32 -> format -> window -> PIL Image.BILINEAR resize of a mode-F image to S x S -> (v - mean_c) / std_c,
+ * one kernel, out = fp32 [n_images][3][S][S].
+ *   format  HU_FLOAT: as is;  HU16_PNG: (u - 32768) * 0.1;  WINDOWED_FLOAT: as is and no window.
+ *   window  clip(x, lo, hi), then (x - lo) / (hi - lo), a true fp32 division; lo and hi arrive as the doubles the reference
+ *           computes (level -+ width / 2) and are rounded as NumPy rounds them against an fp32 array.
+ *   resize  separable, horizontal first, fp32 intermediate; n -> S: scale = n / S, fs = max(scale, 1); output i has centre
+ *           (i + .5) scale, taps [max(int(centre - fs + .5), 0), min(int(centre + fs + .5), n)), weight max(0, 1 - |(x - centre
+ *           + .5) / fs|) renormalised to sum 1 (weights in double, sums in fp32).  n == S is the identity to the bit.
+ * The unit of work is a plane job: jobs[j] = {element offset of the plane in src, H, W, row stride, pixel stride (both in
+ * elements), number of destinations 1..3, three destinations image * 3 + channel (-1: unused)}, int64 [n_jobs][9] in device
+ * memory.  The plane is filtered once and written to each destination with that channel's mean / std -- a replicated (H, W)
+ * image is one job, plane z of a volume feeds the three 2.5D stacks it shows in.  The caller guarantees that every job stays
+ * inside src; a destination outside [0, 3 n_images) is skipped.  src_dtype: DINOX_U16 | DINOX_I16 | DINOX_F32, one per launch.
+ * max_side = the largest H or W in the table (sizes the LDS footprint; a plane that exceeds it is written as NaN).  More than
+ * 150 KiB of LDS (dinox_encode_preprocess_lds_bytes): DINOX_EUNSUPPORTED before any launch.  n_jobs <= 65535.
+ * ------------------------------------------------------------------------------------------ */
+#define DINOX_FMT_HU_FLOAT 0
+#define DINOX_FMT_HU16_PNG 1
+#define DINOX_FMT_WINDOWED_FLOAT 2
+int64_t dinox_encode_preprocess_lds_bytes(int S, int max_side);
+int dinox_encode_preprocess(const void* src, int src_dtype, const int64_t* jobs, int n_jobs, float* out, int n_images, int S,
+                            int max_side, double lo, double hi, int format, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * KoLeo regulariser -- replaces KoLeoLoss.forward (scripts/phase5_big_run.py:742-773), which the loop applies
