@@ -3,7 +3,8 @@ the golden fixtures captured from the reference and against the CPU oracle on th
 
 Tolerances: fp32 "parity mode" must meet the north-star gate of 1e-3 relative (we assert 1e-4 or
 tighter where fp32 round-off allows); bf16 "throughput mode" is compared by relative L2 error, since
-bf16 has 2^-9 relative precision per element (the reference's --amp path has the same property).
+bf16 keeps 8 significant bits, a unit roundoff of 2^-8 per element (the reference's --amp path has the same property);
+tests/test_attention_bounds_gpu.py judges the attention kernels element by element against bounds built from it.
 """
 import contextlib
 import math
