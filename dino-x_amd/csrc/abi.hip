@@ -5,6 +5,7 @@
 #include <unordered_map>
 
 #include "common.h"
+#include "kernels.h"
 
 namespace dinox {
 
@@ -87,4 +88,30 @@ extern "C" int dinox_device_ok(void) {
     return 0;
   }
   return 1;
+}
+
+// ---------------------------------------------------------------- NT-Xent entry points (kernels: ntxent.hip)
+static bool ntxent_rows_ok(int M) { return M >= 2 && M % 2 == 0 && M <= 65535 * 32; }
+
+extern "C" int dinox_ntxent_rows(const float* S, int64_t lds, int M, float inv_tau, float* lse, float* row_loss, float* loss, void* stream) {
+  DX_REQUIRE(S && lse && row_loss && loss, DINOX_EINVAL, "ntxent_rows: null pointer");
+  DX_REQUIRE(ntxent_rows_ok(M), DINOX_EINVAL, "ntxent_rows: M=%d (the rows are [z1; z2]: an even count of at least 2)", M);
+  DX_REQUIRE(lds >= M && inv_tau > 0.f, DINOX_EINVAL, "ntxent_rows: lds=%lld M=%d inv_tau=%g", (long long)lds, M, (double)inv_tau);
+  return dinox::launch_ntxent_rows(S, lds, M, inv_tau, lse, row_loss, loss, dinox::as_stream(stream));
+}
+
+extern "C" int dinox_ntxent_coeff(const float* S, int64_t lds, const float* lse, int M, float inv_tau, float gscale, float* W, int64_t ldw,
+                                  void* stream) {
+  DX_REQUIRE(S && lse && W, DINOX_EINVAL, "ntxent_coeff: null pointer");
+  DX_REQUIRE(ntxent_rows_ok(M), DINOX_EINVAL, "ntxent_coeff: M=%d (the rows are [z1; z2]: an even count of at least 2)", M);
+  DX_REQUIRE(lds >= M && ldw >= M && inv_tau > 0.f, DINOX_EINVAL, "ntxent_coeff: lds=%lld ldw=%lld M=%d inv_tau=%g", (long long)lds,
+             (long long)ldw, M, (double)inv_tau);
+  DX_REQUIRE(W != S, DINOX_EINVAL, "ntxent_coeff: W must not alias S (a tile reads its mirror image, which another workgroup writes)");
+  return dinox::launch_ntxent_coeff(S, lds, lse, M, inv_tau, gscale, W, ldw, dinox::as_stream(stream));
+}
+
+extern "C" int dinox_normalize_bwd(const float* dxh, const float* xh, const float* norm, float* dx, int64_t V, int D, float eps, void* stream) {
+  DX_REQUIRE(dxh && xh && norm && dx, DINOX_EINVAL, "normalize_bwd: null pointer");
+  DX_REQUIRE(V > 0 && V <= 0x7fffffff && D > 0 && eps > 0.f, DINOX_EINVAL, "normalize_bwd: V=%lld D=%d eps=%g", (long long)V, D, (double)eps);
+  return dinox::launch_normalize_bwd(dxh, xh, norm, dx, V, D, eps, dinox::as_stream(stream));
 }

@@ -1,0 +1,141 @@
+// ntxent.hip -- NT-Xent (SimCLR) loss head on the student head output.
+// Replaces SimCLRLoss.forward of the reference (scripts/phase5_big_run.py:776-813, used at :1728-1737) and its autograd backward:
+//     z^ = F.normalize(z) over the M = 2B rows [z1; z2];  s = z^ z^T / tau with the diagonal excluded;
+//     loss = mean_i ( logsumexp_{j != i} s_ij - s_{i p(i)} ),   p(i) = (i + B) mod 2B.
+// The two M x M x D products (S = Z^ Z^T and dZ^ = W Z^) go through dinox_gemm (exact-fp32 MFMA) and the row normalisation through
+// dinox_koleo_normalize (same formula, eps is an argument); here: the row pass over S, the coefficient matrix W of the backward and
+// the backward of the normalisation.
+//
+// Documented deviation: everything is fp32 in BOTH compute modes (as KoLeo).  Under --amp the reference's autocast runs the
+// similarity matmul in bf16; this engine stays at fp32 there, i.e. closer to the reference's own fp32 step.
+// No float atomics: every sum has a fixed order, so a step is bit-reproducible.
+#include "common.h"
+#include "kernels.h"
+
+namespace dinox {
+
+constexpr int NX_THREADS = 256;
+constexpr int NX_TILE = 32;
+
+// One workgroup per row i of S: lse[i] = logsumexp_{j != i} S[i][j] * inv_tau, row_loss[i] = lse[i] - S[i][p(i)] * inv_tau.
+// Skipping the diagonal equals the reference's -9e15 fill: exp(-9e15 - max) is 0 in fp32.
+__global__ __launch_bounds__(NX_THREADS) void ntxent_rows_kernel(const float* __restrict__ S, int64_t lds, int M, float inv_tau,
+                                                                 float* __restrict__ lse, float* __restrict__ row_loss) {
+  __shared__ float red[16];
+  const int i = blockIdx.x;
+  const float* row = S + (int64_t)i * lds;
+  float mx = -INFINITY;
+  for (int j = threadIdx.x; j < M; j += NX_THREADS)
+    if (j != i) mx = fmaxf(mx, row[j] * inv_tau);
+  mx = block_max(mx, red);
+  float a = 0.f;
+  for (int j = threadIdx.x; j < M; j += NX_THREADS)
+    if (j != i) a += expf(row[j] * inv_tau - mx);
+  a = block_sum(a, red);
+  if (threadIdx.x == 0) {
+    const int p = i + (M >> 1) < M ? i + (M >> 1) : i - (M >> 1);
+    const float l = mx + logf(a);
+    lse[i] = l;
+    row_loss[i] = l - row[p] * inv_tau;
+  }
+}
+
+// loss[0] = (sum_i row_loss[i]) / M, added in index order by one thread; the rows pass through LDS in chunks so that the loads are
+// one coalesced sweep and the serial chain is M dependent adds on LDS reads (M = 512: ~2 us).
+__global__ __launch_bounds__(NX_THREADS) void ntxent_mean_kernel(const float* __restrict__ row_loss, int M, float* __restrict__ loss) {
+  __shared__ float buf[1024];
+  float a = 0.f;
+  for (int base = 0; base < M; base += 1024) {
+    const int n = M - base < 1024 ? M - base : 1024;
+    for (int t = threadIdx.x; t < n; t += NX_THREADS) buf[t] = row_loss[base + t];
+    __syncthreads();
+    if (threadIdx.x == 0)
+      for (int t = 0; t < n; ++t) a += buf[t];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) loss[0] = a / (float)M;
+}
+
+// W[i][j] = scale * (exp(S_ij/tau - lse_i) + exp(S_ji/tau - lse_j) - [j = p(i)] - [i = p(j)]),  W[i][i] = 0,  scale = g / (M tau).
+// One workgroup per 32 x 32 tile: it reads the tile and its mirror image (S_ji through LDS, so both reads are coalesced); the GEMM
+// output is not assumed to be bit-symmetric.  W is a separate buffer: the workgroup of the mirror tile reads what this one would
+// overwrite.
+__global__ __launch_bounds__(NX_THREADS) void ntxent_coeff_kernel(const float* __restrict__ S, int64_t lds, const float* __restrict__ lse,
+                                                                  int M, float inv_tau, float scale, float* __restrict__ W, int64_t ldw) {
+  __shared__ float mir[NX_TILE][NX_TILE + 1];
+  const int tx = threadIdx.x & (NX_TILE - 1), ty = threadIdx.x >> 5;  // 32 x 8
+  const int i0 = blockIdx.y * NX_TILE, j0 = blockIdx.x * NX_TILE, half = M >> 1;
+  for (int r = ty; r < NX_TILE; r += NX_THREADS / NX_TILE) {           // mir[r][c] = S[j0 + r][i0 + c]
+    const int jj = j0 + r, ii = i0 + tx;
+    mir[r][tx] = (jj < M && ii < M) ? S[(int64_t)jj * lds + ii] : 0.f;
+  }
+  __syncthreads();
+  const int j = j0 + tx;
+  if (j >= M) return;
+  const float lj = lse[j];
+  for (int r = ty; r < NX_TILE; r += NX_THREADS / NX_TILE) {
+    const int i = i0 + r;
+    if (i >= M) break;
+    float w = 0.f;
+    if (i != j) {
+      const int pi = i + half < M ? i + half : i - half, pj = j + half < M ? j + half : j - half;
+      w = expf(S[(int64_t)i * lds + j] * inv_tau - lse[i]) + expf(mir[tx][r] * inv_tau - lj);
+      w -= (j == pi ? 1.f : 0.f) + (i == pj ? 1.f : 0.f);
+      w *= scale;
+    }
+    W[(int64_t)i * ldw + j] = w;
+  }
+}
+
+// Backward of xh = x / max(||x||, eps), one workgroup per row:  dx = (dxh - xh (xh . dxh)) / ||x||  where ||x|| >= eps, and
+// dx = dxh / eps where the clamp acted (what torch's clamp_min + norm backward give: no gradient reaches the norm there).
+template <bool VEC>
+__global__ __launch_bounds__(NX_THREADS) void normalize_bwd_kernel(const float* __restrict__ dxh, const float* __restrict__ xh,
+                                                                   const float* __restrict__ norm, float* __restrict__ dx, int D, float eps) {
+  __shared__ float red[16];
+  const int64_t r = blockIdx.x;
+  const float* g = dxh + r * D;
+  const float* u = xh + r * D;
+  float* o = dx + r * D;
+  const int D4 = VEC ? D >> 2 : 0;
+  float dot = 0.f;
+  for (int q = threadIdx.x; q < D4; q += NX_THREADS) {
+    const float4 gv = reinterpret_cast<const float4*>(g)[q], uv = reinterpret_cast<const float4*>(u)[q];
+    dot += gv.x * uv.x + gv.y * uv.y + gv.z * uv.z + gv.w * uv.w;
+  }
+  for (int d = 4 * D4 + threadIdx.x; d < D; d += NX_THREADS) dot += g[d] * u[d];
+  dot = block_sum(dot, red);
+  const float n = norm[r];
+  const bool clamped = n < eps;
+  const float inv = 1.0f / (clamped ? eps : n), c = clamped ? 0.f : dot;
+  for (int q = threadIdx.x; q < D4; q += NX_THREADS) {
+    const float4 gv = reinterpret_cast<const float4*>(g)[q], uv = reinterpret_cast<const float4*>(u)[q];
+    reinterpret_cast<float4*>(o)[q] = make_float4((gv.x - uv.x * c) * inv, (gv.y - uv.y * c) * inv, (gv.z - uv.z * c) * inv, (gv.w - uv.w * c) * inv);
+  }
+  for (int d = 4 * D4 + threadIdx.x; d < D; d += NX_THREADS) o[d] = (g[d] - u[d] * c) * inv;
+}
+
+int launch_ntxent_rows(const float* S, int64_t lds, int M, float inv_tau, float* lse, float* row_loss, float* loss, hipStream_t st) {
+  hipLaunchKernelGGL(ntxent_rows_kernel, dim3((unsigned)M), dim3(NX_THREADS), 0, st, S, lds, M, inv_tau, lse, row_loss);
+  const int rc = check_launch("ntxent_rows");
+  if (rc) return rc;
+  hipLaunchKernelGGL(ntxent_mean_kernel, dim3(1), dim3(NX_THREADS), 0, st, row_loss, M, loss);
+  return check_launch("ntxent_rows_mean");
+}
+
+int launch_ntxent_coeff(const float* S, int64_t lds, const float* lse, int M, float inv_tau, float gscale, float* W, int64_t ldw,
+                        hipStream_t st) {
+  const unsigned tiles = (unsigned)ceil_div(M, NX_TILE);
+  const float scale = gscale * inv_tau / (float)M;
+  hipLaunchKernelGGL(ntxent_coeff_kernel, dim3(tiles, tiles), dim3(NX_THREADS), 0, st, S, lds, lse, M, inv_tau, scale, W, ldw);
+  return check_launch("ntxent_coeff");
+}
+
+int launch_normalize_bwd(const float* dxh, const float* xh, const float* norm, float* dx, int64_t V, int D, float eps, hipStream_t st) {
+  const bool vec = D % 4 == 0 && (((uintptr_t)dxh | (uintptr_t)xh | (uintptr_t)dx) & 15) == 0;
+  if (vec) hipLaunchKernelGGL(normalize_bwd_kernel<true>, dim3((unsigned)V), dim3(NX_THREADS), 0, st, dxh, xh, norm, dx, D, eps);
+  else hipLaunchKernelGGL(normalize_bwd_kernel<false>, dim3((unsigned)V), dim3(NX_THREADS), 0, st, dxh, xh, norm, dx, D, eps);
+  return check_launch("normalize_bwd");
+}
+
+}  // namespace dinox

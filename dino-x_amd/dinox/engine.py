@@ -11,6 +11,11 @@ Follows the order of the reference loop (scripts/phase5_big_run.py:1692-1802) fo
     backward                                                        :1772
     global grad-norm, AdamW (wd on every parameter), EMA teacher    :1781-1802
 
+``loss_type="simclr"`` (:1728-1737): student fwd, student head on CLS, NT-Xent loss on the two halves of the logits
+(ops.ntxent_fwd / ntxent_bwd), backward, grad-norm + AdamW.  No teacher forward, no Gram, no KoLeo, no centre update and -- as
+the reference applies it for ``dino`` only (:1799) -- no EMA: teacher arena and centre stay bit-identical.  Single rank, no
+multi-crop (cross-rank negatives are not implemented).
+
 What is different from the reference, by design:
   * parameters, gradients, Adam moments and teacher weights live in flat fp32 arenas, so the grad-norm,
     AdamW and EMA are ONE kernel pass (dinox_adamw_ema) instead of 161 x (.item() + 2 EMA launches); the dW products
@@ -53,6 +58,8 @@ class StepHyperParams:
     beta1: float = 0.9
     beta2: float = 0.999
     adam_eps: float = 1e-8
+    loss_type: str = "dino"          # "dino" | "simclr" (SimCLRLoss on the student head output, reference :1728-1737)
+    simclr_temp: float = 0.1         # the reference hard-codes SimCLRLoss(temperature=0.1)
 
 
 def flatten_parameters(module: torch.nn.Module, align: int = 8) -> Tuple[torch.Tensor, List[torch.nn.Parameter], List[int]]:
@@ -93,6 +100,12 @@ class TrainEngine:
         self.compute_dtype = amp_dtype or torch.float32
         self.group = process_group
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
+        if hp.loss_type not in ("dino", "simclr"):
+            raise ValueError(f"loss_type must be 'dino' or 'simclr', got {hp.loss_type!r}")
+        self.simclr = hp.loss_type == "simclr"
+        if self.simclr and self.world > 1:
+            raise ValueError("loss_type='simclr' runs on a single rank only (the negatives of a row are the rows of ONE batch; "
+                             "cross-rank negatives are not implemented)")
         for p in teacher.parameters():
             p.requires_grad_(False)
         self.flat_p, self.params, self.offsets = flatten_parameters(student)
@@ -182,8 +195,11 @@ class TrainEngine:
         local_batch (L*B,3,s,s), view-major, with local_spacing (L*B,3): the multi-crop extension (not in the reference) --
         the student also sees L smaller crops per sample, which enter the DINO term only (every (teacher view, other student
         view) pair, averaged); Gram and KoLeo stay on the global views.
-        Returns device tensors {loss, dino, gram, koleo, grad_norm_sq} and the python float lr (no sync)."""
+        Returns device tensors {loss, dino, gram, koleo, grad_norm_sq} (plus simclr with ``loss_type="simclr"``) and the python float
+        lr (no sync)."""
         hp = self.hp
+        if self.simclr and local_batch is not None:
+            raise ValueError("loss_type='simclr' takes the two global views only (no local crops)")
         lr = get_lr(self.step_count, hp.max_steps, hp.warmup_steps, hp.lr, hp.min_lr)
         # gradient accumulation with the reference's semantics (phase5_big_run.py:1769-1796): `step` counts micro-batches,
         # loss/accum is back-propagated every micro-batch, the optimiser (and EMA) run when (step+1) % accum == 0 with the LR
@@ -201,6 +217,12 @@ class TrainEngine:
         ops.grad_sink.uses.clear()
         # (the unfolded batch is shared by student and teacher WITHIN this scope, never carried across steps)
         with ops.compute_dtype(self.compute_dtype), ops.unfold_share():
+            if self.simclr:
+                s_feats = self.student.backbone(batch, spacing=spacing2b)
+                self._mark("fwd_student")
+                loss = l_simclr = self._simclr_and_backward(s_feats)
+                l_dino = l_gram = l_koleo = self._zero1.reshape(())
+                return self._step_tail(lr, last, hyper, loss, l_dino, l_gram, l_koleo, l_simclr, None, None)
             main = torch.cuda.current_stream()
             # opt-in (DINOX_SIDE_STREAM=1): +1.3 % measured, but concurrent chains blur per-kernel timings, so bench/profiles keep it off
             side = self.side_stream if os.environ.get("DINOX_SIDE_STREAM") else None
@@ -225,17 +247,25 @@ class TrainEngine:
                     t_out = self.teacher.head(t_feats[:, 0])
                 loss, l_dino, l_gram, l_koleo, bm, bm_work = self._losses_and_backward_autograd(s_feats, t_feats, t_out, batch, local_batch,
                                                                                                 local_spacing)
+        return self._step_tail(lr, last, hyper, loss, l_dino, l_gram, l_koleo, self._zero1.reshape(()), bm, bm_work)
+
+    def _step_tail(self, lr, last, hyper, loss, l_dino, l_gram, l_koleo, l_simclr, bm, bm_work) -> dict:
+        """Everything after the backward pass: centre EMA (dino), gradient exchange, grad-norm + AdamW (+ teacher EMA, dino)."""
+        hp = self.hp
         ops.dw_stream.join()              # (weight-gradient products enqueued on the dW stream, when DINOX_DW_STREAM is set)
         self._mark("bwd")
         if bm_work is not None:
             bm_work.wait()
             bm.div_(self.world)           # (data parallel only)
-        ops.center_ema_(self.center.view(-1), bm, hp.center_momentum)
+        if not self.simclr:
+            ops.center_ema_(self.center.view(-1), bm, hp.center_momentum)
         self.bucketer.finish()
         self._mark("comm_exposed")        # what of the exchanges did not fit under backward (+ the centre EMA launch)
         if last:
             self.opt_steps += 1
-            gsq = ops.adamw_ema_(self.flat_p, self.flat_g, self.adam_m, self.adam_v, self.flat_t, lr=lr,
+            # simclr: no teacher pointer -> the pass has no EMA stage and the teacher arena is not touched (ema = 1.0 would still
+            # rewrite every element as 1.0 * t + 0.0 * w, which turns -0.0 into +0.0 and is NaN where w is not finite)
+            gsq = ops.adamw_ema_(self.flat_p, self.flat_g, self.adam_m, self.adam_v, None if self.simclr else self.flat_t, lr=lr,
                                  weight_decay=hp.weight_decay, beta1=hp.beta1, beta2=hp.beta2, eps=hp.adam_eps,
                                  step_t=self.opt_steps, ema=hp.ema, grad_scale=1.0 / self.world, hyper=hyper)
             ops.weight_cache.clear()     # master weights changed under the bf16 copies
@@ -248,6 +278,8 @@ class TrainEngine:
         self.step_count += 1
         self.last = {"loss": loss.detach(), "dino": l_dino.detach(), "gram": l_gram.detach(), "koleo": l_koleo.detach(),
                      "grad_norm_sq": gsq, "lr": lr}
+        if self.simclr:
+            self.last["simclr"] = l_simclr.detach()
         return self.last
 
     # -- everything above the backbones, without the framework's elementwise kernels ---------------------------------
@@ -341,6 +373,30 @@ class TrainEngine:
         return loss.reshape(()), l_dino.reshape(()), (l_gram if l_gram is not None else z).reshape(()), \
             (l_koleo if l_koleo is not None else z).reshape(()), bm, bm_work
 
+    def _simclr_and_backward(self, s_feats) -> torch.Tensor:
+        """Student head on the CLS rows, NT-Xent on the two halves of its output (reference :1729-1737) and the backward pass.  With the
+        stock head: by hand, like _losses_and_backward -- head products, ops.ntxent_fwd / ntxent_bwd, head backward, the CLS gradient
+        into a zeroed feature gradient, ONE autograd backward from the features down.  Otherwise through the per-op autograd nodes."""
+        hp, dt = self.hp, self.compute_dtype
+        if not self.manual_top:
+            s_out = self.student.head(s_feats[:, 0])
+            half = s_out.shape[0] // 2
+            loss = ops.simclr_loss(s_out[:half], s_out[half:], hp.simclr_temp)
+            self._mark("loss")
+            (loss if self.accum == 1 else loss / self.accum).backward()
+            return loss.detach()
+        with torch.no_grad():
+            sf = s_feats.detach()
+            z, saved = self._head_forward(self.student.head, ops.take_rows(sf, 0, dt), train=True)
+            loss, nsaved = ops.ntxent_fwd(z, hp.simclr_temp)
+            dcls = self._head_backward(self.student.head, saved, ops.ntxent_bwd(nsaved, 1.0 / self.accum))
+            dfeats = torch.empty_like(sf)
+            ops.zero_(dfeats)
+            ops.put_rows_(dfeats, 0, dcls)                                                                            # row 0 (CLS)
+        self._mark("loss")
+        torch.autograd.backward([s_feats], [dfeats])
+        return loss.reshape(())
+
     def _losses_and_backward_autograd(self, s_feats, t_feats, t_out, batch, local_batch, local_spacing):
         """The same through the per-op autograd nodes (a head whose layers were replaced, e.g. LoRA-wrapped)."""
         hp = self.hp
@@ -371,7 +427,11 @@ class TrainEngine:
 
     # -- convenience ------------------------------------------------------------------------------
     def scalars(self) -> dict:
-        """Host copies of the last step's scalars (this is the only place that synchronises)."""
+        """Host copies of the last step's scalars (this is the only place that synchronises).  ``loss_type="simclr"`` adds the key
+        "simclr"; a dino engine returns exactly the keys it always did, so whatever iterates over them sees no new entry."""
         r = self.last
-        return {"loss": float(r["loss"]), "dino": float(r["dino"]), "gram": float(r["gram"]), "koleo": float(r["koleo"]),
-                "grad_norm": float(r["grad_norm_sq"]) ** 0.5, "lr": r["lr"]}
+        out = {"loss": float(r["loss"]), "dino": float(r["dino"]), "gram": float(r["gram"]), "koleo": float(r["koleo"]),
+               "grad_norm": float(r["grad_norm_sq"]) ** 0.5, "lr": r["lr"]}
+        if self.simclr:
+            out["simclr"] = float(r["simclr"])
+        return out

@@ -1854,8 +1854,68 @@ def koleo_loss(x: Tensor, eps: float = 1e-8, group=None) -> Tensor:
     return KoLeoFn.apply(x, eps, group)
 
 
+def ntxent_fwd(z: Tensor, temperature: float = 0.1):
+    """NT-Xent / SimCLR loss on the student head output (reference scripts/phase5_big_run.py:776-813): z [2B, D] = [z1; z2],
+    z^ = F.normalize(z), s = z^ z^T / temperature without the diagonal, cross-entropy of row i against row (i + B) mod 2B, mean over
+    the 2B rows.  fp32 in both modes (the reference's --amp autocasts the similarity matmul to bf16; this stays more accurate).
+    Returns (loss[1], saved) -- no autograd, no framework kernel; ntxent_bwd(saved, gscale) gives d(gscale * loss)/dz."""
+    _need_cuda(z)
+    if z.dim() != 2 or z.shape[0] < 2 or z.shape[0] % 2:
+        raise ValueError(f"ntxent: z must be [2B, D] = [z1; z2] with B >= 1, got {tuple(z.shape)}")
+    if not temperature > 0.0:
+        raise ValueError(f"ntxent: temperature must be positive, got {temperature}")
+    z = _c(z.float())
+    M, D = z.shape
+    f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=z.device)
+    zh, norm, sq = f(M, D), f(M), f(M)
+    check(lib.dinox_koleo_normalize(_p(z), _p(zh), _p(norm), _p(sq), M, D, 1e-12, _stream()), "dinox_koleo_normalize")
+    S = gemm_nt_f32_splitk(zh, zh)                                      # [M, M] inner products, exact-fp32 MFMA
+    lse, row_loss, loss = f(M), f(M), f(1)
+    inv_tau = 1.0 / temperature
+    check(lib.dinox_ntxent_rows(_p(S), M, M, inv_tau, _p(lse), _p(row_loss), _p(loss), _stream()), "dinox_ntxent_rows")
+    return loss, (S, zh, norm, lse, inv_tau)
+
+
+def ntxent_bwd(saved, gscale: float = 1.0) -> Tensor:
+    """dz [2B, D] = d(gscale * NT-Xent loss) / dz (the upstream factor is a host scalar here: 1 / accumulation steps)."""
+    S, zh, norm, lse, inv_tau = saved
+    M, D = zh.shape
+    W = torch.empty_like(S)
+    check(lib.dinox_ntxent_coeff(_p(S), M, _p(lse), M, inv_tau, gscale, _p(W), M, _stream()), "dinox_ntxent_coeff")
+    dzh = gemm(W, zh, transB=True, out_dtype=torch.float32)             # dZ^ = W Z^  (W [M,M] symmetric, zero diagonal)
+    dz = torch.empty_like(zh)
+    check(lib.dinox_normalize_bwd(_p(dzh), _p(zh), _p(norm), _p(dz), M, D, 1e-12, _stream()), "dinox_normalize_bwd")
+    return dz
+
+
+class NTXentFn(torch.autograd.Function):
+    """ntxent_fwd / ntxent_bwd as an autograd node (the engine's fallback path and callers outside the engine)."""
+
+    @staticmethod
+    def forward(ctx, z, temperature):
+        loss, saved = ntxent_fwd(z, temperature)
+        ctx.saved = saved
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        # the upstream gradient is a device scalar: run with gscale = 1 and scale the result (one small elementwise multiply, no host sync)
+        return ntxent_bwd(ctx.saved, 1.0) * g, None
+
+
+def simclr_loss(z1: Tensor, z2: Tensor, temperature: float = 0.1) -> Tensor:
+    """SimCLRLoss(temperature)(z1, z2) of the reference: z1, z2 [B, D] are the head outputs of the two views."""
+    _need_cuda(z1, z2)
+    if z1.shape != z2.shape or z1.dim() != 2:
+        raise ValueError(f"simclr_loss: z1 and z2 must both be [B, D], got {tuple(z1.shape)} and {tuple(z2.shape)}")
+    return NTXentFn.apply(torch.cat([z1, z2], 0), temperature)
+
+
 def adamw_hyper(lr: float, beta1: float, beta2: float, step_t: int) -> list:
     """The three per-step scalars of the optimiser pass -- [lr, 1/(1-beta1^t), 1/sqrt(1-beta2^t)] -- for dinox_adamw_ema_dev."""
+    # with the betas as the fp32 values the C entry receives (dinox_adamw_ema raises (double)(float)beta to the step): the replayed
+    # launch then gets bit-for-bit the corrections of the eager one (0.999 as a double and as a float differ by 6e-6 in the second)
+    beta1, beta2 = C.c_float(beta1).value, C.c_float(beta2).value
     return [lr, 1.0 / (1.0 - beta1 ** step_t), 1.0 / math.sqrt(1.0 - beta2 ** step_t)]
 
 

@@ -17,8 +17,10 @@ loop :1686-1997), and the same importable names other reference scripts/tests us
   seeded 16-bit HU slice stacks for runs without a dataset (this environment has none); ``--gpu-views`` moves everything
   after the PNG decode (window, antialiased bicubic RandomResizedCrop, flip, normalise) into one HIP kernel (dinox/views.py);
 * ``--koleo-weight`` searches nearest neighbours over the GLOBAL batch under data parallelism (dinox.ops.KoLeoFn);
-* not wired to the engine yet (exit with a message): ``--loss-type simclr|mae``, ``--device cpu`` (there is no CPU
-  compute path).
+* ``--loss-type simclr`` (SimCLRLoss, temperature 0.1, on the student head output) runs on the fused NT-Xent kernels
+  (dinox.ops.ntxent_fwd / ntxent_bwd): no teacher forward, no Gram / KoLeo, no centre update and no teacher EMA, as in the
+  reference; one GPU and the two global views only (with ``--local-crops`` or more than one rank it exits with a message);
+* not wired to the engine yet (exit with a message): ``--loss-type mae``, ``--device cpu`` (there is no CPU compute path).
 """
 from __future__ import annotations
 
@@ -617,13 +619,24 @@ def resolve_model_config(args) -> ModelConfig:
     return cfg
 
 
+def check_loss_type(args, world: int = 1) -> None:
+    """Exit with a message for the objectives / combinations the engine does not run (host-side: touches no device)."""
+    if args.loss_type == "mae":
+        raise SystemExit("--loss-type mae is not wired to the MI355X engine yet (only 'dino' and 'simclr'; see DESIGN.md section 7)")
+    if args.loss_type == "simclr" and args.local_crops:
+        raise SystemExit("--loss-type simclr takes the two global views only: drop --local-crops (multi-crop is a DINO-term extension)")
+    if args.loss_type == "simclr" and world > 1:
+        raise SystemExit(f"--loss-type simclr runs on one GPU only (got {world} ranks): the negatives of a row are the rows of one batch, "
+                         "cross-rank negatives are not implemented")
+
+
 def main(argv=None) -> None:
     args = build_parser().parse_args(argv)
-    if args.loss_type != "dino":
-        raise SystemExit(f"--loss-type {args.loss_type} is not wired to the MI355X engine yet (only 'dino'; see DESIGN.md section 7)")
+    check_loss_type(args)
     if args.amp and args.amp_dtype != "bfloat16":
         raise SystemExit("the HIP path supports --amp-dtype bfloat16 only")
     rank, world, local = init_process_group()
+    check_loss_type(args, world)
     main_rank = rank == 0
 
     def say(*a):
@@ -781,7 +794,7 @@ def main(argv=None) -> None:
     hp = StepHyperParams(lr=args.lr, min_lr=args.min_lr, warmup_steps=args.warmup_steps, max_steps=args.max_steps,
                          weight_decay=args.weight_decay, ema=args.ema, teacher_temp=args.teacher_temp, student_temp=args.student_temp,
                          center_momentum=args.center_momentum, gram_weight=args.gram_weight,
-                         koleo_weight=args.koleo_weight)
+                         koleo_weight=args.koleo_weight, loss_type=args.loss_type)
     if args.hip_graph and (world > 1 or args.accumulation_steps != 1 or args.local_crops):
         raise SystemExit("--hip-graph: single GPU, --accumulation-steps 1 and no --local-crops (the captured step has one fixed batch layout)")
     if device.type == "cuda" and not args.hip_graph and args.streams != "off":

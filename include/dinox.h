@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define DINOX_ABI_VERSION 3   /* 3: + dinox_block_forward / _backward, dinox_gemm_timer_*, dinox_retrieval_* (later also dinox_retrieval_rank_windowed*, dinox_row_dots), dinox_knn_*, dinox_gram_*, dinox_softmax_probe* (all additive: no entry
+#define DINOX_ABI_VERSION 3   /* 3: + dinox_block_forward / _backward, dinox_gemm_timer_*, dinox_retrieval_* (later also dinox_retrieval_rank_windowed*, dinox_row_dots), dinox_knn_*, dinox_gram_*, dinox_softmax_probe*, dinox_ntxent_*, dinox_normalize_bwd (all additive: no entry
                                * of an earlier library changed, so the number callers test, dinox_version() == 3, stays; probe the symbol
                                * to learn whether a given build has the later additions) */
 
@@ -325,6 +325,23 @@ int dinox_koleo_nn(const float* G, int64_t ldg, const float* sq_all, const float
 int dinox_koleo_loss(const float* dist, int V, float eps, float* loss, void* stream);
 int dinox_koleo_bwd(const float* xh_all, const int* idx_all, const float* dist_all, const float* norm_loc, int row0, int V_l,
                     int V_g, int D, float gscale, float eps, float norm_eps, float* dx, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * NT-Xent (SimCLR) loss head -- replaces SimCLRLoss.forward (scripts/phase5_big_run.py:776-813, used at :1728-1737) and its
+ * backward: z^ = F.normalize(z) over the M = 2B rows [z1; z2] (dinox_koleo_normalize with eps = 1e-12); S = Z^ Z^T and
+ * dZ^ = W Z^ through dinox_gemm (fp32); these entries are the pieces around them.  fp32 in both compute modes.
+ * p(i) = (i + M/2) mod M is the row of i's positive; M even, >= 2.  Every sum has a fixed order (no atomics).
+ *   rows:          lse[i] = logsumexp_{j != i} S[i][j] * inv_tau;  row_loss[i] = lse[i] - S[i][p(i)] * inv_tau;
+ *                  loss[0] = (sum_i row_loss[i]) / M, added in index order.
+ *   coeff:         W[i][j] = gscale * inv_tau / M * (exp(S_ij inv_tau - lse_i) + exp(S_ji inv_tau - lse_j) - [j = p(i)] - [i = p(j)]),
+ *                  W[i][i] = 0, so that d(gscale * loss)/dZ^ = W Z^.  S_ij and S_ji are both read; W must not alias S.
+ *   normalize_bwd: through xh = x / max(||x||, eps) with norm[r] = ||x_r||:  dx = (dxh - xh (xh . dxh)) / ||x||, and
+ *                  dx = dxh / eps for rows with ||x|| < eps (torch's clamp_min backward).
+ * ------------------------------------------------------------------------------------------ */
+int dinox_ntxent_rows(const float* S, int64_t lds, int M, float inv_tau, float* lse, float* row_loss, float* loss, void* stream);
+int dinox_ntxent_coeff(const float* S, int64_t lds, const float* lse, int M, float inv_tau, float gscale, float* W, int64_t ldw,
+                       void* stream);
+int dinox_normalize_bwd(const float* dxh, const float* xh, const float* norm, float* dx, int64_t V, int D, float eps, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Optimiser tail -- replaces the per-parameter grad-norm loop (scripts/phase5_big_run.py:1784-1789),
