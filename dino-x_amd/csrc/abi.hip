@@ -115,3 +115,15 @@ extern "C" int dinox_normalize_bwd(const float* dxh, const float* xh, const floa
   DX_REQUIRE(V > 0 && V <= 0x7fffffff && D > 0 && eps > 0.f, DINOX_EINVAL, "normalize_bwd: V=%lld D=%d eps=%g", (long long)V, D, (double)eps);
   return dinox::launch_normalize_bwd(dxh, xh, norm, dx, V, D, eps, dinox::as_stream(stream));
 }
+
+// ---------------------------------------------------------------- attention rows (kernel: attention_rows.hip)
+extern "C" int dinox_attention_rows_ok(int B, int N, int heads, int d, int Q) { return dinox::attention_rows_ok(B, N, heads, d, Q) ? 1 : 0; }
+
+extern "C" int dinox_attention_rows(const void* qkv, const int* query_idx, float* probs, float* lse, int B, int N, int heads, int d, int Q,
+                                    int dtype, void* stream) {
+  DX_REQUIRE(qkv && query_idx && probs, DINOX_EINVAL, "attention_rows: null pointer");
+  DX_REQUIRE(dtype == DINOX_F32 || dtype == DINOX_BF16, DINOX_EINVAL, "attention_rows: dtype %d", dtype);
+  DX_REQUIRE(dinox::attention_rows_ok(B, N, heads, d, Q), DINOX_EINVAL,
+             "attention_rows: B=%d N=%d heads=%d d=%d Q=%d (B, N, heads >= 1; 1 <= d <= 256; 1 <= Q <= 8)", B, N, heads, d, Q);
+  return dinox::launch_attention_rows(qkv, query_idx, probs, lse, B, N, heads, d, Q, dtype, dinox::as_stream(stream));
+}

@@ -73,6 +73,11 @@ int launch_ntxent_rows(const float* S, int64_t lds, int M, float inv_tau, float*
 int launch_ntxent_coeff(const float* S, int64_t lds, const float* lse, int M, float inv_tau, float gscale, float* W, int64_t ldw, hipStream_t st);
 int launch_normalize_bwd(const float* dxh, const float* xh, const float* norm, float* dx, int64_t V, int D, float eps, hipStream_t st);
 
+// ---------------------------------------------------------------- attention rows (attention_rows.hip; entry points: abi.hip)
+bool attention_rows_ok(int B, int N, int heads, int d, int Q);
+int launch_attention_rows(const void* qkv, const int* query_idx, float* probs, float* lse, int B, int N, int heads, int d, int Q, int dtype,
+                          hipStream_t st);
+
 // ---------------------------------------------------------------- launch glue shared by the NT launchers
 // Activation index of the <OUT, ACT, RES> kernels (gemm_bf16_pp / _pp128 / _areg): the template argument ACT.
 enum { EPI_ACT_PLAIN = 0, EPI_ACT_GELU = 1, EPI_ACT_DGELU = 2 };

@@ -113,6 +113,8 @@ SIGNATURES = {
     "dinox_ntxent_rows": (i32, [vp, i64, i32, f32, vp, vp, vp, vp]),
     "dinox_ntxent_coeff": (i32, [vp, i64, vp, i32, f32, f32, vp, i64, vp]),
     "dinox_normalize_bwd": (i32, [vp, vp, vp, vp, i64, i32, f32, vp]),
+    "dinox_attention_rows_ok": (i32, [i32, i32, i32, i32, i32]),
+    "dinox_attention_rows": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "dinox_adamw_ema": (i32, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, f32, vp, vp, vp]),
     "dinox_adamw_ema_dev": (i32, [vp, vp, vp, vp, vp, i64, vp, f32, f32, f32, f32, f32, f32, vp, vp, vp]),
     "dinox_sumsq": (i32, [vp, i64, vp, vp, vp]),

@@ -1311,6 +1311,56 @@ class AttentionCoreFn(torch.autograd.Function):
         return attention_bwd(do, qkv, o, lse, ctx.heads), None
 
 
+ATTENTION_ROWS_MAX_Q = 8
+ATTENTION_ROWS_MAX_D = 256
+
+
+def attention_rows(qkv: Tensor, heads: int, query_idx, want_lse: bool = False):
+    """Softmax rows of a few query tokens over all keys, per head (dinox_attention_rows): the probabilities the attention cores never keep.
+    qkv: packed [B, N, 3 heads d] (or [B, N, 3, heads, d]) fp32 or bf16 on the device, as attention_fwd takes it; query_idx: 1..8 token
+    indices in [0, N) (a sequence of ints or an integer tensor; repeats allowed).  -> probs [B, heads, Q, N] fp32, and with want_lse
+    also lse [B, heads, Q] fp32.  No gradient is defined: the result is detached.  Arguments are checked on the host: ValueError."""
+    if not isinstance(qkv, Tensor) or not qkv.is_cuda:
+        raise ValueError("attention_rows: qkv must be a tensor on a CUDA/HIP device (the MI355X kernel library is the only compute path)")
+    if qkv.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"attention_rows: qkv must be float32 or bfloat16, got {qkv.dtype}")
+    if qkv.dim() == 5:
+        if qkv.shape[2] != 3 or qkv.shape[3] != heads:
+            raise ValueError(f"attention_rows: a 5-D qkv must be [B, N, 3, heads={heads}, d], got {tuple(qkv.shape)}")
+        qkv = qkv.reshape(qkv.shape[0], qkv.shape[1], -1)
+    if qkv.dim() != 3:
+        raise ValueError(f"attention_rows: qkv must be [B, N, 3 heads d], got {tuple(qkv.shape)}")
+    B, N, C3 = qkv.shape
+    if not isinstance(heads, int) or heads < 1 or C3 % (3 * heads) or B < 1 or N < 1 or C3 < 1:
+        raise ValueError(f"attention_rows: qkv {tuple(qkv.shape)} is not [B >= 1, N >= 1, 3 x heads={heads} x d]")
+    d = C3 // (3 * heads)
+    if d > ATTENTION_ROWS_MAX_D:
+        raise ValueError(f"attention_rows: head size {d} above {ATTENTION_ROWS_MAX_D}")
+    if isinstance(query_idx, Tensor):
+        if query_idx.dim() != 1 or query_idx.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"attention_rows: query_idx must be a 1-D int32 / int64 tensor, got {query_idx.dtype} {tuple(query_idx.shape)}")
+        idx = query_idx.tolist()
+    else:
+        idx = list(query_idx)
+        if not all(isinstance(i, int) and not isinstance(i, bool) for i in idx):
+            raise ValueError(f"attention_rows: query_idx must hold integers, got {idx}")
+    Q = len(idx)
+    if not 1 <= Q <= ATTENTION_ROWS_MAX_Q:
+        raise ValueError(f"attention_rows: 1 to {ATTENTION_ROWS_MAX_Q} query rows, got {Q}")
+    if any(i < 0 or i >= N for i in idx):
+        raise ValueError(f"attention_rows: query_idx {idx} outside [0, {N})")
+    if not lib.dinox_attention_rows_ok(B, N, heads, d, Q):
+        raise ValueError(f"attention_rows: B={B} N={N} heads={heads} d={d} Q={Q} outside the kernel")
+    qkv = _c(qkv.detach())
+    qi = torch.tensor(idx, dtype=torch.int32, device=qkv.device)
+    probs = torch.empty((B, heads, Q, N), dtype=torch.float32, device=qkv.device)
+    lse = torch.empty((B, heads, Q), dtype=torch.float32, device=qkv.device) if want_lse else None
+    if TRACE_KERNELS is not None:
+        TRACE_KERNELS.append("attention_rows")
+    check(lib.dinox_attention_rows(_p(qkv), _p(qi), _p(probs), _p(lse), B, N, heads, d, Q, _code(qkv.dtype), _stream()), "dinox_attention_rows")
+    return (probs, lse) if want_lse else probs
+
+
 class _UnfoldShare:
     """The student and the teacher of one training step see the same batch (scripts/phase5_big_run.py:1741-1743) and can share
     its unfolded form.  Sharing is OPT-IN and scoped: only inside ``with unfold_share():`` (TrainEngine.step) is an unfolded

@@ -20,6 +20,11 @@ loop :1686-1997), and the same importable names other reference scripts/tests us
 * ``--loss-type simclr`` (SimCLRLoss, temperature 0.1, on the student head output) runs on the fused NT-Xent kernels
   (dinox.ops.ntxent_fwd / ntxent_bwd): no teacher forward, no Gram / KoLeo, no centre update and no teacher EMA, as in the
   reference; one GPU and the two global views only (with ``--local-crops`` or more than one rank it exits with a message);
+* ``--monitor-every N`` (default 1000, 0 = off): every N steps the main rank runs ``dinox.monitor.run_monitor`` on the student
+  backbone and the first (at most 32) images of the current batch and writes ``run_dir/monitor/step_XXXXXXXX/`` -- the reference's
+  patch-norm heatmap, the CLS attention of the last block per head (which the reference cannot produce), the input slice and
+  ``stats.json`` (embedding std / norm, per-head attention entropy) as ``.npy`` and PNG (there is no TensorBoard here); the embedding
+  std feeds ``detect_anomaly``; prints ``monitor_saved=``.  Training is bit-identical with and without it;
 * not wired to the engine yet (exit with a message): ``--loss-type mae``, ``--device cpu`` (there is no CPU compute path).
 """
 from __future__ import annotations
@@ -933,6 +938,18 @@ def main(argv=None) -> None:
             save_checkpoint(path, step + 1, student, teacher, eng, cfg)
             say(f"checkpoint_saved={path}")
             rotate_checkpoints(run_dir, args.ckpt_keep_last)
+        if args.monitor_every and (step + 1) % args.monitor_every == 0 and main_rank:
+            # One no-grad forward of the student backbone on (at most) the first 32 images of this batch, eagerly, after the step
+            # (and between two replays under --hip-graph): no random draw, no write to parameters, centre or optimiser, no collective.
+            from dinox.monitor import first_images, run_monitor
+            mon_batch, mon_plane = first_images(batch, 32)
+            with ops.compute_dtype(eng.compute_dtype):
+                mon = run_monitor(student.backbone, mon_batch, None if sp2 is None else sp2[:mon_batch.shape[0]], run_dir / "monitor", step + 1,
+                                  input_plane=mon_plane)
+            say(f"monitor_saved={mon['dir']} embedding_std_mean={mon['embedding_std_mean']:.6f} embedding_norm_mean={mon['embedding_norm_mean']:.4f}")
+            bad, msg = detect_anomaly(0.0, [], embedding_std=mon["embedding_std_mean"])      # (the loss has its own check above)
+            if bad:
+                say(f"⚠️  WARNING: {msg}")
     for s_, loss_t, lr_ in pending:
         loss_val = read_loss(loss_t)
         loss_history.append(loss_val)

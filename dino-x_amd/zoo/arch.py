@@ -26,7 +26,7 @@ import torch.nn as nn
 from dinox import ops
 
 __all__ = ["Attention", "Mlp", "TransformerBlock", "ScaleEmbedding", "PatchViT", "DinoStudentTeacher",
-           "migrate_state_dict", "needs_migration"]
+           "migrate_state_dict", "needs_migration", "cls_attention_grid"]
 
 
 # ------------------------------------------------------------------------------------------
@@ -219,6 +219,31 @@ class PatchViT(nn.Module):
             nn.init.trunc_normal_(self.registers, std=0.02)
 
     def forward(self, x: torch.Tensor, spacing: Optional[torch.Tensor] = None) -> torch.Tensor:
+        return self._forward(x, spacing, None)
+
+    def last_attention(self, x: torch.Tensor, spacing: Optional[torch.Tensor] = None, query_tokens=(0,), layer: int = -1):
+        """-> (feats, probs): ``feats`` is ``self.forward(x, spacing)`` (the same launches, bit for bit) and ``probs``
+        [B, heads, Q, T], T = 1 + P + registers, holds the softmax rows of block ``layer`` for the query tokens (0 = CLS;
+        1 + P .. are the registers) over all T keys, in fp32 (``ops.attention_rows``).  The fused attention kernels never keep the
+        probabilities, so before block ``layer`` runs its ``norm1`` output goes through ``attn.qkv`` once more and the rows are
+        read from that product; the block itself then runs as usual.  No-grad, in the current compute dtype."""
+        depth = len(self.blocks)
+        if not isinstance(layer, int) or not -depth <= layer < depth:
+            raise ValueError(f"layer {layer} outside a model of {depth} blocks")
+        if x.shape[0] == 0:
+            raise ValueError("last_attention needs at least one image")
+        tap = {"layer": layer % depth, "query": tuple(int(q) for q in query_tokens), "probs": None}
+        with torch.no_grad():
+            feats = self._forward(x, spacing, tap)
+        return feats, tap["probs"]
+
+    @staticmethod
+    def _tap_rows(tap, i: int, blk: "TransformerBlock", t: torch.Tensor, pre) -> None:
+        if tap is not None and tap["layer"] == i:
+            y = pre[0].view(t.shape) if pre is not None else blk.norm1(t)
+            tap["probs"] = ops.attention_rows(blk.attn.qkv(y), blk.attn.num_heads, tap["query"])
+
+    def _forward(self, x: torch.Tensor, spacing: Optional[torch.Tensor], tap) -> torch.Tensor:
         g = x.shape[-1] // self.patch
         if x.shape[-2] != x.shape[-1] or x.shape[-1] % self.patch:
             raise ValueError(f"input {tuple(x.shape[-2:])} is not a square multiple of the {self.patch}-pixel patch")
@@ -245,14 +270,26 @@ class PatchViT(nn.Module):
             pre = None
             for i, blk in enumerate(self.blocks):
                 last = i + 1 == len(self.blocks)
+                self._tap_rows(tap, i, blk, t, pre)
                 t, pre = blk.forward_chained(t, pre, self.norm if last else self.blocks[i + 1].norm1, torch.float32 if last else None)
             return ops.LayerNormPrecomputedFn.apply(t, self.norm.weight, self.norm.bias, *pre)
-        for blk in self.blocks:
+        for i, blk in enumerate(self.blocks):
+            self._tap_rows(tap, i, blk, t, None)
             if self.use_grad_checkpoint and self.training:
                 t = torch.utils.checkpoint.checkpoint(blk, t, use_reentrant=False, context_fn=ops.checkpoint_contexts)
             else:
                 t = blk(t)
         return self.norm(t, out_dtype=torch.float32)
+
+
+def cls_attention_grid(probs: torch.Tensor, n_patches: int) -> torch.Tensor:
+    """Row 0 (the first query token: CLS) of ``last_attention``'s probs [B, heads, Q, T] over the P = n_patches patch keys, columns
+    1 .. P of the [CLS, patches, registers] order, as [B, heads, g, g].  The mass on CLS and the registers is left out, so a map sums
+    to less than 1 by exactly that mass."""
+    g = int(round(n_patches ** 0.5))
+    if probs.dim() != 4 or g * g != n_patches or probs.shape[-1] < 1 + n_patches:
+        raise ValueError(f"probs {tuple(probs.shape)} is not [B, heads, Q, T >= 1 + {n_patches}] with a square number of patches")
+    return probs[:, :, 0, 1:1 + n_patches].reshape(probs.shape[0], probs.shape[1], g, g)
 
 
 class DinoHead(nn.Sequential):

@@ -13,12 +13,12 @@ series: the volume goes to the device once and every plane is resized once for t
 """
 from __future__ import annotations
 
-from typing import List, Literal, Sequence, Tuple, Union
+from typing import List, Literal, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
 
-from zoo.arch import PatchViT
+from zoo.arch import PatchViT, cls_attention_grid
 
 _MEAN = np.array([0.485, 0.456, 0.406], dtype=np.float32).reshape(3, 1, 1)
 _STD = np.array([0.229, 0.224, 0.225], dtype=np.float32).reshape(3, 1, 1)
@@ -97,6 +97,26 @@ def encode(model: PatchViT, image: np.ndarray, pixel_spacing: Tuple[float, float
     with torch.no_grad():
         feats = model(x, spacing=spacing)
     return feats if return_all_tokens else feats[:, 0:1, :]
+
+
+def attention_map(model: PatchViT, image: np.ndarray, pixel_spacing: Optional[Tuple[float, float]] = None,
+                  slice_thickness: Optional[float] = None, *,
+                  input_format: Literal["hu_float", "hu16_png", "windowed_float"] = "hu_float", hu_level: float = 40.0,
+                  hu_width: float = 400.0, layer: int = -1, device: Union[str, torch.device, None] = None,
+                  preprocess: Literal["host", "device", "auto"] = "host") -> torch.Tensor:
+    """CLS attention of block ``layer`` (default: the last) over the patches of one image: ``(heads, g, g)`` fp32 on the CPU, g =
+    img_size / patch.  Same preprocessing, argument checking and spacing convention as ``encode`` (spacing None = 1.0 mm; it is used
+    by scale-aware models only).  Each head's map sums to 1 minus the mass that head puts on CLS and the registers.  The softmax rows
+    come from ``PatchViT.last_attention`` (``csrc/attention_rows.hip``): the probabilities themselves, not a token-norm proxy."""
+    if device is None:
+        device = next(model.parameters()).device
+    x = _batch([image], model.img_size, input_format, hu_level, hu_width, device, preprocess)
+    spacing = None
+    if model.scale_aware:
+        sx, sy = (1.0, 1.0) if pixel_spacing is None else pixel_spacing
+        spacing = torch.tensor([[sx, sy, 1.0 if slice_thickness is None else slice_thickness]], dtype=torch.float32, device=device)
+    _, probs = model.last_attention(x, spacing, query_tokens=(0,), layer=layer)
+    return cls_attention_grid(probs, (model.img_size // model.patch) ** 2)[0].float().cpu()
 
 
 def encode_batch(model: PatchViT, images: Sequence[np.ndarray], spacings: Sequence[Tuple[float, float, float]], *,

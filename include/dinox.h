@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define DINOX_ABI_VERSION 3   /* 3: + dinox_block_forward / _backward, dinox_gemm_timer_*, dinox_retrieval_* (later also dinox_retrieval_rank_windowed*, dinox_row_dots), dinox_knn_*, dinox_gram_*, dinox_softmax_probe*, dinox_ntxent_*, dinox_normalize_bwd (all additive: no entry
+#define DINOX_ABI_VERSION 3   /* 3: + dinox_block_forward / _backward, dinox_gemm_timer_*, dinox_retrieval_* (later also dinox_retrieval_rank_windowed*, dinox_row_dots), dinox_knn_*, dinox_gram_*, dinox_softmax_probe*, dinox_ntxent_*, dinox_normalize_bwd, dinox_attention_rows* (all additive: no entry
                                * of an earlier library changed, so the number callers test, dinox_version() == 3, stays; probe the symbol
                                * to learn whether a given build has the later additions) */
 
@@ -342,6 +342,21 @@ int dinox_ntxent_rows(const float* S, int64_t lds, int M, float inv_tau, float* 
 int dinox_ntxent_coeff(const float* S, int64_t lds, const float* lse, int M, float inv_tau, float gscale, float* W, int64_t ldw,
                        void* stream);
 int dinox_normalize_bwd(const float* dxh, const float* xh, const float* norm, float* dx, int64_t V, int D, float eps, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Attention rows -- the softmax rows of a few query tokens (CLS, the registers) over all keys, per head: the attention map the
+ * reference's roadmap asks for and its fused SDPA cannot return (scripts/phase5_monitor.py draws a patch-norm proxy instead).
+ *   qkv        [B, N, 3, heads, d] packed as dinox_attention_fwd takes it, dtype DINOX_F32 or DINOX_BF16; V is never read
+ *   query_idx  [Q] int32 ON THE DEVICE, each in [0, N); an entry outside turns its row and its lse into NaN (nothing is read for it)
+ *   probs      [B, heads, Q, N] fp32 = softmax_j(q_i . k_j / sqrt(d)); also the kernel's score buffer, so it must not alias qkv
+ *   lse        [B, heads, Q] fp32 log-sum-exp of the scaled scores, or NULL
+ * fp32 scores (bf16 products are exact), fp32 maximum, sum and probabilities; fixed reduction order, no atomics: bit-reproducible.
+ * One workgroup per (image, head).  1 <= Q <= 8, 1 <= d <= 256, B, N, heads >= 1 (dinox_attention_rows_ok: host only, 1 inside);
+ * anything else returns DINOX_EINVAL.
+ * ------------------------------------------------------------------------------------------ */
+int dinox_attention_rows_ok(int B, int N, int heads, int d, int Q);
+int dinox_attention_rows(const void* qkv, const int* query_idx, float* probs, float* lse, int B, int N, int heads, int d, int Q, int dtype,
+                         void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Optimiser tail -- replaces the per-parameter grad-norm loop (scripts/phase5_big_run.py:1784-1789),
