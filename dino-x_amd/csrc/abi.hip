@@ -127,3 +127,21 @@ extern "C" int dinox_attention_rows(const void* qkv, const int* query_idx, float
              "attention_rows: B=%d N=%d heads=%d d=%d Q=%d (B, N, heads >= 1; 1 <= d <= 256; 1 <= Q <= 8)", B, N, heads, d, Q);
   return dinox::launch_attention_rows(qkv, query_idx, probs, lse, B, N, heads, d, Q, dtype, dinox::as_stream(stream));
 }
+
+// ---------------------------------------------------------------- attention rollout step (kernels: attention_rollout.hip)
+extern "C" int dinox_attention_rollout_step_ok(int B, int N, int heads, int d) { return dinox::attention_rollout_step_ok(B, N, heads, d) ? 1 : 0; }
+
+extern "C" size_t dinox_attention_rollout_step_ws_bytes(int B, int N, int heads) { return dinox::attention_rollout_step_ws_bytes(B, N, heads); }
+
+extern "C" int dinox_attention_rollout_step(const void* qkv, const float* w_in, float* w_out, void* ws, int B, int N, int heads, int d,
+                                            float residual, int dtype, void* stream) {
+  DX_REQUIRE(qkv && w_in && w_out && ws, DINOX_EINVAL, "attention_rollout_step: null pointer");
+  DX_REQUIRE(dtype == DINOX_F32 || dtype == DINOX_BF16, DINOX_EINVAL, "attention_rollout_step: dtype %d", dtype);
+  DX_REQUIRE(dinox::attention_rollout_step_ok(B, N, heads, d), DINOX_EINVAL,
+             "attention_rollout_step: B=%d N=%d heads=%d d=%d (B, heads >= 1; 1 <= N <= 4096; 1 <= d <= 256)", B, N, heads, d);
+  DX_REQUIRE(residual >= 0.f && residual <= 1.f, DINOX_EINVAL, "attention_rollout_step: residual %g outside [0, 1]", (double)residual);
+  const float* in_end = w_in + (size_t)B * N;
+  const float* out_end = w_out + (size_t)B * N;
+  DX_REQUIRE(in_end <= w_out || out_end <= w_in, DINOX_EINVAL, "attention_rollout_step: w_out must not alias w_in (the fold reads w_in)");
+  return dinox::launch_attention_rollout_step(qkv, w_in, w_out, ws, B, N, heads, d, residual, dtype, dinox::as_stream(stream));
+}

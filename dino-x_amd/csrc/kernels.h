@@ -78,6 +78,12 @@ bool attention_rows_ok(int B, int N, int heads, int d, int Q);
 int launch_attention_rows(const void* qkv, const int* query_idx, float* probs, float* lse, int B, int N, int heads, int d, int Q, int dtype,
                           hipStream_t st);
 
+// ---------------------------------------------------------------- attention rollout step (attention_rollout.hip; entry points: abi.hip)
+bool attention_rollout_step_ok(int B, int N, int heads, int d);
+size_t attention_rollout_step_ws_bytes(int B, int N, int heads);
+int launch_attention_rollout_step(const void* qkv, const float* w_in, float* w_out, void* ws, int B, int N, int heads, int d, float residual,
+                                  int dtype, hipStream_t st);
+
 // ---------------------------------------------------------------- launch glue shared by the NT launchers
 // Activation index of the <OUT, ACT, RES> kernels (gemm_bf16_pp / _pp128 / _areg): the template argument ACT.
 enum { EPI_ACT_PLAIN = 0, EPI_ACT_GELU = 1, EPI_ACT_DGELU = 2 };

@@ -115,6 +115,8 @@ SIGNATURES = {
     "dinox_normalize_bwd": (i32, [vp, vp, vp, vp, i64, i32, f32, vp]),
     "dinox_attention_rows_ok": (i32, [i32, i32, i32, i32, i32]),
     "dinox_attention_rows": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "dinox_attention_rollout_step_ok": (i32, [i32, i32, i32, i32]),
+    "dinox_attention_rollout_step": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp]),
     "dinox_adamw_ema": (i32, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, f32, vp, vp, vp]),
     "dinox_adamw_ema_dev": (i32, [vp, vp, vp, vp, vp, i64, vp, f32, f32, f32, f32, f32, f32, vp, vp, vp]),
     "dinox_sumsq": (i32, [vp, i64, vp, vp, vp]),
@@ -146,6 +148,12 @@ SIGNATURES = {
 }
 
 
+# Entry points whose return type is size_t (SIGNATURES holds the int / int64_t / const char* ones, which tests/test_abi.py matches
+# against the header one to one).
+SIZE_T_SIGNATURES = {
+    "dinox_attention_rollout_step_ws_bytes": (C.c_size_t, [i32, i32, i32]),
+}
+
 class DinoxLibraryError(ImportError):
     pass
 
@@ -160,7 +168,7 @@ def _load() -> C.CDLL:
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # missing libamdhip64 etc.
         raise DinoxLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **SIZE_T_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

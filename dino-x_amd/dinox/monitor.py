@@ -3,10 +3,13 @@
 Counterpart of the reference's monitoring (``make_attention_heatmap`` of scripts/phase5_big_run.py:85-113, called every
 ``--monitor-every`` steps at :1893-1906, and the statistics of scripts/phase5_monitor.py:245-252).  The reference can draw only a
 patch-token-norm proxy, because its fused SDPA returns no probabilities; here ``PatchViT.last_attention`` reads the CLS softmax rows of
-the last block from the packed qkv rows (``csrc/attention_rows.hip``), so the monitor writes the proxy AND the attention itself.
+the last block from the packed qkv rows (``csrc/attention_rows.hip``), so the monitor writes the proxy AND the attention itself, and on
+request the attention rollout of CLS through every block (``PatchViT.attention_rollout``, ``csrc/attention_rollout.hip``).
 
-``run_monitor`` is one no-grad forward: it draws no random number, writes no parameter, centre or optimiser state and issues no
-collective, so a training run with and without it is bit-identical.
+``run_monitor`` is one no-grad forward (two with ``rollout=True``, plus the rollout chain): it draws no random number, writes no
+parameter, centre or optimiser state and issues no collective, so a training run with and without it is bit-identical.  Under a
+captured training step (``TrainEngine(use_graph=True)``, ``--hip-graph``) nothing of it is part of the graph: the caller runs it after
+a step, eagerly, between two replays, on buffers of its own, and the cached weight images are dropped around it (see ``run_monitor``).
 """
 from __future__ import annotations
 
@@ -76,7 +79,8 @@ def _save_png(arr: np.ndarray, path: str, size: Optional[int] = None) -> None:
     img.save(path)
 
 
-def run_monitor(backbone, batch, spacing, out_dir, step: int, input_plane: Optional[torch.Tensor] = None, extra: Optional[dict] = None) -> dict:
+def run_monitor(backbone, batch, spacing, out_dir, step: int, input_plane: Optional[torch.Tensor] = None, extra: Optional[dict] = None,
+                rollout: bool = False) -> dict:
     """One no-grad ``backbone.last_attention`` on ``batch`` ([B, 3, S, S] or a PatchOperand; ``spacing`` [B, 3] or None), then
     ``out_dir/step_{step:08d}/`` receives
         heatmap.npy    [g, g]         patch-norm heatmap of image 0 (the reference's picture)
@@ -84,7 +88,12 @@ def run_monitor(backbone, batch, spacing, out_dir, step: int, input_plane: Optio
         input.npy      [S, S]         channel 1 (the middle slice) of image 0
         stats.json     step, embedding_std_mean, embedding_norm_mean (over the B CLS embeddings), attention_entropy (per head, mean over
                        the batch, nats), attention_entropy_max = log T, attention_patch_mass (per head), batch
-    and the same three pictures as PNG where PIL imports.  Returns the stats dict plus "dir".  The model's mode is left as it is."""
+    and the same three pictures as PNG where PIL imports.  With ``rollout=True`` a second no-grad forward
+    (``backbone.attention_rollout``, CLS, residual 0.5, every block) adds
+        rollout.npy    [g, g]         attention rollout of CLS over the patches of image 0 (and rollout.png)
+    and the stats keys rollout_patch_mass (share of the rollout row that ends on patches, mean over the batch) and rollout_entropy
+    (entropy of the row over all T tokens, mean over the batch, nats); with ``rollout=False`` files and keys are exactly the ones above.
+    Returns the stats dict plus "dir".  The model's mode is left as it is."""
     B = batch.shape[0]
     if B < 1:
         raise ValueError("run_monitor needs at least one image")
@@ -96,10 +105,11 @@ def run_monitor(backbone, batch, spacing, out_dir, step: int, input_plane: Optio
     ops.weight_cache.clear()
     try:
         feats, probs = backbone.last_attention(batch, spacing, query_tokens=(0,))
+        roll = backbone.attention_rollout(batch, spacing)[1] if rollout else None
     finally:
         ops.weight_cache.clear()
     S, P = batch.shape[-1], (batch.shape[-1] // backbone.patch) ** 2
-    from zoo.arch import cls_attention_grid
+    from zoo.arch import cls_attention_grid, rollout_grid
     heat = patch_norm_heatmap(feats[:1], P)[0]
     grid = cls_attention_grid(probs, P)                                   # [B, heads, g, g]
     stats = {"step": int(step), **embedding_stats(feats[:, 0]),
@@ -107,11 +117,17 @@ def run_monitor(backbone, batch, spacing, out_dir, step: int, input_plane: Optio
              "attention_entropy_max": math.log(probs.shape[-1]),
              "attention_patch_mass": [float(v) for v in grid.sum((-1, -2)).mean(0)],
              "batch": int(B)}
+    if roll is not None:
+        rgrid = rollout_grid(roll, P)                                     # [B, g, g]
+        stats["rollout_patch_mass"] = float(rgrid.sum((-1, -2)).mean())
+        stats["rollout_entropy"] = float(attention_entropy(roll).mean())
     if extra:
         stats.update(extra)
     d = os.path.join(str(out_dir), f"step_{int(step):08d}")
     os.makedirs(d, exist_ok=True)
     arrays = {"heatmap": heat.cpu().numpy(), "attention": grid[0].cpu().numpy(), "input": input_plane.detach().float().cpu().numpy()}
+    if roll is not None:
+        arrays["rollout"] = rgrid[0].cpu().numpy()
     for name, a in arrays.items():
         np.save(os.path.join(d, name + ".npy"), a)
     with open(os.path.join(d, "stats.json"), "w") as f:
@@ -120,4 +136,6 @@ def run_monitor(backbone, batch, spacing, out_dir, step: int, input_plane: Optio
     _save_png(arrays["heatmap"], os.path.join(d, "heatmap.png"), S)
     _save_png(arrays["input"], os.path.join(d, "input.png"))
     _save_png(arrays["attention"].mean(0), os.path.join(d, "attention.png"), S)
+    if roll is not None:
+        _save_png(arrays["rollout"], os.path.join(d, "rollout.png"), S)
     return dict(stats, dir=d)

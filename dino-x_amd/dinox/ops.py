@@ -1361,6 +1361,50 @@ def attention_rows(qkv: Tensor, heads: int, query_idx, want_lse: bool = False):
     return (probs, lse) if want_lse else probs
 
 
+ATTENTION_ROLLOUT_MAX_N = 4096
+
+
+def attention_rollout_step(qkv: Tensor, heads: int, w: Tensor, residual: float = 0.5) -> Tensor:
+    """One step of the rollout chain over one block (dinox_attention_rollout_step):
+        out[b, j] = residual w[b, j] + (1 - residual) / heads * sum_h sum_i w[b, i] softmax_j(q_i . k_j / sqrt(d))
+    qkv: packed [B, N, 3 heads d] (or [B, N, 3, heads, d]) fp32 or bf16 on the device, as attention_fwd takes it; w: [B, N] on the same
+    device (taken as fp32); residual in [0, 1].  -> [B, N] fp32, a new tensor.  No N x N matrix is formed; the workspace is B heads N
+    floats.  No gradient is defined: the result is detached.  Arguments are checked on the host: ValueError."""
+    if not isinstance(qkv, Tensor) or not qkv.is_cuda:
+        raise ValueError("attention_rollout_step: qkv must be a tensor on a CUDA/HIP device (the MI355X kernel library is the only compute path)")
+    if qkv.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"attention_rollout_step: qkv must be float32 or bfloat16, got {qkv.dtype}")
+    if qkv.dim() == 5:
+        if qkv.shape[2] != 3 or qkv.shape[3] != heads:
+            raise ValueError(f"attention_rollout_step: a 5-D qkv must be [B, N, 3, heads={heads}, d], got {tuple(qkv.shape)}")
+        qkv = qkv.reshape(qkv.shape[0], qkv.shape[1], -1)
+    if qkv.dim() != 3:
+        raise ValueError(f"attention_rollout_step: qkv must be [B, N, 3 heads d], got {tuple(qkv.shape)}")
+    B, N, C3 = qkv.shape
+    if not isinstance(heads, int) or isinstance(heads, bool) or heads < 1 or C3 % (3 * heads) or B < 1 or N < 1 or C3 < 1:
+        raise ValueError(f"attention_rollout_step: qkv {tuple(qkv.shape)} is not [B >= 1, N >= 1, 3 x heads={heads} x d]")
+    d = C3 // (3 * heads)
+    if d > ATTENTION_ROWS_MAX_D or N > ATTENTION_ROLLOUT_MAX_N:
+        raise ValueError(f"attention_rollout_step: head size {d} above {ATTENTION_ROWS_MAX_D} or {N} tokens above {ATTENTION_ROLLOUT_MAX_N}")
+    if not isinstance(w, Tensor) or w.device != qkv.device:
+        raise ValueError("attention_rollout_step: w must be a tensor on the device of qkv")
+    if w.dim() != 2 or tuple(w.shape) != (B, N) or not w.dtype.is_floating_point:
+        raise ValueError(f"attention_rollout_step: w must be a float tensor [B={B}, N={N}], got {w.dtype} {tuple(w.shape)}")
+    if isinstance(residual, bool) or not isinstance(residual, (int, float)) or not 0.0 <= float(residual) <= 1.0:
+        raise ValueError(f"attention_rollout_step: residual must be a number in [0, 1], got {residual!r}")
+    if not lib.dinox_attention_rollout_step_ok(B, N, heads, d):
+        raise ValueError(f"attention_rollout_step: B={B} N={N} heads={heads} d={d} outside the kernel")
+    qkv = _c(qkv.detach())
+    w = _c(w.detach().float())
+    out = torch.empty((B, N), dtype=torch.float32, device=qkv.device)
+    ws = torch.empty((lib.dinox_attention_rollout_step_ws_bytes(B, N, heads) // 4,), dtype=torch.float32, device=qkv.device)
+    if TRACE_KERNELS is not None:
+        TRACE_KERNELS.append("attention_rollout_step")
+    check(lib.dinox_attention_rollout_step(_p(qkv), _p(w), _p(out), _p(ws), B, N, heads, d, float(residual), _code(qkv.dtype), _stream()),
+          "dinox_attention_rollout_step")
+    return out
+
+
 class _UnfoldShare:
     """The student and the teacher of one training step see the same batch (scripts/phase5_big_run.py:1741-1743) and can share
     its unfolded form.  Sharing is OPT-IN and scoped: only inside ``with unfold_share():`` (TrainEngine.step) is an unfolded

@@ -10,7 +10,8 @@ and ``stats.json`` with the reference's keys (``step``, ``embedding_std_mean``, 
 reference cannot produce: ``attention`` = the CLS softmax rows of the last block per head, with the per-head entropies in
 ``stats.json``.  Arrays are ``.npy``; PNG copies are written where PIL imports.
 
-Extensions: ``--synthetic N`` (seeded HU stacks of the training script instead of ``--index-csv``), ``--scale-aware`` (must match
+Extensions: ``--rollout`` (also ``rollout`` = the attention rollout of CLS through every block, heads averaged, residual 0.5:
+``PatchViT.attention_rollout``), ``--synthetic N`` (seeded HU stacks of the training script instead of ``--index-csv``), ``--scale-aware`` (must match
 the checkpoint), ``--amp`` (bf16 backbone).  Without a HIP device the script exits with a message: there is no CPU compute path.
 """
 from __future__ import annotations
@@ -44,6 +45,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--synthetic", type=int, default=0, metavar="N", help="extension: N seeded synthetic HU stacks instead of --index-csv")
     ap.add_argument("--scale-aware", action="store_true", help="model with the scale embedding (must match the checkpoint)")
     ap.add_argument("--amp", action="store_true", help="extension: bf16 backbone")
+    ap.add_argument("--rollout", action="store_true",
+                    help="extension: also write the attention rollout of CLS through every block (rollout.npy / rollout.png, "
+                         "rollout_patch_mass and rollout_entropy in stats.json)")
     return ap
 
 
@@ -119,10 +123,12 @@ def main(argv=None) -> int:
 
     run_out = args.out_dir / f"{datetime.now().strftime('%Y%m%d_%H%M%S')}_step{step}"
     with ops.compute_dtype(torch.bfloat16 if args.amp else torch.float32):
-        stats = run_monitor(backbone, x, spacing, run_out, step, extra={"sample": str(target.png_path)})
+        stats = run_monitor(backbone, x, spacing, run_out, step, extra={"sample": str(target.png_path)}, rollout=args.rollout)
     print(f"Saved heatmap, attention and input to: {stats['dir']}")
     print(f"Stats: std={stats['embedding_std_mean']:.4f}, norm={stats['embedding_norm_mean']:.4f}, "
           f"attention_entropy={[round(v, 3) for v in stats['attention_entropy']]} (max {stats['attention_entropy_max']:.3f})")
+    if args.rollout:
+        print(f"Rollout: patch_mass={stats['rollout_patch_mass']:.4f}, entropy={stats['rollout_entropy']:.3f} (max {stats['attention_entropy_max']:.3f})")
     print(f"monitor_dir={stats['dir']}")
     return 0
 

@@ -26,7 +26,7 @@ import torch.nn as nn
 from dinox import ops
 
 __all__ = ["Attention", "Mlp", "TransformerBlock", "ScaleEmbedding", "PatchViT", "DinoStudentTeacher",
-           "migrate_state_dict", "needs_migration", "cls_attention_grid"]
+           "migrate_state_dict", "needs_migration", "cls_attention_grid", "rollout_grid"]
 
 
 # ------------------------------------------------------------------------------------------
@@ -237,11 +237,55 @@ class PatchViT(nn.Module):
             feats = self._forward(x, spacing, tap)
         return feats, tap["probs"]
 
+    def attention_rollout(self, x: torch.Tensor, spacing: Optional[torch.Tensor] = None, query_token: int = 0, residual: float = 0.5,
+                          start_layer: int = 0):
+        """-> (feats, rollout): ``feats`` is ``self.forward(x, spacing)`` (the same launches, bit for bit) and ``rollout`` [B, T] fp32,
+        T = 1 + P + registers, is row ``query_token`` (0 = CLS) of the attention rollout (Abnar & Zuidema 2020)
+            Ahat_L ... Ahat_{start_layer + 1},   Ahat_l = residual I + (1 - residual) mean_h softmax(Q_h K_h^T / sqrt(d)) of block l:
+        how much of each INPUT token of block ``start_layer`` reaches the query token at the output, attention and skip connections
+        only.  Only that row is computed: w = e_query, then one ``ops.attention_rollout_step`` per block from the last one down, each a
+        weighted column sum of the block's softmax rows, so no T x T matrix is stored.  Every block from ``start_layer`` up pushes its
+        ``norm1`` output through ``attn.qkv`` once more during the forward and that product is kept until the chain has run:
+        (depth - start_layer) * B * T * 3D elements of the compute dtype are held.  A row sums to 1 (up to rounding).  No-grad, in the
+        current compute dtype."""
+        depth = len(self.blocks)
+        if isinstance(start_layer, bool) or not isinstance(start_layer, int) or not 0 <= start_layer < depth:
+            raise ValueError(f"start_layer {start_layer!r} outside [0, {depth}) of a model of {depth} blocks")
+        if isinstance(residual, bool) or not isinstance(residual, (int, float)) or not 0.0 <= float(residual) <= 1.0:
+            raise ValueError(f"residual must be a number in [0, 1], got {residual!r}")
+        if x.shape[0] == 0:
+            raise ValueError("attention_rollout needs at least one image")
+        if x.dim() != 4 or x.shape[-2] != x.shape[-1] or x.shape[-1] % self.patch:
+            raise ValueError(f"input {tuple(x.shape)} is not [B, 3, S, S] with S a multiple of the {self.patch}-pixel patch")
+        T = 1 + (x.shape[-1] // self.patch) ** 2 + self.num_registers
+        if isinstance(query_token, bool) or not isinstance(query_token, int) or not 0 <= query_token < T:
+            raise ValueError(f"query_token {query_token!r} outside [0, {T})")
+        tap = {"from": start_layer, "qkv": []}
+        with torch.no_grad():
+            feats = self._forward(x, spacing, tap)
+            w = torch.zeros((x.shape[0], T), dtype=torch.float32, device=feats.device)
+            w[:, query_token] = 1.0
+            while tap["qkv"]:
+                qkv, heads = tap["qkv"].pop()                                     # last block first; each product is freed after its step
+                w = ops.attention_rollout_step(qkv, heads, w, float(residual))
+        return feats, w
+
     @staticmethod
     def _tap_rows(tap, i: int, blk: "TransformerBlock", t: torch.Tensor, pre) -> None:
-        if tap is not None and tap["layer"] == i:
+        """The instrument taps of last_attention ({"layer", "query", "probs"}: the softmax rows of one block) and attention_rollout
+        ({"from", "qkv"}: the qkv product of every block from ``from`` up).  Either reads block i's ``norm1`` output -- the previous
+        product's epilogue where there is one -- and pushes it through ``attn.qkv`` once more; the block itself then runs as usual."""
+        if tap is None:
+            return
+        rows = tap.get("layer") == i
+        keep = "from" in tap and i >= tap["from"]
+        if rows or keep:
             y = pre[0].view(t.shape) if pre is not None else blk.norm1(t)
-            tap["probs"] = ops.attention_rows(blk.attn.qkv(y), blk.attn.num_heads, tap["query"])
+            qkv = blk.attn.qkv(y)
+            if rows:
+                tap["probs"] = ops.attention_rows(qkv, blk.attn.num_heads, tap["query"])
+            if keep:
+                tap["qkv"].append((qkv, blk.attn.num_heads))
 
     def _forward(self, x: torch.Tensor, spacing: Optional[torch.Tensor], tap) -> torch.Tensor:
         g = x.shape[-1] // self.patch
@@ -290,6 +334,15 @@ def cls_attention_grid(probs: torch.Tensor, n_patches: int) -> torch.Tensor:
     if probs.dim() != 4 or g * g != n_patches or probs.shape[-1] < 1 + n_patches:
         raise ValueError(f"probs {tuple(probs.shape)} is not [B, heads, Q, T >= 1 + {n_patches}] with a square number of patches")
     return probs[:, :, 0, 1:1 + n_patches].reshape(probs.shape[0], probs.shape[1], g, g)
+
+
+def rollout_grid(rollout: torch.Tensor, n_patches: int) -> torch.Tensor:
+    """``attention_rollout``'s row [B, T] over the P = n_patches patch tokens, columns 1 .. P of the [CLS, patches, registers] order, as
+    [B, g, g].  The mass on CLS and the registers is left out, so a map sums to less than 1 by exactly that mass."""
+    g = int(round(n_patches ** 0.5))
+    if rollout.dim() != 2 or n_patches < 1 or g * g != n_patches or rollout.shape[-1] < 1 + n_patches:
+        raise ValueError(f"rollout {tuple(rollout.shape)} is not [B, T >= 1 + {n_patches}] with a square number of patches")
+    return rollout[:, 1:1 + n_patches].reshape(rollout.shape[0], g, g)
 
 
 class DinoHead(nn.Sequential):

@@ -18,7 +18,7 @@ from typing import List, Literal, Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 
-from zoo.arch import PatchViT, cls_attention_grid
+from zoo.arch import PatchViT, cls_attention_grid, rollout_grid
 
 _MEAN = np.array([0.485, 0.456, 0.406], dtype=np.float32).reshape(3, 1, 1)
 _STD = np.array([0.229, 0.224, 0.225], dtype=np.float32).reshape(3, 1, 1)
@@ -117,6 +117,26 @@ def attention_map(model: PatchViT, image: np.ndarray, pixel_spacing: Optional[Tu
         spacing = torch.tensor([[sx, sy, 1.0 if slice_thickness is None else slice_thickness]], dtype=torch.float32, device=device)
     _, probs = model.last_attention(x, spacing, query_tokens=(0,), layer=layer)
     return cls_attention_grid(probs, (model.img_size // model.patch) ** 2)[0].float().cpu()
+
+
+def attention_rollout(model: PatchViT, image: np.ndarray, pixel_spacing: Optional[Tuple[float, float]] = None,
+                      slice_thickness: Optional[float] = None, *, residual: float = 0.5, start_layer: int = 0,
+                      input_format: Literal["hu_float", "hu16_png", "windowed_float"] = "hu_float", hu_level: float = 40.0,
+                      hu_width: float = 400.0, device: Union[str, torch.device, None] = None,
+                      preprocess: Literal["host", "device", "auto"] = "host") -> np.ndarray:
+    """Attention rollout of the CLS token over the patches of one image: a ``(g, g)`` float32 numpy map, g = img_size / patch -- where
+    in the image the CLS embedding comes from, through the attention and skip connections of every block from ``start_layer`` up
+    (``PatchViT.attention_rollout``; heads averaged, ``residual`` the weight of the skip connection).  Same preprocessing, argument
+    checking and spacing convention as ``attention_map``.  The map sums to 1 minus the mass that ends on CLS and the registers."""
+    if device is None:
+        device = next(model.parameters()).device
+    x = _batch([image], model.img_size, input_format, hu_level, hu_width, device, preprocess)
+    spacing = None
+    if model.scale_aware:
+        sx, sy = (1.0, 1.0) if pixel_spacing is None else pixel_spacing
+        spacing = torch.tensor([[sx, sy, 1.0 if slice_thickness is None else slice_thickness]], dtype=torch.float32, device=device)
+    _, roll = model.attention_rollout(x, spacing, query_token=0, residual=residual, start_layer=start_layer)
+    return rollout_grid(roll, (model.img_size // model.patch) ** 2)[0].float().cpu().numpy()
 
 
 def encode_batch(model: PatchViT, images: Sequence[np.ndarray], spacings: Sequence[Tuple[float, float, float]], *,

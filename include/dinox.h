@@ -23,13 +23,14 @@
 #ifndef DINOX_H
 #define DINOX_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
 #endif
 
-#define DINOX_ABI_VERSION 3   /* 3: + dinox_block_forward / _backward, dinox_gemm_timer_*, dinox_retrieval_* (later also dinox_retrieval_rank_windowed*, dinox_row_dots), dinox_knn_*, dinox_gram_*, dinox_softmax_probe*, dinox_ntxent_*, dinox_normalize_bwd, dinox_attention_rows* (all additive: no entry
+#define DINOX_ABI_VERSION 3   /* 3: + dinox_block_forward / _backward, dinox_gemm_timer_*, dinox_retrieval_* (later also dinox_retrieval_rank_windowed*, dinox_row_dots), dinox_knn_*, dinox_gram_*, dinox_softmax_probe*, dinox_ntxent_*, dinox_normalize_bwd, dinox_attention_rows*, dinox_attention_rollout_step* (all additive: no entry
                                * of an earlier library changed, so the number callers test, dinox_version() == 3, stays; probe the symbol
                                * to learn whether a given build has the later additions) */
 
@@ -357,6 +358,28 @@ int dinox_normalize_bwd(const float* dxh, const float* xh, const float* norm, fl
 int dinox_attention_rows_ok(int B, int N, int heads, int d, int Q);
 int dinox_attention_rows(const void* qkv, const int* query_idx, float* probs, float* lse, int B, int N, int heads, int d, int Q, int dtype,
                          void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Attention rollout step -- one factor of the CLS row of attention rollout (Abnar & Zuidema 2020), with no N x N matrix stored:
+ *   w_out[b][j] = residual w_in[b][j] + (1 - residual) / heads * sum_h sum_i w_in[b][i] * softmax_j(q_i . k_j / sqrt(d))
+ * Chained from the last block down, starting from the one-hot vector of a query token, it gives that token's row of
+ * Ahat_L ... Ahat_1, Ahat_l = residual I + (1 - residual) mean_h P_l^h.
+ *   qkv        [B, N, 3, heads, d] packed as dinox_attention_fwd takes it, dtype DINOX_F32 or DINOX_BF16; V is never read
+ *   w_in       [B, N] fp32;  w_out [B, N] fp32, must not overlap w_in
+ *   ws         dinox_attention_rollout_step_ws_bytes(B, N, heads) bytes (= B heads N floats: the per-head partial sums)
+ *   residual   in [0, 1]
+ * fp32 scores (bf16 products are exact), fp32 maximum, sum and probabilities, as dinox_attention_rows; the column sum adds the query
+ * rows in index order, the heads in index order; no atomics: bit-reproducible.  Query rows go by in chunks of 8; a chunk whose 8
+ * weights are all exactly 0 is skipped (it would add exactly 0; a non-finite q in such a row is therefore not seen).
+ * Two launches: one workgroup per (image, head), then one thread per (image, key).
+ * Limits (dinox_attention_rollout_step_ok: host only, 1 inside): B, heads >= 1, 1 <= N <= 4096 (the 8 x N score rows of a chunk
+ * sit in LDS), 1 <= d <= 256; anything else, a residual outside [0, 1], a null pointer or overlapping w returns DINOX_EINVAL before
+ * any launch.  dinox_attention_rollout_step_ws_bytes returns 0 for a non-positive size.
+ * ------------------------------------------------------------------------------------------ */
+int dinox_attention_rollout_step_ok(int B, int N, int heads, int d);
+size_t dinox_attention_rollout_step_ws_bytes(int B, int N, int heads);
+int dinox_attention_rollout_step(const void* qkv, const float* w_in, float* w_out, void* ws, int B, int N, int heads, int d, float residual,
+                                 int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Optimiser tail -- replaces the per-parameter grad-norm loop (scripts/phase5_big_run.py:1784-1789),
