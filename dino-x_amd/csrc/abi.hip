@@ -145,3 +145,85 @@ extern "C" int dinox_attention_rollout_step(const void* qkv, const float* w_in, 
   DX_REQUIRE(in_end <= w_out || out_end <= w_in, DINOX_EINVAL, "attention_rollout_step: w_out must not alias w_in (the fold reads w_in)");
   return dinox::launch_attention_rollout_step(qkv, w_in, w_out, ws, B, N, heads, d, residual, dtype, dinox::as_stream(stream));
 }
+
+// ---------------------------------------------------------------- MAE masked-token glue (kernels: mae.hip)
+static bool mae_dtype_ok(int dt) { return dt == DINOX_F32 || dt == DINOX_BF16; }
+// V samples of L patches of which 1 <= Lk < L are kept; D features.  (V * (1 + L) rows index a 32-bit grid in the loss kernels.)
+static bool mae_shape_ok(int V, int L, int Lk, int D) {
+  return V >= 1 && V <= (1 << 20) && L >= 2 && L <= dinox::MAE_MAX_L && Lk >= 1 && Lk < L && D >= 1 && D <= (1 << 16) &&
+         (int64_t)V * (1 + L) <= 0x7fffffff;
+}
+static bool mae_image_ok(int V, int H, int W, int patch, int Lk) {
+  if (!(H > 0 && W > 0 && patch > 0 && H % patch == 0 && W % patch == 0 && H <= (1 << 14) && W <= (1 << 14))) return false;
+  const int64_t L = (int64_t)(H / patch) * (W / patch);
+  return L <= dinox::MAE_MAX_L && mae_shape_ok(V, (int)L, Lk, 1);
+}
+
+extern "C" int dinox_mae_mask_ids(const float* noise, int* ids_restore, int* ids_keep, int V, int L, int Lk, void* stream) {
+  DX_REQUIRE(noise && ids_restore && ids_keep, DINOX_EINVAL, "mae_mask_ids: null pointer");
+  DX_REQUIRE(mae_shape_ok(V, L, Lk, 1), DINOX_EINVAL, "mae_mask_ids: V=%d L=%d Lk=%d (V >= 1, 2 <= L <= %d, 1 <= Lk < L)", V, L, Lk, dinox::MAE_MAX_L);
+  return dinox::launch_mae_mask_ids(noise, ids_restore, ids_keep, V, L, Lk, dinox::as_stream(stream));
+}
+
+extern "C" int dinox_mae_gather_unfold(const float* x, const int* ids_keep, void* u, int V, int H, int W, int patch, int Lk, int ld,
+                                       int out_dtype, void* stream) {
+  DX_REQUIRE(x && ids_keep && u, DINOX_EINVAL, "mae_gather_unfold: null pointer");
+  DX_REQUIRE(mae_dtype_ok(out_dtype), DINOX_EINVAL, "mae_gather_unfold: dtype %d", out_dtype);
+  DX_REQUIRE(mae_image_ok(V, H, W, patch, Lk) && patch <= 1024 && ld >= 3 * patch * patch && ld <= (1 << 22), DINOX_EINVAL,
+             "mae_gather_unfold: V=%d H=%d W=%d patch=%d Lk=%d ld=%d (H, W multiples of patch; 2 <= L <= %d; 1 <= Lk < L; ld >= 3 patch^2)", V, H,
+             W, patch, Lk, ld, dinox::MAE_MAX_L);
+  return dinox::launch_mae_gather_unfold(x, ids_keep, u, V, H, W, patch, Lk, ld, out_dtype, dinox::as_stream(stream));
+}
+
+extern "C" int dinox_mae_tokens_fwd(const void* patches, const float* cls, const float* pos, const int* ids_keep, float* tokens, int V, int L,
+                                    int Lk, int D, int patches_dtype, void* stream) {
+  DX_REQUIRE(patches && cls && pos && ids_keep && tokens, DINOX_EINVAL, "mae_tokens_fwd: null pointer");
+  DX_REQUIRE(mae_dtype_ok(patches_dtype), DINOX_EINVAL, "mae_tokens_fwd: dtype %d", patches_dtype);
+  DX_REQUIRE(mae_shape_ok(V, L, Lk, D), DINOX_EINVAL, "mae_tokens_fwd: V=%d L=%d Lk=%d D=%d (2 <= L <= %d, 1 <= Lk < L)", V, L, Lk, D, dinox::MAE_MAX_L);
+  return dinox::launch_mae_tokens_fwd(patches, cls, pos, ids_keep, tokens, V, L, Lk, D, patches_dtype, dinox::as_stream(stream));
+}
+
+extern "C" int dinox_mae_tokens_bwd(const float* dtokens, const int* ids_restore, void* dpatches, float* dcls, float* dpos, int V, int L, int Lk,
+                                    int D, int patches_dtype, void* stream) {
+  DX_REQUIRE(dtokens && ids_restore && dpatches && dcls && dpos, DINOX_EINVAL, "mae_tokens_bwd: null pointer");
+  DX_REQUIRE(mae_dtype_ok(patches_dtype), DINOX_EINVAL, "mae_tokens_bwd: dtype %d", patches_dtype);
+  DX_REQUIRE(mae_shape_ok(V, L, Lk, D), DINOX_EINVAL, "mae_tokens_bwd: V=%d L=%d Lk=%d D=%d (2 <= L <= %d, 1 <= Lk < L)", V, L, Lk, D, dinox::MAE_MAX_L);
+  return dinox::launch_mae_tokens_bwd(dtokens, ids_restore, dpatches, dcls, dpos, V, L, Lk, D, patches_dtype, dinox::as_stream(stream));
+}
+
+extern "C" int dinox_mae_unshuffle_fwd(const void* e, const float* mask_token, const float* dec_pos, const int* ids_restore, float* xd, int V,
+                                       int L, int Lk, int D, int e_dtype, void* stream) {
+  DX_REQUIRE(e && mask_token && dec_pos && ids_restore && xd, DINOX_EINVAL, "mae_unshuffle_fwd: null pointer");
+  DX_REQUIRE(mae_dtype_ok(e_dtype), DINOX_EINVAL, "mae_unshuffle_fwd: dtype %d", e_dtype);
+  DX_REQUIRE(mae_shape_ok(V, L, Lk, D), DINOX_EINVAL, "mae_unshuffle_fwd: V=%d L=%d Lk=%d D=%d (2 <= L <= %d, 1 <= Lk < L)", V, L, Lk, D, dinox::MAE_MAX_L);
+  return dinox::launch_mae_unshuffle_fwd(e, mask_token, dec_pos, ids_restore, xd, V, L, Lk, D, e_dtype, dinox::as_stream(stream));
+}
+
+extern "C" int dinox_mae_unshuffle_bwd(const float* g, const int* ids_keep, const int* ids_restore, void* de, float* dmask_token, float* ws,
+                                       int V, int L, int Lk, int D, int de_dtype, void* stream) {
+  DX_REQUIRE(g && ids_keep && ids_restore && de && dmask_token && ws, DINOX_EINVAL, "mae_unshuffle_bwd: null pointer");
+  DX_REQUIRE(mae_dtype_ok(de_dtype), DINOX_EINVAL, "mae_unshuffle_bwd: dtype %d", de_dtype);
+  DX_REQUIRE(mae_shape_ok(V, L, Lk, D), DINOX_EINVAL, "mae_unshuffle_bwd: V=%d L=%d Lk=%d D=%d (2 <= L <= %d, 1 <= Lk < L)", V, L, Lk, D, dinox::MAE_MAX_L);
+  return dinox::launch_mae_unshuffle_bwd(g, ids_keep, ids_restore, de, dmask_token, ws, V, L, Lk, D, de_dtype, dinox::as_stream(stream));
+}
+
+extern "C" int dinox_mae_loss_fwd(const void* pred, const float* x, const int* ids_restore, float* loss, float* ws, int V, int H, int W, int patch,
+                                  int Lk, int lead, int pred_dtype, void* stream) {
+  DX_REQUIRE(pred && x && ids_restore && loss && ws, DINOX_EINVAL, "mae_loss_fwd: null pointer");
+  DX_REQUIRE(mae_dtype_ok(pred_dtype), DINOX_EINVAL, "mae_loss_fwd: dtype %d", pred_dtype);
+  DX_REQUIRE(mae_image_ok(V, H, W, patch, Lk) && patch <= dinox::MAE_MAX_PATCH && (lead == 0 || lead == 1), DINOX_EINVAL,
+             "mae_loss_fwd: V=%d H=%d W=%d patch=%d Lk=%d lead=%d (H, W multiples of patch <= %d; 2 <= L <= %d; 1 <= Lk < L; lead 0 or 1)", V, H, W,
+             patch, Lk, lead, dinox::MAE_MAX_PATCH, dinox::MAE_MAX_L);
+  return dinox::launch_mae_loss_fwd(pred, x, ids_restore, loss, ws, V, H, W, patch, Lk, lead, pred_dtype, dinox::as_stream(stream));
+}
+
+extern "C" int dinox_mae_loss_bwd(const void* pred, const float* x, const int* ids_restore, void* dpred, float gscale, int V, int H, int W,
+                                  int patch, int Lk, int lead, int pred_dtype, int dpred_dtype, void* stream) {
+  DX_REQUIRE(pred && x && ids_restore && dpred, DINOX_EINVAL, "mae_loss_bwd: null pointer");
+  DX_REQUIRE(mae_dtype_ok(pred_dtype) && mae_dtype_ok(dpred_dtype), DINOX_EINVAL, "mae_loss_bwd: dtypes %d, %d", pred_dtype, dpred_dtype);
+  DX_REQUIRE(mae_image_ok(V, H, W, patch, Lk) && patch <= dinox::MAE_MAX_PATCH && (lead == 0 || lead == 1), DINOX_EINVAL,
+             "mae_loss_bwd: V=%d H=%d W=%d patch=%d Lk=%d lead=%d (H, W multiples of patch <= %d; 2 <= L <= %d; 1 <= Lk < L; lead 0 or 1)", V, H, W,
+             patch, Lk, lead, dinox::MAE_MAX_PATCH, dinox::MAE_MAX_L);
+  DX_REQUIRE(dpred != pred, DINOX_EINVAL, "mae_loss_bwd: dpred must not alias pred");
+  return dinox::launch_mae_loss_bwd(pred, x, ids_restore, dpred, gscale, V, H, W, patch, Lk, lead, pred_dtype, dpred_dtype, dinox::as_stream(stream));
+}

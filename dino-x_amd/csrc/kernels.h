@@ -84,6 +84,25 @@ size_t attention_rollout_step_ws_bytes(int B, int N, int heads);
 int launch_attention_rollout_step(const void* qkv, const float* w_in, float* w_out, void* ws, int B, int N, int heads, int d, float residual,
                                   int dtype, hipStream_t st);
 
+// ---------------------------------------------------------------- MAE masked-token glue (mae.hip; entry points and argument checks: abi.hip)
+constexpr int MAE_MAX_L = 4096;      // patches per sample: the sort keys of one sample sit in LDS
+constexpr int MAE_MAX_PATCH = 32;    // patch edge of the loss kernels: one target patch (3 p^2 floats) sits in LDS
+int launch_mae_mask_ids(const float* noise, int* ids_restore, int* ids_keep, int V, int L, int Lk, hipStream_t st);
+int launch_mae_gather_unfold(const float* x, const int* ids_keep, void* u, int V, int H, int W, int patch, int Lk, int ld, int dtype,
+                             hipStream_t st);
+int launch_mae_tokens_fwd(const void* patches, const float* cls, const float* pos, const int* ids_keep, float* tok, int V, int L, int Lk,
+                          int D, int dtype, hipStream_t st);
+int launch_mae_tokens_bwd(const float* dtok, const int* ids_restore, void* dpatches, float* dcls, float* dpos, int V, int L, int Lk, int D,
+                          int dtype, hipStream_t st);
+int launch_mae_unshuffle_fwd(const void* e, const float* mask_token, const float* dpe, const int* ids_restore, float* xd, int V, int L,
+                             int Lk, int D, int dtype, hipStream_t st);
+int launch_mae_unshuffle_bwd(const float* g, const int* ids_keep, const int* ids_restore, void* de, float* dmask, float* ws, int V, int L,
+                             int Lk, int D, int dtype, hipStream_t st);
+int launch_mae_loss_fwd(const void* pred, const float* x, const int* ids_restore, float* loss, float* ws, int V, int H, int W, int patch,
+                        int Lk, int lead, int dtype, hipStream_t st);
+int launch_mae_loss_bwd(const void* pred, const float* x, const int* ids_restore, void* dpred, float gscale, int V, int H, int W, int patch,
+                        int Lk, int lead, int dtype, int out_dtype, hipStream_t st);
+
 // ---------------------------------------------------------------- launch glue shared by the NT launchers
 // Activation index of the <OUT, ACT, RES> kernels (gemm_bf16_pp / _pp128 / _areg): the template argument ACT.
 enum { EPI_ACT_PLAIN = 0, EPI_ACT_GELU = 1, EPI_ACT_DGELU = 2 };

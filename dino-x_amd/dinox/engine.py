@@ -16,6 +16,13 @@ Follows the order of the reference loop (scripts/phase5_big_run.py:1692-1802) fo
 the reference applies it for ``dino`` only (:1799) -- no EMA: teacher arena and centre stay bit-identical.  Single rank, no
 multi-crop (cross-rank negatives are not implemented).
 
+``loss_type="mae"`` (:1627-1632, :1724-1727): the student is a ``dinox.mae.MaeModel`` and there is no teacher: forward with random
+masking, reconstruction loss on the removed patches (ops.mae_loss_fwd / mae_loss_bwd), backward, AdamW.  No head, centre or EMA.
+The parameters the MAE graph never reaches (``encoder.registers``, ``encoder.scale_embed.*``, the fixed ``decoder.decoder_pos_embed``)
+form the TAIL of the arena and the optimiser pass runs over the prefix only, so they stay bit-identical (the reference's AdamW skips
+``.grad is None``).  The logged grad-norm is the reference's: over the ENCODER's gradients (its loop walks ``student.parameters()``,
+and the MAE decoder is not part of ``student``, :1785).  Single rank, eager launches, fp32 image batches only.
+
 What is different from the reference, by design:
   * parameters, gradients, Adam moments and teacher weights live in flat fp32 arenas, so the grad-norm,
     AdamW and EMA are ONE kernel pass (dinox_adamw_ema) instead of 161 x (.item() + 2 EMA launches); the dW products
@@ -58,14 +65,21 @@ class StepHyperParams:
     beta1: float = 0.9
     beta2: float = 0.999
     adam_eps: float = 1e-8
-    loss_type: str = "dino"          # "dino" | "simclr" (SimCLRLoss on the student head output, reference :1728-1737)
+    loss_type: str = "dino"          # "dino" | "simclr" (SimCLRLoss on the student head output, reference :1728-1737) | "mae"
     simclr_temp: float = 0.1         # the reference hard-codes SimCLRLoss(temperature=0.1)
+    mae_mask_ratio: float = 0.75     # the reference hard-codes MaeModel(mask_ratio=0.75); the engine sets it on the model it is given
 
 
-def flatten_parameters(module: torch.nn.Module, align: int = 8) -> Tuple[torch.Tensor, List[torch.nn.Parameter], List[int]]:
+def flatten_parameters(module: torch.nn.Module, align: int = 8, order: Optional[List[torch.nn.Parameter]] = None
+                       ) -> Tuple[torch.Tensor, List[torch.nn.Parameter], List[int]]:
     """Move every parameter of ``module`` into one flat fp32 arena (each at an offset of a multiple of 8 elements, so that
-    both the fp32 slice and the same slice of a bf16 image of the arena are 16-byte aligned) and re-point ``p.data`` at its slice.  Returns (arena, params in arena order, element offsets)."""
+    both the fp32 slice and the same slice of a bf16 image of the arena are 16-byte aligned) and re-point ``p.data`` at its slice.  Returns (arena, params in arena order, element offsets).
+    ``order``: the same parameters in another arena order (default: ``module.parameters()``)."""
     params = list(module.parameters())
+    if order is not None:
+        if len(order) != len(params) or {id(p) for p in order} != {id(p) for p in params}:
+            raise ValueError("order must be a permutation of module.parameters()")
+        params = list(order)
     if not params:
         raise ValueError("module has no parameters")
     dev = params[0].device
@@ -100,9 +114,13 @@ class TrainEngine:
         self.compute_dtype = amp_dtype or torch.float32
         self.group = process_group
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
-        if hp.loss_type not in ("dino", "simclr"):
-            raise ValueError(f"loss_type must be 'dino' or 'simclr', got {hp.loss_type!r}")
+        if hp.loss_type not in ("dino", "simclr", "mae"):
+            raise ValueError(f"loss_type must be 'dino', 'simclr' or 'mae', got {hp.loss_type!r}")
         self.simclr = hp.loss_type == "simclr"
+        self.mae = hp.loss_type == "mae"
+        if self.mae:
+            self._init_mae(student, teacher, out_dim, hp, process_group, bucket_bytes, use_graph)
+            return
         if self.simclr and self.world > 1:
             raise ValueError("loss_type='simclr' runs on a single rank only (the negatives of a row are the rows of ONE batch; "
                              "cross-rank negatives are not implemented)")
@@ -131,20 +149,68 @@ class TrainEngine:
         self.use_graph = bool(use_graph)
         if self.use_graph and (self.accum != 1 or exchanging(process_group)):
             raise ValueError("use_graph: single rank and accumulation_steps == 1 only")
-        self._graph = None
-        self._static: Optional[list] = None
-        self._eager_steps = 0
         self._hyper_dev = torch.zeros(3, dtype=torch.float32, device=dev)
         self._hyper_host = torch.zeros(3, dtype=torch.float32).pin_memory() if dev.type == "cuda" else torch.zeros(3)
         import zoo.arch as _arch
         self.manual_top = all(type(m.head) is _arch.DinoHead and type(m.head[0]) is _arch.Linear and type(m.head[2]) is _arch.Linear
                               and m.head[0].bias is not None and m.head[2].bias is not None for m in (student, teacher)) \
             and not os.environ.get("DINOX_AUTOGRAD_TOP")
+        self._init_counters(dev)
+
+    def _init_counters(self, dev) -> None:
+        """The state every objective's step keeps, whatever its arenas look like."""
+        self._graph = None
+        self._static: Optional[list] = None
+        self._eager_steps = 0
         self._zero1 = torch.zeros(1, dtype=torch.float32, device=dev)
         self.marks = None            # bench.py: a list -> (phase name, HIP event on the launch stream) at every phase boundary of step()
         self.step_count = 0          # micro-batches seen (drives the LR schedule, like the reference)
         self.opt_steps = 0           # optimiser steps taken (AdamW bias correction)
         self.last = {}
+
+    def _init_mae(self, student, teacher, out_dim, hp, process_group, bucket_bytes, use_graph) -> None:
+        """One arena [encoder, reached | decoder, reached | never reached], no teacher arena; the optimiser sees the first two parts."""
+        from .mae import MaeModel
+        if not isinstance(student, MaeModel):
+            raise ValueError(f"loss_type='mae' takes a dinox.mae.MaeModel as the student (encoder + decoder), got {type(student).__name__}")
+        if teacher is not None:
+            raise ValueError("loss_type='mae' has no teacher: pass teacher=None")
+        if self.world > 1:
+            raise ValueError("loss_type='mae' runs on a single rank only (data-parallel MAE is not implemented)")
+        if use_graph:
+            raise ValueError("loss_type='mae' does not support use_graph (the step is launched eagerly)")
+        student.mask_ratio = hp.mae_mask_ratio
+        enc, dec = student.encoder, student.decoder
+        tail_ids = {id(dec.decoder_pos_embed)}
+        if getattr(enc, "num_registers", 0) > 0:
+            tail_ids.add(id(enc.registers))
+        if getattr(enc, "scale_aware", False):
+            tail_ids.update(id(p) for p in enc.scale_embed.parameters())
+        enc_ids = {id(p) for p in enc.parameters()}
+        every = list(student.parameters())
+        head = [p for p in every if id(p) in enc_ids and id(p) not in tail_ids]
+        body = [p for p in every if id(p) not in enc_ids and id(p) not in tail_ids]
+        tail = [p for p in every if id(p) in tail_ids]
+        self.unreached = tail
+        pos_of = {id(p): i for i, p in enumerate(every)}
+        self.flat_p, self.params, self.offsets = flatten_parameters(student, order=head + body + tail)
+        self.state_index = [pos_of[id(p)] for p in self.params]      # position in student.parameters(): the optimiser-state keys of a checkpoint
+        ends = self.offsets + [self.flat_p.numel()]
+        self.enc_numel, self.opt_numel = ends[len(head)], ends[len(head) + len(body)]      # (multiples of 8: slices stay 16-byte aligned)
+        self.flat_t = None
+        self.flat_g = torch.zeros_like(self.flat_p)
+        self.adam_m = torch.zeros_like(self.flat_p)
+        self.adam_v = torch.zeros_like(self.flat_p)
+        n_opt = len(head) + len(body)
+        for p, off in zip(self.params[:n_opt], self.offsets[:n_opt]):      # the tail keeps .grad = None, as under the reference
+            p.grad = self.flat_g[off:off + p.numel()].view(p.shape)
+        dev = self.flat_p.device
+        self.center = torch.zeros(1, out_dim, dtype=torch.float32, device=dev)      # (the step never reads it; a checkpoint's "dino_loss" entry holds it)
+        self.side_stream = None
+        self.shadows = [ops.ArenaShadow(self.flat_p, self.params, self.offsets)]
+        self.use_graph = False
+        self.manual_top = False
+        self._init_counters(dev)
 
     def _mark(self, name: str) -> None:
         if self.marks is not None:
@@ -154,7 +220,13 @@ class TrainEngine:
 
     # -- one optimiser step ---------------------------------------------------------------------
     def step(self, batch: torch.Tensor, spacing2b: Optional[torch.Tensor] = None, local_batch: Optional[torch.Tensor] = None,
-             local_spacing: Optional[torch.Tensor] = None) -> dict:
+             local_spacing: Optional[torch.Tensor] = None, mask_noise: Optional[torch.Tensor] = None) -> dict:
+        """``mask_noise`` ([V, L] fp32, ``loss_type="mae"`` only): the noise whose per-sample order decides which patches are kept;
+        None draws it from torch's global device generator."""
+        if self.mae:
+            return self._step_mae(batch, local_batch, mask_noise)
+        if mask_noise is not None:
+            raise ValueError("mask_noise belongs to loss_type='mae'")
         if not self.use_graph:
             return self._step_eager(batch, spacing2b, local_batch, local_spacing)
         return self._step_graph([batch, spacing2b, local_batch, local_spacing])
@@ -248,6 +320,55 @@ class TrainEngine:
                 loss, l_dino, l_gram, l_koleo, bm, bm_work = self._losses_and_backward_autograd(s_feats, t_feats, t_out, batch, local_batch,
                                                                                                 local_spacing)
         return self._step_tail(lr, last, hyper, loss, l_dino, l_gram, l_koleo, self._zero1.reshape(()), bm, bm_work)
+
+    def _step_mae(self, batch, local_batch, mask_noise) -> dict:
+        """batch (V,3,H,W) fp32 on the device -- every view is one sample, as in the reference (:1725); spacing is ignored there and here.
+        Returns device tensors {loss, dino, gram, koleo, grad_norm_sq, mae} and the python float lr (no sync)."""
+        hp = self.hp
+        if local_batch is not None:
+            raise ValueError("loss_type='mae' takes the global views only (no local crops)")
+        if isinstance(batch, ops.PatchOperand):
+            raise ValueError("loss_type='mae' takes the fp32 image batch (the loss reads its pixels), not a PatchOperand")
+        lr = get_lr(self.step_count, hp.max_steps, hp.warmup_steps, hp.lr, hp.min_lr)
+        first = self.step_count % self.accum == 0
+        last = (self.step_count + 1) % self.accum == 0
+        self._mark("start")
+        if first:
+            ops.zero_(self.flat_g)
+        if ops.grad_sink.owner is not self:
+            ops.grad_sink.register(self, self.params[:len(self.params) - len(self.unreached)], None)
+            ops.weight_cache.shadows = self.shadows
+        ops.grad_sink.uses.clear()
+        model = self.student
+        with ops.compute_dtype(self.compute_dtype):
+            pred_full, ids_restore = model.forward_full(batch, mask_noise)
+            self._mark("fwd_student")
+            with torch.no_grad():
+                loss, saved = ops.mae_loss_fwd(pred_full.detach(), batch, ids_restore, model.len_keep, model.encoder.patch, lead=1)
+                dpred = ops.mae_loss_bwd(saved, 1.0 / self.accum)
+            self._mark("loss")
+            torch.autograd.backward([pred_full], [dpred])
+        ops.dw_stream.join()
+        self._mark("bwd")
+        self._mark("comm_exposed")
+        z = self._zero1.reshape(())
+        if last:
+            self.opt_steps += 1
+            kw = dict(lr=lr, weight_decay=hp.weight_decay, beta1=hp.beta1, beta2=hp.beta2, eps=hp.adam_eps, step_t=self.opt_steps, ema=hp.ema)
+            a, b = self.enc_numel, self.opt_numel
+            gsq = ops.adamw_ema_(self.flat_p[:a], self.flat_g[:a], self.adam_m[:a], self.adam_v[:a], None, **kw)      # (the logged norm)
+            ops.adamw_ema_(self.flat_p[a:b], self.flat_g[a:b], self.adam_m[a:b], self.adam_v[a:b], None, **kw)
+            ops.weight_cache.clear()
+            if self.compute_dtype == torch.bfloat16:
+                for sh in self.shadows:
+                    sh.refresh()
+        else:
+            gsq = self._zero1
+        self._mark("optimiser_tail")
+        self.step_count += 1
+        loss = loss.reshape(())
+        self.last = {"loss": loss, "dino": z, "gram": z, "koleo": z, "grad_norm_sq": gsq, "lr": lr, "mae": loss}
+        return self.last
 
     def _step_tail(self, lr, last, hyper, loss, l_dino, l_gram, l_koleo, l_simclr, bm, bm_work) -> dict:
         """Everything after the backward pass: centre EMA (dino), gradient exchange, grad-norm + AdamW (+ teacher EMA, dino)."""
@@ -434,4 +555,6 @@ class TrainEngine:
                "grad_norm": float(r["grad_norm_sq"]) ** 0.5, "lr": r["lr"]}
         if self.simclr:
             out["simclr"] = float(r["simclr"])
+        if self.mae:
+            out["mae"] = float(r["mae"])
         return out

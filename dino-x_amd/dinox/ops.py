@@ -2005,6 +2005,201 @@ def simclr_loss(z1: Tensor, z2: Tensor, temperature: float = 0.1) -> Tensor:
     return NTXentFn.apply(torch.cat([z1, z2], 0), temperature)
 
 
+# ------------------------------------------------------------------------------------------
+# MAE masked-token glue (csrc/mae.hip; reference scripts/phase5_big_run.py:816-1023)
+# ------------------------------------------------------------------------------------------
+def mae_len_keep(L: int, mask_ratio: float) -> int:
+    """``int(L * (1 - mask_ratio))`` as the reference's random_masking computes it (:976)."""
+    return int(L * (1 - mask_ratio))
+
+
+def _mae_ids(ids: Tensor, V: int, n: int, what: str) -> Tensor:
+    _need_cuda(ids)
+    if ids.dtype != torch.int32 or tuple(ids.shape) != (V, n):
+        raise ValueError(f"mae: {what} must be int32 [{V}, {n}], got {ids.dtype} {tuple(ids.shape)}")
+    return _c(ids)
+
+
+def mae_mask_ids(noise: Tensor, len_keep: int):
+    """noise [V, L] fp32 -> (ids_restore [V, L] int32, ids_keep [V, len_keep] int32): ``argsort(argsort(noise))`` and the first
+    ``len_keep`` columns of ``argsort(noise)`` of the reference's random_masking (:981-985), ties resolved as a stable sort."""
+    _need_cuda(noise)
+    if noise.dim() != 2:
+        raise ValueError(f"mae_mask_ids: noise must be [V, L], got {tuple(noise.shape)}")
+    noise = _c(noise.float())
+    V, L = noise.shape
+    ids_restore = torch.empty((V, L), dtype=torch.int32, device=noise.device)
+    ids_keep = torch.empty((V, max(int(len_keep), 0)), dtype=torch.int32, device=noise.device)
+    check(lib.dinox_mae_mask_ids(_p(noise), _p(ids_restore), _p(ids_keep), V, L, int(len_keep), _stream()), "dinox_mae_mask_ids")
+    return ids_restore, ids_keep
+
+
+def mae_gather_unfold(x: Tensor, ids_keep: Tensor, patch: int, dt: torch.dtype) -> Tensor:
+    """[V,3,H,W] fp32 -> the patch-embed operand of the kept patches only: [V*Lk, patch_cols(patch, dt)] in dt, the rows
+    v*L + ids_keep[v, r] of ``patch_unfold`` bit for bit."""
+    if isinstance(x, PatchOperand):
+        raise ValueError("mae: the batch must be the fp32 image batch (the loss reads its pixels), not a PatchOperand")
+    _need_cuda(x)
+    x = _c(x)
+    if x.dtype != torch.float32:
+        x = x.float()
+    V, Cn, H, W = x.shape
+    assert Cn == 3, "2.5D slice stacks have 3 channels"
+    ids_keep = _mae_ids(ids_keep, V, ids_keep.shape[-1], "ids_keep")
+    Lk = ids_keep.shape[1]
+    cols = patch_cols(patch, dt)
+    u = torch.empty((V * Lk, cols), dtype=dt, device=x.device)
+    check(lib.dinox_mae_gather_unfold(_p(x), _p(ids_keep), _p(u), V, H, W, patch, Lk, cols, _code(dt), _stream()), "dinox_mae_gather_unfold")
+    return u
+
+
+class MaeTokensFn(torch.autograd.Function):
+    """Encoder input of the MAE pass: the patch-embedding product on the KEPT patches only (M = V*Lk rows instead of V*L), then
+    [cls + pos[0] | patches[r] + pos[1 + ids_keep[r]]] (reference MaeModel.forward :998-1013).  Same conventions as TokensFn."""
+
+    @staticmethod
+    def forward(ctx, x, pw, pb, cls, pos, ids_restore, ids_keep, patch):
+        dt = current_dtype()
+        _need_cuda(x, pw, cls, pos)
+        V = x.shape[0]
+        D = pw.shape[0]
+        L = pos.shape[1] - 1
+        ids_restore = _mae_ids(ids_restore, V, L, "ids_restore")
+        u = mae_gather_unfold(x, ids_keep, patch, dt)
+        Lk = u.shape[0] // V
+        K0 = 3 * patch * patch
+        wop = weight_operand(pw, dt) if u.shape[1] == K0 else padded_patch_weight(pw, dt, u.shape[1])
+        patches = gemm(u, wop, bias=pb, out_dtype=dt)
+        tokens = torch.empty((V, 1 + Lk, D), dtype=torch.float32, device=x.device)
+        check(lib.dinox_mae_tokens_fwd(_p(patches), _p(_c(cls)), _p(_c(pos)), _p(_c(ids_keep)), _p(tokens), V, L, Lk, D, _code(dt), _stream()),
+              "dinox_mae_tokens_fwd")
+        ctx.save_for_backward(u, pw, pb, ids_restore)
+        ctx.small = (cls, pos)
+        grad_sink.use(pw, pb, cls, pos)
+        ctx.dims, ctx.dt = (V, L, Lk, D), dt
+        return tokens
+
+    @staticmethod
+    def backward(ctx, dtok):
+        u, pw, pb, ids_restore = ctx.saved_tensors
+        V, L, Lk, D = ctx.dims
+        dt = ctx.dt
+        dtok = _c(dtok)
+        dev = dtok.device
+        dpatches = torch.empty((V * Lk, D), dtype=dt, device=dev)
+        dcls = torch.empty((1, 1, D), dtype=torch.float32, device=dev)
+        dpos = torch.empty((1, 1 + L, D), dtype=torch.float32, device=dev)
+        check(lib.dinox_mae_tokens_bwd(_p(dtok), _p(ids_restore), _p(dpatches), _p(dcls), _p(dpos), V, L, Lk, D, _code(dt), _stream()),
+              "dinox_mae_tokens_bwd")
+        K0 = pw[0].numel()
+        if u.shape[1] == K0:
+            dw, db = weight_grad(dpatches, u, pw, pb, pb is not None)
+        else:
+            # padded operand (3 p^2 % 8 != 0 in bf16): as TokensFn.backward -- the first 3 p^2 columns of the product are the gradient
+            dbt = torch.empty(D, dtype=torch.float32, device=dev) if pb is not None else None
+            dwp = gemm(dpatches, u, transA=True, transB=True, out_dtype=torch.float32, colsum_out=dbt)
+            sw, sb = grad_sink.lookup(pw), (grad_sink.lookup(pb) if pb is not None else None)
+            if sw is not None and (pb is None or sb is not None):
+                sw[1].grad.view(D, K0).add_(dwp[:, :K0])
+                grad_sink.ready(sw)
+                if pb is not None:
+                    axpy_(sb[1].grad.view(-1), dbt, 1.0)
+                    grad_sink.ready(sb)
+                dw = db = None
+            else:
+                dw, db = dwp[:, :K0].reshape(pw.shape).contiguous(), dbt
+        cls, pos = ctx.small
+        return None, dw, db, small_grad(cls, dcls), small_grad(pos, dpos), None, None, None
+
+
+class MaeUnshuffleFn(torch.autograd.Function):
+    """Decoder input (reference MaeDecoder.forward :864-870): e [V, 1+Lk, Dd] (the decoder_embed output, fp32 or bf16) -> fp32
+    [V, 1+L, Dd] with the kept rows back at their patch positions, mask_token elsewhere, plus the fixed decoder_pos_embed (which gets
+    no gradient)."""
+
+    @staticmethod
+    def forward(ctx, e, mask_token, dec_pos, ids_restore, ids_keep):
+        _need_cuda(e, mask_token, dec_pos)
+        if e.dtype not in (torch.float32, torch.bfloat16):
+            e = e.float()
+        e = _c(e)
+        V, Ne, Dd = e.shape
+        L, Lk = dec_pos.shape[1] - 1, Ne - 1
+        ids_restore = _mae_ids(ids_restore, V, L, "ids_restore")
+        ids_keep = _mae_ids(ids_keep, V, Lk, "ids_keep")
+        xd = torch.empty((V, 1 + L, Dd), dtype=torch.float32, device=e.device)
+        check(lib.dinox_mae_unshuffle_fwd(_p(e), _p(_c(mask_token)), _p(_c(dec_pos)), _p(ids_restore), _p(xd), V, L, Lk, Dd, _code(e.dtype),
+                                          _stream()), "dinox_mae_unshuffle_fwd")
+        ctx.save_for_backward(ids_restore, ids_keep)
+        ctx.mask_token = mask_token
+        grad_sink.use(mask_token)
+        ctx.dims, ctx.edt = (V, L, Lk, Dd), e.dtype
+        return xd
+
+    @staticmethod
+    def backward(ctx, g):
+        ids_restore, ids_keep = ctx.saved_tensors
+        V, L, Lk, Dd = ctx.dims
+        g = _c(g)
+        dev = g.device
+        de = torch.empty((V, 1 + Lk, Dd), dtype=ctx.edt, device=dev)
+        dmask = torch.empty((1, 1, Dd), dtype=torch.float32, device=dev)
+        ws = torch.empty((V, Dd), dtype=torch.float32, device=dev)
+        check(lib.dinox_mae_unshuffle_bwd(_p(g), _p(ids_keep), _p(ids_restore), _p(de), _p(dmask), _p(ws), V, L, Lk, Dd, _code(ctx.edt),
+                                          _stream()), "dinox_mae_unshuffle_bwd")
+        return de, small_grad(ctx.mask_token, dmask), None, None, None
+
+
+def mae_loss_fwd(pred: Tensor, x: Tensor, ids_restore: Tensor, len_keep: int, patch: int, lead: int = 0):
+    """Reconstruction loss of the reference's forward_loss (:955-969) without a patchified copy of the batch: pred
+    [V, lead + L, 3 p^2] (fp32 or bf16; lead = 1 when the decoder's CLS row is still in front), x [V,3,H,W] fp32, ids_restore [V, L].
+    Returns (loss[1] fp32 on the device, saved); mae_loss_bwd(saved, gscale) gives d(gscale * loss)/dpred."""
+    _need_cuda(pred, x, ids_restore)
+    if isinstance(x, PatchOperand):
+        raise ValueError("mae: the batch must be the fp32 image batch (the loss reads its pixels), not a PatchOperand")
+    if pred.dtype not in (torch.float32, torch.bfloat16):
+        pred = pred.float()
+    pred, x = _c(pred), _c(x.float())
+    V, Cn, H, W = x.shape
+    L = (H // patch) * (W // patch) if patch > 0 else 0
+    if Cn != 3 or pred.dim() != 3 or tuple(pred.shape) != (V, lead + L, 3 * patch * patch):
+        raise ValueError(f"mae_loss: pred {tuple(pred.shape)} is not [V, {lead} + L, 3 p^2] = [{V}, {lead + L}, {3 * patch * patch}] "
+                         f"for images {tuple(x.shape)} and patch {patch}")
+    ids_restore = _mae_ids(ids_restore, V, L, "ids_restore")
+    loss = torch.empty(1, dtype=torch.float32, device=x.device)
+    ws = torch.empty(V * L, dtype=torch.float32, device=x.device)
+    check(lib.dinox_mae_loss_fwd(_p(pred), _p(x), _p(ids_restore), _p(loss), _p(ws), V, H, W, patch, int(len_keep), lead, _code(pred.dtype),
+                                 _stream()), "dinox_mae_loss_fwd")
+    return loss, (pred, x, ids_restore, int(len_keep), patch, lead)
+
+
+def mae_loss_bwd(saved, gscale: float = 1.0, out_dtype: Optional[torch.dtype] = None) -> Tensor:
+    """dpred (the layout of pred; ``out_dtype`` defaults to pred's dtype) = d(gscale * loss)/dpred: exactly 0 on kept patches and on the
+    lead rows.  The upstream factor is a host scalar (1 / accumulation steps)."""
+    pred, x, ids_restore, len_keep, patch, lead = saved
+    V, _, H, W = x.shape
+    dpred = torch.empty(pred.shape, dtype=out_dtype or pred.dtype, device=pred.device)
+    check(lib.dinox_mae_loss_bwd(_p(pred), _p(x), _p(ids_restore), _p(dpred), float(gscale), V, H, W, patch, len_keep, lead,
+                                 _code(pred.dtype), _code(dpred.dtype), _stream()), "dinox_mae_loss_bwd")
+    return dpred
+
+
+class MaeLossFn(torch.autograd.Function):
+    """mae_loss_fwd / mae_loss_bwd as an autograd node (callers outside the engine)."""
+
+    @staticmethod
+    def forward(ctx, pred, x, ids_restore, len_keep, patch, lead):
+        loss, saved = mae_loss_fwd(pred, x, ids_restore, len_keep, patch, lead)
+        ctx.saved, ctx.pdt = saved, pred.dtype
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        # the upstream gradient is a device scalar: run with gscale = 1 and scale the result (no host sync)
+        d = mae_loss_bwd(ctx.saved, 1.0) * g
+        return (d if d.dtype == ctx.pdt else d.to(ctx.pdt)), None, None, None, None, None
+
+
 def adamw_hyper(lr: float, beta1: float, beta2: float, step_t: int) -> list:
     """The three per-step scalars of the optimiser pass -- [lr, 1/(1-beta1^t), 1/sqrt(1-beta2^t)] -- for dinox_adamw_ema_dev."""
     # with the betas as the fp32 values the C entry receives (dinox_adamw_ema raises (double)(float)beta to the step): the replayed

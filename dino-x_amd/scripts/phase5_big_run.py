@@ -25,7 +25,13 @@ loop :1686-1997), and the same importable names other reference scripts/tests us
   patch-norm heatmap, the CLS attention of the last block per head (which the reference cannot produce), the input slice and
   ``stats.json`` (embedding std / norm, per-head attention entropy) as ``.npy`` and PNG (there is no TensorBoard here); the embedding
   std feeds ``detect_anomaly``; prints ``monitor_saved=``.  Training is bit-identical with and without it;
-* not wired to the engine yet (exit with a message): ``--loss-type mae``, ``--device cpu`` (there is no CPU compute path).
+* ``--loss-type mae`` runs the reference's masked-autoencoder mode (dinox.mae.MaeModel on the masked-token kernels of
+  dinox.ops.mae_*) when ``--mae-decoder DIMxDEPTHxHEADS`` is given (the reference's hard-coded decoder is ``512x8x16``;
+  ``--mae-mask-ratio``, default 0.75): no teacher, no EMA; checkpoints hold the MaeModel state dict (``encoder.*`` / ``decoder.*``)
+  under both ``student`` and ``teacher``, as the reference's do; ``--gpu-views`` hands over fp32 image batches (the loss reads
+  pixels); the monitor runs on the encoder.  One GPU, no ``--hip-graph``, no ``--local-crops``.  Without ``--mae-decoder`` the bare
+  spelling still exits with a message;
+* not wired to the engine (exit with a message): ``--device cpu`` (there is no CPU compute path).
 """
 from __future__ import annotations
 
@@ -58,6 +64,7 @@ from dinox import ops  # noqa: E402
 from dinox.dp import init_process_group  # noqa: E402
 from dinox.engine import StepHyperParams, TrainEngine  # noqa: E402
 from dinox.hostinfo import usable_cpus  # noqa: E402
+from dinox.mae import MaeDecoder, MaeModel, parse_decoder_spec  # noqa: E402,F401  (the reference defines the two classes in this script)
 from dinox.schedule import get_lr  # noqa: E402,F401
 from zoo.arch import DinoStudentTeacher, PatchViT, ScaleEmbedding, TransformerBlock, migrate_state_dict, needs_migration  # noqa: E402,F401
 
@@ -355,6 +362,54 @@ class DiverseBatchSampler(torch.utils.data.Sampler):
             yield order[full:]
 
 
+class StepKeyedBatchSampler(torch.utils.data.Sampler):
+    """``--loss-type mae``: the batch of training step ``s`` is a function of ``(seed, s)`` alone, so a resumed run reads the batches the
+    interrupted one would have read.  Epoch ``e = s // batches_per_epoch`` is a permutation seeded with ``(seed, e)``; the sampler
+    starts at ``start_step``, never ends, and yields ``(s, index)`` keys for StepKeyedDataset."""
+
+    def __init__(self, n: int, batch_size: int, seed: int, start_step: int = 0):
+        self.n, self.batch_size, self.seed, self.start_step = n, batch_size, seed, start_step
+
+    def __len__(self):
+        return self.n // self.batch_size
+
+    def __iter__(self):
+        s, per, epoch, order = self.start_step, len(self), -1, None
+        while True:
+            if s // per != epoch:
+                epoch = s // per
+                order = torch.randperm(self.n, generator=torch.Generator().manual_seed(self.seed * 1_000_003 + epoch)).tolist()
+            b = s % per
+            yield [(s, i) for i in order[b * self.batch_size:(b + 1) * self.batch_size]]
+            s += 1
+
+
+class StepKeyedDataset(torch.utils.data.Dataset):
+    """Item ``(s, i)`` of StepKeyedBatchSampler: row ``i`` of ``inner`` with every random draw of its augmentation seeded by
+    ``(seed, s, i)``.  The generators of the calling process (Python, NumPy, torch CPU) are put back afterwards, so neither the number
+    of loader workers nor a restart changes a batch, and with ``--num-workers 0`` the step's own draws are not disturbed."""
+
+    def __init__(self, inner, seed: int):
+        self.inner, self.seed = inner, seed
+
+    def __len__(self):
+        return len(self.inner)
+
+    def __getitem__(self, key):
+        s, i = key
+        saved = (random.getstate(), np.random.get_state(), torch.get_rng_state())
+        k = (self.seed * 1_000_003 + s) * 1_000_003 + i
+        random.seed(k)
+        np.random.seed(k % 2 ** 32)
+        torch.default_generator.manual_seed(k)
+        try:
+            return self.inner[i]
+        finally:
+            random.setstate(saved[0])
+            np.random.set_state(saved[1])
+            torch.set_rng_state(saved[2])
+
+
 class ShardedBatchSampler(torch.utils.data.Sampler):
     """Data-parallel sharding of a batch sampler: ``inner`` yields GLOBAL batches (world x per-rank batch indices) from a
     generator seeded identically on every rank, and rank r keeps the contiguous slice dp.shard_range gives it.  The union over
@@ -439,8 +494,11 @@ def adamw_state_dict(eng: TrainEngine, lr: float) -> dict:
     template = torch.optim.AdamW(eng.params, lr=lr, betas=(eng.hp.beta1, eng.hp.beta2), eps=eng.hp.adam_eps,
                                  weight_decay=eng.hp.weight_decay).state_dict()
     state = {}
+    index = getattr(eng, "state_index", None) or range(len(eng.params))      # (mae: the arena order differs from parameters())
     if eng.opt_steps > 0:
-        for i, (p, off) in enumerate(zip(eng.params, eng.offsets)):
+        for i, p, off in zip(index, eng.params, eng.offsets):
+            if p.grad is None:                                                # (mae: never reached -- the reference's AdamW has no state for it)
+                continue
             n = p.numel()
             state[i] = {"step": torch.tensor(float(eng.opt_steps)),
                         "exp_avg": eng.adam_m[off:off + n].view(p.shape).clone(),
@@ -452,7 +510,8 @@ def adamw_state_dict(eng: TrainEngine, lr: float) -> dict:
 def load_adamw_state_dict(eng: TrainEngine, sd: dict) -> None:
     state = sd.get("state", {})
     steps = 0
-    for i, (p, off) in enumerate(zip(eng.params, eng.offsets)):
+    index = getattr(eng, "state_index", None) or range(len(eng.params))
+    for i, p, off in zip(index, eng.params, eng.offsets):
         st = state.get(i, state.get(str(i)))
         if st is None:
             continue
@@ -604,6 +663,26 @@ def build_parser() -> argparse.ArgumentParser:
     return ap
 
 
+def build_mae_parser() -> argparse.ArgumentParser:
+    """The options of the MAE objective.  They are a parser of their own: ``build_parser()`` stays the reference's flag surface plus
+    the general extensions, and ``parse_cli`` reads these two out of the command line first."""
+    ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    ap.add_argument("--mae-decoder", type=str, default=None, metavar="DIMxDEPTHxHEADS",
+                    help="Run --loss-type mae with this decoder (the reference hard-codes 512x8x16); without it --loss-type mae exits")
+    ap.add_argument("--mae-mask-ratio", type=float, default=0.75, help="Share of the patches the MAE encoder does not see (default: 0.75)")
+    return ap
+
+
+def parse_cli(argv=None) -> argparse.Namespace:
+    """The MAE options (build_mae_parser) first, everything else through build_parser; one namespace."""
+    mae, rest = build_mae_parser().parse_known_args(argv)
+    ap = build_parser()
+    ap.epilog = "MAE objective: " + " ".join(build_mae_parser().format_help().split()[1:])
+    args = ap.parse_args(rest)
+    args.mae_decoder, args.mae_mask_ratio = mae.mae_decoder, mae.mae_mask_ratio
+    return args
+
+
 def resolve_model_config(args) -> ModelConfig:
     presets = _presets()
     if args.config == "custom":
@@ -627,7 +706,22 @@ def resolve_model_config(args) -> ModelConfig:
 def check_loss_type(args, world: int = 1) -> None:
     """Exit with a message for the objectives / combinations the engine does not run (host-side: touches no device)."""
     if args.loss_type == "mae":
-        raise SystemExit("--loss-type mae is not wired to the MI355X engine yet (only 'dino' and 'simclr'; see DESIGN.md section 7)")
+        if not getattr(args, "mae_decoder", None):
+            raise SystemExit("--loss-type mae is not wired to the MI355X engine unless --mae-decoder is given (the reference's decoder is 512x8x16)")
+        try:
+            parse_decoder_spec(args.mae_decoder)
+        except ValueError as e:
+            raise SystemExit(str(e)) from None
+        if not 0.0 < args.mae_mask_ratio < 1.0:
+            raise SystemExit(f"--mae-mask-ratio must lie strictly between 0 and 1, got {args.mae_mask_ratio}")
+        if args.local_crops:
+            raise SystemExit("--loss-type mae takes the global views only: drop --local-crops (multi-crop is a DINO-term extension)")
+        if args.hip_graph:
+            raise SystemExit("--loss-type mae does not run under --hip-graph yet (the step is launched eagerly)")
+        if getattr(args, "diverse_batches", False):
+            raise SystemExit("--loss-type mae draws batches keyed on the step (bit-identical --resume): drop --diverse-batches")
+        if world > 1:
+            raise SystemExit(f"--loss-type mae runs on one GPU only (got {world} ranks): data-parallel MAE is not implemented")
     if args.loss_type == "simclr" and args.local_crops:
         raise SystemExit("--loss-type simclr takes the two global views only: drop --local-crops (multi-crop is a DINO-term extension)")
     if args.loss_type == "simclr" and world > 1:
@@ -636,7 +730,7 @@ def check_loss_type(args, world: int = 1) -> None:
 
 
 def main(argv=None) -> None:
-    args = build_parser().parse_args(argv)
+    args = parse_cli(argv)
     check_loss_type(args)
     if args.amp and args.amp_dtype != "bfloat16":
         raise SystemExit("the HIP path supports --amp-dtype bfloat16 only")
@@ -769,7 +863,15 @@ def main(argv=None) -> None:
                   collate_fn=collate_stacks if args.gpu_views else dino_collate, persistent_workers=hw.num_workers > 0)
     if len(ds) < args.batch_size * world:
         raise SystemExit(f"dataset size ({len(ds)}) is smaller than the global batch ({args.batch_size} x {world} ranks)")
-    if args.diverse_batches:
+    loader_ds = ds
+    if args.loss_type == "mae":
+        # batches keyed on the step (StepKeyedBatchSampler): --resume then continues with the batches, augmentations and mask noise the
+        # interrupted run would have used.  The step is read here because the loader starts before the model exists
+        from zoo.hub import read_checkpoint
+        first = int(read_checkpoint(resume_from, "cpu")["step"]) if resume_from else 0
+        sampler = StepKeyedBatchSampler(len(ds), args.batch_size, args.train_seed, first)
+        loader_ds = StepKeyedDataset(ds, args.train_seed)
+    elif args.diverse_batches:
         sampler = DiverseBatchSampler(rows, batch_size=args.batch_size * world, drop_last=True, generator=gen)
         say(f"diverse_batches=True batches_per_epoch={len(sampler)}")
     else:
@@ -777,13 +879,14 @@ def main(argv=None) -> None:
                                                 drop_last=True)
     if world > 1:
         sampler = ShardedBatchSampler(sampler, rank, world)
-    dl = torch.utils.data.DataLoader(ds, batch_sampler=sampler, **common)
+    dl = torch.utils.data.DataLoader(loader_ds, batch_sampler=sampler, **common)
     # (iter(dl) draws the loader's base seed from torch's global generator: both pipelines do it here, before the model is initialised,
     #  so that the same --train-seed gives the same initial weights with and without --gpu-views)
     it, prefetch = None, None
     # --gpu-views writes the patch-embed operand itself (dinox_slice_views_patches): the fp32 image batch never exists.
     # DINOX_VIEWS_IMAGE=1: the image batch + the separate unfold launch instead (A/B; bit-identical operand)
-    view_kw = {} if os.environ.get("DINOX_VIEWS_IMAGE") else dict(patch=model_cfg.patch, operand_dtype=torch.bfloat16 if args.amp else torch.float32)
+    # --loss-type mae: the image batch too (the reconstruction loss reads fp32 pixels)
+    view_kw = {} if os.environ.get("DINOX_VIEWS_IMAGE") or args.loss_type == "mae" else dict(patch=model_cfg.patch, operand_dtype=torch.bfloat16 if args.amp else torch.float32)
     if args.gpu_views:
         from dinox.views import DevicePrefetcher
         prefetch = DevicePrefetcher(dl, device, ahead=not os.environ.get("DINOX_NO_PREFETCH"))     # the next batch crosses PCIe under this step
@@ -799,7 +902,7 @@ def main(argv=None) -> None:
     hp = StepHyperParams(lr=args.lr, min_lr=args.min_lr, warmup_steps=args.warmup_steps, max_steps=args.max_steps,
                          weight_decay=args.weight_decay, ema=args.ema, teacher_temp=args.teacher_temp, student_temp=args.student_temp,
                          center_momentum=args.center_momentum, gram_weight=args.gram_weight,
-                         koleo_weight=args.koleo_weight, loss_type=args.loss_type)
+                         koleo_weight=args.koleo_weight, loss_type=args.loss_type, mae_mask_ratio=args.mae_mask_ratio)
     if args.hip_graph and (world > 1 or args.accumulation_steps != 1 or args.local_crops):
         raise SystemExit("--hip-graph: single GPU, --accumulation-steps 1 and no --local-crops (the captured step has one fixed batch layout)")
     if device.type == "cuda" and not args.hip_graph and args.streams != "off":
@@ -809,12 +912,23 @@ def main(argv=None) -> None:
         if "DINOX_DW_STREAM" not in os.environ:
             ops.dw_stream.enabled = True
         say(f"streams side={int(bool(os.environ.get('DINOX_SIDE_STREAM')))} dw={int(ops.dw_stream.enabled)}")
-    eng = TrainEngine(student, teacher, model_cfg.out_dim, hp, amp_dtype=torch.bfloat16 if args.amp else None,
-                      accumulation_steps=args.accumulation_steps, use_graph=bool(args.hip_graph))
+    ckpt_student, ckpt_teacher = student, teacher
+    if args.loss_type == "mae":
+        # reference :1627-1632, :1879-1881: MaeModel around the student's backbone; it is what trains and what both checkpoint entries hold
+        d_dim, d_depth, d_heads = parse_decoder_spec(args.mae_decoder)
+        mae_model = MaeModel(student.backbone, decoder_dim=d_dim, mask_ratio=args.mae_mask_ratio, decoder_depth=d_depth,
+                             decoder_heads=d_heads).to(device)
+        say(f"mae_decoder={d_dim}x{d_depth}x{d_heads} mask_ratio={args.mae_mask_ratio} kept_patches={mae_model.len_keep}/{mae_model.num_patches}")
+        ckpt_student = ckpt_teacher = mae_model
+        eng = TrainEngine(mae_model, None, model_cfg.out_dim, hp, amp_dtype=torch.bfloat16 if args.amp else None,
+                          accumulation_steps=args.accumulation_steps)
+    else:
+        eng = TrainEngine(student, teacher, model_cfg.out_dim, hp, amp_dtype=torch.bfloat16 if args.amp else None,
+                          accumulation_steps=args.accumulation_steps, use_graph=bool(args.hip_graph))
     start_step = 0
     if resume_from:
         say(f"resume=true checkpoint={resume_from}")
-        start_step, loaded = load_checkpoint(resume_from, student, teacher, eng, device, scale_aware=args.scale_aware)
+        start_step, loaded = load_checkpoint(resume_from, ckpt_student, ckpt_teacher, eng, device, scale_aware=args.scale_aware)
         say(f"resumed_from_step={start_step}")
         if loaded and loaded.model and loaded.model.name != model_cfg.name:
             warnings.warn(f"Model config mismatch: checkpoint={loaded.model.name} requested={model_cfg.name}")
@@ -929,13 +1043,13 @@ def main(argv=None) -> None:
             if bad and ("NaN" in msg or "Inf" in msg):
                 say(f"❌ CRITICAL: {msg}")
                 if main_rank:
-                    save_checkpoint(run_dir / f"emergency_checkpoint_step{s_}.pth", s_, student, teacher, eng, cfg)
+                    save_checkpoint(run_dir / f"emergency_checkpoint_step{s_}.pth", s_, ckpt_student, ckpt_teacher, eng, cfg)
                 raise RuntimeError(msg)
             if bad:
                 say(f"⚠️  WARNING: {msg}")
         if (step + 1) % args.ckpt_every == 0 and main_rank:
             path = run_dir / f"checkpoint_{step + 1:08d}.pth"
-            save_checkpoint(path, step + 1, student, teacher, eng, cfg)
+            save_checkpoint(path, step + 1, ckpt_student, ckpt_teacher, eng, cfg)
             say(f"checkpoint_saved={path}")
             rotate_checkpoints(run_dir, args.ckpt_keep_last)
         if args.monitor_every and (step + 1) % args.monitor_every == 0 and main_rank:
@@ -959,7 +1073,7 @@ def main(argv=None) -> None:
     final_step = step + 1
     if main_rank:
         final = run_dir / f"checkpoint_final_{final_step:08d}.pth"
-        save_checkpoint(final, final_step, student, teacher, eng, cfg)
+        save_checkpoint(final, final_step, ckpt_student, ckpt_teacher, eng, cfg)
         say(f"final_checkpoint={final}")
     say("─" * 80)
     say(f"Training complete: {final_step - start_step} steps in {time.time() - t0:.1f}s")

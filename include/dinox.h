@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define DINOX_ABI_VERSION 3   /* 3: + dinox_block_forward / _backward, dinox_gemm_timer_*, dinox_retrieval_* (later also dinox_retrieval_rank_windowed*, dinox_row_dots), dinox_knn_*, dinox_gram_*, dinox_softmax_probe*, dinox_ntxent_*, dinox_normalize_bwd, dinox_attention_rows*, dinox_attention_rollout_step* (all additive: no entry
+#define DINOX_ABI_VERSION 3   /* 3: + dinox_block_forward / _backward, dinox_gemm_timer_*, dinox_retrieval_* (later also dinox_retrieval_rank_windowed*, dinox_row_dots), dinox_knn_*, dinox_gram_*, dinox_softmax_probe*, dinox_ntxent_*, dinox_normalize_bwd, dinox_mae_*, dinox_attention_rows*, dinox_attention_rollout_step* (all additive: no entry
                                * of an earlier library changed, so the number callers test, dinox_version() == 3, stays; probe the symbol
                                * to learn whether a given build has the later additions) */
 
@@ -343,6 +343,46 @@ int dinox_ntxent_rows(const float* S, int64_t lds, int M, float inv_tau, float* 
 int dinox_ntxent_coeff(const float* S, int64_t lds, const float* lse, int M, float inv_tau, float gscale, float* W, int64_t ldw,
                        void* stream);
 int dinox_normalize_bwd(const float* dxh, const float* xh, const float* norm, float* dx, int64_t V, int D, float eps, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * MAE masked-token glue -- replaces MaeModel.random_masking / forward / patchify / forward_loss and the un-shuffle of
+ * MaeDecoder.forward (scripts/phase5_big_run.py:816-1023) and their backward.  V samples of L = (H/patch)(W/patch) patches, of which
+ * the Lk of lowest noise are kept.  ids_restore [V][L] int32 = rank of every patch; ids_keep [V][Lk] int32 = patch of every kept rank.
+ * A patch is "removed" when its rank is outside [0, Lk).  Limits: 1 <= V <= 2^20, 2 <= L <= 4096, 1 <= Lk < L, 1 <= D <= 65536,
+ * patch <= 32 for the loss entries; anything else, a null pointer or a dtype other than DINOX_F32 / DINOX_BF16 returns DINOX_EINVAL
+ * before any launch.  Indices read from ids_* are range-checked on the device before use.  No float atomics; every sum has a fixed order.
+ *   mask_ids:      ids_restore[v][p] = #{q : noise[v][q] < noise[v][p], or equal and q < p} (torch.argsort(stable=True) twice; -0 == +0,
+ *                  NaN above everything); ids_keep[v][r] = p where the rank r < Lk.  One workgroup per sample.
+ *   gather_unfold: u[(v Lk + r)][c p p + py p + px] = x[v][c][gy p + py][gx p + px] for patch ids_keep[v][r] = gy (W/p) + gx, rows of
+ *                  ld >= 3 p^2 elements with a zero tail: rows v L + ids_keep[v][r] of dinox_patch_unfold / _ld, bit for bit.
+ *   tokens_fwd:    tokens [V][1 + Lk][D] fp32: [v][0] = cls + pos[0];  [v][1 + r] = patches[v][r] + pos[1 + ids_keep[v][r]].
+ *   tokens_bwd:    dpatches[v][r] = dtokens[v][1 + r] (operand dtype);  dpos[0] = dcls = sum_v dtokens[v][0];
+ *                  dpos[1 + p] = sum_{v : ids_restore[v][p] < Lk} dtokens[v][1 + ids_restore[v][p]], ascending v (dpos is [1 + L][D]).
+ *   unshuffle_fwd: xd [V][1 + L][D] fp32: [v][0] = e[v][0] + dec_pos[0];  [v][1 + p] = (kept ? e[v][1 + ids_restore[v][p]] : mask_token)
+ *                  + dec_pos[1 + p];  e is [V][1 + Lk][D] in e_dtype.
+ *   unshuffle_bwd: de[v][0] = g[v][0], de[v][1 + r] = g[v][1 + ids_keep[v][r]] (de_dtype);  dmask_token = sum of g over the removed
+ *                  (v, p): per sample in ascending p into ws [V][D] fp32, then over ascending v.  dec_pos gets no gradient.
+ *   loss_fwd:      pred [V][lead + L][3 p^2] (lead = 1: the CLS row is still in front; 0: it was dropped), target pixel
+ *                  x[v][c][gy p + py][gx p + px] at column (py p + px) 3 + c, read from the image.
+ *                  loss[0] = sum_{removed (v,l)} mean_j (pred - target)^2 / (V (L - Lk));  ws: V L floats (the per-patch means).
+ *   loss_bwd:      dpred (same layout, dpred_dtype) = gscale 2 (pred - target) / (3 p^2 V (L - Lk)) on removed patches, exactly 0 on kept
+ *                  ones and on the lead rows.  dpred must not alias pred.
+ * ------------------------------------------------------------------------------------------ */
+int dinox_mae_mask_ids(const float* noise, int* ids_restore, int* ids_keep, int V, int L, int Lk, void* stream);
+int dinox_mae_gather_unfold(const float* x, const int* ids_keep, void* u, int V, int H, int W, int patch, int Lk, int ld, int out_dtype,
+                            void* stream);
+int dinox_mae_tokens_fwd(const void* patches, const float* cls, const float* pos, const int* ids_keep, float* tokens, int V, int L, int Lk,
+                         int D, int patches_dtype, void* stream);
+int dinox_mae_tokens_bwd(const float* dtokens, const int* ids_restore, void* dpatches, float* dcls, float* dpos, int V, int L, int Lk, int D,
+                         int patches_dtype, void* stream);
+int dinox_mae_unshuffle_fwd(const void* e, const float* mask_token, const float* dec_pos, const int* ids_restore, float* xd, int V, int L,
+                            int Lk, int D, int e_dtype, void* stream);
+int dinox_mae_unshuffle_bwd(const float* g, const int* ids_keep, const int* ids_restore, void* de, float* dmask_token, float* ws, int V,
+                            int L, int Lk, int D, int de_dtype, void* stream);
+int dinox_mae_loss_fwd(const void* pred, const float* x, const int* ids_restore, float* loss, float* ws, int V, int H, int W, int patch,
+                       int Lk, int lead, int pred_dtype, void* stream);
+int dinox_mae_loss_bwd(const void* pred, const float* x, const int* ids_restore, void* dpred, float gscale, int V, int H, int W, int patch,
+                       int Lk, int lead, int pred_dtype, int dpred_dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Attention rows -- the softmax rows of a few query tokens (CLS, the registers) over all keys, per head: the attention map the
