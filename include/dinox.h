@@ -69,6 +69,19 @@ int dinox_device_ok(void);
  *   DGELU     acc *= gelu_erf'(aux[m][n])          (aux read, out_dtype)
  *   RESIDUAL  acc += residual[m][n]                (fp32, ld = ldr)
  *   ACCUM     C += acc instead of C = acc          (fp32 C only)
+ *
+ * Addressing (every kernel, tests/test_gemm_contract_gpu.py holds each of them to it):
+ *   A(b,m,k) = A[b strideA + m lda + k]  (transA = 1: A[b strideA + k lda + m]);  B alike;  C[b strideC + m ldc + n].
+ *   Leading dimensions may exceed the width; what lies between the width and the leading dimension, between batch items and
+ *   around the operands is never used (inputs) and never written (C, aux, colsum) -- vector stores included.
+ *   strideA / strideB = 0 shares the operand between the batch items; strideC must keep the items of C apart.
+ *   aux and residual have NO stride field: item b starts M ldaux / M ldr elements after item b - 1, i.e.
+ *   aux[b M ldaux + m ldaux + n], residual[b M ldr + m ldr + n] (rows of all items at one pitch, as a [batch M][N] matrix).
+ *   bias is shared by the batch items.  alpha scales the product only (before BIAS), never colsum.
+ *   Alignment never changes the result, only the kernel: the bf16 MFMA kernels need A, B on 16 bytes and lda, ldb, strideA,
+ *   strideB multiples of 8; those that store by 16-byte vectors also C, aux, residual, bias on 16 bytes, rows of C and aux of
+ *   a multiple of 16 bytes and ldr a multiple of 4.  Anything else runs on a kernel that takes it (in the end gemm_f32, which
+ *   multiplies the bf16 values in exact fp32); dinox_gemm_kernel_name tells which.
  * ------------------------------------------------------------------------------------------ */
 #define DINOX_EPI_BIAS 1
 #define DINOX_EPI_GELU 2
@@ -110,10 +123,15 @@ typedef struct dinox_gemm_args {
 } dinox_gemm_args;
 
 int dinox_gemm(const dinox_gemm_args* args, void* stream);
-/* Bytes of workspace that make this product deterministic (0: it needs none / cannot use one). */
+/* Bytes of workspace that make this product deterministic (0: it needs none / cannot use one: only a split-K TN product with ONE
+ * contiguous fp32 result -- batch = 1, ldc = N, epilogue empty or ACCUM -- has a two-stage reduction; with ldc != N or batch > 1
+ * the partial sums meet through fp32 atomics under ACCUM, and without ACCUM, where C would have to be zeroed first and is not
+ * contiguous, the product runs as one split). */
 int64_t dinox_gemm_ws_bytes(const dinox_gemm_args* args);
-/* Name of the device kernel dinox_gemm would launch for these arguments ("gemm_bf16_nt", "gemm_bf16_tn",
- * "gemm_f32"); host-only query used by bench.py to attribute per-launch timings.  Static string. */
+/* Name of the device kernel dinox_gemm would launch for these arguments ("gemm_bf16_nt", "gemm_bf16_nt_glds", "gemm_bf16_nt_areg",
+ * "gemm_bf16_nt_pp", "gemm_bf16_nt_pp128", "gemm_bf16_nt_pp384", "gemm_bf16_tn", "gemm_bf16_tn_dma", "gemm_bf16_tn_big",
+ * "gemm_f32"); host-only query used by bench.py to attribute per-launch timings and by the tests to see that a case ran on the
+ * kernel it is about.  Static string. */
 const char* dinox_gemm_kernel_name(const dinox_gemm_args* args);
 
 /* out[n] (+)= sum_m x[m][n]   -- bias gradients (autograd of nn.Linear bias, zoo/arch.py:40-41,71-73). */
