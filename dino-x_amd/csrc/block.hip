@@ -4,10 +4,13 @@
 // call them one by one -- ~13 launches forward, ~15 backward.  What changes is the host: a Python caller pays one foreign call and one
 // struct per block instead of ~35 us per launch (24 ms of enqueue per ViT-S bs-256 step, of a 38 ms step), and the sequencing works under
 // data parallelism and gradient accumulation, where a captured hipGraph (TrainEngine(use_graph=True)) does not.
+// Which of those launches run fused is the caller's to pass in (fuse_proj_ln, fuse_fc2_ln, fuse_ln_bwd, qkv == NULL) and dinox_block_plan's
+// to decide: the one home of the block-level fusion rules and their knobs, host logic that a CPU test can pin (tests/test_block_plan_cpu.py).
 // Reference: zoo/arch.py:94-97 (TransformerBlock.forward) with Attention :43-54 and Mlp :75-76, and their autograd backward.
 #include <cstring>
 
 #include "common.h"
+#include "kernels.h"
 
 using namespace dinox;
 
@@ -55,7 +58,53 @@ int weight_grad(const void* dy, const void* x, float* dw, float* db, int64_t M, 
   return dinox_gemm(&g, stream);
 }
 
+// ---- the measured rules behind dinox_block_plan (MI355X, hot-path shape M = 102 912 rows unless a line says otherwise)
+
+// A width-384 product + the LayerNorm behind it as ONE launch (dinox_linear_residual_ln)?
+//   * on the full-row kernel's LayerNorm epilogue (linear_residual_ln_full_row: bf16 y, M >= 40000): proj + LN 103 us against 85 + 44 us
+//     for the two launches, fc2 + LN 206 us against 177 + 44 -> both fused (DINOX_ROWLN_FC2=0 keeps fc2 apart: the A/B of that gain);
+//   * on the 128 x 384 kernel (fp32 y, small M): proj + LN 130 us against 85 + 44 -> fused for short reductions (K <= 576); fc2 + LN
+//     256 us against 177 + 44 -> not fused.
+// DINOX_ROWLN: 0 = never, 1 = every product in dinox_linear_residual_ln_ok.
+bool fuse_linear_ln(int64_t M, int N, int K, int y_dtype) {
+  const int mode = knob_int("DINOX_ROWLN", -1);
+  if (mode == 0 || !dinox_linear_residual_ln_ok(M, N, K)) return false;
+  return mode > 0 || K <= 576 || (linear_residual_ln_full_row(M, K, y_dtype) && knob_int("DINOX_ROWLN_FC2", 1) != 0);
+}
+
+// The input-gradient product into a LayerNorm + that LayerNorm's backward as ONE launch (dinox_linear_ln_bwd; the results equal the two
+// launches' to the last bit)?  On a chip's worth of rows; DINOX_LNBWD_PP: 0 = never, 1 = wherever the kernel applies.
+bool fuse_linear_ln_bwd(int64_t M, int N, int K) {
+  const int mode = knob_int("DINOX_LNBWD_PP", -1);
+  return mode != 0 && dinox_linear_ln_bwd_ok(M, N, K) && (mode > 0 || M >= 8192);
+}
+
+// A pass that keeps nothing for a backward (the teacher of a step, encode()): qkv projection + attention as ONE launch
+// (dinox_qkv_attention_fwd)?  In isolation a tie at ViT-S (219-227 us against 208-222) and slower at ViT-L (500 against 408 us; DESIGN.md
+// section 4); in the step, where the teacher's qkv tensor is 237 MB written and read back between two kernels that each start cold,
+// 0.2 ms per step faster at width 384 (35.01 -> 34.80 ms, interleaved on one box) -> widths up to 512.  DINOX_QKV_FUSED: 0 = never,
+// 1 = every width.
+bool fuse_qkv_attention(int64_t V, int64_t N, int D, int heads) {
+  if (!knob_int("DINOX_QKV_FUSED", D <= 512) || D % heads != 0 || V > INT32_MAX || N > INT32_MAX) return false;
+  return dinox_qkv_attention_ok((int)V, (int)N, heads, D / heads, D) != 0;
+}
+
 }  // namespace
+
+// Host logic only: reads the four knobs above (per call), launches nothing, dereferences nothing but `out`.
+extern "C" int dinox_block_plan(int64_t V, int64_t N, int D, int H, int heads, int dtype, int train, int next_dtype, dinox_block_plan_t* out) {
+  DX_REQUIRE(out, DINOX_EINVAL, "block_plan: null plan");
+  DX_REQUIRE(V > 0 && N > 0 && D > 0 && H > 0 && heads > 0 && (dtype == DINOX_F32 || dtype == DINOX_BF16), DINOX_EINVAL,
+             "block_plan: V=%lld N=%lld D=%d H=%d heads=%d dtype=%d", (long long)V, (long long)N, D, H, heads, dtype);
+  memset(out, 0, sizeof *out);
+  if (dtype != DINOX_BF16) return 0;      // the fp32 parity mode fuses nothing
+  const int64_t M = V * N;
+  out->qkv_fused = !train && fuse_qkv_attention(V, N, D, heads);
+  out->fuse_proj_ln = fuse_linear_ln(M, D, D, DINOX_BF16);
+  out->fuse_fc2_ln = next_dtype >= 0 && fuse_linear_ln(M, D, H, next_dtype);
+  out->fuse_ln_bwd = fuse_linear_ln_bwd(M, D, H) && fuse_linear_ln_bwd(M, D, 3 * D);
+  return 0;
+}
 
 #define BLK_TRY(call)        \
   do {                       \
@@ -151,7 +200,7 @@ extern "C" int dinox_block_backward(const dinox_block_bwd_args* a, void* stream)
     BLK_TRY(dinox_gemm(&g, stream));
   }
   BLK_TRY(weight_grad(g_op, a->act, a->dw2, a->db2, M, D, H, a->tn_ws, a->tn_ws_bytes, stream));
-  const bool fuse_ln = (a->reserved & 1) != 0;                    // dX product + LayerNorm backward in one launch (dinox_linear_ln_bwd)
+  const bool fuse_ln = a->fuse_ln_bwd != 0;                       // dX product + LayerNorm backward in one launch (dinox_linear_ln_bwd)
   if (!fuse_ln) {
     dinox_gemm_args g = gemm_args(a->dpre, a->w1_t, a->dxn2, M, D, H, DINOX_BF16);
     BLK_TRY(dinox_gemm(&g, stream));

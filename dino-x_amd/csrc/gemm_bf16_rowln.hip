@@ -380,6 +380,14 @@ extern "C" int dinox_linear_residual_ln_ok(int64_t M, int N, int K) {
           (int64_t)RL_BM * K * 2 < ((int64_t)1 << 31)) ? 1 : 0;
 }
 
+// The full-row 208 x 384 kernel with the LayerNorm epilogue (gemm_bf16_pp384.hip) for bf16 y on a chip's worth of rows.
+// DINOX_ROWLN_PP (read per call): 0 = never, 1 = every shape in its envelope (tests), unset = M >= 40000 (about a round of its 208-row
+// tiles: at bs 64, M = 25 728 = 124 tiles, the step is 0.25 ms shorter on the 128 x 384 kernel's 201 tiles).
+bool dinox::linear_residual_ln_full_row(int64_t M, int K, int y_dtype) {
+  const int mode = knob_int("DINOX_ROWLN_PP", -1);
+  return y_dtype == DINOX_BF16 && mode != 0 && gemm_bf16_nt_pp384_ln_ok(M, K) && (mode > 0 || M >= 40000);
+}
+
 extern "C" int dinox_linear_residual_ln(const void* a, const void* w, const float* bias, const float* residual, float* x_out,
                                         const float* gamma, const float* beta, float eps, void* y, int y_dtype, float* mean,
                                         float* rstd, int64_t M, int N, int K, void* stream) {
@@ -392,14 +400,8 @@ extern "C" int dinox_linear_residual_ln(const void* a, const void* w, const floa
   RowLnParams p{(const bf16_t*)a, (const bf16_t*)w, bias, residual, x_out, gamma, beta, y, mean, rstd, M, K, eps};
   const unsigned tiles = (unsigned)ceil_div(M, (int64_t)RL_BM);
   hipStream_t st = as_stream(stream);
-  {
-    // The full-row 208 x 384 kernel with the LayerNorm epilogue (gemm_bf16_pp384.hip) for bf16 y on a chip's worth of rows.
-    // DINOX_ROWLN_PP (read per call): 0 = never, 1 = every shape in its envelope (tests), unset = M >= 40000 (about a round of its 208-row
-    // tiles: at bs 64, M = 25 728 = 124 tiles, the step is 0.25 ms shorter on the 128 x 384 kernel's 201 tiles).
-    const int mode = knob_int("DINOX_ROWLN_PP", -1);
-    if (y_dtype == DINOX_BF16 && mode != 0 && gemm_bf16_nt_pp384_ln_ok(M, K) && (mode > 0 || M >= 40000))
-      return launch_gemm_bf16_nt_pp384_ln(a, w, bias, residual, x_out, gamma, beta, eps, y, mean, rstd, M, K, st);
-  }
+  if (linear_residual_ln_full_row(M, K, y_dtype))
+    return launch_gemm_bf16_nt_pp384_ln(a, w, bias, residual, x_out, gamma, beta, eps, y, mean, rstd, M, K, st);
 #define RL_LAUNCH(YDT, NS)                                                                                                        \
   do {                                                                                                                            \
     if (int rc = reserve_lds(reinterpret_cast<const void*>(gemm_bf16_rowln<YDT, NS>), rl_lds(NS), "linear_residual_ln")) return rc; \

@@ -50,6 +50,9 @@ int launch_gemm_bf16_nt_pp384_ln(const void* a, const void* w, const float* bias
 int pp384_lnbwd_tiles(int64_t M);
 int launch_gemm_bf16_nt_pp384_lnbwd(const void* a, const void* w, const float* x, const float* gamma, const float* mean, const float* rstd,
                                     float* dx, const float* dx_add, void* dx_lowp, float* ws, int64_t M, int K, hipStream_t st);
+// gemm_bf16_rowln.hip: does dinox_linear_residual_ln run this width-384 product + LayerNorm (y in y_dtype) on the full-row kernel's
+// LayerNorm epilogue instead of its own 128 x 384 kernel?  (callers: dinox_linear_residual_ln's launch choice, dinox_block_plan)
+bool linear_residual_ln_full_row(int64_t M, int K, int y_dtype);
 // gemm_bf16_tnbig.hip
 int tn_big_plan(const GemmParams& p, int& tiles_m, int& tiles_n, int& splits, int64_t& kps);
 int64_t tn_big_ws_bytes(const GemmParams& p);

@@ -20,6 +20,13 @@
 //   DINOX_PP_STAGGER        their workgroup start stagger in cycles, 0 = off (unset: by epilogue and K)      kernels.h (pp, pp128)    call
 //   DINOX_ROWLN_PP          product + LayerNorm on the full-row kernel: 0 never, 1 whole envelope            gemm_bf16_rowln.hip      call
 //                           (unset: bf16 y and M >= 40000)
+//   DINOX_ROWLN             block plan, product + LayerNorm as one launch: 0 never, 1 proj and fc2           block.hip                call
+//                           (unset: proj; fc2 where DINOX_ROWLN_PP's kernel takes it)
+//   DINOX_ROWLN_FC2         0: fc2 + LayerNorm stays two launches on the full-row kernel's shapes too (unset) block.hip                call
+//   DINOX_LNBWD_PP          block plan, dX product + LayerNorm backward as one launch: 0 never, 1 whole      block.hip                call
+//                           envelope (unset: M >= 8192)
+//   DINOX_QKV_FUSED         block plan, no-grad qkv projection + attention as one launch: 0 never, 1 every   block.hip                call
+//                           width (unset: D <= 512); attention_bf16.hip's notes name it
 //   DINOX_TN_BIG_OFF        set: dW products stay on 128 x 128 tiles (unset)                                gemm_bf16_tnbig.hip      once
 //   DINOX_TN_FORM           1 | 2 | 3 force a big-tile shape (0 = cheapest plan)                            gemm_bf16_tnbig.hip      call
 //   DINOX_TN_PP             dW K loop: 0 waves in step, 1 anti-phase 32x32x16, 2 anti-phase 16x16x32 (2)     gemm_bf16_tnbig.hip      call
@@ -29,7 +36,6 @@
 //   DINOX_ATTN_BWD_SPLIT    set: two-kernel attention backward (unset)                                      attention_bf16.hip       once
 //
 // Named in csrc/ but not read here:
-//   DINOX_QKV_FUSED         read by dinox/ops.py (which passes route to dinox_qkv_attention_fwd); attention_bf16.hip's notes name it
 //   DINOX_PLAIN_OUT_STORES  compile-time macro (common.h, store_stream): ordinary instead of non-temporal stores, alternate builds only
 #pragma once
 #include <cstdlib>

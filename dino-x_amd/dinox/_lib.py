@@ -52,7 +52,7 @@ class BlockFwdArgs(C.Structure):
 class BlockBwdArgs(C.Structure):
     """struct dinox_block_bwd_args (include/dinox.h)."""
     _fields_ = [
-        ("V", i64), ("N", i64), ("D", i32), ("H", i32), ("heads", i32), ("reserved", i32),
+        ("V", i64), ("N", i64), ("D", i32), ("H", i32), ("heads", i32), ("fuse_ln_bwd", i32),
         ("g", vp), ("g_lowp", vp), ("g_lowp_buf", vp),
         ("x0", vp), ("x1", vp), ("xn1", vp), ("xn2", vp), ("qkv", vp), ("o", vp), ("lse", vp), ("pre", vp), ("act", vp),
         ("mean1", vp), ("rstd1", vp), ("mean2", vp), ("rstd2", vp), ("n1w", vp), ("n2w", vp),
@@ -62,6 +62,11 @@ class BlockBwdArgs(C.Structure):
         ("dpre", vp), ("dxn2", vp), ("d_o", vp), ("dqkv", vp), ("dxn1", vp), ("g1", vp), ("g1_lowp", vp), ("g0_lowp", vp),
         ("attn_ws", vp), ("ln_ws", vp), ("tn_ws", vp), ("tn_ws_bytes", i64),
     ]
+
+
+class BlockPlan(C.Structure):
+    """struct dinox_block_plan_t (include/dinox.h)."""
+    _fields_ = [("qkv_fused", i32), ("fuse_proj_ln", i32), ("fuse_fc2_ln", i32), ("fuse_ln_bwd", i32)]
 
 
 # name -> (restype, argtypes); order and types mirror include/dinox.h exactly.
@@ -138,6 +143,7 @@ SIGNATURES = {
     "dinox_zero": (i32, [vp, i64, vp]),
     "dinox_gelu_fwd": (i32, [vp, vp, i64, vp]),
     "dinox_gelu_bwd": (i32, [vp, vp, vp, i64, vp]),
+    "dinox_block_plan": (i32, [i64, i64, i32, i32, i32, i32, i32, i32, C.POINTER(BlockPlan)]),
     "dinox_block_forward": (i32, [C.POINTER(BlockFwdArgs), vp]),
     "dinox_block_backward": (i32, [C.POINTER(BlockBwdArgs), vp]),
     "dinox_retrieval_ws_bytes": (i64, [i64, i64, i64]),

@@ -22,7 +22,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import BF16, EPI_ACCUM, EPI_AUXGRAD, EPI_BIAS, EPI_DGELU, EPI_GELU, EPI_RESIDUAL, F32, BlockBwdArgs, BlockFwdArgs, GemmArgs, check, lib
+from ._lib import BF16, EPI_ACCUM, EPI_AUXGRAD, EPI_BIAS, EPI_DGELU, EPI_GELU, EPI_RESIDUAL, F32, BlockBwdArgs, BlockFwdArgs, BlockPlan, GemmArgs, check, lib
 
 Tensor = torch.Tensor
 _OVERRIDE: list = []
@@ -457,23 +457,6 @@ def layernorm_fwd(x: Tensor, w: Tensor, b: Tensor, out_dtype: torch.dtype, eps: 
     return y, mean, rstd
 
 
-_ROWLN_PP = os.environ.get("DINOX_ROWLN_PP")    # "0": never the full-row kernel's LayerNorm epilogue (the library reads it per call too)
-_ROWLN = os.environ.get("DINOX_ROWLN")          # "1": every width-384 product, "0": none, unset: the short reductions (proj) only
-
-
-def rowln_ok(M: int, N: int, K: int, dt: torch.dtype, y_dtype: Optional[torch.dtype] = None) -> bool:
-    """Should this product + the LayerNorm behind it run as ONE launch (bf16 mode, N = 384)?  Measured on MI355X at the hot-path shape
-    (M = 102 912):
-      * csrc/gemm_bf16_pp384.hip's LayerNorm epilogue (bf16 y, M >= 40000 = about a round of its 208 x 384 tiles; DINOX_ROWLN_PP=0 disables):
-        proj + LN 103 us against 85 + 44 us for the two launches; fc2 + LN 206 us against 177 + 44 -> both fused;
-      * csrc/gemm_bf16_rowln.hip (128 x 384 tiles: fp32 y, small M): proj + LN 130 us against 85 + 44 -> fused for short reductions
-        (K <= 576); fc2 + LN 256 us against 177 + 44 -> not fused unless DINOX_ROWLN=1."""
-    if dt != torch.bfloat16 or _ROWLN == "0" or not lib.dinox_linear_residual_ln_ok(M, N, K):
-        return False
-    full_row = _ROWLN_PP != "0" and M >= 40000 and (y_dtype or dt) == torch.bfloat16 and K >= 128     # (the library's rule)
-    return _ROWLN == "1" or K <= 576 or (full_row and os.environ.get("DINOX_ROWLN_FC2") != "0")
-
-
 def linear_residual_ln(a: Tensor, w: Tensor, bias: Optional[Tensor], residual: Optional[Tensor], gamma: Tensor, beta: Tensor, eps: float,
                        y_dtype: torch.dtype):
     """x = residual + a W^T + bias (fp32) and y = LayerNorm(x) (y_dtype) with its row statistics, one launch.
@@ -520,17 +503,6 @@ def layernorm_bwd(dy: Tensor, x: Tensor, w: Tensor, mean: Tensor, rstd: Tensor, 
         grad_sink.ready(sb)
         return dx, None, None, lowp
     return dx, dw, db, lowp
-
-
-_LNBWD_PP = os.environ.get("DINOX_LNBWD_PP")    # "0": never fuse the dX product with the LayerNorm backward behind it; "1": wherever the kernel applies
-
-
-def linear_ln_bwd_ok(M: int, D: int, K: int, dt: torch.dtype) -> bool:
-    """Should the input-gradient product into a LayerNorm and that LayerNorm's backward run as ONE launch (csrc/gemm_bf16_pp384.hip's
-    LayerNorm-backward epilogue; bf16 mode, width 384)?  Unset: on a chip's worth of rows (M >= 8192); the results equal the two launches' to the last bit."""
-    if dt != torch.bfloat16 or _LNBWD_PP == "0" or not lib.dinox_linear_ln_bwd_ok(M, D, K):
-        return False
-    return _LNBWD_PP == "1" or M >= 8192
 
 
 def linear_ln_bwd(a: Tensor, w_t: Tensor, x: Tensor, w: Tensor, mean: Tensor, rstd: Tensor, dx: Optional[Tensor] = None,
@@ -669,18 +641,6 @@ def attention_fwd(qkv: Tensor, heads: int):
         return o32.to(qkv.dtype), lse
     check(lib.dinox_attention_fwd(_p(qkv), _p(o), _p(lse), B, N, heads, d, _code(qkv.dtype), _stream()), "dinox_attention_fwd")
     return o, lse
-
-
-# "1": no-grad blocks (teacher, encode()) run qkv projection + attention as one launch.  Off by default: measured no faster than the two
-# launches at ViT-S (219-227 us against 208-222) and slower at ViT-L (500 against 408 us); csrc/attention_bf16.hip, DESIGN.md section 4
-_QKV_FUSED = {"1": True, "0": False}.get(os.environ.get("DINOX_QKV_FUSED", ""))      # None: by width (below)
-
-
-def _qkv_fused(D: int) -> bool:
-    """No-grad blocks (the teacher of a step, encode()) run qkv projection + attention as ONE launch?  In isolation a tie at ViT-S and slower
-    at ViT-L; in the step, where the teacher's qkv tensor is 237 MB written and read back between two kernels that
-    each start cold, 0.2 ms per step faster at width 384 (35.01 -> 34.80 ms, interleaved on one box).  Unset: widths up to 512."""
-    return _QKV_FUSED if _QKV_FUSED is not None else D <= 512
 
 
 def qkv_attention_ok(B: int, N: int, heads: int, D: int, C: int) -> bool:
@@ -948,6 +908,17 @@ def weight_grad(dy: Tensor, x: Tensor, w: Tensor, bias: Optional[Tensor], want_d
     return dw.reshape(w.shape), db
 
 
+def block_plan(V: int, N: int, D: int, H: int, heads: int, dt: torch.dtype, train: bool, next_dtype: Optional[torch.dtype] = None) -> BlockPlan:
+    """Which launches of one transformer block (V views of N tokens, width D, hidden width H; compute mode dt; next_dtype = dtype of the
+    LayerNorm that follows the block, None without one) run fused: .qkv_fused, .fuse_proj_ln, .fuse_fc2_ln, .fuse_ln_bwd.  The library
+    decides (dinox_block_plan, csrc/block.hip: the measured rules and their DINOX_* switches, read at every call); both sequencers of
+    BlockFn and both of its passes act on this one answer."""
+    plan = BlockPlan()
+    check(lib.dinox_block_plan(V, N, D, H, heads, _code(dt), int(train), -1 if next_dtype is None else _code(next_dtype), C.byref(plan)),
+          "dinox_block_plan")
+    return plan
+
+
 _BLOCK_NATIVE = os.environ.get("DINOX_BLOCK_NATIVE", "1") != "0"      # "0": the block node issues its launches one by one from Python (A/B, tests)
 
 
@@ -958,7 +929,7 @@ def _block_native_ok(dt: torch.dtype, x0: Tensor, wqkv: Tensor) -> bool:
     return _BLOCK_NATIVE and dt == torch.bfloat16 and x0.is_cuda and TRACE_KERNELS is None and not dw_stream.enabled
 
 
-def _block_forward_native(ctx, x0, n1w, n1b, wqkv, bqkv, wproj, bproj, n2w, n2b, w1, b1, w2, b2, heads, eps, pre_ln, next_ln, train):
+def _block_forward_native(ctx, x0, n1w, n1b, wqkv, bqkv, wproj, bproj, n2w, n2b, w1, b1, w2, b2, heads, eps, pre_ln, next_ln, train, plan):
     """BlockFn.forward through dinox_block_forward: the same kernels in the same order, one foreign call."""
     dt = torch.bfloat16
     V, N, D = x0.shape
@@ -970,7 +941,7 @@ def _block_forward_native(ctx, x0, n1w, n1b, wqkv, bqkv, wproj, bproj, n2w, n2b,
         xn1, mean1, rstd1 = bf(V, N, D), f32(M), f32(M)
     else:
         xn1, mean1, rstd1 = pre_ln
-    if not train and _qkv_fused(D) and qkv_attention_ok(V, N, heads, D, D):      # no backward: projection + attention in one launch, no qkv tensor
+    if plan.qkv_fused:      # no backward: projection + attention in one launch, no qkv tensor
         qkv, o, lse = None, bf(V, N, D), None
     else:
         qkv, o, lse = bf(M, 3 * D), bf(V, N, D), f32(V, heads, N)
@@ -980,7 +951,7 @@ def _block_forward_native(ctx, x0, n1w, n1b, wqkv, bqkv, wproj, bproj, n2w, n2b,
     x2 = f32(V, N, D)
     nxt = None
     wops = [weight_operand(w_, dt) for w_ in (wqkv, wproj, w1, w2)]          # (held until the call is enqueued: a per-call cast would otherwise be freed)
-    a = BlockFwdArgs(V=V, N=N, D=D, H=H, heads=heads, train=int(train), fuse_proj_ln=int(rowln_ok(M, D, D, dt)), fuse_fc2_ln=0, eps=eps,
+    a = BlockFwdArgs(V=V, N=N, D=D, H=H, heads=heads, train=int(train), fuse_proj_ln=plan.fuse_proj_ln, fuse_fc2_ln=plan.fuse_fc2_ln, eps=eps,
                      x0=_p(x0), qkv=_p(qkv), o=_p(o), lse=_p(lse), x1=_p(x1), xn2=_p(xn2), mean2=_p(mean2), rstd2=_p(rstd2), act=_p(act), pre=_p(pre),
                      x2=_p(x2), n1w=_p(n1w), n1b=_p(n1b), n2w=_p(n2w), n2b=_p(n2b), wqkv=_p(wops[0]), wproj=_p(wops[1]), w1=_p(wops[2]), w2=_p(wops[3]),
                      bqkv=_p(bqkv), bproj=_p(bproj), b1=_p(b1), b2=_p(b2))
@@ -993,13 +964,12 @@ def _block_forward_native(ctx, x0, n1w, n1b, wqkv, bqkv, wproj, bproj, n2w, n2b,
         yn, mn, rn = torch.empty((V, N, D), dtype=ydt, device=dev), f32(M), f32(M)
         a.next_g, a.next_b, a.next_eps, a.next_dtype = _p(next_ln[0]), _p(next_ln[1]), next_ln[2], _code(ydt)
         a.yn, a.meann, a.rstdn = _p(yn), _p(mn), _p(rn)
-        a.fuse_fc2_ln = int(rowln_ok(M, D, H, dt, ydt))
         nxt = (yn, mn, rn)
     check(lib.dinox_block_forward(C.byref(a), _stream()), "dinox_block_forward")
     if train:
         ctx.save_for_backward(x0, x1, xn1, xn2, qkv, o, lse, pre, act, mean1, rstd1, mean2, rstd2, n1w, n2w, wqkv, wproj, w1, w2,
                               bqkv, bproj, b1, b2, n1b, n2b)
-        ctx.dt, ctx.heads, ctx.shape, ctx.native = dt, heads, (V, N, D), True
+        ctx.dt, ctx.heads, ctx.shape, ctx.native, ctx.fuse_ln_bwd = dt, heads, (V, N, D), True, plan.fuse_ln_bwd
         grad_sink.use(wqkv, bqkv, wproj, bproj, w1, b1, w2, b2, n1w, n1b, n2w, n2b)
     if next_ln is None:
         return x2
@@ -1053,8 +1023,7 @@ def _block_backward_native(ctx, g: Tensor, saved):
                    attn_ws=torch.empty(lib.dinox_attention_bwd_ws_bytes(V, N, heads), dtype=torch.uint8, device=dev),
                    ln_ws=torch.empty(lib.dinox_layernorm_bwd_ws_bytes(M, D), dtype=torch.uint8, device=dev))
     wts = [weight_operand(w_, dt, transposed=True) for w_ in (wqkv, wproj, w1, w2)]
-    fuse_ln = linear_ln_bwd_ok(M, D, H, dt) and linear_ln_bwd_ok(M, D, 3 * D, dt)      # (the same decision as the Python-sequenced backward)
-    a = BlockBwdArgs(V=V, N=N, D=D, H=H, heads=heads, reserved=int(fuse_ln), g=_p(g), g_lowp=_p(g_lp), g_lowp_buf=_p(scratch["g_lowp_buf"]),
+    a = BlockBwdArgs(V=V, N=N, D=D, H=H, heads=heads, fuse_ln_bwd=ctx.fuse_ln_bwd, g=_p(g), g_lowp=_p(g_lp), g_lowp_buf=_p(scratch["g_lowp_buf"]),
                      x0=_p(x0), x1=_p(x1), xn1=_p(xn1), xn2=_p(xn2), qkv=_p(qkv), o=_p(o), lse=_p(lse), pre=_p(pre), act=_p(act), mean1=_p(mean1),
                      rstd1=_p(rstd1), mean2=_p(mean2), rstd2=_p(rstd2), n1w=_p(n1w), n2w=_p(n2w),
                      wqkv_t=_p(wts[0]), wproj_t=_p(wts[1]), w1_t=_p(wts[2]), w2_t=_p(wts[3]),
@@ -1076,7 +1045,7 @@ _outer_grad_mode = [True]
 
 def block_fn(*args):
     """BlockFn.apply that also tells the node whether the caller runs with gradients enabled (a no-grad pass saves nothing: no GELU' side
-    tensor, and with DINOX_QKV_FUSED=1 no packed qkv tensor either)."""
+    tensor, and where block_plan says qkv_fused no packed qkv tensor either)."""
     prev = _outer_grad_mode[0]
     _outer_grad_mode[0] = torch.is_grad_enabled()
     try:
@@ -1109,19 +1078,20 @@ class BlockFn(torch.autograd.Function):
         # needs_input_grad says which inputs COULD take a gradient; under torch.no_grad() (encode(), an evaluation loop over a model whose
         # parameters still require grad) nothing will ever ask for one: block_fn() notes the caller's grad mode (inside forward it is always off)
         train = any(ctx.needs_input_grad) and _outer_grad_mode[0]
+        plan = block_plan(V, N, D, w1.shape[0], heads, dt, train, None if next_ln is None else next_ln[3] or dt)
         if _block_native_ok(dt, x0, wqkv):
-            return _block_forward_native(ctx, x0, n1w, n1b, wqkv, bqkv, wproj, bproj, n2w, n2b, w1, b1, w2, b2, heads, eps, pre_ln, next_ln, train)
+            return _block_forward_native(ctx, x0, n1w, n1b, wqkv, bqkv, wproj, bproj, n2w, n2b, w1, b1, w2, b2, heads, eps, pre_ln, next_ln, train, plan)
         ctx.native = False
         if pre_ln is None:
             xn1, mean1, rstd1 = layernorm_fwd(x0, n1w, n1b, dt, eps)
         else:
             xn1, mean1, rstd1 = pre_ln
-        if not train and dt == torch.bfloat16 and _qkv_fused(D) and qkv_attention_ok(V, N, heads, D, D):
+        if plan.qkv_fused:
             o, qkv, lse = qkv_attention(xn1.view(V, N, D), weight_operand(wqkv, dt), bqkv, heads)      # one launch, no qkv tensor
         else:
             qkv = gemm(xn1.view(M, D), weight_operand(wqkv, dt), bias=bqkv, out_dtype=dt)
             o, lse = attention_fwd(qkv.view(V, N, 3 * D), heads)
-        if rowln_ok(M, D, D, dt):
+        if plan.fuse_proj_ln:
             x1, xn2, mean2, rstd2 = linear_residual_ln(o.view(M, D), weight_operand(wproj, dt), bproj, x0.view(M, D), n2w, n2b, eps, dt)
         else:
             x1 = gemm(o.view(M, D), weight_operand(wproj, dt), bias=bproj, residual=x0.view(M, D), out_dtype=torch.float32)
@@ -1133,7 +1103,7 @@ class BlockFn(torch.autograd.Function):
             H = w1.shape[0]
             pre = torch.empty((M, H), dtype=dt, device=x0.device) if train else None
             act = gemm(xn2, weight_operand(w1, dt), bias=b1, gelu=True, aux=pre, auxgrad=True, out_dtype=dt)   # pre := gelu'(fc1 out)
-            if next_ln is not None and rowln_ok(M, D, H, dt, next_ln[3] or dt):
+            if plan.fuse_fc2_ln:
                 x2, yn, mn, rn = linear_residual_ln(act, weight_operand(w2, dt), b2, x1, next_ln[0], next_ln[1], next_ln[2], next_ln[3] or dt)
                 nxt = (yn.view(V, N, D), mn, rn)
             else:
@@ -1141,7 +1111,7 @@ class BlockFn(torch.autograd.Function):
             if train:
                 ctx.save_for_backward(x0, x1, xn1, xn2, qkv, o, lse, pre, act, mean1, rstd1, mean2, rstd2, n1w, n2w, wqkv, wproj, w1, w2,
                                       bqkv, bproj, b1, b2, n1b, n2b)
-                ctx.dt, ctx.heads, ctx.shape = dt, heads, (V, N, D)
+                ctx.dt, ctx.heads, ctx.shape, ctx.fuse_ln_bwd = dt, heads, (V, N, D), plan.fuse_ln_bwd
                 grad_sink.use(wqkv, bqkv, wproj, bproj, w1, b1, w2, b2, n1w, n1b, n2w, n2b)
         x2 = x2.view(V, N, D)
         if next_ln is None:
@@ -1177,7 +1147,7 @@ class BlockFn(torch.autograd.Function):
         dpre = gemm(g_op, b, dgelu=True, aux=pre, auxgrad=True, out_dtype=dt, **kw)
         dw2, db2 = weight_grad(g_op, act, w2, b2, b2 is not None)
         b, kw = wt(w1)
-        fuse_ln = bf and linear_ln_bwd_ok(M, D, dpre.shape[1], dt) and linear_ln_bwd_ok(M, D, 3 * D, dt)
+        fuse_ln = ctx.fuse_ln_bwd
         if not fuse_ln:
             dxn2 = gemm(dpre, b, out_dtype=dt, **kw)
         dw1, db1 = weight_grad(dpre, xn2.view(M, D), w1, b1, b1 is not None)

@@ -505,7 +505,21 @@ int dinox_gelu_bwd(const float* dy, const float* x, float* dx, int64_t n, void* 
  *           Outputs: g0 = d loss / d x0 written IN PLACE of g1 (same buffer), g0_lowp its bf16 copy.
  *           attn_ws: dinox_attention_bwd_ws_bytes; ln_ws: dinox_layernorm_bwd_ws_bytes(M, D) (used twice, in stream order);
  *           tn_ws / tn_ws_bytes: workspace of the deterministic dW products (>= the largest dinox_gemm_ws_bytes of the four).
+ * plan:     dinox_block_forward / _backward do what their flags say; WHICH launches to fuse is decided in one place, dinox_block_plan
+ *           (measured rules per shape; their A/B environment switches, read at every call, are listed in csrc/knobs.h).
+ *           Ask it once per block forward, pass fuse_proj_ln / fuse_fc2_ln on, leave qkv NULL when qkv_fused, and hand
+ *           fuse_ln_bwd to the backward of the same block.  Host logic only: no launch, nothing dereferenced but `out`.
+ *           dtype = compute mode (DINOX_F32, the parity mode, fuses nothing: an all-zero plan); train != 0 = the pass keeps tensors
+ *           for a backward; next_dtype = dtype of the LayerNorm that follows the block (next_g), or -1 when there is none.
  * ------------------------------------------------------------------------------------------ */
+typedef struct dinox_block_plan_t {
+  int32_t qkv_fused;      /* no-grad pass: qkv projection + attention as one launch (dinox_qkv_attention_fwd), no qkv tensor */
+  int32_t fuse_proj_ln;   /* proj + residual + norm2 as dinox_linear_residual_ln */
+  int32_t fuse_fc2_ln;    /* fc2 + residual + the LayerNorm that follows the block, likewise (0 when next_dtype < 0) */
+  int32_t fuse_ln_bwd;    /* both dX products into the LayerNorms as dinox_linear_ln_bwd */
+} dinox_block_plan_t;
+int dinox_block_plan(int64_t V, int64_t N, int D, int H, int heads, int dtype, int train, int next_dtype, dinox_block_plan_t* out);
+
 typedef struct dinox_block_fwd_args {
   int64_t V, N;                        /* views, tokens per view: M = V * N rows */
   int32_t D, H, heads;                 /* width, MLP hidden width, attention heads */
@@ -529,7 +543,7 @@ typedef struct dinox_block_fwd_args {
 typedef struct dinox_block_bwd_args {
   int64_t V, N;
   int32_t D, H, heads;
-  int32_t reserved;                             /* flags: bit 0 = the two dX products into the LayerNorms run dinox_linear_ln_bwd */
+  int32_t fuse_ln_bwd;                          /* != 0: the two dX products into the LayerNorms run dinox_linear_ln_bwd */
   const float* g; const void* g_lowp; void* g_lowp_buf;
   /* saved by the forward */
   const float* x0; const float* x1; const void* xn1; const void* xn2; const void* qkv; const void* o; const float* lse;

@@ -66,12 +66,12 @@ def test_gemm_args_struct_layout():
 
 
 def test_block_args_struct_layout(tmp_path):
-    """The ctypes mirrors of dinox_block_fwd_args / dinox_block_bwd_args against the C structs themselves: a small C program that
+    """The ctypes mirrors of dinox_block_fwd_args / dinox_block_bwd_args / dinox_block_plan_t against the C structs themselves: a small C program that
     includes include/dinox.h prints sizeof / offsetof, compiled with the host compiler (a mismatch would hand the kernels garbage
     pointers)."""
     import shutil
     import subprocess
-    from dinox._lib import BlockBwdArgs as B, BlockFwdArgs as F
+    from dinox._lib import BlockBwdArgs as B, BlockFwdArgs as F, BlockPlan as P
     cc = shutil.which("gcc") or shutil.which("cc")
     if cc is None:
         pytest.skip("no host C compiler")
@@ -80,12 +80,16 @@ def test_block_args_struct_layout(tmp_path):
                    "printf(\"%zu %zu %zu %zu %zu %zu\\n\", sizeof(dinox_block_fwd_args), offsetof(dinox_block_fwd_args, x0), offsetof(dinox_block_fwd_args, eps),"
                    " offsetof(dinox_block_fwd_args, next_eps), offsetof(dinox_block_fwd_args, yn), offsetof(dinox_block_fwd_args, b2));\n"
                    "printf(\"%zu %zu %zu %zu %zu\\n\", sizeof(dinox_block_bwd_args), offsetof(dinox_block_bwd_args, g), offsetof(dinox_block_bwd_args, dwqkv),"
-                   " offsetof(dinox_block_bwd_args, g0_lowp), offsetof(dinox_block_bwd_args, tn_ws_bytes));\nreturn 0;}\n")
+                   " offsetof(dinox_block_bwd_args, g0_lowp), offsetof(dinox_block_bwd_args, tn_ws_bytes));\n"
+                   "printf(\"%zu %zu %zu\\n\", sizeof(dinox_block_plan_t), offsetof(dinox_block_plan_t, fuse_ln_bwd), offsetof(dinox_block_bwd_args, fuse_ln_bwd));\n"
+                   "return 0;}\n")
     exe = tmp_path / "sz"
     subprocess.run([cc, "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
     got = subprocess.run([str(exe)], check=True, stdout=subprocess.PIPE).stdout.decode().split()
     want = [ctypes.sizeof(F), F.x0.offset, F.eps.offset, F.next_eps.offset, F.yn.offset, F.b2.offset,
-            ctypes.sizeof(B), B.g.offset, B.dwqkv.offset, B.g0_lowp.offset, B.tn_ws_bytes.offset]
+            ctypes.sizeof(B), B.g.offset, B.dwqkv.offset, B.g0_lowp.offset, B.tn_ws_bytes.offset,
+            ctypes.sizeof(P), P.fuse_ln_bwd.offset, B.fuse_ln_bwd.offset]
+    assert B.fuse_ln_bwd.offset == 28                       # where the field lay under its former name: no layout change, no new ABI version
     assert [int(v) for v in got] == want
 
 

@@ -484,6 +484,61 @@ def test_native_block_sequencing_changes_no_bit(dx, accum, ckpt):
     assert math.isfinite(a[5]["loss"]) and a[5]["grad_norm"] > 0
 
 
+def test_block_plan_steers_both_sequencers_in_one_process(dx, monkeypatch):
+    """ops.block_plan (dinox_block_plan, csrc/block.hip) is the only place that decides a block's fused launches, and it reads its switches
+    at every call: one process turns the product + LayerNorm and the dX + LayerNorm-backward fusions on, then off, and each time the
+    Python-sequenced block issues exactly those launches and ends bit-identical to dinox_block_forward / _backward -- outputs, the next
+    LayerNorm's outputs, the input gradient and all twelve parameter gradients.  One block at the smallest shape inside all three fused
+    kernels' envelopes.  (Before block_plan the Python side read these switches at import: a mid-process setenv steered only the library.)"""
+    ops, arch = dx
+    import dinox._lib as L_
+    V, N, D, H, heads = 2, 201, 384, 1536, 6
+    M = V * N
+    assert L_.lib.dinox_linear_residual_ln_ok(M, D, D) == 1 and L_.lib.dinox_linear_residual_ln_ok(M, D, H) == 1
+    assert L_.lib.dinox_linear_ln_bwd_ok(M, D, H) == 1 and L_.lib.dinox_linear_ln_bwd_ok(M, D, 3 * D) == 1
+    assert ops.qkv_attention_ok(V, N, heads, D, D)
+    torch.manual_seed(17)
+    blk, nxt = arch.TransformerBlock(D, heads).to(DEV), arch.LayerNorm(D).to(DEV)
+    with torch.no_grad():
+        for p_ in list(blk.parameters()) + list(nxt.parameters()):
+            if p_.ndim == 1:
+                p_.add_(0.05 * torch.randn_like(p_))
+    params = list(blk.parameters())
+    assert len(params) == 12 and blk.mlp.fc1.weight.shape[0] == H
+    x0 = torch.randn(V, N, D, device=DEV)
+    dy = torch.randn(V, N, D, device=DEV)
+
+    def run(native):
+        for p_ in params:
+            p_.grad = torch.zeros_like(p_)
+        x = x0.clone().requires_grad_(True)
+        monkeypatch.setattr(ops, "_BLOCK_NATIVE", native)
+        ops.grad_sink.register("test", params, None)      # every parameter gradient straight into p.grad: what dinox_block_backward needs
+        ops.TRACE_KERNELS = None if native else []
+        try:
+            with ops.compute_dtype(torch.bfloat16):
+                y, (yn, mn, rn) = blk.forward_chained(x, None, nxt)
+                assert y.grad_fn.native is native
+                y.backward(dy)
+            trace = ops.TRACE_KERNELS
+        finally:
+            ops.TRACE_KERNELS = None
+            ops.grad_sink.clear()
+        return [y.detach(), yn, mn, rn, x.grad] + [p_.grad for p_ in params], trace
+
+    for rowln, lnbwd, count in (("1", "1", 2), ("0", "0", 0)):
+        monkeypatch.setenv("DINOX_ROWLN", rowln)
+        monkeypatch.setenv("DINOX_ROWLN_PP", "1")
+        monkeypatch.setenv("DINOX_LNBWD_PP", lnbwd)
+        a, _ = run(True)
+        b, trace = run(False)
+        assert trace.count("gemm_bf16_rowln") == count and trace.count("gemm_bf16_nt_pp384(ln_bwd)") == count, trace
+        assert len(a) == len(b) == 17
+        for i, (t_a, t_b) in enumerate(zip(a, b)):
+            assert torch.equal(t_a, t_b), i
+        assert all(bool(torch.isfinite(t_a).all()) for t_a in a) and float(a[5].abs().max()) > 0
+
+
 def test_vit_plain_golden_no_registers(dx):
     ops, arch = dx
     g = load_golden("vit_plain.npz")
@@ -1807,7 +1862,7 @@ def test_no_grad_forward_with_fused_qkv_attention(dx, native, monkeypatch):
 
     def fwd(fused, grad):
         """-> (features, dinox_gemm launches with N = 3 D: the qkv products that ran as launches of their own)"""
-        monkeypatch.setattr(ops, "_QKV_FUSED", fused)
+        monkeypatch.setenv("DINOX_QKV_FUSED", "1" if fused else "0")
         t = ops.GemmTimer(every=1 << 20)
         with t, ops.compute_dtype(torch.bfloat16), (torch.enable_grad() if grad else torch.no_grad()):
             y = net(x)
