@@ -106,7 +106,11 @@ class TrainEngine:
         a hipGraph and every later step is one graph launch -- for the launch-bound small-batch regime (at bs 64 the host needs
         10-14 ms to enqueue the ~700 launches of a step that the GPU finishes in 11).  The C ABI was designed for it: no
         allocation, no synchronisation, no host-dependent scalar inside a launch (lr and the Adam bias corrections come from
-        device memory, dinox_adamw_ema_dev).  Single rank, accumulation_steps == 1, fixed batch shape."""
+        device memory, dinox_adamw_ema_dev).  Single rank, accumulation_steps == 1, fixed batch shape.
+
+        The objective is chosen here, once: ``self._objective`` runs forward, loss and backward between ``_begin`` and ``_finish``,
+        and what it lacks it declares -- ``bucketer`` None (no gradient exchange), no teacher in ``spans`` (no EMA stage), no batch
+        mean returned (no centre move)."""
         self.student, self.teacher, self.hp = student, teacher, hp
         if accumulation_steps < 1:
             raise ValueError("accumulation_steps must be >= 1")
@@ -116,49 +120,17 @@ class TrainEngine:
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
         if hp.loss_type not in ("dino", "simclr", "mae"):
             raise ValueError(f"loss_type must be 'dino', 'simclr' or 'mae', got {hp.loss_type!r}")
-        self.simclr = hp.loss_type == "simclr"
-        self.mae = hp.loss_type == "mae"
-        if self.mae:
-            self._init_mae(student, teacher, out_dim, hp, process_group, bucket_bytes, use_graph)
-            return
-        if self.simclr and self.world > 1:
-            raise ValueError("loss_type='simclr' runs on a single rank only (the negatives of a row are the rows of ONE batch; "
-                             "cross-rank negatives are not implemented)")
-        for p in teacher.parameters():
-            p.requires_grad_(False)
-        self.flat_p, self.params, self.offsets = flatten_parameters(student)
-        self.flat_t, t_params, t_off = flatten_parameters(teacher)
-        if t_off != self.offsets or self.flat_t.numel() != self.flat_p.numel():
-            raise ValueError("student and teacher must have identical parameter layouts")
-        if exchanging(process_group):                        # identical start on every rank
-            dist.broadcast(self.flat_p, src=0, group=process_group)
-            dist.broadcast(self.flat_t, src=0, group=process_group)
-        self.flat_g = torch.zeros_like(self.flat_p)
-        self.adam_m = torch.zeros_like(self.flat_p)
-        self.adam_v = torch.zeros_like(self.flat_p)
-        for p, off in zip(self.params, self.offsets):
-            p.grad = self.flat_g[off:off + p.numel()].view(p.shape)
+        if hp.loss_type == "mae":
+            self._mae_arena(student, teacher, use_graph)
+        else:
+            self._two_net_arenas(student, teacher, process_group, bucket_bytes)
         dev = self.flat_p.device
-        self.center = torch.zeros(1, out_dim, dtype=torch.float32, device=dev)
-        self.bucketer = GradBucketer(self.params, self.offsets, self.flat_g, bucket_bytes=bucket_bytes, group=process_group)
-        self.bucketer.pre_exchange = ops.dw_stream.join
-        # the teacher forward has no data dependence on the student forward: it runs on its own HIP stream so the two
-        # kernel chains fill each other's tails (every launch ends with a partial last round of workgroups)
-        self.side_stream = torch.cuda.Stream(device=dev) if dev.type == "cuda" else None
-        self.shadows = [ops.ArenaShadow(self.flat_p, self.params, self.offsets), ops.ArenaShadow(self.flat_t, t_params, t_off)]
+        self.center = torch.zeros(1, out_dim, dtype=torch.float32, device=dev)      # (mae never reads it; a checkpoint's "dino_loss" entry holds it)
         self.use_graph = bool(use_graph)
         if self.use_graph and (self.accum != 1 or exchanging(process_group)):
             raise ValueError("use_graph: single rank and accumulation_steps == 1 only")
         self._hyper_dev = torch.zeros(3, dtype=torch.float32, device=dev)
         self._hyper_host = torch.zeros(3, dtype=torch.float32).pin_memory() if dev.type == "cuda" else torch.zeros(3)
-        import zoo.arch as _arch
-        self.manual_top = all(type(m.head) is _arch.DinoHead and type(m.head[0]) is _arch.Linear and type(m.head[2]) is _arch.Linear
-                              and m.head[0].bias is not None and m.head[2].bias is not None for m in (student, teacher)) \
-            and not os.environ.get("DINOX_AUTOGRAD_TOP")
-        self._init_counters(dev)
-
-    def _init_counters(self, dev) -> None:
-        """The state every objective's step keeps, whatever its arenas look like."""
         self._graph = None
         self._static: Optional[list] = None
         self._eager_steps = 0
@@ -168,7 +140,50 @@ class TrainEngine:
         self.opt_steps = 0           # optimiser steps taken (AdamW bias correction)
         self.last = {}
 
-    def _init_mae(self, student, teacher, out_dim, hp, process_group, bucket_bytes, use_graph) -> None:
+    def _build_arena(self, module: torch.nn.Module, order=None, n_optimised: Optional[int] = None) -> None:
+        """flat_p / params / offsets of ``module`` (flatten_parameters) with gradient and Adam-moment arenas of the same layout;
+        ``p.grad`` of the first ``n_optimised`` parameters (default: all) is its slice of the gradient arena."""
+        self.flat_p, self.params, self.offsets = flatten_parameters(module, order=order)
+        self.flat_g = torch.zeros_like(self.flat_p)
+        self.adam_m = torch.zeros_like(self.flat_p)
+        self.adam_v = torch.zeros_like(self.flat_p)
+        self.sunk = self.params[:n_optimised]             # what the gradient sink knows: the rest keeps .grad = None
+        for p, off in zip(self.sunk, self.offsets):
+            p.grad = self.flat_g[off:off + p.numel()].view(p.shape)
+
+    def _two_net_arenas(self, student, teacher, process_group, bucket_bytes) -> None:
+        """dino and simclr: a student and a teacher arena of one layout, gradient buckets, the teacher's side stream."""
+        simclr = self.hp.loss_type == "simclr"
+        if simclr and self.world > 1:
+            raise ValueError("loss_type='simclr' runs on a single rank only (the negatives of a row are the rows of ONE batch; "
+                             "cross-rank negatives are not implemented)")
+        for p in teacher.parameters():
+            p.requires_grad_(False)
+        self._build_arena(student)
+        self.flat_t, t_params, t_off = flatten_parameters(teacher)
+        if t_off != self.offsets or self.flat_t.numel() != self.flat_p.numel():
+            raise ValueError("student and teacher must have identical parameter layouts")
+        if exchanging(process_group):                        # identical start on every rank
+            dist.broadcast(self.flat_p, src=0, group=process_group)
+            dist.broadcast(self.flat_t, src=0, group=process_group)
+        dev = self.flat_p.device
+        self.bucketer = GradBucketer(self.params, self.offsets, self.flat_g, bucket_bytes=bucket_bytes, group=process_group)
+        self.bucketer.pre_exchange = ops.dw_stream.join
+        # the teacher forward has no data dependence on the student forward: it runs on its own HIP stream so the two
+        # kernel chains fill each other's tails (every launch ends with a partial last round of workgroups)
+        self.side_stream = torch.cuda.Stream(device=dev) if dev.type == "cuda" else None
+        self.shadows = [ops.ArenaShadow(self.flat_p, self.params, self.offsets), ops.ArenaShadow(self.flat_t, t_params, t_off)]
+        # simclr: no teacher pointer -> the optimiser pass has no EMA stage and the teacher arena is not touched (ema = 1.0 would still
+        # rewrite every element as 1.0 * t + 0.0 * w, which turns -0.0 into +0.0 and is NaN where w is not finite)
+        self.spans = [(0, self.flat_p.numel(), None if simclr else self.flat_t)]
+        import zoo.arch as _arch
+        self.manual_top = all(type(m.head) is _arch.DinoHead and type(m.head[0]) is _arch.Linear and type(m.head[2]) is _arch.Linear
+                              and m.head[0].bias is not None and m.head[2].bias is not None for m in (student, teacher)) \
+            and not os.environ.get("DINOX_AUTOGRAD_TOP")
+        self._objective = self._simclr_objective if simclr else self._dino_objective
+        self._no_local_crops = "loss_type='simclr' takes the two global views only (no local crops)" if simclr else None
+
+    def _mae_arena(self, student, teacher, use_graph) -> None:
         """One arena [encoder, reached | decoder, reached | never reached], no teacher arena; the optimiser sees the first two parts."""
         from .mae import MaeModel
         if not isinstance(student, MaeModel):
@@ -179,7 +194,7 @@ class TrainEngine:
             raise ValueError("loss_type='mae' runs on a single rank only (data-parallel MAE is not implemented)")
         if use_graph:
             raise ValueError("loss_type='mae' does not support use_graph (the step is launched eagerly)")
-        student.mask_ratio = hp.mae_mask_ratio
+        student.mask_ratio = self.hp.mae_mask_ratio
         enc, dec = student.encoder, student.decoder
         tail_ids = {id(dec.decoder_pos_embed)}
         if getattr(enc, "num_registers", 0) > 0:
@@ -191,26 +206,18 @@ class TrainEngine:
         head = [p for p in every if id(p) in enc_ids and id(p) not in tail_ids]
         body = [p for p in every if id(p) not in enc_ids and id(p) not in tail_ids]
         tail = [p for p in every if id(p) in tail_ids]
-        self.unreached = tail
         pos_of = {id(p): i for i, p in enumerate(every)}
-        self.flat_p, self.params, self.offsets = flatten_parameters(student, order=head + body + tail)
+        self._build_arena(student, order=head + body + tail, n_optimised=len(head) + len(body))
         self.state_index = [pos_of[id(p)] for p in self.params]      # position in student.parameters(): the optimiser-state keys of a checkpoint
         ends = self.offsets + [self.flat_p.numel()]
-        self.enc_numel, self.opt_numel = ends[len(head)], ends[len(head) + len(body)]      # (multiples of 8: slices stay 16-byte aligned)
-        self.flat_t = None
-        self.flat_g = torch.zeros_like(self.flat_p)
-        self.adam_m = torch.zeros_like(self.flat_p)
-        self.adam_v = torch.zeros_like(self.flat_p)
-        n_opt = len(head) + len(body)
-        for p, off in zip(self.params[:n_opt], self.offsets[:n_opt]):      # the tail keeps .grad = None, as under the reference
-            p.grad = self.flat_g[off:off + p.numel()].view(p.shape)
-        dev = self.flat_p.device
-        self.center = torch.zeros(1, out_dim, dtype=torch.float32, device=dev)      # (the step never reads it; a checkpoint's "dino_loss" entry holds it)
-        self.side_stream = None
+        enc_end, opt_end = ends[len(head)], ends[len(head) + len(body)]      # (multiples of 8: slices stay 16-byte aligned)
+        # two optimiser passes; the logged grad-norm is the first one's, over the ENCODER's gradients, as the reference's is
+        self.spans = [(0, enc_end, None), (enc_end, opt_end, None)]
+        self.flat_t = self.bucketer = self.side_stream = None
         self.shadows = [ops.ArenaShadow(self.flat_p, self.params, self.offsets)]
-        self.use_graph = False
         self.manual_top = False
-        self._init_counters(dev)
+        self._objective = self._mae_objective
+        self._no_local_crops = "loss_type='mae' takes the global views only (no local crops)"
 
     def _mark(self, name: str) -> None:
         if self.marks is not None:
@@ -221,14 +228,24 @@ class TrainEngine:
     # -- one optimiser step ---------------------------------------------------------------------
     def step(self, batch: torch.Tensor, spacing2b: Optional[torch.Tensor] = None, local_batch: Optional[torch.Tensor] = None,
              local_spacing: Optional[torch.Tensor] = None, mask_noise: Optional[torch.Tensor] = None) -> dict:
-        """``mask_noise`` ([V, L] fp32, ``loss_type="mae"`` only): the noise whose per-sample order decides which patches are kept;
-        None draws it from torch's global device generator."""
-        if self.mae:
-            return self._step_mae(batch, local_batch, mask_noise)
-        if mask_noise is not None:
+        """batch: (2B,3,H,W) = [view1; view2] on the device; spacing2b: (2B,3) or None.
+        local_batch (L*B,3,s,s), view-major, with local_spacing (L*B,3): the multi-crop extension (not in the reference, dino only) --
+        the student also sees L smaller crops per sample, which enter the DINO term only (every (teacher view, other student
+        view) pair, averaged); Gram and KoLeo stay on the global views.
+        ``loss_type="mae"``: batch (V,3,H,W) fp32 -- every view is one sample, as in the reference (:1725); spacing is ignored there and
+        here.  ``mask_noise`` ([V, L] fp32, mae only): the noise whose per-sample order decides which patches are kept; None draws it
+        from torch's global device generator.
+        Returns device tensors {loss, dino, gram, koleo, grad_norm_sq} (plus simclr / mae with that ``loss_type``) and the python
+        float lr (no sync)."""
+        mae = self.hp.loss_type == "mae"          # (refusals come before anything is launched or counted)
+        if mask_noise is not None and not mae:
             raise ValueError("mask_noise belongs to loss_type='mae'")
+        if local_batch is not None and self._no_local_crops:
+            raise ValueError(self._no_local_crops)
+        if mae and isinstance(batch, ops.PatchOperand):
+            raise ValueError("loss_type='mae' takes the fp32 image batch (the loss reads its pixels), not a PatchOperand")
         if not self.use_graph:
-            return self._step_eager(batch, spacing2b, local_batch, local_spacing)
+            return self._step_eager(batch, spacing2b, local_batch, local_spacing, mask_noise)
         return self._step_graph([batch, spacing2b, local_batch, local_spacing])
 
     def _step_graph(self, inputs: list) -> dict:
@@ -261,17 +278,15 @@ class TrainEngine:
         self.last = dict(self._captured, lr=lr)
         return self.last
 
-    def _step_eager(self, batch: torch.Tensor, spacing2b: Optional[torch.Tensor] = None, local_batch: Optional[torch.Tensor] = None,
-                    local_spacing: Optional[torch.Tensor] = None, hyper: Optional[torch.Tensor] = None) -> dict:
-        """batch: (2B,3,H,W) = [view1; view2] on the device; spacing2b: (2B,3) or None.
-        local_batch (L*B,3,s,s), view-major, with local_spacing (L*B,3): the multi-crop extension (not in the reference) --
-        the student also sees L smaller crops per sample, which enter the DINO term only (every (teacher view, other student
-        view) pair, averaged); Gram and KoLeo stay on the global views.
-        Returns device tensors {loss, dino, gram, koleo, grad_norm_sq} (plus simclr with ``loss_type="simclr"``) and the python float
-        lr (no sync)."""
+    def _step_eager(self, batch, spacing2b=None, local_batch=None, local_spacing=None, mask_noise=None, hyper: Optional[torch.Tensor] = None) -> dict:
+        """The skeleton every objective shares.  The objective returns (its scalars by name, batch mean of the teacher output or None, the
+        batch mean's pending all-reduce or None)."""
+        lr, last = self._begin()
+        scalars, bm, bm_work = self._objective(batch, spacing2b, local_batch, local_spacing, mask_noise)
+        return self._finish(lr, last, hyper, scalars, bm, bm_work)
+
+    def _begin(self):
         hp = self.hp
-        if self.simclr and local_batch is not None:
-            raise ValueError("loss_type='simclr' takes the two global views only (no local crops)")
         lr = get_lr(self.step_count, hp.max_steps, hp.warmup_steps, hp.lr, hp.min_lr)
         # gradient accumulation with the reference's semantics (phase5_big_run.py:1769-1796): `step` counts micro-batches,
         # loss/accum is back-propagated every micro-batch, the optimiser (and EMA) run when (step+1) % accum == 0 with the LR
@@ -281,20 +296,57 @@ class TrainEngine:
         self._mark("start")
         if first:
             ops.zero_(self.flat_g)
-        self.bucketer.active = last
-        self.bucketer.arm()
+        on_ready = None
+        if self.bucketer is not None:
+            self.bucketer.active = last
+            self.bucketer.arm()
+            if self.bucketer.exchange:
+                on_ready = self.bucketer.grad_ready
         if ops.grad_sink.owner is not self:      # weight gradients accumulate straight into flat_g (ops._GradSink)
-            ops.grad_sink.register(self, self.params, self.bucketer.grad_ready if self.bucketer.exchange else None)
+            ops.grad_sink.register(self, self.sunk, on_ready)
             ops.weight_cache.shadows = self.shadows
         ops.grad_sink.uses.clear()
+        return lr, last
+
+    def _finish(self, lr, last, hyper, scalars, bm, bm_work) -> dict:
+        """Everything after the backward pass: centre EMA, gradient exchange, grad-norm + AdamW (+ teacher EMA) over ``spans``."""
+        hp = self.hp
+        ops.dw_stream.join()              # (weight-gradient products enqueued on the dW stream, when DINOX_DW_STREAM is set)
+        self._mark("bwd")
+        if bm_work is not None:
+            bm_work.wait()
+            bm.div_(self.world)           # (data parallel only)
+        if bm is not None:
+            ops.center_ema_(self.center.view(-1), bm, hp.center_momentum)
+        if self.bucketer is not None:
+            self.bucketer.finish()
+        self._mark("comm_exposed")        # what of the exchanges did not fit under backward (+ the centre EMA launch)
+        if last:
+            self.opt_steps += 1
+            norms = [ops.adamw_ema_(self.flat_p[lo:hi], self.flat_g[lo:hi], self.adam_m[lo:hi], self.adam_v[lo:hi],
+                                    None if teacher is None else teacher[lo:hi], lr=lr, weight_decay=hp.weight_decay, beta1=hp.beta1,
+                                    beta2=hp.beta2, eps=hp.adam_eps, step_t=self.opt_steps, ema=hp.ema, grad_scale=1.0 / self.world, hyper=hyper)
+                     for lo, hi, teacher in self.spans]
+            gsq = norms[0]
+            ops.weight_cache.clear()     # master weights changed under the bf16 copies
+            if self.compute_dtype == torch.bfloat16:
+                for sh in self.shadows:  # one cast launch per arena (+ one for every transposed matrix backward uses)
+                    sh.refresh()
+        else:
+            gsq = self._zero1                                # the reference logs grad-norm 0 between optimiser steps
+        self._mark("optimiser_tail")
+        self.step_count += 1
+        z = self._zero1
+        named = {k: (z if v is None else v).detach().reshape(()) for k, v in scalars.items()}
+        # (dino / gram / koleo: every objective reports them, as zeros where it has none -- callers rely on the keys)
+        self.last = {"loss": named.pop("loss"), "dino": named.pop("dino", z.reshape(())), "gram": named.pop("gram", z.reshape(())),
+                     "koleo": named.pop("koleo", z.reshape(())), "grad_norm_sq": gsq, "lr": lr, **named}
+        return self.last
+
+    # -- the objectives: forward, loss, backward -----------------------------------------------------------------------
+    def _dino_objective(self, batch, spacing2b, local_batch, local_spacing, mask_noise):
         # (the unfolded batch is shared by student and teacher WITHIN this scope, never carried across steps)
         with ops.compute_dtype(self.compute_dtype), ops.unfold_share():
-            if self.simclr:
-                s_feats = self.student.backbone(batch, spacing=spacing2b)
-                self._mark("fwd_student")
-                loss = l_simclr = self._simclr_and_backward(s_feats)
-                l_dino = l_gram = l_koleo = self._zero1.reshape(())
-                return self._step_tail(lr, last, hyper, loss, l_dino, l_gram, l_koleo, l_simclr, None, None)
             main = torch.cuda.current_stream()
             # opt-in (DINOX_SIDE_STREAM=1): +1.3 % measured, but concurrent chains blur per-kernel timings, so bench/profiles keep it off
             side = self.side_stream if os.environ.get("DINOX_SIDE_STREAM") else None
@@ -313,32 +365,13 @@ class TrainEngine:
                     t_feats = self.teacher.backbone(batch, spacing=spacing2b)
                 self._mark("fwd_teacher")
             if self.manual_top:
-                loss, l_dino, l_gram, l_koleo, bm, bm_work = self._losses_and_backward(s_feats, t_feats, batch, local_batch, local_spacing)
-            else:
-                with torch.no_grad():
-                    t_out = self.teacher.head(t_feats[:, 0])
-                loss, l_dino, l_gram, l_koleo, bm, bm_work = self._losses_and_backward_autograd(s_feats, t_feats, t_out, batch, local_batch,
-                                                                                                local_spacing)
-        return self._step_tail(lr, last, hyper, loss, l_dino, l_gram, l_koleo, self._zero1.reshape(()), bm, bm_work)
+                return self._losses_and_backward(s_feats, t_feats, local_batch, local_spacing)
+            with torch.no_grad():
+                t_out = self.teacher.head(t_feats[:, 0])
+            return self._losses_and_backward_autograd(s_feats, t_feats, t_out, batch, local_batch, local_spacing)
 
-    def _step_mae(self, batch, local_batch, mask_noise) -> dict:
-        """batch (V,3,H,W) fp32 on the device -- every view is one sample, as in the reference (:1725); spacing is ignored there and here.
-        Returns device tensors {loss, dino, gram, koleo, grad_norm_sq, mae} and the python float lr (no sync)."""
-        hp = self.hp
-        if local_batch is not None:
-            raise ValueError("loss_type='mae' takes the global views only (no local crops)")
-        if isinstance(batch, ops.PatchOperand):
-            raise ValueError("loss_type='mae' takes the fp32 image batch (the loss reads its pixels), not a PatchOperand")
-        lr = get_lr(self.step_count, hp.max_steps, hp.warmup_steps, hp.lr, hp.min_lr)
-        first = self.step_count % self.accum == 0
-        last = (self.step_count + 1) % self.accum == 0
-        self._mark("start")
-        if first:
-            ops.zero_(self.flat_g)
-        if ops.grad_sink.owner is not self:
-            ops.grad_sink.register(self, self.params[:len(self.params) - len(self.unreached)], None)
-            ops.weight_cache.shadows = self.shadows
-        ops.grad_sink.uses.clear()
+    def _mae_objective(self, batch, spacing2b, local_batch, local_spacing, mask_noise):
+        """Forward with random masking, reconstruction loss on the removed patches, backward (no unfold sharing: one net, one forward)."""
         model = self.student
         with ops.compute_dtype(self.compute_dtype):
             pred_full, ids_restore = model.forward_full(batch, mask_noise)
@@ -348,94 +381,23 @@ class TrainEngine:
                 dpred = ops.mae_loss_bwd(saved, 1.0 / self.accum)
             self._mark("loss")
             torch.autograd.backward([pred_full], [dpred])
-        ops.dw_stream.join()
-        self._mark("bwd")
-        self._mark("comm_exposed")
-        z = self._zero1.reshape(())
-        if last:
-            self.opt_steps += 1
-            kw = dict(lr=lr, weight_decay=hp.weight_decay, beta1=hp.beta1, beta2=hp.beta2, eps=hp.adam_eps, step_t=self.opt_steps, ema=hp.ema)
-            a, b = self.enc_numel, self.opt_numel
-            gsq = ops.adamw_ema_(self.flat_p[:a], self.flat_g[:a], self.adam_m[:a], self.adam_v[:a], None, **kw)      # (the logged norm)
-            ops.adamw_ema_(self.flat_p[a:b], self.flat_g[a:b], self.adam_m[a:b], self.adam_v[a:b], None, **kw)
-            ops.weight_cache.clear()
-            if self.compute_dtype == torch.bfloat16:
-                for sh in self.shadows:
-                    sh.refresh()
-        else:
-            gsq = self._zero1
-        self._mark("optimiser_tail")
-        self.step_count += 1
-        loss = loss.reshape(())
-        self.last = {"loss": loss, "dino": z, "gram": z, "koleo": z, "grad_norm_sq": gsq, "lr": lr, "mae": loss}
-        return self.last
-
-    def _step_tail(self, lr, last, hyper, loss, l_dino, l_gram, l_koleo, l_simclr, bm, bm_work) -> dict:
-        """Everything after the backward pass: centre EMA (dino), gradient exchange, grad-norm + AdamW (+ teacher EMA, dino)."""
-        hp = self.hp
-        ops.dw_stream.join()              # (weight-gradient products enqueued on the dW stream, when DINOX_DW_STREAM is set)
-        self._mark("bwd")
-        if bm_work is not None:
-            bm_work.wait()
-            bm.div_(self.world)           # (data parallel only)
-        if not self.simclr:
-            ops.center_ema_(self.center.view(-1), bm, hp.center_momentum)
-        self.bucketer.finish()
-        self._mark("comm_exposed")        # what of the exchanges did not fit under backward (+ the centre EMA launch)
-        if last:
-            self.opt_steps += 1
-            # simclr: no teacher pointer -> the pass has no EMA stage and the teacher arena is not touched (ema = 1.0 would still
-            # rewrite every element as 1.0 * t + 0.0 * w, which turns -0.0 into +0.0 and is NaN where w is not finite)
-            gsq = ops.adamw_ema_(self.flat_p, self.flat_g, self.adam_m, self.adam_v, None if self.simclr else self.flat_t, lr=lr,
-                                 weight_decay=hp.weight_decay, beta1=hp.beta1, beta2=hp.beta2, eps=hp.adam_eps,
-                                 step_t=self.opt_steps, ema=hp.ema, grad_scale=1.0 / self.world, hyper=hyper)
-            ops.weight_cache.clear()     # master weights changed under the bf16 copies
-            if self.compute_dtype == torch.bfloat16:
-                for sh in self.shadows:  # one cast launch per arena (+ one for every transposed matrix backward uses)
-                    sh.refresh()
-        else:
-            gsq = self._zero1                                # the reference logs grad-norm 0 between optimiser steps
-        self._mark("optimiser_tail")
-        self.step_count += 1
-        self.last = {"loss": loss.detach(), "dino": l_dino.detach(), "gram": l_gram.detach(), "koleo": l_koleo.detach(),
-                     "grad_norm_sq": gsq, "lr": lr}
-        if self.simclr:
-            self.last["simclr"] = l_simclr.detach()
-        return self.last
+        return {"loss": loss, "mae": loss}, None, None
 
     # -- everything above the backbones, without the framework's elementwise kernels ---------------------------------
-    def _head_forward(self, head, cls_op: torch.Tensor, train: bool):
-        """DinoHead = Linear(D,D) -> GELU -> Linear(D,out) (zoo/arch.py:252-256) on the CLS rows: two products, GELU (and GELU' for the
-        backward) in the first one's epilogue.  Returns (logits fp32, saved)."""
-        dt = self.compute_dtype
+    def _head(self, head, cls_op: torch.Tensor, train: bool):
+        """DinoHead = Linear(D,D) -> GELU -> Linear(D,out) (zoo/arch.py:252-256) on the CLS rows, by the MLP core of ops: (logits fp32, saved)."""
         l0, l2 = head[0], head[2]
-        pre0 = torch.empty((cls_op.shape[0], l0.weight.shape[0]), dtype=dt, device=cls_op.device) if train else None
-        h0 = ops.gemm(cls_op, ops.weight_operand(l0.weight, dt), bias=l0.bias, gelu=True, aux=pre0, auxgrad=True, out_dtype=dt)
-        out = ops.gemm(h0, ops.weight_operand(l2.weight, dt), bias=l2.bias, out_dtype=torch.float32)
-        if train:
-            ops.grad_sink.use(l0.weight, l0.bias, l2.weight, l2.bias)
-        return out, (cls_op, h0, pre0)
+        return ops.mlp_forward(cls_op, l0.weight, l0.bias, l2.weight, l2.bias, None, torch.float32, self.compute_dtype, train)
 
-    def _head_backward(self, head, saved, ds: torch.Tensor) -> torch.Tensor:
+    def _student_head_backward(self, saved, ds: torch.Tensor) -> torch.Tensor:
         """d logits [V,out] fp32 -> d CLS rows [V,D]; the four parameter gradients go straight into the gradient arena."""
         dt = self.compute_dtype
-        l0, l2 = head[0], head[2]
-        cls_op, h0, pre0 = saved
-        dy = ops.to_mode(ds, dt)
-        if dt == torch.float32:
-            dpre = ops.gemm(dy, l2.weight.detach(), transB=True, dgelu=True, aux=pre0, auxgrad=True, out_dtype=dt)
-        else:
-            dpre = ops.gemm(dy, ops.weight_operand(l2.weight, dt, transposed=True), dgelu=True, aux=pre0, auxgrad=True, out_dtype=dt)
-        g2 = ops.weight_grad(dy, h0, l2.weight, l2.bias, True)
-        if dt == torch.float32:
-            dcls = ops.gemm(dpre, l0.weight.detach(), transB=True, out_dtype=dt)
-        else:
-            dcls = ops.gemm(dpre, ops.weight_operand(l0.weight, dt, transposed=True), out_dtype=dt)
-        g0 = ops.weight_grad(dpre, cls_op, l0.weight, l0.bias, True)
-        assert g2 == (None, None) and g0 == (None, None), "the head's parameters must live in the engine's gradient arena"
+        l0, l2 = self.student.head[0], self.student.head[2]
+        dcls, *sunk = ops.mlp_backward(saved, ops.to_mode(ds, dt), l0.weight, l0.bias, l2.weight, l2.bias, dt, True)
+        assert sunk == [None] * 4, "the head's parameters must live in the engine's gradient arena"
         return dcls
 
-    def _losses_and_backward(self, s_feats, t_feats, batch, local_batch, local_spacing):
+    def _losses_and_backward(self, s_feats, t_feats, local_batch, local_spacing):
         """Heads, DINO CE (pre-update centre), Gram, KoLeo and the gradient of their weighted sum w.r.t. the student features, written
         out by hand -- every step is one of the library's kernels -- then ONE autograd backward from the features down.  (Through
         autograd the same thing costs a strided CLS copy + cast per head, `ds * g` / `d * g` multiplies, a zero fill + slice copy +
@@ -445,7 +407,7 @@ class TrainEngine:
         V = s_feats.shape[0]
         with torch.no_grad():
             sf = s_feats.detach()
-            t_out, _ = self._head_forward(self.teacher.head, ops.take_rows(t_feats, 0, dt), train=False)
+            t_out, _ = self._head(self.teacher.head, ops.take_rows(t_feats, 0, dt), train=False)
             if local_batch is None:
                 l_feats = None
                 cls = ops.take_rows(sf, 0, dt)
@@ -455,7 +417,7 @@ class TrainEngine:
                 lf = l_feats.detach()
                 cls = ops.take_rows(sf, 0, dt, out_rows=V + lf.shape[0])
                 ops.take_rows(lf, 0, dt, out=cls, out_row0=V)
-            s_all, saved = self._head_forward(self.student.head, cls, train=True)
+            s_all, saved = self._head(self.student.head, cls, train=True)
             if local_batch is None:
                 l_dino, ds = ops.dino_ce(s_all, t_out, self.center, hp.student_temp, hp.teacher_temp, True, grad_scale=scale)
             else:
@@ -478,7 +440,7 @@ class TrainEngine:
             if kstate is not None:
                 l_koleo, ksaved = ops.koleo_end(kstate)
                 ops.axpy_(ds[:V], ops.koleo_bwd(ksaved, hp.koleo_weight * scale), 1.0)      # (ds[:V]: the leading rows, contiguous)
-            dcls = self._head_backward(self.student.head, saved, ds)
+            dcls = self._student_head_backward(saved, ds)
             ops.put_rows_(dfeats, 0, dcls)                                                                            # row 0 (CLS)
             roots, grads = [s_feats], [dfeats]
             if l_feats is not None:
@@ -490,33 +452,35 @@ class TrainEngine:
             loss = ops.lincomb3(l_dino, l_gram, l_koleo, hp.gram_weight, hp.koleo_weight)
         self._mark("loss")
         torch.autograd.backward(roots, grads)
-        z = self._zero1
-        return loss.reshape(()), l_dino.reshape(()), (l_gram if l_gram is not None else z).reshape(()), \
-            (l_koleo if l_koleo is not None else z).reshape(()), bm, bm_work
+        return {"loss": loss, "dino": l_dino, "gram": l_gram, "koleo": l_koleo}, bm, bm_work
 
-    def _simclr_and_backward(self, s_feats) -> torch.Tensor:
-        """Student head on the CLS rows, NT-Xent on the two halves of its output (reference :1729-1737) and the backward pass.  With the
-        stock head: by hand, like _losses_and_backward -- head products, ops.ntxent_fwd / ntxent_bwd, head backward, the CLS gradient
-        into a zeroed feature gradient, ONE autograd backward from the features down.  Otherwise through the per-op autograd nodes."""
+    def _simclr_objective(self, batch, spacing2b, local_batch, local_spacing, mask_noise):
+        """Student forward, student head on the CLS rows, NT-Xent on the two halves of its output (reference :1729-1737) and the backward
+        pass.  With the stock head: by hand, like _losses_and_backward -- head products, ops.ntxent_fwd / ntxent_bwd, head backward, the
+        CLS gradient into a zeroed feature gradient, ONE autograd backward from the features down.  Otherwise through the per-op
+        autograd nodes."""
         hp, dt = self.hp, self.compute_dtype
-        if not self.manual_top:
-            s_out = self.student.head(s_feats[:, 0])
-            half = s_out.shape[0] // 2
-            loss = ops.simclr_loss(s_out[:half], s_out[half:], hp.simclr_temp)
-            self._mark("loss")
-            (loss if self.accum == 1 else loss / self.accum).backward()
-            return loss.detach()
-        with torch.no_grad():
-            sf = s_feats.detach()
-            z, saved = self._head_forward(self.student.head, ops.take_rows(sf, 0, dt), train=True)
-            loss, nsaved = ops.ntxent_fwd(z, hp.simclr_temp)
-            dcls = self._head_backward(self.student.head, saved, ops.ntxent_bwd(nsaved, 1.0 / self.accum))
-            dfeats = torch.empty_like(sf)
-            ops.zero_(dfeats)
-            ops.put_rows_(dfeats, 0, dcls)                                                                            # row 0 (CLS)
-        self._mark("loss")
-        torch.autograd.backward([s_feats], [dfeats])
-        return loss.reshape(())
+        with ops.compute_dtype(dt), ops.unfold_share():
+            s_feats = self.student.backbone(batch, spacing=spacing2b)
+            self._mark("fwd_student")
+            if not self.manual_top:
+                s_out = self.student.head(s_feats[:, 0])
+                half = s_out.shape[0] // 2
+                loss = ops.simclr_loss(s_out[:half], s_out[half:], hp.simclr_temp)
+                self._mark("loss")
+                (loss if self.accum == 1 else loss / self.accum).backward()
+            else:
+                with torch.no_grad():
+                    sf = s_feats.detach()
+                    z, saved = self._head(self.student.head, ops.take_rows(sf, 0, dt), train=True)
+                    loss, nsaved = ops.ntxent_fwd(z, hp.simclr_temp)
+                    dcls = self._student_head_backward(saved, ops.ntxent_bwd(nsaved, 1.0 / self.accum))
+                    dfeats = torch.empty_like(sf)
+                    ops.zero_(dfeats)
+                    ops.put_rows_(dfeats, 0, dcls)                                                                        # row 0 (CLS)
+                self._mark("loss")
+                torch.autograd.backward([s_feats], [dfeats])
+        return {"loss": loss, "simclr": loss}, None, None
 
     def _losses_and_backward_autograd(self, s_feats, t_feats, t_out, batch, local_batch, local_spacing):
         """The same through the per-op autograd nodes (a head whose layers were replaced, e.g. LoRA-wrapped)."""
@@ -544,17 +508,17 @@ class TrainEngine:
             l_koleo = torch.zeros((), device=batch.device)
         self._mark("loss")            # (local-crop forward, student head, DINO CE, Gram, KoLeo forward)
         (loss if self.accum == 1 else loss / self.accum).backward()
-        return loss.detach(), l_dino.detach(), l_gram.detach(), l_koleo.detach(), bm, bm_work
+        return {"loss": loss, "dino": l_dino, "gram": l_gram, "koleo": l_koleo}, bm, bm_work
 
     # -- convenience ------------------------------------------------------------------------------
     def scalars(self) -> dict:
-        """Host copies of the last step's scalars (this is the only place that synchronises).  ``loss_type="simclr"`` adds the key
-        "simclr"; a dino engine returns exactly the keys it always did, so whatever iterates over them sees no new entry."""
-        r = self.last
-        out = {"loss": float(r["loss"]), "dino": float(r["dino"]), "gram": float(r["gram"]), "koleo": float(r["koleo"]),
-               "grad_norm": float(r["grad_norm_sq"]) ** 0.5, "lr": r["lr"]}
-        if self.simclr:
-            out["simclr"] = float(r["simclr"])
-        if self.mae:
-            out["mae"] = float(r["mae"])
+        """Host copies of the last step's scalars (this is the only place that synchronises): what the objective returned (simclr adds
+        the key "simclr", mae "mae"; a dino engine returns exactly the keys it always did, so whatever iterates over them sees no new
+        entry), the grad-norm and the lr."""
+        out = {}
+        for k, v in self.last.items():
+            if k == "grad_norm_sq":
+                out["grad_norm"] = float(v) ** 0.5
+            else:
+                out[k] = v if k == "lr" else float(v)
         return out

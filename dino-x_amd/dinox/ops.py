@@ -444,6 +444,20 @@ def weight_operand(w: Tensor, dt: torch.dtype, transposed=False) -> Tensor:
     return weight_cache.get(w, transposed)
 
 
+def dx_operand(w: Tensor, dt: torch.dtype):
+    """W as the B operand of dX = dY . W  (dY [M,N], W [N,K]): returns (B, transB).  The fp32 kernels read W itself through the
+    trans flag, the bf16 kernels take the cached W^T image."""
+    if dt == torch.float32:
+        return w.detach(), True
+    return weight_operand(w, dt, transposed=True), False
+
+
+def dx_product(dy: Tensor, w: Tensor, dt: torch.dtype, **epilogue_kw) -> Tensor:
+    """dX = dY . W in compute mode dt; dgelu / aux / auxgrad / out_dtype go to gemm."""
+    b, transB = dx_operand(w, dt)
+    return gemm(dy, b, transB=transB, **epilogue_kw)
+
+
 def layernorm_fwd(x: Tensor, w: Tensor, b: Tensor, out_dtype: torch.dtype, eps: float = 1e-5):
     _need_cuda(x, w, b)
     assert x.dtype == torch.float32
@@ -1138,38 +1152,35 @@ class BlockFn(torch.autograd.Function):
             if native is not None:
                 return native
 
-        def wt(w):      # W^T operand for dX = dY . W
-            return (w.detach(), dict(transB=True)) if not bf else (weight_operand(w, dt, transposed=True), {})
-
         g_op = grad_operand(g, dt).view(M, D)
         # ---- MLP: x2 = x1 + fc2(gelu(fc1(xn2)))
-        b, kw = wt(w2)
-        dpre = gemm(g_op, b, dgelu=True, aux=pre, auxgrad=True, out_dtype=dt, **kw)
+        dpre = dx_product(g_op, w2, dt, dgelu=True, aux=pre, auxgrad=True, out_dtype=dt)
         dw2, db2 = weight_grad(g_op, act, w2, b2, b2 is not None)
-        b, kw = wt(w1)
         fuse_ln = ctx.fuse_ln_bwd
-        if not fuse_ln:
-            dxn2 = gemm(dpre, b, out_dtype=dt, **kw)
+        if fuse_ln:
+            w1t, _ = dx_operand(w1, dt)
+        else:
+            dxn2 = dx_product(dpre, w1, dt, out_dtype=dt)
         dw1, db1 = weight_grad(dpre, xn2.view(M, D), w1, b1, b1 is not None)
         if fuse_ln:     # g1 = g + LN2'(dpre W1): product and LayerNorm backward in one launch
-            g1, dn2w, dn2b, g1_lp = linear_ln_bwd(dpre, b, x1, n2w, mean2, rstd2, dx_add=g.view(M, D), want_lowp=True, b=n2b)
+            g1, dn2w, dn2b, g1_lp = linear_ln_bwd(dpre, w1t, x1, n2w, mean2, rstd2, dx_add=g.view(M, D), want_lowp=True, b=n2b)
         else:
             g1, dn2w, dn2b, g1_lp = layernorm_bwd(dxn2, x1, n2w, mean2, rstd2, dx_add=g.view(M, D), want_lowp=bf, b=n2b)   # g1 = g + LN2'(.)
         del dpre
         g1_op = g1_lp if bf else g1
         # ---- attention: x1 = x0 + proj(attn(qkv(xn1)))
-        b, kw = wt(wproj)
-        do = gemm(g1_op, b, out_dtype=dt, **kw)
+        do = dx_product(g1_op, wproj, dt, out_dtype=dt)
         dwp, dbp = weight_grad(g1_op, o.view(M, D), wproj, bproj, bproj is not None)
         dqkv = attention_bwd(do.view(V, N, D), qkv.view(V, N, 3 * D), o, lse, heads).view(M, 3 * D)
-        b, kw = wt(wqkv)
-        if not fuse_ln:
-            dxn1 = gemm(dqkv, b, out_dtype=dt, **kw)
+        if fuse_ln:
+            wqkvt, _ = dx_operand(wqkv, dt)
+        else:
+            dxn1 = dx_product(dqkv, wqkv, dt, out_dtype=dt)
         dwq, dbq = weight_grad(dqkv, xn1.view(M, D), wqkv, bqkv, bqkv is not None)
         if not bf:
             dw_stream.join()        # fp32 mode: the proj dW product reads g1 itself (bf16 mode: its own low-precision copy)
         if fuse_ln:
-            g0, dn1w, dn1b, g0_lp = linear_ln_bwd(dqkv, b, x0, n1w, mean1, rstd1, dx=g1, dx_add=g1, want_lowp=True, b=n1b)   # in place on our own g1
+            g0, dn1w, dn1b, g0_lp = linear_ln_bwd(dqkv, wqkvt, x0, n1w, mean1, rstd1, dx=g1, dx_add=g1, want_lowp=True, b=n1b)   # in place on our own g1
         else:
             g0, dn1w, dn1b, g0_lp = layernorm_bwd(dxn1, x0, n1w, mean1, rstd1, dx=g1, dx_add=g1, want_lowp=bf, b=n1b)      # in place on our own g1
         g0 = g0.view(V, N, D)
@@ -1204,12 +1215,9 @@ class LinearFn(torch.autograd.Function):
         dy2 = to_mode(dy.reshape(-1, w.shape[0]), dt)
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            if dt == torch.float32:
-                dx = gemm(dy2, w.detach(), transB=True, out_dtype=ctx.xdtype)            # dy [M,N] . W [N,K]
-            else:
-                dx = gemm(dy2, weight_operand(w, dt, transposed=True), out_dtype=ctx.xdtype if ctx.xdtype == dt else dt)
-                if dx.dtype != ctx.xdtype:
-                    dx = dx.to(ctx.xdtype)
+            dx = dx_product(dy2, w, dt, out_dtype=dt if dt == torch.bfloat16 else ctx.xdtype)       # dy [M,N] . W [N,K]
+            if dx.dtype != ctx.xdtype:
+                dx = dx.to(ctx.xdtype)
             dx = dx.reshape(ctx.xshape)
         want_db = ctx.has_bias and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1]:
@@ -1220,48 +1228,52 @@ class LinearFn(torch.autograd.Function):
         return dx, dw, db, dres, None
 
 
+def mlp_forward(x2: Tensor, w1: Tensor, b1: Optional[Tensor], w2: Tensor, b2: Optional[Tensor], residual: Optional[Tensor],
+                out_dtype: Optional[torch.dtype], dt: torch.dtype, train: bool):
+    """fc2(GELU_erf(fc1(x2))) (+ residual) on rows x2 [M,K] that are already operands of mode dt, without autograd: two products, GELU
+    (and, with ``train``, GELU' for the backward as a side tensor) in the first one's epilogue.  Returns (y [M,N], saved for mlp_backward)."""
+    M = x2.shape[0]
+    pre = torch.empty((M, w1.shape[0]), dtype=dt, device=x2.device) if train else None
+    act = gemm(x2, weight_operand(w1, dt), bias=b1, gelu=True, aux=pre, auxgrad=True, out_dtype=dt)
+    odt = torch.float32 if residual is not None else (out_dtype or dt)
+    y = gemm(act, weight_operand(w2, dt), bias=b2, residual=None if residual is None else _c(residual).reshape(M, w2.shape[0]),
+             out_dtype=odt)
+    if train:
+        grad_sink.use(w1, b1, w2, b2)
+    return y, (x2, pre, act)
+
+
+def mlp_backward(saved, dy2: Tensor, w1: Tensor, b1: Optional[Tensor], w2: Tensor, b2: Optional[Tensor], dt: torch.dtype, want_dx: bool):
+    """dy2 [M,N] (mode dt) -> (dx [M,K] in dt or None, dw1, db1, dw2, db2); a parameter gradient that went straight into the
+    gradient arena comes back as None (weight_grad)."""
+    x2, pre, act = saved
+    dpre = dx_product(dy2, w2, dt, dgelu=True, aux=pre, auxgrad=True, out_dtype=dt)
+    dw2, db2 = weight_grad(dy2, act, w2, b2, b2 is not None)
+    dx = dx_product(dpre, w1, dt, out_dtype=dt) if want_dx else None
+    dw1, db1 = weight_grad(dpre, x2, w1, b1, b1 is not None)
+    return dx, dw1, db1, dw2, db2
+
+
 class MlpFn(torch.autograd.Function):
-    """fc2(GELU_erf(fc1(x))) (+ residual) with GELU / GELU' fused into the GEMM epilogues
-    (reference zoo/arch.py:71-76; also the DINO head, zoo/arch.py:252-256)."""
+    """mlp_forward / mlp_backward as an autograd node (reference zoo/arch.py:71-76; also the DINO head, zoo/arch.py:252-256)."""
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, residual, out_dtype):
         _need_cuda(x, w1, w2)
         dt = current_dtype()
         xm = to_mode(x, dt)
-        x2 = xm.reshape(-1, xm.shape[-1])
-        M, H = x2.shape[0], w1.shape[0]
-        pre = torch.empty((M, H), dtype=dt, device=x.device) if any(ctx.needs_input_grad[:5]) else None
-        act = gemm(x2, weight_operand(w1, dt), bias=b1, gelu=True, aux=pre, auxgrad=True, out_dtype=dt)
-        odt = torch.float32 if residual is not None else (out_dtype or dt)
-        y = gemm(act, weight_operand(w2, dt), bias=b2, residual=None if residual is None else _c(residual).reshape(M, w2.shape[0]),
-                 out_dtype=odt)
-        ctx.save_for_backward(x2, w1, w2, pre, act, b1, b2)
-        if pre is not None:
-            grad_sink.use(w1, b1, w2, b2)
+        y, saved = mlp_forward(xm.reshape(-1, xm.shape[-1]), w1, b1, w2, b2, residual, out_dtype, dt, any(ctx.needs_input_grad[:5]))
+        ctx.save_for_backward(*saved, w1, b1, w2, b2)
         ctx.dt, ctx.has_res, ctx.xshape, ctx.xdtype = dt, residual is not None, x.shape, x.dtype
         return y.reshape(*x.shape[:-1], w2.shape[0])
 
     @staticmethod
     def backward(ctx, dy):
-        x2, w1, w2, pre, act, b1, b2 = ctx.saved_tensors
-        dt = ctx.dt
-        dy2 = to_mode(dy.reshape(-1, w2.shape[0]), dt)
-        if dt == torch.float32:
-            dpre = gemm(dy2, w2.detach(), transB=True, dgelu=True, aux=pre, auxgrad=True, out_dtype=dt)
-        else:
-            dpre = gemm(dy2, weight_operand(w2, dt, transposed=True), dgelu=True, aux=pre, auxgrad=True, out_dtype=dt)
-        dw2, db2 = weight_grad(dy2, act, w2, b2, b2 is not None)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            if dt == torch.float32:
-                dx = gemm(dpre, w1.detach(), transB=True, out_dtype=dt)
-            else:
-                dx = gemm(dpre, weight_operand(w1, dt, transposed=True), out_dtype=dt)
-            if dx.dtype != ctx.xdtype:
-                dx = dx.to(ctx.xdtype)
-            dx = dx.reshape(ctx.xshape)
-        dw1, db1 = weight_grad(dpre, x2, w1, b1, b1 is not None)
+        x2, pre, act, w1, b1, w2, b2 = ctx.saved_tensors
+        dx, dw1, db1, dw2, db2 = mlp_backward((x2, pre, act), to_mode(dy.reshape(-1, w2.shape[0]), ctx.dt), w1, b1, w2, b2, ctx.dt,
+                                              ctx.needs_input_grad[0])
+        if dx is not None:
+            dx = (dx if dx.dtype == ctx.xdtype else dx.to(ctx.xdtype)).reshape(ctx.xshape)
         return dx, dw1, db1, dw2, db2, (dy if ctx.has_res else None), None
 
 

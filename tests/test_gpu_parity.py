@@ -586,10 +586,16 @@ def test_adamw_ema_vs_np(dx):
     assert float(ops.sumsq(G)) == pytest.approx(float((g_ * g_).sum()), rel=1e-5)
 
 
-def test_three_training_steps_golden(dx):
-    """The engine's step() against 3 consecutive steps of the reference loop (fp32 parity mode)."""
+@pytest.mark.parametrize("top", ["manual", "autograd"])
+def test_three_training_steps_golden(dx, monkeypatch, top):
+    """The engine's step() against 3 consecutive steps of the reference loop (fp32 parity mode), with everything above the backbones
+    written out by hand (the default) and through the per-op autograd nodes (DINOX_AUTOGRAD_TOP=1, read when the engine is built)."""
     ops, arch = dx
     from dinox.engine import StepHyperParams, TrainEngine
+    if top == "autograd":
+        monkeypatch.setenv("DINOX_AUTOGRAD_TOP", "1")
+    else:
+        monkeypatch.delenv("DINOX_AUTOGRAD_TOP", raising=False)
     g = load_golden("step_tiny.npz")
     cfg, out_dim = _cfg(g["cfg"])
     lr, min_lr, warm, max_steps, wd, ema, ts, tt, cm, gw = [float(v) for v in g["hp"]]
@@ -598,6 +604,7 @@ def test_three_training_steps_golden(dx):
     student = _load(arch.DinoStudentTeacher(arch.PatchViT(**cfg), out_dim), sub(g, "init"))
     teacher = _load(arch.DinoStudentTeacher(arch.PatchViT(**cfg), out_dim), sub(g, "init"))
     eng = TrainEngine(student, teacher, out_dim, hp)
+    assert eng.manual_top == (top == "manual")
     for step in range(3):
         eng.step(t(g[f"batch{step}"]).to(DEV), t(g[f"spacing{step}"]).to(DEV))
         r = eng.scalars()
@@ -900,6 +907,88 @@ def test_grad_sink_accumulates_in_place(dx, mode):
     got, events = run(True)
     assert sorted(events) == [0, 0, 1, 1, 2, 2, 3, 3]                    # every parameter announced once per backward
     assert rel_l2(got, ref) < (1e-6 if mode == "fp32" else 1e-5)
+
+
+@pytest.mark.parametrize("sink", [False, True], ids=["returned", "arena"])
+@pytest.mark.parametrize("residual", [False, True], ids=["plain", "residual"])
+@pytest.mark.parametrize("mode", ["fp32", "bf16"])
+def test_mlp_node_equals_core(dx, mode, residual, sink):
+    """ops.MlpFn through autograd and ops.mlp_forward / mlp_backward called directly (as the engine calls them for the heads) are the
+    same launches on the same operands: y, dx and the four parameter gradients bit-equal, whether the gradients are returned or
+    accumulated into a registered arena.  34 rows, widths 64 -> 128 -> 40: the ragged row count and the non-power-of-two output width
+    are the smallest shapes that reach the edge tiles of the products."""
+    ops, _ = dx
+    from dinox.engine import flatten_parameters
+    dt = torch.float32 if mode == "fp32" else torch.bfloat16
+    torch.manual_seed(7)
+    mlp = torch.nn.ModuleList([torch.nn.Linear(64, 128), torch.nn.Linear(128, 40)]).to(DEV)
+    flat, params, offs = flatten_parameters(mlp)
+    w1, b1, w2, b2 = params
+    x, dy = torch.randn(34, 64, device=DEV), torch.randn(34, 40, device=DEV)
+    res = torch.randn(34, 40, device=DEV) if residual else None
+
+    def run(core):
+        g = torch.zeros_like(flat)
+        for p, o in zip(params, offs):
+            p.grad = g[o:o + p.numel()].view(p.shape) if sink else None
+        events = []
+        if sink:
+            ops.grad_sink.register("test", params, events.append)
+        else:
+            ops.grad_sink.clear()
+        try:
+            with ops.compute_dtype(dt):
+                if core:
+                    with torch.no_grad():
+                        y, saved = ops.mlp_forward(ops.to_mode(x, dt), w1, b1, w2, b2, res, None, dt, True)
+                        dx_, *grads = ops.mlp_backward(saved, ops.to_mode(dy.to(y.dtype), dt), w1, b1, w2, b2, dt, True)
+                        dx_ = dx_.to(x.dtype)                     # (the node's cast back to the dtype of its input)
+                else:
+                    xr = x.clone().requires_grad_(True)
+                    y = ops.MlpFn.apply(xr, w1, b1, w2, b2, res, None)
+                    y.backward(dy.to(y.dtype))
+                    dx_, grads = xr.grad, [None] * 4 if sink else [p.grad for p in params]
+        finally:
+            ops.grad_sink.clear()
+        if sink:
+            assert grads == [None] * 4                            # everything went into the arena
+            grads = [g[o:o + p.numel()].view(p.shape).clone() for p, o in zip(params, offs)]
+        for p in params:
+            p.grad = None
+        return [y.detach(), dx_] + list(grads), events
+
+    node, node_events = run(False)
+    core, core_events = run(True)
+    assert node[0].dtype == (torch.float32 if residual else dt) and node[1].dtype == torch.float32
+    for name, a, b in zip(("y", "dx", "dW1", "db1", "dW2", "db2"), node, core):
+        assert a.shape == b.shape and a.dtype == b.dtype and torch.equal(a, b), name
+        assert bool(torch.isfinite(a).all()) and float(a.abs().max()) > 0.0, name
+    assert node_events == core_events and len(core_events) == (4 if sink else 0)
+
+
+@pytest.mark.parametrize("mode", ["fp32", "bf16"])
+def test_dx_product_equals_the_spelled_out_products(dx, mode):
+    """ops.dx_product (dX = dY . W) against the two gemm calls it replaces -- W itself with transB in fp32, the cached W^T image in
+    bf16 -- on the two products of an MLP backward (34 rows, 40 -> 128 with the GELU' epilogue, 128 -> 64 plain): bit-equal."""
+    ops, _ = dx
+    dt = torch.float32 if mode == "fp32" else torch.bfloat16
+    torch.manual_seed(8)
+    w2, w1 = torch.randn(40, 128, device=DEV, requires_grad=True), torch.randn(128, 64, device=DEV, requires_grad=True)
+    dy, dpre = torch.randn(34, 40, device=DEV).to(dt), torch.randn(34, 128, device=DEV).to(dt)
+    gprime = torch.rand(34, 128, device=DEV).to(dt)
+    with torch.no_grad():
+        got = [ops.dx_product(dy, w2, dt, dgelu=True, aux=gprime, auxgrad=True, out_dtype=dt), ops.dx_product(dpre, w1, dt, out_dtype=dt)]
+        if mode == "fp32":
+            want = [ops.gemm(dy, w2.detach(), transB=True, dgelu=True, aux=gprime, auxgrad=True, out_dtype=dt),
+                    ops.gemm(dpre, w1.detach(), transB=True, out_dtype=dt)]
+        else:
+            want = [ops.gemm(dy, ops.weight_operand(w2, dt, transposed=True), dgelu=True, aux=gprime, auxgrad=True, out_dtype=dt),
+                    ops.gemm(dpre, ops.weight_operand(w1, dt, transposed=True), out_dtype=dt)]
+        b, transB = ops.dx_operand(w1, dt)
+    assert transB == (mode == "fp32") and tuple(b.shape) == ((128, 64) if transB else (64, 128)) and b.dtype == dt
+    for a, w, shape in zip(got, want, ((34, 128), (34, 64))):
+        assert tuple(a.shape) == shape and a.dtype == dt and torch.equal(a, w)
+        assert bool(torch.isfinite(a).all()) and float(a.float().abs().max()) > 0.0
 
 
 @pytest.mark.parametrize("tag", ["small", "mm"])

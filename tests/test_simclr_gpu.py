@@ -137,12 +137,19 @@ def _batch(g, step):
     return t(g[f"batch{step}"]).float().to(DEV), t(g[f"spacing{step}"]).to(DEV)
 
 
-def test_engine_three_steps_match_the_reference(dx):
+@pytest.mark.parametrize("top", ["manual", "autograd"])
+def test_engine_three_steps_match_the_reference(dx, monkeypatch, top):
     """fp32 mode against three steps of the reference loop with loss_type="simclr": scalars per step, every gradient of step 0, the
-    weights after step 3 -- and the teacher and the centre exactly as initialised."""
+    weights after step 3 -- and the teacher and the centre exactly as initialised.  Both tops: the head and the loss written out by hand
+    (the default) and through the per-op autograd nodes (DINOX_AUTOGRAD_TOP=1, read when the engine is built)."""
     _, arch = dx
+    if top == "autograd":
+        monkeypatch.setenv("DINOX_AUTOGRAD_TOP", "1")
+    else:
+        monkeypatch.delenv("DINOX_AUTOGRAD_TOP", raising=False)
     g = load_golden("simclr_step_tiny.npz")
     eng, student, teacher, init = _tiny_engine(arch, g)
+    assert eng.manual_top == (top == "manual")
     names = [str(n) for n in g["param_order"]]
     for step in range(3):
         eng.step(*_batch(g, step))
@@ -283,34 +290,46 @@ def test_graph_replay_equals_eager_bitwise(dx):
 
 def test_dino_step_keeps_its_phases_and_simclr_drops_the_teacher(dx, monkeypatch):
     """What can be observed of the launch sequence from the host: a dino step still passes its seven phase marks in order and moves the
-    teacher and the centre; a simclr step on the same model has no teacher phase and launches fewer products."""
+    teacher and the centre; a simclr step on the same model has no teacher phase and launches fewer products; a mae step (a tiny
+    encoder under a tiny decoder, no teacher at all) passes the same six marks as simclr and leaves the centre alone."""
     ops, arch = dx
     from dinox.engine import StepHyperParams, TrainEngine
+    from dinox.mae import MaeModel
     monkeypatch.delenv("DINOX_SIDE_STREAM", raising=False)     # (a CLI run earlier in the process sets it: the forked teacher chain has no marks)
     g = load_golden("simclr_step_tiny.npz")
     cfg, out_dim = _cfg(g["cfg"])
     init = {k: v.float() for k, v in sub(g, "init").items()}
     seen = {}
-    for loss_type in ("dino", "simclr"):
-        s_ = arch.DinoStudentTeacher(arch.PatchViT(**cfg), out_dim)
-        t_ = arch.DinoStudentTeacher(arch.PatchViT(**cfg), out_dim)
-        s_.load_state_dict(init)
-        t_.load_state_dict(init)
-        eng = TrainEngine(s_.to(DEV), t_.to(DEV), out_dim, StepHyperParams(lr=1e-3, warmup_steps=2, max_steps=10, ema=0.9, loss_type=loss_type))
-        t0 = eng.flat_t.clone()
+    for loss_type in ("dino", "simclr", "mae"):
+        if loss_type == "mae":                                 # (the shapes of tests/golden/mae_step_tiny.npz)
+            torch.manual_seed(4)
+            s_ = MaeModel(arch.PatchViT(img_size=32, patch=8, dim=32, depth=2, heads=2, num_registers=2, scale_aware=True), decoder_dim=32,
+                          decoder_depth=2, decoder_heads=4).to(DEV)
+            t_, inputs = None, (torch.randn(6, 3, 32, 32, device=DEV), None)
+        else:
+            s_ = arch.DinoStudentTeacher(arch.PatchViT(**cfg), out_dim)
+            t_ = arch.DinoStudentTeacher(arch.PatchViT(**cfg), out_dim)
+            s_.load_state_dict(init)
+            t_.load_state_dict(init)
+            s_, t_, inputs = s_.to(DEV), t_.to(DEV), _batch(g, 0)
+        eng = TrainEngine(s_, t_, out_dim, StepHyperParams(lr=1e-3, warmup_steps=2, max_steps=10, ema=0.9, loss_type=loss_type))
+        t0 = None if eng.flat_t is None else eng.flat_t.clone()
         eng.marks, ops.TRACE_KERNELS = [], []
         try:
-            eng.step(*_batch(g, 0))
+            eng.step(*inputs)
         finally:
             products, ops.TRACE_KERNELS = ops.TRACE_KERNELS, None
-        seen[loss_type] = ([n for n, _ in eng.marks], len(products), not torch.equal(eng.flat_t, t0), bool((eng.center != 0).any()),
-                           set(eng.scalars()))
+        seen[loss_type] = ([n for n, _ in eng.marks], len(products), t0 is not None and not torch.equal(eng.flat_t, t0),
+                           bool((eng.center != 0).any()), set(eng.scalars()))
     assert seen["dino"][0] == ["start", "fwd_student", "fwd_teacher", "loss", "bwd", "comm_exposed", "optimiser_tail"]
     assert seen["dino"][2] and seen["dino"][3]
     assert seen["simclr"][0] == ["start", "fwd_student", "loss", "bwd", "comm_exposed", "optimiser_tail"]
     assert not seen["simclr"][2] and not seen["simclr"][3] and seen["simclr"][1] < seen["dino"][1]
-    # a dino engine reports exactly the scalars it always did (callers iterate over them); simclr adds its own
+    assert seen["mae"][0] == ["start", "fwd_student", "loss", "bwd", "comm_exposed", "optimiser_tail"]
+    assert not seen["mae"][2] and not seen["mae"][3]
+    # a dino engine reports exactly the scalars it always did (callers iterate over them); simclr and mae add their own
     assert seen["dino"][4] == {"loss", "dino", "gram", "koleo", "grad_norm", "lr"} and seen["simclr"][4] == seen["dino"][4] | {"simclr"}
+    assert seen["mae"][4] == seen["dino"][4] | {"mae"}
 
 
 # ------------------------------------------------------------------------------------------ CLI end to end
