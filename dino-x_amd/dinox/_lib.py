@@ -101,6 +101,10 @@ SIGNATURES = {
     "dinox_dino_ce_multi": (i32, [vp, vp, vp, f32, f32, f32, vp, vp, vp, i32, i32, i32, i32, vp]),
     "dinox_colmean": (i32, [vp, vp, i32, i32, vp]),
     "dinox_center_ema": (i32, [vp, vp, f32, i32, vp]),
+    "dinox_sk_ws_floats": (i64, [i32, i32]),
+    "dinox_sk_col_lse": (i32, [vp, vp, f32, f32, vp, vp, i32, i32, vp]),
+    "dinox_sk_row_lse": (i32, [vp, vp, f32, f32, vp, i32, i32, vp]),
+    "dinox_sk_center": (i32, [vp, f32, i32, vp, vp, i32, i32, vp]),
     "dinox_gram_normalize": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "dinox_sqsum": (i32, [vp, i64, f32, vp, vp, vp]),
     "dinox_gram_normalize_bwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),

@@ -68,6 +68,8 @@ class StepHyperParams:
     loss_type: str = "dino"          # "dino" | "simclr" (SimCLRLoss on the student head output, reference :1728-1737) | "mae"
     simclr_temp: float = 0.1         # the reference hard-codes SimCLRLoss(temperature=0.1)
     mae_mask_ratio: float = 0.75     # the reference hard-codes MaeModel(mask_ratio=0.75); the engine sets it on the model it is given
+    centering: str = "ema"           # "ema" (the reference's centre) | "sinkhorn" (DINOv2/v3 Sinkhorn-Knopp targets; extension, dino only)
+    sk_iters: int = 3                # Sinkhorn-Knopp iterations (DINOv2: 3)
 
 
 def flatten_parameters(module: torch.nn.Module, align: int = 8, order: Optional[List[torch.nn.Parameter]] = None
@@ -120,6 +122,12 @@ class TrainEngine:
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
         if hp.loss_type not in ("dino", "simclr", "mae"):
             raise ValueError(f"loss_type must be 'dino', 'simclr' or 'mae', got {hp.loss_type!r}")
+        if hp.centering not in ("ema", "sinkhorn"):
+            raise ValueError(f"centering must be 'ema' or 'sinkhorn', got {hp.centering!r}")
+        if hp.sk_iters < 1:
+            raise ValueError(f"sk_iters must be >= 1, got {hp.sk_iters}")
+        if hp.centering == "sinkhorn" and hp.loss_type != "dino":
+            raise ValueError(f"centering='sinkhorn' shapes the teacher targets of loss_type='dino'; loss_type={hp.loss_type!r} has none")
         if hp.loss_type == "mae":
             self._mae_arena(student, teacher, use_graph)
         else:
@@ -383,6 +391,14 @@ class TrainEngine:
             torch.autograd.backward([pred_full], [dpred])
         return {"loss": loss, "mae": loss}, None, None
 
+    def _target_center(self, t_out: torch.Tensor) -> torch.Tensor:
+        """The centre the cross-entropy subtracts from the teacher logits.  "ema": the running centre, as in the reference.  "sinkhorn":
+        the vector c of THIS batch's teacher rows for which softmax((t - c) / teacher_temp) are the Sinkhorn-Knopp targets (ops.sk_center;
+        all global views in one problem, over the global batch under data parallelism).  The EMA centre is maintained either way."""
+        if self.hp.centering == "sinkhorn":
+            return ops.sk_center(t_out, self.hp.teacher_temp, self.hp.sk_iters, group=self.group)
+        return self.center
+
     # -- everything above the backbones, without the framework's elementwise kernels ---------------------------------
     def _head(self, head, cls_op: torch.Tensor, train: bool):
         """DinoHead = Linear(D,D) -> GELU -> Linear(D,out) (zoo/arch.py:252-256) on the CLS rows, by the MLP core of ops: (logits fp32, saved)."""
@@ -418,10 +434,11 @@ class TrainEngine:
                 cls = ops.take_rows(sf, 0, dt, out_rows=V + lf.shape[0])
                 ops.take_rows(lf, 0, dt, out=cls, out_row0=V)
             s_all, saved = self._head(self.student.head, cls, train=True)
+            center = self._target_center(t_out)
             if local_batch is None:
-                l_dino, ds = ops.dino_ce(s_all, t_out, self.center, hp.student_temp, hp.teacher_temp, True, grad_scale=scale)
+                l_dino, ds = ops.dino_ce(s_all, t_out, center, hp.student_temp, hp.teacher_temp, True, grad_scale=scale)
             else:
-                l_dino, ds = ops.dino_ce_multi(s_all, t_out, self.center, hp.student_temp, hp.teacher_temp, 2, grad_scale=scale)
+                l_dino, ds = ops.dino_ce_multi(s_all, t_out, center, hp.student_temp, hp.teacher_temp, 2, grad_scale=scale)
             # centre EMA after the loss used the old centre; batch mean is global under DP (the centre itself moves after backward,
             # so the exchange runs under the backward pass)
             bm = ops.colmean(t_out)
@@ -485,14 +502,16 @@ class TrainEngine:
     def _losses_and_backward_autograd(self, s_feats, t_feats, t_out, batch, local_batch, local_spacing):
         """The same through the per-op autograd nodes (a head whose layers were replaced, e.g. LoRA-wrapped)."""
         hp = self.hp
+        with torch.no_grad():
+            center = self._target_center(t_out)
         if local_batch is None:
             s_out = self.student.head(s_feats[:, 0])
-            l_dino = ops.DinoCEFn.apply(s_out, t_out, self.center, hp.student_temp, hp.teacher_temp)
+            l_dino = ops.DinoCEFn.apply(s_out, t_out, center, hp.student_temp, hp.teacher_temp)
         else:
             l_feats = self.student.backbone(local_batch, spacing=local_spacing)
             s_all = self.student.head(torch.cat([s_feats[:, 0], l_feats[:, 0]], 0))       # one head product for all views
             s_out = s_all[:s_feats.shape[0]]
-            l_dino = ops.DinoCEMultiFn.apply(s_all, t_out, self.center, hp.student_temp, hp.teacher_temp, 2)
+            l_dino = ops.DinoCEMultiFn.apply(s_all, t_out, center, hp.student_temp, hp.teacher_temp, 2)
         bm = ops.colmean(t_out)
         bm_work = dist.all_reduce(bm, op=dist.ReduceOp.SUM, group=self.group, async_op=True) if exchanging(self.group) else None
         if hp.gram_weight != 0.0:

@@ -1788,6 +1788,68 @@ def center_ema_(center: Tensor, batch_mean: Tensor, momentum: float) -> None:
     check(lib.dinox_center_ema(_p(center), _p(batch_mean), momentum, center.numel(), _stream()), "dinox_center_ema")
 
 
+def _sk_operand(t: Tensor) -> Tensor:
+    _need_cuda(t)
+    t = _c(t.float())
+    assert t.dim() == 2, tuple(t.shape)
+    return t
+
+
+def _sk_ws(R: int, K: int, device) -> Tensor:
+    return torch.empty(max(1, lib.dinox_sk_ws_floats(R, K)), dtype=torch.float32, device=device)
+
+
+def sk_col_lse(t: Tensor, a: Optional[Tensor] = None, inv_temp: float = 1.0, out_scale: float = 1.0) -> Tensor:
+    """out[k] = out_scale * log sum_i exp(t[i,k] * inv_temp + a[i])  (t [R,K] fp32; a [R] or None = zeros): the column pass of
+    Sinkhorn-Knopp in the log domain (include/dinox.h)."""
+    t = _sk_operand(t)
+    R, K = t.shape
+    if a is not None:
+        assert a.dtype == torch.float32 and a.is_contiguous() and a.numel() == R, (tuple(a.shape), R)
+    out = torch.empty(K, dtype=torch.float32, device=t.device)
+    check(lib.dinox_sk_col_lse(_p(t), _p(a), inv_temp, out_scale, _p(out), _p(_sk_ws(R, K, t.device)), R, K, _stream()), "dinox_sk_col_lse")
+    return out
+
+
+def sk_row_lse(t: Tensor, b: Optional[Tensor] = None, inv_temp: float = 1.0, out_scale: float = 1.0) -> Tensor:
+    """out[i] = out_scale * log sum_k exp(t[i,k] * inv_temp + b[k])  (b [K] or None = zeros): the row pass."""
+    t = _sk_operand(t)
+    R, K = t.shape
+    if b is not None:
+        assert b.dtype == torch.float32 and b.is_contiguous() and b.numel() == K, (tuple(b.shape), K)
+    out = torch.empty(R, dtype=torch.float32, device=t.device)
+    check(lib.dinox_sk_row_lse(_p(t), _p(b), inv_temp, out_scale, _p(out), R, K, _stream()), "dinox_sk_row_lse")
+    return out
+
+
+def sk_center(t: Tensor, teacher_temp: float, n_iters: int = 3, group=None) -> Tensor:
+    """The centre c [K] of the teacher logits t [R,K] for which softmax((t - c) / teacher_temp), row by row, are the Sinkhorn-Knopp
+    targets of DINOv2/v3 after ``n_iters`` iterations -- what dino_ce / dino_ce_multi take in place of the EMA centre.
+
+    Without an exchanging ``group``: one call of dinox_sk_center (2 n_iters - 1 passes over t).  With one, Sinkhorn-Knopp runs over the
+    GLOBAL batch, as in DINOv2: every column pass is the local sk_col_lse, an all-gather of its K results into [world][K] and
+    sk_col_lse on that matrix; the row passes are local.  n_iters all-gathers of K floats, no framework kernel."""
+    import torch.distributed as dist
+    from .dp import exchanging
+    t = _sk_operand(t)
+    R, K = t.shape
+    if n_iters < 1:
+        raise ValueError(f"sk_center: n_iters must be >= 1, got {n_iters}")
+    if not exchanging(group):
+        out = torch.empty(K, dtype=torch.float32, device=t.device)
+        check(lib.dinox_sk_center(_p(t), teacher_temp, n_iters, _p(out), _p(_sk_ws(R, K, t.device)), R, K, _stream()), "dinox_sk_center")
+        return out
+    world = dist.get_world_size(group)
+    inv = C.c_float(1.0 / C.c_float(teacher_temp).value).value     # 1.0f / tau, as the library forms it (a double quotient rounds to the same float)
+    gathered = torch.empty((world, K), dtype=torch.float32, device=t.device)
+    a = None
+    for n in range(1, n_iters + 1):
+        dist.all_gather_into_tensor(gathered, sk_col_lse(t, a, inv), group=group)
+        if n == n_iters:
+            return sk_col_lse(gathered, None, 1.0, teacher_temp)                   # c = -tau b = tau lse
+        a = sk_row_lse(t, sk_col_lse(gathered, None, 1.0, -1.0), inv, -1.0)
+
+
 def gram_loss_fwd(sf: Tensor, tf: Tensor, dt: torch.dtype):
     """Returns (loss[1], saved) with saved = (diff [V,T,T] fp32, shat, snorm) for backward."""
     _need_cuda(sf, tf)

@@ -531,7 +531,7 @@ def save_checkpoint(path: Path, step: int, student: nn.Module, teacher: nn.Modul
         "scaler": None,                                   # bf16 needs no GradScaler (reference: None unless fp16)
         "dino_loss": {"center": eng.center.detach().cpu().clone()},
         "rng": _get_rng_state(),
-        "config": asdict(config),
+        "config": config_dict(config, getattr(eng, "hp", None)),
     }
     torch.save(payload, path)
 
@@ -673,13 +673,29 @@ def build_mae_parser() -> argparse.ArgumentParser:
     return ap
 
 
+def build_centering_parser() -> argparse.ArgumentParser:
+    """The options of the teacher centring, a parser of their own like the MAE options (``build_parser()`` stays the reference's flag
+    surface plus the general extensions)."""
+    ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    ap.add_argument("--centering", choices=["ema", "sinkhorn"], default="ema",
+                    help="Teacher centring of the DINO term (the reference has the EMA centre only): sinkhorn = the DINOv2/v3 "
+                         "Sinkhorn-Knopp targets, computed from each batch's teacher logits (over the global batch under data parallelism); "
+                         "the EMA centre keeps being maintained and checkpointed, so a run resumes with either setting")
+    ap.add_argument("--sk-iters", type=int, default=3, metavar="N", help="Sinkhorn-Knopp iterations with --centering sinkhorn (default: 3)")
+    return ap
+
+
 def parse_cli(argv=None) -> argparse.Namespace:
-    """The MAE options (build_mae_parser) first, everything else through build_parser; one namespace."""
+    """The MAE options (build_mae_parser) and the centring options (build_centering_parser) first, everything else through build_parser;
+    one namespace."""
     mae, rest = build_mae_parser().parse_known_args(argv)
+    cen, rest = build_centering_parser().parse_known_args(rest)
     ap = build_parser()
-    ap.epilog = "MAE objective: " + " ".join(build_mae_parser().format_help().split()[1:])
+    ap.epilog = ("MAE objective: " + " ".join(build_mae_parser().format_help().split()[1:])
+                 + "  Teacher centring: " + " ".join(build_centering_parser().format_help().split()[1:]))
     args = ap.parse_args(rest)
     args.mae_decoder, args.mae_mask_ratio = mae.mae_decoder, mae.mae_mask_ratio
+    args.centering, args.sk_iters = cen.centering, cen.sk_iters
     return args
 
 
@@ -722,6 +738,7 @@ def check_loss_type(args, world: int = 1) -> None:
             raise SystemExit("--loss-type mae draws batches keyed on the step (bit-identical --resume): drop --diverse-batches")
         if world > 1:
             raise SystemExit(f"--loss-type mae runs on one GPU only (got {world} ranks): data-parallel MAE is not implemented")
+    check_centering(args)
     if args.loss_type == "simclr" and args.local_crops:
         raise SystemExit("--loss-type simclr takes the two global views only: drop --local-crops (multi-crop is a DINO-term extension)")
     if args.loss_type == "simclr" and world > 1:
@@ -729,7 +746,45 @@ def check_loss_type(args, world: int = 1) -> None:
                          "cross-rank negatives are not implemented")
 
 
+def check_centering(args) -> None:
+    """``--centering sinkhorn`` shapes the teacher targets of the DINO term: the other objectives have none."""
+    if getattr(args, "centering", "ema") != "sinkhorn":
+        return
+    if args.loss_type != "dino":
+        raise SystemExit(f"--centering sinkhorn belongs to --loss-type dino (--loss-type {args.loss_type} has no teacher targets to centre): "
+                         "drop it or train with --loss-type dino")
+    if args.sk_iters < 1:
+        raise SystemExit(f"--sk-iters must be >= 1, got {args.sk_iters}")
+
+
+def config_dict(config: TrainingConfig, centring=None) -> dict:
+    """What config.json and a checkpoint's "config" entry hold: the dataclass, plus ``centering`` and ``sk_iters`` of ``centring`` (the
+    parsed arguments or the engine's StepHyperParams) whenever either differs from its default -- a default run writes the bytes it
+    always wrote, and TrainingConfig keeps the reference's fields."""
+    d = asdict(config)
+    mode, iters = getattr(centring, "centering", "ema"), getattr(centring, "sk_iters", 3)
+    if (mode, iters) != ("ema", 3):
+        d.update(centering=mode, sk_iters=iters)
+    return d
+
+
 def main(argv=None) -> None:
+    """Run the script; what it switches on process-wide for its own step (the weight-gradient stream of dinox.ops, DINOX_SIDE_STREAM) is
+    joined and put back when it returns, so a caller that goes on using the package in this process finds it as it left it."""
+    dw_was, side_was = ops.dw_stream.enabled, os.environ.get("DINOX_SIDE_STREAM")
+    try:
+        _main(argv)
+    finally:
+        if torch.cuda.is_available():
+            ops.dw_stream.join()
+        ops.dw_stream.enabled = dw_was
+        if side_was is None:
+            os.environ.pop("DINOX_SIDE_STREAM", None)
+        else:
+            os.environ["DINOX_SIDE_STREAM"] = side_was
+
+
+def _main(argv=None) -> None:
     args = parse_cli(argv)
     check_loss_type(args)
     if args.amp and args.amp_dtype != "bfloat16":
@@ -772,6 +827,8 @@ def main(argv=None) -> None:
         monitor_every=args.monitor_every, train_seed=args.train_seed, sdp_backend=args.sdp_backend, amp_dtype=args.amp_dtype,
         index_csv=str(args.index_csv), split_manifest=str(args.split_manifest) if args.split_manifest else None,
         git_commit=git_commit, data_manifest_hash=data_hash)
+    if args.centering == "sinkhorn":
+        say(f"centering=sinkhorn sk_iters={args.sk_iters}")
     say(f"effective_batch_size={cfg.effective_batch_size * world} (batch={args.batch_size} × accum={args.accumulation_steps} × ranks={world})")
     _seed_all(args.train_seed)
     local = local % torch.cuda.device_count()          # (rehearsals may put several gloo ranks on one GPU)
@@ -800,7 +857,7 @@ def main(argv=None) -> None:
         run_dir = args.run_dir / rid
     if main_rank:
         run_dir.mkdir(parents=True, exist_ok=True)
-        (run_dir / "config.json").write_text(json.dumps(asdict(cfg), indent=2) + "\n")
+        (run_dir / "config.json").write_text(json.dumps(config_dict(cfg, args), indent=2) + "\n")
     say(f"run_dir={run_dir}")
 
     # ---- data
@@ -902,7 +959,8 @@ def main(argv=None) -> None:
     hp = StepHyperParams(lr=args.lr, min_lr=args.min_lr, warmup_steps=args.warmup_steps, max_steps=args.max_steps,
                          weight_decay=args.weight_decay, ema=args.ema, teacher_temp=args.teacher_temp, student_temp=args.student_temp,
                          center_momentum=args.center_momentum, gram_weight=args.gram_weight,
-                         koleo_weight=args.koleo_weight, loss_type=args.loss_type, mae_mask_ratio=args.mae_mask_ratio)
+                         koleo_weight=args.koleo_weight, loss_type=args.loss_type, mae_mask_ratio=args.mae_mask_ratio,
+                         centering=args.centering, sk_iters=args.sk_iters)
     if args.hip_graph and (world > 1 or args.accumulation_steps != 1 or args.local_crops):
         raise SystemExit("--hip-graph: single GPU, --accumulation-steps 1 and no --local-crops (the captured step has one fixed batch layout)")
     if device.type == "cuda" and not args.hip_graph and args.streams != "off":

@@ -263,6 +263,29 @@ int dinox_colmean(const float* t, float* out, int rows, int K, void* stream);
 int dinox_center_ema(float* center, const float* batch_mean, float momentum, int K, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Sinkhorn-Knopp teacher centring (DINOv2/v3; an extension, the reference keeps the EMA centre only) -- csrc/sinkhorn.hip.
+ * t: [R][K] fp32 teacher logits, row-major; z[i][k] = t[i][k] / tau.  The published loop (exp(z)^T normalised by its sum, then n_iters
+ * times: over prototypes, over samples) ends on rows  Q[i][:] = softmax_k((t[i][k] - c[k]) / tau)  with  c = -tau b_n,
+ *     a_0 = 0,   b_n[k] = -log sum_i exp(z[i][k] + a_{n-1}[i]),   a_n[i] = -log sum_k exp(z[i][k] + b_n[k]),
+ * which is the form dinox_dino_ce / dinox_dino_ce_multi take their targets in: c goes where the EMA centre goes.
+ *   sk_col_lse: out[k] = out_scale * log sum_i exp(t[i][k] * inv_temp + a[i])   (a NULL: zeros);  ws: 2 * ceil(R/32) * K floats
+ *               (dinox_sk_ws_floats(R, K) covers it), per-chunk (max, sum) partials that a second launch meets in chunk order.
+ *   sk_row_lse: out[i] = out_scale * log sum_k exp(t[i][k] * inv_temp + b[k])   (b NULL: zeros).
+ *   sk_center:  the 2 n_iters - 1 passes of one rank, center_out[k] = c[k];  ws: dinox_sk_ws_floats(R, K) floats
+ *               (= 2 * ceil(R/32) * K + K + R).
+ * out_scale = -1 turns a pass into the next pass's a / b; under data parallelism a column pass over the global batch is sk_col_lse on
+ * the local rows, an all-gather of the K results into [world][K], and sk_col_lse on that matrix (inv_temp 1, a NULL).
+ * fp32, max-shifted (no exp of an unshifted logit), fixed reduction order, no atomics: a pure function of the inputs; finite inputs
+ * give finite outputs.  float4 loads when K % 4 == 0 and t (and ws, b) are 16-byte aligned, scalar kernels otherwise.  R < 1, K < 1,
+ * n_iters < 1, teacher_temp <= 0, a null pointer, or R > 65535 * 32 in a column pass return DINOX_EINVAL before any launch.
+ * ------------------------------------------------------------------------------------------ */
+int64_t dinox_sk_ws_floats(int R, int K);
+int dinox_sk_col_lse(const float* t, const float* a, float inv_temp, float out_scale, float* out, float* ws, int R, int K,
+                     void* stream);
+int dinox_sk_row_lse(const float* t, const float* b, float inv_temp, float out_scale, float* out, int R, int K, void* stream);
+int dinox_sk_center(const float* t, float teacher_temp, int n_iters, float* center_out, float* ws, int R, int K, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Gram anchoring -- replaces compute_gram_matrix / compute_gram_anchoring_loss
  * (scripts/phase5_big_run.py:723-739): tokens 1..N-1 (registers included), F.normalize eps 1e-12,
  * G = Xh Xh^T, mse_loss mean.  The Gram products themselves go through dinox_gemm (batched);
