@@ -44,7 +44,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp(GemmParams p, int tile
   const int grp = wv >> 2, wc = wv & 3;
   const int nk = (int)(p.K / PP_BK);
 
-  const int w = (int)blockIdx.x;
   int u_first, u_step, my, my_max;
   pp_my_tiles(order, units, u_first, u_step, my, my_max);
   if (my <= 0) return;                                         // (workgroup-uniform)
@@ -74,23 +73,13 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp(GemmParams p, int tile
   // Tile bookkeeping is kept out of the K loop (a division and 64-bit address arithmetic in one L slot held all eight waves at the next
   // barrier for ~950 cycles per tile): the scalars of the tile the stream enters NEXT are computed inside an epilogue (`nx_*`), and the
   // per-lane offsets are recomputed at a crossing only when an edge tile is involved.
-  struct TileAt { const char* a; const char* b; int mlast, nlast; };
-  auto tile_at = [&](int t) {
-    const int u = u_first + t * u_step, tm = u / tiles_n, tn = u - tm * tiles_n;
-    const int64_t m0 = (int64_t)tm * PP_BM, n0 = (int64_t)tn * PP_BN;
-    TileAt r;
-    r.a = (const char*)((const bf16_t*)p.A + m0 * p.lda);
-    r.b = (const char*)((const bf16_t*)p.B + n0 * p.ldb);
-    r.mlast = (int)(p.M - m0 < PP_BM ? p.M - m0 : PP_BM) - 1;
-    r.nlast = (int)(p.N - n0 < PP_BN ? p.N - n0 : PP_BN) - 1;
-    return r;
-  };
+  auto tile_at = [&](int t) { return pp_tile_at<PP_BM, PP_BN>(p, u_first + t * u_step, tiles_n); };
   const char* ia = nullptr;                                    // uniform: A + (tile row origin) * lda + k offset, bytes
   const char* ib = nullptr;
   unsigned oa[2], ob[2], oc[2], od[2];
   bool cur_full = false;
   int iu = 0, ik = 0;                                          // tile (index into this workgroup's list) and K-tile of the next request
-  auto enter_tile = [&](const TileAt& ta) {
+  auto enter_tile = [&](const PpTileAt& ta) {
     ia = ta.a;
     ib = ta.b;
     const bool full = ta.mlast == PP_BM - 1 && ta.nlast == PP_BN - 1;
@@ -108,7 +97,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp(GemmParams p, int tile
     }
     cur_full = full;
   };
-  TileAt nx = tile_at(my > 1 ? 1 : 0);
+  PpTileAt nx = tile_at(my > 1 ? 1 : 0);
   auto issue = [&](const char* base, const unsigned (&off)[2], const unsigned (&dst)[2], int buf) {
     char* l = smem + buf * PP_KT_BYTES;
 #pragma unroll
@@ -161,43 +150,14 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp(GemmParams p, int tile
       acc[(MH) * 4 + i][(NH) * 2 + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j][ks], af[i][ks], acc[(MH) * 4 + i][(NH) * 2 + j], 0, 0, 0); \
     __builtin_amdgcn_s_setprio(0);                                                                                        \
   }
-  // slot boundary: my LDS reads have returned (they are the next M slot's operands, and the buffer may be refilled behind the barrier)
-#define PP_SYNC                                                                                                           \
-  {                                                                                                                       \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                                    \
-    __builtin_amdgcn_s_barrier();                                                                                         \
-    __builtin_amdgcn_sched_barrier(0);                                                                                    \
-  }
-  // Counted waits.  gfx950 retires loads, LDS-DMA and stores of a wave in ONE issue-ordered counter, so "piece X has landed" is
-  // vmcnt(number of operations issued after X), and that number includes the output stores of the previous tile's epilogue whenever X
-  // was requested before them.  `sq` says how many stores that epilogue certainly issued (a full tile: 16 or 32; an edge tile or the
-  // first tile: 0 -- a LOWER bound is always safe, it only waits for more than necessary).
-#define PP_VMCNT(BASE)                                                                                                    \
-  {                                                                                                                       \
-    if (sq == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(BASE) : "memory");                                              \
-    else if (sq == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((BASE) + 16) : "memory");                                  \
-    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"((BASE) + 32) : "memory");                                               \
-  }
 
   char* const stage = smem + PP_STAGE0 + wv * 4096;
   const bool two_out = ACT == PP_GELU && p.aux != nullptr;
   // stores one full tile's epilogue issues per wave: 16 row passes x (1 | 2 sixteen-byte stores per output) x outputs; capped at 32
   const int sq_full = (OUT_DT == DINOX_BF16 && !two_out) ? 1 : 2;
-  // diagnostic cycle stamps (tools/pp_stamps.py hands a buffer over in p.ws, which NT products never use otherwise):
-  // waves 0 and 4 of every workgroup write s_memtime at the marked points, 256 slots per wave
-  long long* const dbg = (p.ws && (wv & 3) == 0) ? (long long*)p.ws + ((int64_t)w * 2 + grp) * 256 : nullptr;
-  int dbgi = 0;
-#define PP_STAMP if (dbg && dbgi < 256 && lane == 0) dbg[dbgi] = (long long)__builtin_amdgcn_s_memtime(); ++dbgi;
+  PP_STAMPS(stamps, p, wv, grp)                                 // diagnostic cycle stamps at the marked points
 
-  // ---- de-phasing.  Every workgroup has the same work per tile, so without it all 256 run in lockstep: every CU is in its K loop (no
-  // stores at all) or in its epilogue (stores only) at the same time, and the output stream meets HBM in bursts of twice its bandwidth
-  // (measured: the plain bf16 epilogue took 5.4k cycles, GELU + side tensor 28k, against ~2k / ~12k of instructions).  Workgroups that own
-  // one tile less than the busiest ones have a whole tile period to spare: they start late by a pseudo-random share of `stagger` cycles.
-  if (stagger > 0 && (my < my_max || (order & 512))) {          // (order bit 9: diagnostic -- every workgroup starts late)
-    const unsigned h = ((unsigned)w * 2654435761u) >> 16;      // 16 bits
-    const int naps = (int)(((int64_t)stagger * h) >> 26);       // stagger * h / 65536 cycles, in naps of 1024
-    for (int i = 0; i < naps; ++i) __builtin_amdgcn_s_sleep(16);
-  }
+  pp_start_late(stagger, order, my, my_max);                    // de-phasing
 
   // ---- prologue: K-tiles 0 and 1 of the first tile; the first one is retired before anybody reads
   enter_tile(tile_at(0));
@@ -208,9 +168,9 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp(GemmParams p, int tile
   __builtin_amdgcn_sched_barrier(0);
 
   int g = 0;                                                    // K-tiles done (over all tiles): buffer = g & 1
-  int sq = 0;                                                   // stores of the previous epilogue standing in the counter: 0 / 16 / 32
+  int sq = 0;                                                   // stores of the previous epilogue standing in the counter, in sixteens: 0 / 1 / 2
   for (int t = 0; t < my; ++t) {
-    PP_STAMP
+    PP_STAMP(stamps, lane)
     if (grp == 1) {                                             // the second row group runs one barrier interval behind the first
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
@@ -220,50 +180,50 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp(GemmParams p, int tile
       // K-tile g + 1 is requested in this K-tile's L slots -- except in the first K-tile of a tile: that request went out ahead of
       // the previous epilogue's stores (or in the prologue)
       const bool req = kt > 0 && g + 1 < total, last = kt + 1 == nk;
-      PP_STAMP
+      PP_STAMP(stamps, lane)
       // L0: piece c of this K-tile must have landed
       read_a(buf, 0);
       read_b(buf, 0);
       if (req) issue(ia, oa, dst_a, nbuf);
-      if (kt == 0) PP_VMCNT(10)                                 // younger: d, the whole next K-tile, the stores
+      if (kt == 0) PP_WAIT_BEHIND_STORES(10, 16, sq)            // younger: d, the whole next K-tile, the stores
       else if (!req) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      else if (kt == 1) PP_VMCNT(4)                             // younger: d, the stores, a of the next
+      else if (kt == 1) PP_WAIT_BEHIND_STORES(4, 16, sq)        // younger: d, the stores, a of the next
       else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      PP_SYNC
+      pp_sync();
       PP_MMA(0, 0)
-      PP_SYNC
+      pp_sync();
       // L1: piece d
       read_b(buf, 1);
       if (req) issue(ib, ob, dst_b, nbuf);
-      if (kt == 0) PP_VMCNT(8)
+      if (kt == 0) PP_WAIT_BEHIND_STORES(8, 16, sq)
       else if (!req) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      else if (kt == 1) PP_VMCNT(4)
+      else if (kt == 1) PP_WAIT_BEHIND_STORES(4, 16, sq)
       else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      PP_SYNC
+      pp_sync();
       PP_MMA(0, 1)
-      PP_SYNC
+      pp_sync();
       // L2
       read_a(buf, 1);
       if (req) issue(ib, oc, dst_c, nbuf);
-      PP_SYNC
+      pp_sync();
       PP_MMA(1, 1)
-      PP_SYNC
+      pp_sync();
       // L3: pieces a, b of the next K-tile
       read_b(buf, 0);
       if (req) {
         issue(ia, od, dst_d, nbuf);
         advance();
       }
-      if (kt == 0) PP_VMCNT(4)                                  // younger: c, d of the next K-tile and the stores
+      if (kt == 0) PP_WAIT_BEHIND_STORES(4, 16, sq)             // younger: c, d of the next K-tile and the stores
       else if (!req) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");     // (kt == 1: the stores are older than a, b -- they are waited for here)
-      PP_SYNC
+      pp_sync();
       PP_MMA(1, 0)
-      if (!(last && grp == 1)) PP_SYNC
+      if (!(last && grp == 1)) pp_sync();
     }
 
     // ---- epilogue of tile t
-    PP_STAMP
+    PP_STAMP(stamps, lane)
     {
       const int u = u_first + t * u_step, tm = u / tiles_n, tn = u - tm * tiles_n;
       const int64_t m0t = (int64_t)tm * PP_BM, n0t = (int64_t)tn * PP_BN, mw = m0t + grp * 128, nw = n0t + wc * 64;     // this wave's block
@@ -273,15 +233,12 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp(GemmParams p, int tile
         // count the stores instead of standing behind them (the buffer of this tile's last K-tile is free: every wave is past its reads).
         if (t + 2 < my) nx = tile_at(t + 2);                    // (the stream may cross into it below when nk == 2)
         if (g + 1 < total) issue_ktile((g + 1) & 1);
-        PP_STAMP
+        PP_STAMP(stamps, lane)
       });
     }
-    PP_STAMP
+    PP_STAMP(stamps, lane)
   }
-#undef PP_STAMP
 #undef PP_MMA
-#undef PP_SYNC
-#undef PP_VMCNT
 }
 
 // Shapes and epilogues this kernel takes (the caller has checked in_dtype == bf16, transA == transB == 0).
@@ -292,15 +249,9 @@ int launch_gemm_bf16_nt_pp(const GemmParams& p, hipStream_t st) {
   // epilogue is long (GELU' product 184 -> 172 us, fc2 180 -> 176), costs where it is short (qkv 104 vs 112 us): off for plain / bias
   const bool heavy = (p.epilogue & (DINOX_EPI_GELU | DINOX_EPI_DGELU | DINOX_EPI_RESIDUAL)) != 0;
   const int stagger = heavy ? (int)(p.K / PP_BK) * 2600 + ((p.epilogue & (DINOX_EPI_GELU | DINOX_EPI_DGELU)) ? 12000 : 4000) : 0;
-  PersistPlan pl;
-  if (!persist_plan(p, PP_BM, PP_BN, stagger, pl)) return DINOX_EUNSUPPORTED;
-  const int rc = with_epilogue_case(p, [&](auto out, auto act, auto res) {
-    auto kern = gemm_bf16_nt_pp<decltype(out)::value, decltype(act)::value, decltype(res)::value>;
-    if (int rc = reserve_lds(reinterpret_cast<const void*>(kern), PP_LDS, "gemm_bf16_nt_pp")) return rc;
-    hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(512), PP_LDS, st, p, pl.tiles_n, pl.units, pl.order, pl.stagger);
-    return 0;
+  return pp_launch_persistent<PP_BM, PP_BN, PP_LDS>(p, stagger, "gemm_bf16_nt_pp", st, [](auto out, auto act, auto res) {
+    return gemm_bf16_nt_pp<decltype(out)::value, decltype(act)::value, decltype(res)::value>;
   });
-  return rc ? rc : check_launch("gemm_bf16_nt_pp");
 }
 
 }  // namespace dinox

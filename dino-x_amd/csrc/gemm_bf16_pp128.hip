@@ -37,7 +37,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp128(GemmParams p, int t
   const int grp = wv >> 2, wm = wv >> 1, wn = wv & 1;          // row block wm (64 rows), column block wn (64 columns)
   const int nk = (int)(p.K / PQ_BK);
 
-  const int w = (int)blockIdx.x;
   int u_first, u_step, my, my_max;
   pp_my_tiles(order, units, u_first, u_step, my, my_max);
   if (my <= 0) return;                                         // (workgroup-uniform)
@@ -63,23 +62,13 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp128(GemmParams p, int t
     dst_b[q] = (unsigned)(PQ_A_BYTES + i0 * 128);
   }
   const unsigned src_chunk = (unsigned)((((lane & 7) ^ (lane >> 3)) & 7) << 4);
-  struct TileAt { const char* a; const char* b; int mlast, nlast; };
-  auto tile_at = [&](int t) {
-    const int u = u_first + t * u_step, tm = u / tiles_n, tn = u - tm * tiles_n;
-    const int64_t m0 = (int64_t)tm * PQ_BM, n0 = (int64_t)tn * PQ_BN;
-    TileAt r;
-    r.a = (const char*)((const bf16_t*)p.A + m0 * p.lda);
-    r.b = (const char*)((const bf16_t*)p.B + n0 * p.ldb);
-    r.mlast = (int)(p.M - m0 < PQ_BM ? p.M - m0 : PQ_BM) - 1;
-    r.nlast = (int)(p.N - n0 < PQ_BN ? p.N - n0 : PQ_BN) - 1;
-    return r;
-  };
+  auto tile_at = [&](int t) { return pp_tile_at<PQ_BM, PQ_BN>(p, u_first + t * u_step, tiles_n); };
   const char* ia = nullptr;
   const char* ib = nullptr;
   unsigned oa[2], ob[2], od[2];
   bool cur_full = false;
   int iu = 0, ik = 0;
-  auto enter_tile = [&](const TileAt& ta) {
+  auto enter_tile = [&](const PpTileAt& ta) {
     ia = ta.a;
     ib = ta.b;
     const bool full = ta.mlast == PQ_BM - 1 && ta.nlast == PQ_BN - 1;
@@ -96,7 +85,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp128(GemmParams p, int t
     }
     cur_full = full;
   };
-  TileAt nx = tile_at(my > 1 ? 1 : 0);
+  PpTileAt nx = tile_at(my > 1 ? 1 : 0);
   auto advance = [&]() {
     ia += PQ_BK * 2;
     ib += PQ_BK * 2;
@@ -134,33 +123,13 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp128(GemmParams p, int t
     __builtin_amdgcn_s_setprio(0);                                                                                        \
     __builtin_amdgcn_sched_barrier(0);                                                                                    \
   }
-#define PQ_SYNC                                                                                                           \
-  {                                                                                                                       \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                                    \
-    __builtin_amdgcn_s_barrier();                                                                                         \
-    __builtin_amdgcn_sched_barrier(0);                                                                                    \
-  }
   // "K-tile g + 1 has landed" = vmcnt(operations issued after it): the five requests of K-tile g + 2 issued so far (the sixth follows in
-  // the M slot behind the wait) and, for the first K-tile after an epilogue, that epilogue's stores (sq = 0 / 8 / 16 of them for certain:
-  // a LOWER bound is always safe).
-#define PQ_VMCNT(BASE)                                                                                                    \
-  {                                                                                                                       \
-    if (sq == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(BASE) : "memory");                                              \
-    else if (sq == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((BASE) + 8) : "memory");                                   \
-    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"((BASE) + 16) : "memory");                                               \
-  }
+  // the M slot behind the wait) and, for the first K-tile after an epilogue, that epilogue's stores (sq = 0 / 1 / 2 eights of them for certain).
   const bool two_out = ACT == PP_GELU && p.aux != nullptr;
   const int sq_full = (OUT_DT == DINOX_BF16 && !two_out) ? 1 : 2;     // 8 row passes x (1 | 2) sixteen-byte stores x outputs, capped at 16
-  long long* const dbg = (p.ws && (wv & 3) == 0) ? (long long*)p.ws + ((int64_t)w * 2 + grp) * 256 : nullptr;
-  int dbgi = 0;
-#define PQ_STAMP if (dbg && dbgi < 256 && lane == 0) dbg[dbgi] = (long long)__builtin_amdgcn_s_memtime(); ++dbgi;
+  PP_STAMPS(stamps, p, wv, grp)                                 // diagnostic cycle stamps at the marked points
 
-  // de-phasing of the workgroups that own one tile less than the busiest ones (see gemm_bf16_pp.hip)
-  if (stagger > 0 && (my < my_max || (order & 512))) {
-    const unsigned h = ((unsigned)w * 2654435761u) >> 16;
-    const int naps = (int)(((int64_t)stagger * h) >> 26);
-    for (int i = 0; i < naps; ++i) __builtin_amdgcn_s_sleep(16);
-  }
+  pp_start_late(stagger, order, my, my_max);                    // de-phasing of the workgroups that own one tile less than the busiest ones
 
   // ---- prologue: K-tiles 0 and 1; the first one is retired before anybody reads
   enter_tile(tile_at(0));
@@ -181,7 +150,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp128(GemmParams p, int t
   int g = 0, buf = 0;                                           // K-tiles done (over all tiles); ring slot of K-tile g
   int sq = 0;
   for (int t = 0; t < my; ++t) {
-    PQ_STAMP
+    PP_STAMP(stamps, lane)
     if (grp == 1) {                                             // the second row group runs one barrier interval behind the first
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
@@ -190,17 +159,17 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp128(GemmParams p, int t
       const char* const cur = smem + buf * PQ_KT_BYTES;
       const int rbuf = buf == 0 ? 2 : buf - 1;                  // ring slot of K-tile g + 2 (= of K-tile g - 1: every wave is past its reads)
       const bool req = g + 2 < total, last = kt + 1 == nk;
-      PQ_STAMP
+      PP_STAMP(stamps, lane)
       // L0
       read_ab(cur, 0);
       if (req) {
         dma(ia, oa[0], dst_a[0], rbuf);
         dma(ia, oa[1], dst_a[1], rbuf);
       }
-      PQ_SYNC
+      pp_sync();
       PQ_MMA
       if (req) dma(ib, ob[0], dst_b[0], rbuf);
-      PQ_SYNC
+      pp_sync();
       // L1: K-tile g + 1 must have landed before the barrier in front of its first read
       read_ab(cur, 1);
       if (req) {
@@ -209,22 +178,22 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp128(GemmParams p, int t
       }
       if (g + 1 < total) {
         if (!req) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else if (kt == 0) PQ_VMCNT(5)                           // younger: five requests of K-tile g + 2 and the previous epilogue's stores
+        else if (kt == 0) PP_WAIT_BEHIND_STORES(5, 8, sq)        // younger: five requests of K-tile g + 2 and the previous epilogue's stores
         else asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
       }
-      PQ_SYNC
+      pp_sync();
       PQ_MMA
       if (req) {
         dma(ia, od[1], dst_d[1], rbuf);
         advance();
       }
-      if (!(last && grp == 1)) PQ_SYNC
+      if (!(last && grp == 1)) pp_sync();
       buf = buf == 2 ? 0 : buf + 1;
     }
 
     // ---- epilogue of tile t: staging in the ring slot of the tile's last K-tile (free until the next tile's first L slot requests
     // into it, which lies behind the barrier below)
-    PQ_STAMP
+    PP_STAMP(stamps, lane)
     {
       const int u = u_first + t * u_step, tm = u / tiles_n, tn = u - tm * tiles_n;
       const int64_t m0t = (int64_t)tm * PQ_BM, n0t = (int64_t)tn * PQ_BN, mw = m0t + wm * 64, nw = n0t + wn * 64;
@@ -232,19 +201,14 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp128(GemmParams p, int t
       sq = (p.M - mw >= 64 && nw + 64 <= p.N) ? sq_full : 0;
       pp_epilogue<OUT_DT, ACT, RES, 4>(p, acc, stage, mw, nw, m0t, n0t, lane, (order & 256) != 0, [&]() {
         if (t + 2 < my) nx = tile_at(t + 2);                    // (the stream crosses into it during the next tile)
-        PQ_STAMP
+        PP_STAMP(stamps, lane)
       });
     }
-    PQ_STAMP
+    PP_STAMP(stamps, lane)
     // every wave is done with its staging tile before the next request may land there
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
+    pp_sync();
   }
-#undef PQ_STAMP
 #undef PQ_MMA
-#undef PQ_SYNC
-#undef PQ_VMCNT
 }
 
 bool gemm_bf16_nt_pp128_ok(const GemmParams& p) { return pp_envelope_ok(p, PQ_BK) && p.K >= 3 * PQ_BK; }
@@ -252,15 +216,10 @@ bool gemm_bf16_nt_pp128_ok(const GemmParams& p) { return pp_envelope_ok(p, PQ_BK
 int launch_gemm_bf16_nt_pp128(const GemmParams& p, hipStream_t st) {
   // start stagger as in gemm_bf16_pp.hip (heavy epilogues only), scaled to this tile's period
   const bool heavy = (p.epilogue & (DINOX_EPI_GELU | DINOX_EPI_DGELU | DINOX_EPI_RESIDUAL)) != 0;
-  PersistPlan pl;
-  if (!persist_plan(p, PQ_BM, PQ_BN, heavy ? (int)(p.K / PQ_BK) * 1300 + 3000 : 0, pl)) return DINOX_EUNSUPPORTED;
-  const int rc = with_epilogue_case(p, [&](auto out, auto act, auto res) {
-    auto kern = gemm_bf16_nt_pp128<decltype(out)::value, decltype(act)::value, decltype(res)::value>;
-    if (int rc = reserve_lds(reinterpret_cast<const void*>(kern), PQ_LDS, "gemm_bf16_nt_pp128")) return rc;
-    hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(512), PQ_LDS, st, p, pl.tiles_n, pl.units, pl.order, pl.stagger);
-    return 0;
+  const int stagger = heavy ? (int)(p.K / PQ_BK) * 1300 + 3000 : 0;
+  return pp_launch_persistent<PQ_BM, PQ_BN, PQ_LDS>(p, stagger, "gemm_bf16_nt_pp128", st, [](auto out, auto act, auto res) {
+    return gemm_bf16_nt_pp128<decltype(out)::value, decltype(act)::value, decltype(res)::value>;
   });
-  return rc ? rc : check_launch("gemm_bf16_nt_pp128");
 }
 
 }  // namespace dinox

@@ -111,12 +111,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp384(GemmParams p, PpLnE
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
   };
-#define PR_SYNC                                                                                                           \
-  {                                                                                                                       \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                                    \
-    __builtin_amdgcn_s_barrier();                                                                                         \
-    __builtin_amdgcn_sched_barrier(0);                                                                                    \
-  }
 
   // ---- K loop; NM = this wave's requests per K-tile (5; 2 for wave 7)
   auto kloop = [&](auto nm_c) {
@@ -145,14 +139,14 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp384(GemmParams p, PpLnE
       asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NM) : "memory");
       PR_DMA(0, rb, koff);
       PR_DMA(1, rb, koff);
-      PR_SYNC
+      pp_sync();
       mma();
       if constexpr (NM == 5) {
         PR_DMA(2, rb, koff);
         PR_DMA(3, rb, koff);
         PR_DMA(4, rb, koff);
       }
-      PR_SYNC
+      pp_sync();
       buf = buf == PR_NSLOT - 1 ? 0 : buf + 1;
       koff += 64;
     }
@@ -160,9 +154,9 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp384(GemmParams p, PpLnE
       read_frags(smem + buf * PR_KT_BYTES);
       if (g + 2 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NM) : "memory");
       else if (g + 1 < nk) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      PR_SYNC
+      pp_sync();
       mma();
-      if (!(g + 1 == nk && grp == 1)) PR_SYNC
+      if (!(g + 1 == nk && grp == 1)) pp_sync();
       buf = buf == PR_NSLOT - 1 ? 0 : buf + 1;
     }
   };
@@ -171,7 +165,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp384(GemmParams p, PpLnE
 #undef PR_DMA
 
   // ---- epilogue
-  PR_SYNC                                                       // every wave is past its last read of the ring
+  pp_sync();                                                    // every wave is past its last read of the ring
   const bool hb = (p.epilogue & DINOX_EPI_BIAS) != 0;
   const float alpha = p.alpha;
   float4 bias[3];
@@ -192,7 +186,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp384(GemmParams p, PpLnE
         pk.y = pp_pack2(v[2] * alpha, v[3] * alpha);
         *reinterpret_cast<uint2*>(orow + i * 16 * PR_OROW + j * 32) = pk;
       }
-    PR_SYNC
+    pp_sync();
     const int hl = lane & 31, hh = lane >> 5;
     const float* const xg = ln.beta;                            // (x rides in the beta slot)
     const float* const gadd = p.residual;
@@ -262,7 +256,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp384(GemmParams p, PpLnE
         }
       }
     }
-    PR_SYNC                                                     // the image is dead: the sixteen half-waves' column sums meet in its place
+    pp_sync();                                                  // the image is dead: the sixteen half-waves' column sums meet in its place
     {
       float* const cs = reinterpret_cast<float*>(smem) + (size_t)(2 * wv + hh) * 2 * PR_BN;
 #pragma unroll
@@ -271,7 +265,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp384(GemmParams p, PpLnE
         reinterpret_cast<float4*>(cs + PR_BN)[hl + 32 * j] = ab[j];
       }
     }
-    PR_SYNC
+    pp_sync();
     float* const wsrow = (float*)p.aux + (size_t)blockIdx.x * 2 * PR_BN;
     for (int c = (int)threadIdx.x; c < 2 * PR_BN; c += 512) {
       float v = 0.f;
@@ -292,7 +286,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp384(GemmParams p, PpLnE
         pk.y = pp_pack2(v[2] * alpha + bias[j].z, v[3] * alpha + bias[j].w);
         *reinterpret_cast<uint2*>(orow + i * 16 * PR_OROW + j * 32) = pk;
       }
-    PR_SYNC
+    pp_sync();
     char* const cbase = (char*)p.C + m0 * p.ldc * 2;
     const int npiece = rows * 48;                               // 16-byte pieces of the tile's valid rows
     for (int u = (int)threadIdx.x; u < npiece; u += 512) {
@@ -338,7 +332,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp384(GemmParams p, PpLnE
           *reinterpret_cast<pp_f32x4*>(orow + i * 16 * PR_FROW + j * 64) =
               pp_f32x4{v[0] * alpha + bias[j].x, v[1] * alpha + bias[j].y, v[2] * alpha + bias[j].z, v[3] * alpha + bias[j].w};
         }
-      PR_SYNC
+      pp_sync();
 #pragma unroll
       for (int q = 0; q < NP; ++q) {
         const int lr = wv + 16 * q + 8 * hh, row = r0 + lr;
@@ -382,7 +376,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp384(GemmParams p, PpLnE
           }
         }
       }
-      PR_SYNC                                                   // the slab is overwritten by the next one
+      pp_sync();                                                // the slab is overwritten by the next one
     };
     slab(std::integral_constant<int, 0>{}, std::integral_constant<int, 5>{});
     slab(std::integral_constant<int, 5>{}, std::integral_constant<int, 4>{});
@@ -401,7 +395,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp384(GemmParams p, PpLnE
           *reinterpret_cast<pp_f32x4*>(orow + i * 16 * PR_FROW + j * 64) =
               pp_f32x4{v[0] * alpha + bias[j].x, v[1] * alpha + bias[j].y, v[2] * alpha + bias[j].z, v[3] * alpha + bias[j].w};
         }
-      PR_SYNC
+      pp_sync();
       const int r0 = IB * 16;
       const int vrows = rows - r0 < 0 ? 0 : (rows - r0 < NB * 16 ? rows - r0 : NB * 16);
       const int npiece = vrows * 96;                            // 16-byte pieces of the slab's valid rows
@@ -430,13 +424,12 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp384(GemmParams p, PpLnE
           }
         }
       }
-      PR_SYNC                                                   // the slab is overwritten by the next one
+      pp_sync();                                                // the slab is overwritten by the next one
     };
     slab(std::integral_constant<int, 0>{}, std::integral_constant<int, 5>{});
     slab(std::integral_constant<int, 5>{}, std::integral_constant<int, 4>{});
     slab(std::integral_constant<int, 9>{}, std::integral_constant<int, 4>{});
   }
-#undef PR_SYNC
 }
 
 bool gemm_bf16_nt_pp384_ok(const GemmParams& p) {

@@ -1,5 +1,7 @@
-// gemm_pp_common.h -- shared pieces of the persistent ping-pong NT kernels (gemm_bf16_pp.hip: 256 x 256 tiles, gemm_bf16_pp128.hip: 256 x 128):
-// the fused epilogue of one wave's accumulator block and the workgroup -> tile assignment.
+// gemm_pp_common.h -- shared pieces of the ping-pong NT kernels.  All three (gemm_bf16_pp.hip: 256 x 256 tiles, gemm_bf16_pp128.hip:
+// 256 x 128, gemm_bf16_pp384.hip: 208 x 384) use the slot boundary, the pack and the envelope; the two persistent ones (pp, pp128) also
+// the workgroup -> tile assignment, the tile origins, the start stagger, the store-counting wait, the cycle stamps, the fused
+// epilogue of one wave's accumulator block and the launcher.
 #pragma once
 #include "common.h"
 #include "kernels.h"
@@ -19,6 +21,64 @@ enum { PP_PLAIN = EPI_ACT_PLAIN, PP_GELU = EPI_ACT_GELU, PP_DGELU = EPI_ACT_DGEL
 __device__ __forceinline__ unsigned pp_pack2(float a, float b) {
   const pp_bf16x2 r = __builtin_convertvector(pp_f32x2{a, b}, pp_bf16x2);
   return __builtin_bit_cast(unsigned, r);
+}
+
+// Slot boundary: my LDS reads have returned (they are the next M slot's operands, and the buffer may be refilled behind the barrier).
+__device__ __forceinline__ void pp_sync() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// Counted wait.  gfx950 retires loads, LDS-DMA and stores of a wave in ONE issue-ordered counter, so "piece X has landed" is
+// vmcnt(number of operations issued after X), and that number includes the output stores of the previous tile's epilogue whenever X
+// was requested before them: BASE younger requests + sq * STEP stores.  `sq` (0 / 1 / 2) says how many STEPs of stores that epilogue
+// certainly issued (an edge tile or the first tile: 0 -- a LOWER bound is always safe, it only waits for more than necessary).
+// (This and PP_STAMPS / PP_STAMP below are macros, and their names are reserved in every file that includes this header: as inlined functions
+// they change the register allocation of both K loops.)
+#define PP_WAIT_BEHIND_STORES(BASE, STEP, sq)                                                                             \
+  {                                                                                                                       \
+    if ((sq) == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(BASE) : "memory");                                            \
+    else if ((sq) == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((BASE) + (STEP)) : "memory");                            \
+    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"((BASE) + 2 * (STEP)) : "memory");                                       \
+  }
+
+// De-phasing.  Every workgroup has the same work per tile, so without it all 256 run in lockstep: every CU is in its K loop (no
+// stores at all) or in its epilogue (stores only) at the same time, and the output stream meets HBM in bursts of twice its bandwidth
+// (measured: the plain bf16 epilogue took 5.4k cycles, GELU + side tensor 28k, against ~2k / ~12k of instructions).  Workgroups that own
+// one tile less than the busiest ones have a whole tile period to spare: they start late by a pseudo-random share of `stagger` cycles.
+__device__ __forceinline__ void pp_start_late(int stagger, int order, int my, int my_max) {
+  if (stagger > 0 && (my < my_max || (order & 512))) {          // (order bit 9: diagnostic -- every workgroup starts late)
+    const unsigned h = ((unsigned)(int)blockIdx.x * 2654435761u) >> 16;   // 16 bits
+    const int naps = (int)(((int64_t)stagger * h) >> 26);       // stagger * h / 65536 cycles, in naps of 1024
+    for (int i = 0; i < naps; ++i) __builtin_amdgcn_s_sleep(16);
+  }
+}
+
+// Diagnostic cycle stamps (tools/pp_stamps.py hands a buffer over in p.ws, which NT products never use otherwise): waves 0 and 4 of
+// every workgroup (wave group grp = 0 / 1) write s_memtime at the marked points, 256 slots per wave.  PP_STAMPS(st, ...) declares the
+// two locals st_slots and st_n once, PP_STAMP(st, lane) marks a point.
+#define PP_STAMPS(st, p, wv, grp)                                                                                                        \
+  long long* const st##_slots = ((p).ws && ((wv) & 3) == 0) ? (long long*)(p).ws + ((int64_t)(int)blockIdx.x * 2 + (grp)) * 256 : nullptr; \
+  int st##_n = 0;
+#define PP_STAMP(st, lane)                                                                                                \
+  {                                                                                                                       \
+    if (st##_slots && st##_n < 256 && (lane) == 0) st##_slots[st##_n] = (long long)__builtin_amdgcn_s_memtime();          \
+    ++st##_n;                                                                                                             \
+  }
+
+// Tile u of the row-major tile list: operand origins and the last valid row of each operand inside the tile.
+struct PpTileAt { const char* a; const char* b; int mlast, nlast; };
+template <int BM, int BN>
+__device__ __forceinline__ PpTileAt pp_tile_at(const GemmParams& p, int u, int tiles_n) {
+  const int tm = u / tiles_n, tn = u - tm * tiles_n;
+  const int64_t m0 = (int64_t)tm * BM, n0 = (int64_t)tn * BN;
+  PpTileAt r;
+  r.a = (const char*)((const bf16_t*)p.A + m0 * p.lda);
+  r.b = (const char*)((const bf16_t*)p.B + n0 * p.ldb);
+  r.mlast = (int)(p.M - m0 < BM ? p.M - m0 : BM) - 1;
+  r.nlast = (int)(p.N - n0 < BN ? p.N - n0 : BN) - 1;
+  return r;
 }
 
 // This workgroup's tiles.  order 0: a contiguous run of the row-major tile list (the column tiles of a row panel follow each other in
@@ -197,7 +257,7 @@ __device__ __forceinline__ void pp_epilogue(const GemmParams& p, pp_f32x4 (&acc)
   }
 }
 
-// Epilogue / operand envelope shared by both kernels (the caller has checked in_dtype == bf16 and transA == transB == 0).
+// Epilogue / operand envelope shared by the three kernels (the caller has checked in_dtype == bf16 and transA == transB == 0).
 static inline bool pp_al16(const void* q) { return (((uintptr_t)q) & 15) == 0; }
 static inline bool pp_envelope_ok(const GemmParams& p, int bk) {
   const int64_t ldmax = 1 << 21;                                // 32-bit byte offsets inside a tile
@@ -218,6 +278,21 @@ static inline bool pp_envelope_ok(const GemmParams& p, int bk) {
   }
   if ((e & DINOX_EPI_RESIDUAL) && (!pp_al16(p.residual) || (p.ldr & 3) || p.ldr >= ldmax)) return false;
   return true;
+}
+
+// Launcher of the two persistent kernels: one workgroup per CU (persist_plan: tile order and DINOX_PP_STAGGER over the kernel's own
+// stagger rule), the <OUT, ACT, RES> instance for p's epilogue -- kern_of(out, act, res) names it -- with its LDS reserved.
+template <int BM, int BN, int LDS, typename KernOf>
+static inline int pp_launch_persistent(const GemmParams& p, int stagger_auto, const char* what, hipStream_t st, KernOf&& kern_of) {
+  PersistPlan pl;
+  if (!persist_plan(p, BM, BN, stagger_auto, pl)) return DINOX_EUNSUPPORTED;
+  const int rc = with_epilogue_case(p, [&](auto out, auto act, auto res) {
+    auto kern = kern_of(out, act, res);
+    if (int rc = reserve_lds(reinterpret_cast<const void*>(kern), LDS, what)) return rc;
+    hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(512), LDS, st, p, pl.tiles_n, pl.units, pl.order, pl.stagger);
+    return 0;
+  });
+  return rc ? rc : check_launch(what);
 }
 
 }  // namespace dinox

@@ -90,23 +90,18 @@ __global__ __launch_bounds__(LN_THREADS) void ln_fwd_384(const float* __restrict
     ww[j] = reinterpret_cast<const float4*>(w)[sl + 32 * j];
     bb[j] = reinterpret_cast<const float4*>(b)[sl + 32 * j];
   }
-  auto sum32 = [](float v) {
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-  };
   auto finish = [&](const float4 (&v)[3], int64_t r) {
     float s = 0.f;
 #pragma unroll
     for (int j = 0; j < 3; ++j) s += (v[j].x + v[j].y) + (v[j].z + v[j].w);
-    const float mu = sum32(s) * (1.0f / DIM);
+    const float mu = half_wave_sum(s) * (1.0f / DIM);
     float q = 0.f;
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
       const float a = v[j].x - mu, c = v[j].y - mu, d = v[j].z - mu, e = v[j].w - mu;
       q += (a * a + c * c) + (d * d + e * e);
     }
-    const float rs = rsqrtf(sum32(q) * (1.0f / DIM) + eps);
+    const float rs = rsqrtf(half_wave_sum(q) * (1.0f / DIM) + eps);
     if (sl == 0) {
       mean[r] = mu;
       rstd[r] = rs;
@@ -284,11 +279,6 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_384(const void* __restrict_
     ab[j] = make_float4(0.f, 0.f, 0.f, 0.f);
     wreg[j] = reinterpret_cast<const float4*>(w)[sl + 32 * j];
   }
-  auto sum32 = [](float v) {
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-  };
   auto fetch = [&](int64_t r, float4 (&xv)[3], float4 (&d)[3], float4 (&a)[3]) {
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
@@ -316,7 +306,7 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_384(const void* __restrict_
       s1 += (g[j].x + g[j].y) + (g[j].z + g[j].w);
       s2 += (g[j].x * xh[j].x + g[j].y * xh[j].y) + (g[j].z * xh[j].z + g[j].w * xh[j].w);
     }
-    const float m1 = sum32(s1) * (1.0f / DIM), m2 = sum32(s2) * (1.0f / DIM);
+    const float m1 = half_wave_sum(s1) * (1.0f / DIM), m2 = half_wave_sum(s2) * (1.0f / DIM);
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
       const int c = sl + 32 * j;
