@@ -110,6 +110,35 @@ extern "C" int dinox_ntxent_coeff(const float* S, int64_t lds, const float* lse,
   return dinox::launch_ntxent_coeff(S, lds, lse, M, inv_tau, gscale, W, ldw, dinox::as_stream(stream));
 }
 
+// The rectangular forms: Ml = 2 Bl local rows against Mg = world * Ml gathered columns, this rank's block at column row0.
+static int ntxent_rect_ok(const char* what, int64_t lds, int Ml, int Mg, int row0, int Bl, float inv_tau) {
+  DX_REQUIRE(ntxent_rows_ok(Ml), DINOX_EINVAL, "%s: Ml=%d (the local rows are [z1; z2]: an even count of at least 2)", what, Ml);
+  DX_REQUIRE(Bl * 2 == Ml, DINOX_EINVAL, "%s: Bl=%d is not half of Ml=%d", what, Bl, Ml);
+  DX_REQUIRE(Mg >= Ml && Mg % Ml == 0 && Mg <= 65535 * 32, DINOX_EINVAL, "%s: Mg=%d is not a multiple of Ml=%d (every rank holds Ml rows)", what,
+             Mg, Ml);
+  DX_REQUIRE(row0 >= 0 && row0 <= Mg - Ml && row0 % Ml == 0, DINOX_EINVAL, "%s: row0=%d is not the start of a rank's block (Ml=%d, Mg=%d)", what,
+             row0, Ml, Mg);
+  DX_REQUIRE(lds >= Mg && inv_tau > 0.f, DINOX_EINVAL, "%s: lds=%lld Mg=%d inv_tau=%g", what, (long long)lds, Mg, (double)inv_tau);
+  return 0;
+}
+
+extern "C" int dinox_ntxent_rows_rect(const float* S, int64_t lds, int Ml, int Mg, int row0, int Bl, float inv_tau, float* lse, float* row_loss,
+                                      float* loss_sum, void* stream) {
+  DX_REQUIRE(S && lse && row_loss && loss_sum, DINOX_EINVAL, "ntxent_rows_rect: null pointer");
+  const int rc = ntxent_rect_ok("ntxent_rows_rect", lds, Ml, Mg, row0, Bl, inv_tau);
+  if (rc) return rc;
+  return dinox::launch_ntxent_rows_rect(S, lds, Ml, Mg, row0, Bl, inv_tau, lse, row_loss, loss_sum, dinox::as_stream(stream));
+}
+
+extern "C" int dinox_ntxent_coeff_rect(const float* S, int64_t lds, const float* lse_local, const float* lse_all, int Ml, int Mg, int row0,
+                                       int Bl, float inv_tau, float gscale, float* W, int64_t ldw, void* stream) {
+  DX_REQUIRE(S && lse_local && lse_all && W, DINOX_EINVAL, "ntxent_coeff_rect: null pointer");
+  const int rc = ntxent_rect_ok("ntxent_coeff_rect", lds, Ml, Mg, row0, Bl, inv_tau);
+  if (rc) return rc;
+  DX_REQUIRE(ldw >= Mg, DINOX_EINVAL, "ntxent_coeff_rect: ldw=%lld Mg=%d", (long long)ldw, Mg);
+  return dinox::launch_ntxent_coeff_rect(S, lds, lse_local, lse_all, Ml, Mg, row0, Bl, inv_tau, gscale, W, ldw, dinox::as_stream(stream));
+}
+
 extern "C" int dinox_normalize_bwd(const float* dxh, const float* xh, const float* norm, float* dx, int64_t V, int D, float eps, void* stream) {
   DX_REQUIRE(dxh && xh && norm && dx, DINOX_EINVAL, "normalize_bwd: null pointer");
   DX_REQUIRE(V > 0 && V <= 0x7fffffff && D > 0 && eps > 0.f, DINOX_EINVAL, "normalize_bwd: V=%lld D=%d eps=%g", (long long)V, D, (double)eps);

@@ -74,6 +74,10 @@ int launch_attention_flash_bwd(const void* d_o, const void* qkv, const void* o, 
 // ---------------------------------------------------------------- NT-Xent (ntxent.hip; entry points and argument checks: abi.hip)
 int launch_ntxent_rows(const float* S, int64_t lds, int M, float inv_tau, float* lse, float* row_loss, float* loss, hipStream_t st);
 int launch_ntxent_coeff(const float* S, int64_t lds, const float* lse, int M, float inv_tau, float gscale, float* W, int64_t ldw, hipStream_t st);
+int launch_ntxent_rows_rect(const float* S, int64_t lds, int Ml, int Mg, int row0, int Bl, float inv_tau, float* lse, float* row_loss,
+                            float* loss_sum, hipStream_t st);
+int launch_ntxent_coeff_rect(const float* S, int64_t lds, const float* lse_local, const float* lse_all, int Ml, int Mg, int row0, int Bl,
+                             float inv_tau, float gscale, float* W, int64_t ldw, hipStream_t st);
 int launch_normalize_bwd(const float* dxh, const float* xh, const float* norm, float* dx, int64_t V, int D, float eps, hipStream_t st);
 
 // ---------------------------------------------------------------- attention rows (attention_rows.hip; entry points: abi.hip)

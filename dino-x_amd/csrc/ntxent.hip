@@ -4,7 +4,8 @@
 //     loss = mean_i ( logsumexp_{j != i} s_ij - s_{i p(i)} ),   p(i) = (i + B) mod 2B.
 // The two M x M x D products (S = Z^ Z^T and dZ^ = W Z^) go through dinox_gemm (exact-fp32 MFMA) and the row normalisation through
 // dinox_koleo_normalize (same formula, eps is an argument); here: the row pass over S, the coefficient matrix W of the backward and
-// the backward of the normalisation.
+// the backward of the normalisation.  Under data parallelism the rows are this rank's and the columns every rank's: the
+// rectangular forms below (ntxent_rows_rect / ntxent_coeff_rect), [Ml, Mg] instead of [M, M].
 //
 // Documented deviation: everything is fp32 in BOTH compute modes (as KoLeo).  Under --amp the reference's autocast runs the
 // similarity matmul in bf16; this engine stays at fp32 there, i.e. closer to the reference's own fp32 step.
@@ -87,6 +88,75 @@ __global__ __launch_bounds__(NX_THREADS) void ntxent_coeff_kernel(const float* _
   }
 }
 
+// ---------------------------------------------------------------- rectangular forms: local rows x global columns (data parallel)
+// A rank holds Ml = 2 Bl rows [z1_local; z2_local]; S [Ml, Mg] is their product with the Mg = world * Ml gathered rows, rank r's
+// block starting at column row0 = r * Ml.  For local row i the excluded column is its own global index dg(i) = row0 + i and its
+// positive is p(i) = row0 + (i + Bl) mod Ml.  The square kernels above stay as they are (same device code, same bits); with
+// Mg = Ml and row0 = 0 these compute the same lse from the same S.
+__device__ __forceinline__ int ntxent_rect_pos(int i, int row0, int Bl) { return row0 + (i + Bl < 2 * Bl ? i + Bl : i - Bl); }
+
+__global__ __launch_bounds__(NX_THREADS) void ntxent_rows_rect_kernel(const float* __restrict__ S, int64_t lds, int Mg, int row0, int Bl,
+                                                                      float inv_tau, float* __restrict__ lse, float* __restrict__ row_loss) {
+  __shared__ float red[16];
+  const int i = blockIdx.x, dg = row0 + i;
+  const float* row = S + (int64_t)i * lds;
+  float mx = -INFINITY;
+  for (int j = threadIdx.x; j < Mg; j += NX_THREADS)
+    if (j != dg) mx = fmaxf(mx, row[j] * inv_tau);
+  mx = block_max(mx, red);
+  float a = 0.f;
+  for (int j = threadIdx.x; j < Mg; j += NX_THREADS)
+    if (j != dg) a += expf(row[j] * inv_tau - mx);
+  a = block_sum(a, red);
+  if (threadIdx.x == 0) {
+    const float l = mx + logf(a);
+    lse[i] = l;
+    row_loss[i] = l - row[ntxent_rect_pos(i, row0, Bl)] * inv_tau;
+  }
+}
+
+// loss_sum[0] = sum_i row_loss[i] in index order (ntxent_mean_kernel without the division: the ranks' sums meet on the host side of
+// the all-gather, which divides by Mg once).
+__global__ __launch_bounds__(NX_THREADS) void ntxent_sum_kernel(const float* __restrict__ row_loss, int M, float* __restrict__ loss_sum) {
+  __shared__ float buf[1024];
+  float a = 0.f;
+  for (int base = 0; base < M; base += 1024) {
+    const int n = M - base < 1024 ? M - base : 1024;
+    for (int t = threadIdx.x; t < n; t += NX_THREADS) buf[t] = row_loss[base + t];
+    __syncthreads();
+    if (threadIdx.x == 0)
+      for (int t = 0; t < n; ++t) a += buf[t];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) loss_sum[0] = a;
+}
+
+// W[i][j] = scale * (exp(S_ij/tau - lse_local[i]) + exp(S_ij/tau - lse_all[j]) - 2 [j = p(i)]),  W[i][dg(i)] = 0,  scale = g / (Ml tau).
+// The second term is P_ji: S_ji lives on the rank that owns row j, so S_ij stands in for it (the product is symmetric up to rounding)
+// with the gathered lse of row j; [i = p(j)] = [j = p(i)] for this pairing.  One workgroup per 32 x 32 tile, every element read and
+// written by one thread: no mirror tile, no LDS.
+__global__ __launch_bounds__(NX_THREADS) void ntxent_coeff_rect_kernel(const float* __restrict__ S, int64_t lds,
+                                                                       const float* __restrict__ lse_local, const float* __restrict__ lse_all,
+                                                                       int Ml, int Mg, int row0, int Bl, float inv_tau, float scale,
+                                                                       float* __restrict__ W, int64_t ldw) {
+  const int tx = threadIdx.x & (NX_TILE - 1), ty = threadIdx.x >> 5;  // 32 x 8
+  const int i0 = blockIdx.y * NX_TILE, j = blockIdx.x * NX_TILE + tx;
+  if (j >= Mg) return;
+  const float lj = lse_all[j];
+  for (int r = ty; r < NX_TILE; r += NX_THREADS / NX_TILE) {
+    const int i = i0 + r;
+    if (i >= Ml) break;
+    float w = 0.f;
+    if (j != row0 + i) {
+      const float s = S[(int64_t)i * lds + j] * inv_tau;
+      w = expf(s - lse_local[i]) + expf(s - lj);
+      w -= j == ntxent_rect_pos(i, row0, Bl) ? 2.f : 0.f;
+      w *= scale;
+    }
+    W[(int64_t)i * ldw + j] = w;
+  }
+}
+
 // Backward of xh = x / max(||x||, eps), one workgroup per row:  dx = (dxh - xh (xh . dxh)) / ||x||  where ||x|| >= eps, and
 // dx = dxh / eps where the clamp acted (what torch's clamp_min + norm backward give: no gradient reaches the norm there).
 template <bool VEC>
@@ -129,6 +199,23 @@ int launch_ntxent_coeff(const float* S, int64_t lds, const float* lse, int M, fl
   const float scale = gscale * inv_tau / (float)M;
   hipLaunchKernelGGL(ntxent_coeff_kernel, dim3(tiles, tiles), dim3(NX_THREADS), 0, st, S, lds, lse, M, inv_tau, scale, W, ldw);
   return check_launch("ntxent_coeff");
+}
+
+int launch_ntxent_rows_rect(const float* S, int64_t lds, int Ml, int Mg, int row0, int Bl, float inv_tau, float* lse, float* row_loss,
+                            float* loss_sum, hipStream_t st) {
+  hipLaunchKernelGGL(ntxent_rows_rect_kernel, dim3((unsigned)Ml), dim3(NX_THREADS), 0, st, S, lds, Mg, row0, Bl, inv_tau, lse, row_loss);
+  const int rc = check_launch("ntxent_rows_rect");
+  if (rc) return rc;
+  hipLaunchKernelGGL(ntxent_sum_kernel, dim3(1), dim3(NX_THREADS), 0, st, row_loss, Ml, loss_sum);
+  return check_launch("ntxent_rows_rect_sum");
+}
+
+int launch_ntxent_coeff_rect(const float* S, int64_t lds, const float* lse_local, const float* lse_all, int Ml, int Mg, int row0, int Bl,
+                             float inv_tau, float gscale, float* W, int64_t ldw, hipStream_t st) {
+  const float scale = gscale * inv_tau / (float)Ml;
+  hipLaunchKernelGGL(ntxent_coeff_rect_kernel, dim3((unsigned)ceil_div(Mg, NX_TILE), (unsigned)ceil_div(Ml, NX_TILE)), dim3(NX_THREADS), 0, st,
+                     S, lds, lse_local, lse_all, Ml, Mg, row0, Bl, inv_tau, scale, W, ldw);
+  return check_launch("ntxent_coeff_rect");
 }
 
 int launch_normalize_bwd(const float* dxh, const float* xh, const float* norm, float* dx, int64_t V, int D, float eps, hipStream_t st) {

@@ -122,6 +122,8 @@ SIGNATURES = {
     "dinox_ntxent_rows": (i32, [vp, i64, i32, f32, vp, vp, vp, vp]),
     "dinox_ntxent_coeff": (i32, [vp, i64, vp, i32, f32, f32, vp, i64, vp]),
     "dinox_normalize_bwd": (i32, [vp, vp, vp, vp, i64, i32, f32, vp]),
+    "dinox_ntxent_rows_rect": (i32, [vp, i64, i32, i32, i32, i32, f32, vp, vp, vp, vp]),
+    "dinox_ntxent_coeff_rect": (i32, [vp, i64, vp, vp, i32, i32, i32, i32, f32, f32, vp, i64, vp]),
     "dinox_mae_mask_ids": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "dinox_mae_gather_unfold": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "dinox_mae_tokens_fwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),

@@ -70,6 +70,7 @@ class StepHyperParams:
     mae_mask_ratio: float = 0.75     # the reference hard-codes MaeModel(mask_ratio=0.75); the engine sets it on the model it is given
     centering: str = "ema"           # "ema" (the reference's centre) | "sinkhorn" (DINOv2/v3 Sinkhorn-Knopp targets; extension, dino only)
     sk_iters: int = 3                # Sinkhorn-Knopp iterations (DINOv2: 3)
+    simclr_negatives: str = "local"  # "local" (one rank's batch; single rank only) | "global" (the rows of every rank: extension, simclr only)
 
 
 def flatten_parameters(module: torch.nn.Module, align: int = 8, order: Optional[List[torch.nn.Parameter]] = None
@@ -128,6 +129,10 @@ class TrainEngine:
             raise ValueError(f"sk_iters must be >= 1, got {hp.sk_iters}")
         if hp.centering == "sinkhorn" and hp.loss_type != "dino":
             raise ValueError(f"centering='sinkhorn' shapes the teacher targets of loss_type='dino'; loss_type={hp.loss_type!r} has none")
+        if hp.simclr_negatives not in ("local", "global"):
+            raise ValueError(f"simclr_negatives must be 'local' or 'global', got {hp.simclr_negatives!r}")
+        if hp.simclr_negatives == "global" and hp.loss_type != "simclr":
+            raise ValueError(f"simclr_negatives='global' belongs to loss_type='simclr'; loss_type={hp.loss_type!r} has no negatives")
         if hp.loss_type == "mae":
             self._mae_arena(student, teacher, use_graph)
         else:
@@ -162,9 +167,14 @@ class TrainEngine:
     def _two_net_arenas(self, student, teacher, process_group, bucket_bytes) -> None:
         """dino and simclr: a student and a teacher arena of one layout, gradient buckets, the teacher's side stream."""
         simclr = self.hp.loss_type == "simclr"
-        if simclr and self.world > 1:
+        if simclr and self.world > 1 and self.hp.simclr_negatives != "global":
             raise ValueError("loss_type='simclr' runs on a single rank only (the negatives of a row are the rows of ONE batch; "
-                             "cross-rank negatives are not implemented)")
+                             "cross-rank negatives are not implemented) unless simclr_negatives='global' gathers them from every rank")
+        # simclr_negatives="global": NT-Xent over the rows of every rank (ops.ntxent_fwd(group=)); None keeps the square single-rank kernels
+        # (ops takes group=None as "no exchange", so the default process group is named)
+        self._ntxent_group = None
+        if simclr and self.hp.simclr_negatives == "global" and dist.is_initialized():
+            self._ntxent_group = process_group if process_group is not None else dist.group.WORLD
         for p in teacher.parameters():
             p.requires_grad_(False)
         self._build_arena(student)
@@ -483,14 +493,14 @@ class TrainEngine:
             if not self.manual_top:
                 s_out = self.student.head(s_feats[:, 0])
                 half = s_out.shape[0] // 2
-                loss = ops.simclr_loss(s_out[:half], s_out[half:], hp.simclr_temp)
+                loss = ops.simclr_loss(s_out[:half], s_out[half:], hp.simclr_temp, group=self._ntxent_group)
                 self._mark("loss")
                 (loss if self.accum == 1 else loss / self.accum).backward()
             else:
                 with torch.no_grad():
                     sf = s_feats.detach()
                     z, saved = self._head(self.student.head, ops.take_rows(sf, 0, dt), train=True)
-                    loss, nsaved = ops.ntxent_fwd(z, hp.simclr_temp)
+                    loss, nsaved = ops.ntxent_fwd(z, hp.simclr_temp, group=self._ntxent_group)
                     dcls = self._student_head_backward(saved, ops.ntxent_bwd(nsaved, 1.0 / self.accum))
                     dfeats = torch.empty_like(sf)
                     ops.zero_(dfeats)

@@ -1992,35 +1992,83 @@ def koleo_loss(x: Tensor, eps: float = 1e-8, group=None) -> Tensor:
     return KoLeoFn.apply(x, eps, group)
 
 
-def ntxent_fwd(z: Tensor, temperature: float = 0.1):
+def ntxent_fwd(z: Tensor, temperature: float = 0.1, group=None, force_rect: bool = False):
     """NT-Xent / SimCLR loss on the student head output (reference scripts/phase5_big_run.py:776-813): z [2B, D] = [z1; z2],
     z^ = F.normalize(z), s = z^ z^T / temperature without the diagonal, cross-entropy of row i against row (i + B) mod 2B, mean over
     the 2B rows.  fp32 in both modes (the reference's --amp autocasts the similarity matmul to bf16; this stays more accurate).
-    Returns (loss[1], saved) -- no autograd, no framework kernel; ntxent_bwd(saved, gscale) gives d(gscale * loss)/dz."""
+    Returns (loss[1], saved) -- no autograd, no framework kernel; ntxent_bwd(saved, gscale) gives d(gscale * loss)/dz.
+
+    Data parallel (``group`` a process group -- not None -- with more than one rank, dp.exchanging): the negatives of a row are the rows of the GLOBAL batch, as the
+    single-process reference has them at that batch size.  z holds this rank's Ml = 2 Bl rows [z1_local; z2_local]; the unit rows
+    are all-gathered into Z^_all [Mg = world * Ml, D] (rank r's block at row0 = r * Ml), S = Z^_local Z^_all^T is [Ml, Mg], and for
+    local row i the excluded column is row0 + i and the positive is row0 + (i + Bl) mod Ml (dinox_ntxent_rows_rect).  Three
+    all-gathers: Ml * D floats (unit rows), Ml floats (lse, for the backward's transposed term) and 1 float (the rank's sum of row
+    losses).  The loss returned is the GLOBAL mean L = (1 / Mg) sum over all rows: the ``world`` partial sums added in rank order,
+    then divided by Mg (a handful of one-element adds) -- the same bits on every rank.  Without an exchanging group the square kernels run, bit for bit as ever;
+    ``force_rect`` sends a single rank through the rectangular kernels (world = 1, row0 = 0).
+
+    Gradient convention: a rank's rows enter L through their own row terms AND as columns of every other rank's rows.  The W of
+    dinox_ntxent_coeff_rect holds both (the second through the gathered lse, S_ij standing in for S_ji) at scale 1 / (Ml tau), so
+    what ntxent_bwd returns is Mg / Ml = world times dL/dz_local -- the factor the engine needs: GradBucketer SUMS the ranks'
+    parameter gradients and AdamW applies 1 / world, so the averaged gradient is the single-process gradient of the global batch."""
     _need_cuda(z)
     if z.dim() != 2 or z.shape[0] < 2 or z.shape[0] % 2:
         raise ValueError(f"ntxent: z must be [2B, D] = [z1; z2] with B >= 1, got {tuple(z.shape)}")
     if not temperature > 0.0:
         raise ValueError(f"ntxent: temperature must be positive, got {temperature}")
+    from .dp import exchanging
+    gather = group is not None and exchanging(group)                    # group=None: never a collective, whatever is initialised
     z = _c(z.float())
     M, D = z.shape
     f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=z.device)
     zh, norm, sq = f(M, D), f(M), f(M)
     check(lib.dinox_koleo_normalize(_p(z), _p(zh), _p(norm), _p(sq), M, D, 1e-12, _stream()), "dinox_koleo_normalize")
-    S = gemm_nt_f32_splitk(zh, zh)                                      # [M, M] inner products, exact-fp32 MFMA
-    lse, row_loss, loss = f(M), f(M), f(1)
     inv_tau = 1.0 / temperature
-    check(lib.dinox_ntxent_rows(_p(S), M, M, inv_tau, _p(lse), _p(row_loss), _p(loss), _stream()), "dinox_ntxent_rows")
-    return loss, (S, zh, norm, lse, inv_tau)
+    if not (gather or force_rect):
+        S = gemm_nt_f32_splitk(zh, zh)                                  # [M, M] inner products, exact-fp32 MFMA
+        lse, row_loss, loss = f(M), f(M), f(1)
+        check(lib.dinox_ntxent_rows(_p(S), M, M, inv_tau, _p(lse), _p(row_loss), _p(loss), _stream()), "dinox_ntxent_rows")
+        return loss, (S, zh, norm, lse, inv_tau)
+    import torch.distributed as dist
+    world = dist.get_world_size(group) if gather else 1
+    rank = dist.get_rank(group) if gather else 0
+    Mg, row0, Bl = world * M, rank * M, M // 2
+    if gather:
+        zh_all = f(Mg, D)
+        dist.all_gather_into_tensor(zh_all, zh, group=group)
+    else:
+        zh_all = zh
+    S = gemm_nt_f32_splitk(zh, zh_all)                                  # [Ml, Mg]: local rows x global columns
+    lse, row_loss, part = f(M), f(M), f(1)
+    check(lib.dinox_ntxent_rows_rect(_p(S), Mg, M, Mg, row0, Bl, inv_tau, _p(lse), _p(row_loss), _p(part), _stream()), "dinox_ntxent_rows_rect")
+    if gather:
+        lse_all, parts = f(Mg), f(world)
+        dist.all_gather_into_tensor(lse_all, lse, group=group)
+        dist.all_gather_into_tensor(parts, part, group=group)
+    else:
+        lse_all, parts = lse, part
+    loss = parts[0:1].clone()
+    for r in range(1, world):                                           # rank order: every rank adds the same floats the same way
+        loss += parts[r:r + 1]
+    loss /= float(Mg)
+    return loss, (S, zh, norm, lse, inv_tau, (zh_all, lse_all, row0))
 
 
 def ntxent_bwd(saved, gscale: float = 1.0) -> Tensor:
-    """dz [2B, D] = d(gscale * NT-Xent loss) / dz (the upstream factor is a host scalar here: 1 / accumulation steps)."""
-    S, zh, norm, lse, inv_tau = saved
+    """dz [2B, D] = d(gscale * NT-Xent loss) / dz (the upstream factor is a host scalar here: 1 / accumulation steps).  After a
+    data-parallel ntxent_fwd: world * d(gscale * global loss) / dz_local (see there), from gathered data alone -- no collective."""
+    S, zh, norm, lse, inv_tau, *rect = saved
     M, D = zh.shape
     W = torch.empty_like(S)
-    check(lib.dinox_ntxent_coeff(_p(S), M, _p(lse), M, inv_tau, gscale, _p(W), M, _stream()), "dinox_ntxent_coeff")
-    dzh = gemm(W, zh, transB=True, out_dtype=torch.float32)             # dZ^ = W Z^  (W [M,M] symmetric, zero diagonal)
+    if rect:
+        zh_all, lse_all, row0 = rect[0]
+        Mg = zh_all.shape[0]
+        check(lib.dinox_ntxent_coeff_rect(_p(S), Mg, _p(lse), _p(lse_all), M, Mg, row0, M // 2, inv_tau, gscale, _p(W), Mg, _stream()),
+              "dinox_ntxent_coeff_rect")
+        dzh = gemm(W, zh_all, transB=True, out_dtype=torch.float32)     # dZ^_local = W Z^_all  (W [Ml, Mg])
+    else:
+        check(lib.dinox_ntxent_coeff(_p(S), M, _p(lse), M, inv_tau, gscale, _p(W), M, _stream()), "dinox_ntxent_coeff")
+        dzh = gemm(W, zh, transB=True, out_dtype=torch.float32)         # dZ^ = W Z^  (W [M,M] symmetric, zero diagonal)
     dz = torch.empty_like(zh)
     check(lib.dinox_normalize_bwd(_p(dzh), _p(zh), _p(norm), _p(dz), M, D, 1e-12, _stream()), "dinox_normalize_bwd")
     return dz
@@ -2030,23 +2078,24 @@ class NTXentFn(torch.autograd.Function):
     """ntxent_fwd / ntxent_bwd as an autograd node (the engine's fallback path and callers outside the engine)."""
 
     @staticmethod
-    def forward(ctx, z, temperature):
-        loss, saved = ntxent_fwd(z, temperature)
+    def forward(ctx, z, temperature, group=None, force_rect=False):
+        loss, saved = ntxent_fwd(z, temperature, group, force_rect)
         ctx.saved = saved
         return loss.reshape(())
 
     @staticmethod
     def backward(ctx, g):
         # the upstream gradient is a device scalar: run with gscale = 1 and scale the result (one small elementwise multiply, no host sync)
-        return ntxent_bwd(ctx.saved, 1.0) * g, None
+        return ntxent_bwd(ctx.saved, 1.0) * g, None, None, None
 
 
-def simclr_loss(z1: Tensor, z2: Tensor, temperature: float = 0.1) -> Tensor:
-    """SimCLRLoss(temperature)(z1, z2) of the reference: z1, z2 [B, D] are the head outputs of the two views."""
+def simclr_loss(z1: Tensor, z2: Tensor, temperature: float = 0.1, group=None, force_rect: bool = False) -> Tensor:
+    """SimCLRLoss(temperature)(z1, z2) of the reference: z1, z2 [B, D] are the head outputs of the two views.  ``group``: the negatives
+    span the global batch and the value is the global mean loss (ntxent_fwd); its gradient is then world times the global loss's."""
     _need_cuda(z1, z2)
     if z1.shape != z2.shape or z1.dim() != 2:
         raise ValueError(f"simclr_loss: z1 and z2 must both be [B, D], got {tuple(z1.shape)} and {tuple(z2.shape)}")
-    return NTXentFn.apply(torch.cat([z1, z2], 0), temperature)
+    return NTXentFn.apply(torch.cat([z1, z2], 0), temperature, group, force_rect)
 
 
 # ------------------------------------------------------------------------------------------

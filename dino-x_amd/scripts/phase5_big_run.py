@@ -20,6 +20,7 @@ loop :1686-1997), and the same importable names other reference scripts/tests us
 * ``--loss-type simclr`` (SimCLRLoss, temperature 0.1, on the student head output) runs on the fused NT-Xent kernels
   (dinox.ops.ntxent_fwd / ntxent_bwd): no teacher forward, no Gram / KoLeo, no centre update and no teacher EMA, as in the
   reference; one GPU and the two global views only (with ``--local-crops`` or more than one rank it exits with a message);
+  ``--simclr-negatives global`` runs it data parallel with the negatives of a row taken from every rank's batch;
 * ``--monitor-every N`` (default 1000, 0 = off): every N steps the main rank runs ``dinox.monitor.run_monitor`` on the student
   backbone and the first (at most 32) images of the current batch and writes ``run_dir/monitor/step_XXXXXXXX/`` -- the reference's
   patch-norm heatmap, the CLS attention of the last block per head (which the reference cannot produce), the input slice and
@@ -685,17 +686,30 @@ def build_centering_parser() -> argparse.ArgumentParser:
     return ap
 
 
+def build_simclr_parser() -> argparse.ArgumentParser:
+    """The option of the SimCLR objective, a parser of its own like the MAE and the centring options."""
+    ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    ap.add_argument("--simclr-negatives", choices=["local", "global"], default="local",
+                    help="Where --loss-type simclr takes a row's negatives from: local = this GPU's batch (one GPU only, the reference); "
+                         "global = the batches of every rank under data parallelism (three small all-gathers per step), as one process "
+                         "at the global batch size would have them")
+    return ap
+
+
 def parse_cli(argv=None) -> argparse.Namespace:
-    """The MAE options (build_mae_parser) and the centring options (build_centering_parser) first, everything else through build_parser;
-    one namespace."""
+    """The MAE options (build_mae_parser), the centring options (build_centering_parser) and the SimCLR option (build_simclr_parser)
+    first, everything else through build_parser; one namespace."""
     mae, rest = build_mae_parser().parse_known_args(argv)
     cen, rest = build_centering_parser().parse_known_args(rest)
+    sim, rest = build_simclr_parser().parse_known_args(rest)
     ap = build_parser()
     ap.epilog = ("MAE objective: " + " ".join(build_mae_parser().format_help().split()[1:])
-                 + "  Teacher centring: " + " ".join(build_centering_parser().format_help().split()[1:]))
+                 + "  Teacher centring: " + " ".join(build_centering_parser().format_help().split()[1:])
+                 + "  SimCLR objective: " + " ".join(build_simclr_parser().format_help().split()[1:]))
     args = ap.parse_args(rest)
     args.mae_decoder, args.mae_mask_ratio = mae.mae_decoder, mae.mae_mask_ratio
     args.centering, args.sk_iters = cen.centering, cen.sk_iters
+    args.simclr_negatives = sim.simclr_negatives
     return args
 
 
@@ -741,9 +755,19 @@ def check_loss_type(args, world: int = 1) -> None:
     check_centering(args)
     if args.loss_type == "simclr" and args.local_crops:
         raise SystemExit("--loss-type simclr takes the two global views only: drop --local-crops (multi-crop is a DINO-term extension)")
-    if args.loss_type == "simclr" and world > 1:
-        raise SystemExit(f"--loss-type simclr runs on one GPU only (got {world} ranks): the negatives of a row are the rows of one batch, "
-                         "cross-rank negatives are not implemented")
+    check_simclr_negatives(args)
+    if args.loss_type == "simclr" and world > 1 and getattr(args, "simclr_negatives", "local") != "global":
+        raise SystemExit(f"--loss-type simclr runs on one GPU only (got {world} ranks) with --simclr-negatives local: the negatives of a "
+                         "row are the rows of one batch; --simclr-negatives global takes them from every rank")
+
+
+def check_simclr_negatives(args) -> None:
+    """``--simclr-negatives global`` gathers the negatives of the NT-Xent loss: the other objectives have none."""
+    if getattr(args, "simclr_negatives", "local") == "local":
+        return
+    if args.loss_type != "simclr":
+        raise SystemExit(f"--simclr-negatives {args.simclr_negatives} belongs to --loss-type simclr (--loss-type {args.loss_type} has no "
+                         "negatives to gather): drop it or train with --loss-type simclr")
 
 
 def check_centering(args) -> None:
@@ -759,12 +783,15 @@ def check_centering(args) -> None:
 
 def config_dict(config: TrainingConfig, centring=None) -> dict:
     """What config.json and a checkpoint's "config" entry hold: the dataclass, plus ``centering`` and ``sk_iters`` of ``centring`` (the
-    parsed arguments or the engine's StepHyperParams) whenever either differs from its default -- a default run writes the bytes it
+    parsed arguments or the engine's StepHyperParams) whenever either differs from its default, and ``simclr_negatives`` likewise -- a default run writes the bytes it
     always wrote, and TrainingConfig keeps the reference's fields."""
     d = asdict(config)
     mode, iters = getattr(centring, "centering", "ema"), getattr(centring, "sk_iters", 3)
     if (mode, iters) != ("ema", 3):
         d.update(centering=mode, sk_iters=iters)
+    negatives = getattr(centring, "simclr_negatives", "local")
+    if negatives != "local":
+        d.update(simclr_negatives=negatives)
     return d
 
 
@@ -829,6 +856,8 @@ def _main(argv=None) -> None:
         git_commit=git_commit, data_manifest_hash=data_hash)
     if args.centering == "sinkhorn":
         say(f"centering=sinkhorn sk_iters={args.sk_iters}")
+    if args.simclr_negatives != "local":
+        say(f"simclr_negatives={args.simclr_negatives}")
     say(f"effective_batch_size={cfg.effective_batch_size * world} (batch={args.batch_size} × accum={args.accumulation_steps} × ranks={world})")
     _seed_all(args.train_seed)
     local = local % torch.cuda.device_count()          # (rehearsals may put several gloo ranks on one GPU)
@@ -960,7 +989,7 @@ def _main(argv=None) -> None:
                          weight_decay=args.weight_decay, ema=args.ema, teacher_temp=args.teacher_temp, student_temp=args.student_temp,
                          center_momentum=args.center_momentum, gram_weight=args.gram_weight,
                          koleo_weight=args.koleo_weight, loss_type=args.loss_type, mae_mask_ratio=args.mae_mask_ratio,
-                         centering=args.centering, sk_iters=args.sk_iters)
+                         centering=args.centering, sk_iters=args.sk_iters, simclr_negatives=args.simclr_negatives)
     if args.hip_graph and (world > 1 or args.accumulation_steps != 1 or args.local_crops):
         raise SystemExit("--hip-graph: single GPU, --accumulation-steps 1 and no --local-crops (the captured step has one fixed batch layout)")
     if device.type == "cuda" and not args.hip_graph and args.streams != "off":

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define DINOX_ABI_VERSION 3   /* 3: + dinox_block_forward / _backward, dinox_gemm_timer_*, dinox_retrieval_* (later also dinox_retrieval_rank_windowed*, dinox_row_dots), dinox_knn_*, dinox_gram_*, dinox_softmax_probe*, dinox_ntxent_*, dinox_normalize_bwd, dinox_mae_*, dinox_attention_rows*, dinox_attention_rollout_step* (all additive: no entry
+#define DINOX_ABI_VERSION 3   /* 3: + dinox_block_forward / _backward, dinox_gemm_timer_*, dinox_retrieval_* (later also dinox_retrieval_rank_windowed*, dinox_row_dots), dinox_knn_*, dinox_gram_*, dinox_softmax_probe*, dinox_ntxent_* (later also dinox_ntxent_*_rect), dinox_normalize_bwd, dinox_mae_*, dinox_attention_rows*, dinox_attention_rollout_step* (all additive: no entry
                                * of an earlier library changed, so the number callers test, dinox_version() == 3, stays; probe the symbol
                                * to learn whether a given build has the later additions) */
 
@@ -384,6 +384,21 @@ int dinox_ntxent_rows(const float* S, int64_t lds, int M, float inv_tau, float* 
 int dinox_ntxent_coeff(const float* S, int64_t lds, const float* lse, int M, float inv_tau, float gscale, float* W, int64_t ldw,
                        void* stream);
 int dinox_normalize_bwd(const float* dxh, const float* xh, const float* norm, float* dx, int64_t V, int D, float eps, void* stream);
+/* Rectangular forms for data parallelism: a rank holds Ml = 2 Bl local rows [z1_local; z2_local]; S [Ml][Mg] is their product with the
+ * Mg = world * Ml gathered rows (all_gather_into_tensor order: rank r's block starts at row0 = r * Ml).  For local row i the excluded
+ * column is dg(i) = row0 + i and the positive is p(i) = row0 + (i + Bl) mod Ml; world = 1, row0 = 0 are the square rules.
+ *   rows_rect:  lse[i] = logsumexp_{j != dg(i)} S[i][j] * inv_tau;  row_loss[i] = lse[i] - S[i][p(i)] * inv_tau;
+ *               loss_sum[0] = sum_i row_loss[i], added in index order and NOT divided (the caller adds the ranks' sums and divides by Mg).
+ *   coeff_rect: W[i][j] = gscale * inv_tau / Ml * (exp(S_ij inv_tau - lse_local[i]) + exp(S_ij inv_tau - lse_all[j]) - 2 [j = p(i)]),
+ *               W[i][dg(i)] = 0.  The second term is P_ji with S_ij standing in for S_ji (which another rank holds; the product is
+ *               symmetric up to rounding) and lse_all [Mg] the gathered lse.  W Z^_all is Mg / Ml = world times the gradient of the
+ *               global mean loss with respect to the local Z^: the factor the sum over ranks and AdamW's 1 / world take out again.
+ * DINOX_EINVAL before any launch: Ml odd or < 2, Bl * 2 != Ml, Mg not a multiple of Ml, row0 not a multiple of Ml or outside
+ * [0, Mg - Ml], lds < Mg, ldw < Mg, inv_tau <= 0, a null pointer. */
+int dinox_ntxent_rows_rect(const float* S, int64_t lds, int Ml, int Mg, int row0, int Bl, float inv_tau, float* lse, float* row_loss,
+                           float* loss_sum, void* stream);
+int dinox_ntxent_coeff_rect(const float* S, int64_t lds, const float* lse_local, const float* lse_all, int Ml, int Mg, int row0, int Bl,
+                            float inv_tau, float gscale, float* W, int64_t ldw, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * MAE masked-token glue -- replaces MaeModel.random_masking / forward / patchify / forward_loss and the un-shuffle of
