@@ -256,3 +256,63 @@ extern "C" int dinox_mae_loss_bwd(const void* pred, const float* x, const int* i
   DX_REQUIRE(dpred != pred, DINOX_EINVAL, "mae_loss_bwd: dpred must not alias pred");
   return dinox::launch_mae_loss_bwd(pred, x, ids_restore, dpred, gscale, V, H, W, patch, Lk, lead, pred_dtype, dpred_dtype, dinox::as_stream(stream));
 }
+
+// ---------------------------------------------------------------- iBOT masked-patch objective (kernels: ibot.hip)
+// M masked rows out of `rows` (flat int32 positions), D features.
+static bool ibot_rows_ok(int64_t M, int64_t rows, int D) {
+  return M >= 1 && M <= 0x7fffffff && rows >= 1 && rows <= 0x7fffffff && D >= 1 && D <= (1 << 16);
+}
+
+extern "C" int dinox_ibot_put_mask(void* patches, const float* mask_token, const int* idx, int M, int64_t rows, int D, int dtype, void* stream) {
+  DX_REQUIRE(patches && mask_token && idx, DINOX_EINVAL, "ibot_put_mask: null pointer");
+  DX_REQUIRE(mae_dtype_ok(dtype), DINOX_EINVAL, "ibot_put_mask: dtype %d", dtype);
+  DX_REQUIRE(ibot_rows_ok(M, rows, D), DINOX_EINVAL, "ibot_put_mask: M=%d rows=%lld D=%d (M, rows >= 1; 1 <= D <= 65536)", M, (long long)rows, D);
+  return dinox::launch_ibot_put_mask(patches, mask_token, idx, M, rows, D, dtype, dinox::as_stream(stream));
+}
+
+extern "C" int dinox_ibot_put_mask_bwd(void* dpatches, const int* idx, float* dmask_token, float* ws, int M, int64_t rows, int D, int dtype,
+                                       void* stream) {
+  DX_REQUIRE(dpatches && idx && dmask_token && ws, DINOX_EINVAL, "ibot_put_mask_bwd: null pointer");
+  DX_REQUIRE(mae_dtype_ok(dtype), DINOX_EINVAL, "ibot_put_mask_bwd: dtype %d", dtype);
+  DX_REQUIRE(ibot_rows_ok(M, rows, D) && M <= 65535 * dinox::IBOT_MASK_CHUNK, DINOX_EINVAL,
+             "ibot_put_mask_bwd: M=%d rows=%lld D=%d (1 <= M <= %d; rows >= 1; 1 <= D <= 65536)", M, (long long)rows, D,
+             65535 * dinox::IBOT_MASK_CHUNK);
+  return dinox::launch_ibot_put_mask_bwd(dpatches, idx, dmask_token, ws, M, rows, D, dtype, dinox::as_stream(stream));
+}
+
+extern "C" int dinox_gather_rows(const float* src, const int* row, void* dst, int64_t M, int64_t src_rows, int D, int64_t dst_row0, int dst_dtype,
+                                 void* stream) {
+  DX_REQUIRE(src && row && dst, DINOX_EINVAL, "gather_rows: null pointer");
+  DX_REQUIRE(mae_dtype_ok(dst_dtype), DINOX_EINVAL, "gather_rows: dtype %d", dst_dtype);
+  DX_REQUIRE(ibot_rows_ok(M, src_rows, D) && dst_row0 >= 0, DINOX_EINVAL, "gather_rows: M=%lld src_rows=%lld D=%d dst_row0=%lld", (long long)M,
+             (long long)src_rows, D, (long long)dst_row0);
+  return dinox::launch_gather_rows(src, row, dst, M, src_rows, D, dst_row0, dst_dtype, dinox::as_stream(stream));
+}
+
+extern "C" int dinox_scatter_add_rows(const void* src, const int* row, float* dst, int64_t M, int64_t dst_rows, int D, int64_t src_row0,
+                                      int src_dtype, void* stream) {
+  DX_REQUIRE(src && row && dst, DINOX_EINVAL, "scatter_add_rows: null pointer");
+  DX_REQUIRE(mae_dtype_ok(src_dtype), DINOX_EINVAL, "scatter_add_rows: dtype %d", src_dtype);
+  DX_REQUIRE(ibot_rows_ok(M, dst_rows, D) && src_row0 >= 0, DINOX_EINVAL, "scatter_add_rows: M=%lld dst_rows=%lld D=%d src_row0=%lld", (long long)M,
+             (long long)dst_rows, D, (long long)src_row0);
+  return dinox::launch_scatter_add_rows(src, row, dst, M, dst_rows, D, src_row0, src_dtype, dinox::as_stream(stream));
+}
+
+extern "C" int dinox_ibot_ce(const float* s, const float* t, const float* center, const float* w, float student_temp, float teacher_temp,
+                             float scale, float grad_scale, float* loss, float* ds, float* row_loss, int M, int K, void* stream) {
+  DX_REQUIRE(s && t && center && w && loss && row_loss, DINOX_EINVAL, "ibot_ce: null pointer");
+  DX_REQUIRE(M >= 1 && K >= 1, DINOX_EINVAL, "ibot_ce: M=%d K=%d", M, K);
+  DX_REQUIRE(student_temp > 0.f && teacher_temp > 0.f, DINOX_EINVAL, "ibot_ce: temperatures must be > 0");
+  if (ds) {
+    const size_t n = (size_t)M * (size_t)K;
+    const float* de = ds + n;
+    DX_REQUIRE((de <= s || s + n <= ds) && (de <= t || t + n <= ds), DINOX_EINVAL, "ibot_ce: ds must not alias s or t");
+  }
+  return dinox::launch_ibot_ce(s, t, center, w, 1.0f / student_temp, 1.0f / teacher_temp, scale, grad_scale * scale, loss, ds, row_loss, M, K,
+                               dinox::as_stream(stream));
+}
+
+extern "C" int dinox_ibot_center_ema(float* center, const float* sum_count, float momentum, int K, void* stream) {
+  DX_REQUIRE(center && sum_count && K >= 1, DINOX_EINVAL, "ibot_center_ema: bad arguments");
+  return dinox::launch_ibot_center_ema(center, sum_count, momentum, K, dinox::as_stream(stream));
+}

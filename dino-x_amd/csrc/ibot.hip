@@ -1,0 +1,282 @@
+// ibot.hip -- the masked-patch (iBOT / DINOv2) objective's kernels.  An extension: the reference trains with the image-level DINO term only.
+//     put_mask          patches[idx[m]][:] = mask_token, in place on the patch product's output (the student sees a learned token there)
+//     put_mask_bwd      dmask_token = sum_m dpatches[idx[m]][:], then those rows of dpatches = 0 (no gradient into the patch product)
+//     gather_rows       dst[dst_row0 + m] = src[row[m]]: the masked patch tokens of the final features, appended to the head's CLS operand
+//     scatter_add_rows  dst[row[m]] += src[src_row0 + m]: the head's input gradient back into the feature gradient (rows distinct)
+//     ibot_center_ema   the patch centre's EMA from (column sums, row count) -- what the ranks add up under data parallelism
+//     ibot_ce           centring / sharpening cross-entropy of M unpaired rows with per-row weights, loss and d loss / d logits
+// fp32 math.  No float atomics: every sum has a fixed order (stated at each kernel), so a step is bit-reproducible.  Every index read from
+// device memory is range-checked before it becomes an address; an entry outside is skipped.
+#include "common.h"
+#include "kernels.h"
+
+namespace dinox {
+
+constexpr int IB_THREADS = 256;
+
+static unsigned ib_grid(int64_t total) {
+  const int64_t b = ceil_div(total, IB_THREADS);
+  return (unsigned)(b < 1 ? 1 : (b < 4096 ? b : 4096));
+}
+
+// ---------------------------------------------------------------- mask token in / out of the patch rows
+template <int DT>
+__global__ __launch_bounds__(IB_THREADS) void ibot_put_mask_kernel(void* __restrict__ patches, const float* __restrict__ mask_token,
+                                                                   const int* __restrict__ idx, int M, int64_t rows, int D) {
+  const int64_t total = (int64_t)M * D;
+  for (int64_t i = (int64_t)blockIdx.x * IB_THREADS + threadIdx.x; i < total; i += (int64_t)gridDim.x * IB_THREADS) {
+    const int64_t m = i / D;
+    const int d = (int)(i - m * D);
+    const int64_t r = idx[m];
+    if (r < 0 || r >= rows) continue;
+    elem<DT>::st(patches, r * D + d, mask_token[d]);
+  }
+}
+
+// ws[c][d] = sum of dpatches[idx[m]][d] over the m of chunk c = [c CH, min(M, (c + 1) CH)), ascending m: one thread per (chunk, feature).
+template <int DT>
+__global__ __launch_bounds__(IB_THREADS) void ibot_mask_partial_kernel(const void* __restrict__ dpatches, const int* __restrict__ idx,
+                                                                       float* __restrict__ ws, int M, int64_t rows, int D) {
+  const int d = blockIdx.x * IB_THREADS + threadIdx.x, c = blockIdx.y;
+  if (d >= D) return;
+  const int m0 = c * IBOT_MASK_CHUNK, m1 = min(M, m0 + IBOT_MASK_CHUNK);
+  float acc = 0.f;
+  for (int m = m0; m < m1; ++m) {
+    const int64_t r = idx[m];
+    if (r < 0 || r >= rows) continue;
+    acc += elem<DT>::ld(dpatches, r * D + d);
+  }
+  ws[(int64_t)c * D + d] = acc;
+}
+
+// One launch, two roles, both after every partial was read.  The first `sum_blocks` workgroups: dmask[d] = sum_c ws[c][d], ascending c
+// (a chain of ceil(M / CH) fp32 adds on top of the chunk's CH).  The remaining workgroups set the masked rows of dpatches to 0.
+template <int DT>
+__global__ __launch_bounds__(IB_THREADS) void ibot_mask_combine_kernel(void* __restrict__ dpatches, const int* __restrict__ idx,
+                                                                       const float* __restrict__ ws, float* __restrict__ dmask, int M,
+                                                                       int64_t rows, int D, int chunks, int sum_blocks) {
+  if ((int)blockIdx.x < sum_blocks) {
+    const int d = blockIdx.x * IB_THREADS + threadIdx.x;
+    if (d >= D) return;
+    float acc = 0.f;
+    for (int c = 0; c < chunks; ++c) acc += ws[(int64_t)c * D + d];
+    dmask[d] = acc;
+    return;
+  }
+  const int64_t total = (int64_t)M * D, nb = gridDim.x - sum_blocks;
+  for (int64_t i = (int64_t)(blockIdx.x - sum_blocks) * IB_THREADS + threadIdx.x; i < total; i += nb * IB_THREADS) {
+    const int64_t m = i / D;
+    const int d = (int)(i - m * D);
+    const int64_t r = idx[m];
+    if (r < 0 || r >= rows) continue;
+    elem<DT>::st(dpatches, r * D + d, 0.f);
+  }
+}
+
+// ---------------------------------------------------------------- indexed row gather / scatter-add
+template <int DT>
+__global__ __launch_bounds__(IB_THREADS) void gather_rows_kernel(const float* __restrict__ src, const int* __restrict__ row, void* __restrict__ dst,
+                                                                 int64_t M, int64_t src_rows, int D, int64_t dst_row0) {
+  const int64_t total = M * D;
+  for (int64_t i = (int64_t)blockIdx.x * IB_THREADS + threadIdx.x; i < total; i += (int64_t)gridDim.x * IB_THREADS) {
+    const int64_t m = i / D;
+    const int d = (int)(i - m * D);
+    const int64_t r = row[m];
+    if (r < 0 || r >= src_rows) continue;
+    elem<DT>::st(dst, (dst_row0 + m) * D + d, src[r * D + d]);
+  }
+}
+
+// dst[row[m]][d] += src[src_row0 + m][d]: one fp32 add per element; the rows are distinct by contract, so no two threads meet.
+template <int DT>
+__global__ __launch_bounds__(IB_THREADS) void scatter_add_rows_kernel(const void* __restrict__ src, const int* __restrict__ row,
+                                                                      float* __restrict__ dst, int64_t M, int64_t dst_rows, int D,
+                                                                      int64_t src_row0) {
+  const int64_t total = M * D;
+  for (int64_t i = (int64_t)blockIdx.x * IB_THREADS + threadIdx.x; i < total; i += (int64_t)gridDim.x * IB_THREADS) {
+    const int64_t m = i / D;
+    const int d = (int)(i - m * D);
+    const int64_t r = row[m];
+    if (r < 0 || r >= dst_rows) continue;
+    dst[r * D + d] += elem<DT>::ld(src, (src_row0 + m) * D + d);
+  }
+}
+
+// ---------------------------------------------------------------- cross-entropy of M unpaired rows
+// One workgroup per row m, log-sum-exp form throughout as dino_ce_kernel (loss.hip), with the same operations per element:
+//     zs = s / ts - max,   p_t = exp((t - c) / tt - max) / sum,   row_loss = -sum_k p_t (zs - log sum exp zs),
+//     ds = g_m (exp(zs) / sum - p_t) / ts,   g_m = gscale * w[m]  (one rounded multiply).
+// Register-resident form: thread i holds float4 groups i, i + 256, ... of the row (NV of them per matrix: K <= 1024 NV), each loaded ONCE
+// and already scaled; the max, the sum and the output pass read registers, so s, t and ds cross the memory bus once each.  At K = 8192
+// that is 64 VGPRs of row data per lane (128 allocated, no scratch: 4 waves per SIMD, i.e. 4 rows in flight per CU; 256 threads keep the
+// block reductions at four waves).  A group past the row's end holds -inf and is left out of the output pass.
+template <int NV>
+__global__ __launch_bounds__(IB_THREADS) void ibot_ce_reg_kernel(const float* __restrict__ s, const float* __restrict__ t,
+                                                                 const float* __restrict__ center, const float* __restrict__ w, float inv_ts,
+                                                                 float inv_tt, float gscale, float* __restrict__ ds,
+                                                                 float* __restrict__ row_loss, int K4) {
+  __shared__ float red[16];
+  const int64_t base = (int64_t)blockIdx.x * K4;
+  const float4* sr = reinterpret_cast<const float4*>(s) + base;
+  const float4* tr = reinterpret_cast<const float4*>(t) + base;
+  const float4* cr = reinterpret_cast<const float4*>(center);
+  float4 zs[NV], zt[NV];
+  float ms = -INFINITY, mt = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const int k = threadIdx.x + j * IB_THREADS;
+    if (k < K4) {
+      const float4 a = sr[k], b = tr[k], c = cr[k];
+      zs[j] = make_float4(a.x * inv_ts, a.y * inv_ts, a.z * inv_ts, a.w * inv_ts);
+      zt[j] = make_float4((b.x - c.x) * inv_tt, (b.y - c.y) * inv_tt, (b.z - c.z) * inv_tt, (b.w - c.w) * inv_tt);
+    } else {
+      zs[j] = zt[j] = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+    }
+    ms = fmaxf(fmaxf(ms, fmaxf(zs[j].x, zs[j].y)), fmaxf(zs[j].z, zs[j].w));
+    mt = fmaxf(fmaxf(mt, fmaxf(zt[j].x, zt[j].y)), fmaxf(zt[j].z, zt[j].w));
+  }
+  ms = block_max(ms, red);
+  mt = block_max(mt, red);
+  float ss = 0.f, st = 0.f;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {      // (zs becomes the shifted logit, zt the unnormalised target: exp(-inf) is an exact 0)
+    zs[j] = make_float4(zs[j].x - ms, zs[j].y - ms, zs[j].z - ms, zs[j].w - ms);
+    zt[j] = make_float4(expf(zt[j].x - mt), expf(zt[j].y - mt), expf(zt[j].z - mt), expf(zt[j].w - mt));
+    ss += expf(zs[j].x); ss += expf(zs[j].y); ss += expf(zs[j].z); ss += expf(zs[j].w);
+    st += zt[j].x; st += zt[j].y; st += zt[j].z; st += zt[j].w;
+  }
+  ss = block_sum(ss, red);
+  st = block_sum(st, red);
+  const float log_ss = logf(ss), inv_ss = 1.0f / ss, inv_st = 1.0f / st;
+  const float g = gscale * w[blockIdx.x];
+  float4* dr = ds ? reinterpret_cast<float4*>(ds) + base : nullptr;
+  float acc = 0.f;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const int k = threadIdx.x + j * IB_THREADS;
+    if (k >= K4) continue;
+    const float4 tp = make_float4(zt[j].x * inv_st, zt[j].y * inv_st, zt[j].z * inv_st, zt[j].w * inv_st);
+    acc -= tp.x * (zs[j].x - log_ss); acc -= tp.y * (zs[j].y - log_ss); acc -= tp.z * (zs[j].z - log_ss); acc -= tp.w * (zs[j].w - log_ss);
+    if (dr)
+      store_stream(dr + k, make_float4(g * (expf(zs[j].x) * inv_ss - tp.x) * inv_ts, g * (expf(zs[j].y) * inv_ss - tp.y) * inv_ts,
+                                       g * (expf(zs[j].z) * inv_ss - tp.z) * inv_ts, g * (expf(zs[j].w) * inv_ss - tp.w) * inv_ts));
+  }
+  acc = block_sum(acc, red);
+  if (threadIdx.x == 0) row_loss[blockIdx.x] = acc;
+}
+
+// Any K and alignment: three passes over the row (the re-reads come from L2).
+__global__ __launch_bounds__(IB_THREADS) void ibot_ce_scalar_kernel(const float* __restrict__ s, const float* __restrict__ t,
+                                                                    const float* __restrict__ center, const float* __restrict__ w, float inv_ts,
+                                                                    float inv_tt, float gscale, float* __restrict__ ds,
+                                                                    float* __restrict__ row_loss, int K) {
+  __shared__ float red[16];
+  const int64_t base = (int64_t)blockIdx.x * K;
+  const float* sr = s + base;
+  const float* tr = t + base;
+  float ms = -INFINITY, mt = -INFINITY;
+  for (int k = threadIdx.x; k < K; k += IB_THREADS) {
+    ms = fmaxf(ms, sr[k] * inv_ts);
+    mt = fmaxf(mt, (tr[k] - center[k]) * inv_tt);
+  }
+  ms = block_max(ms, red);
+  mt = block_max(mt, red);
+  float ss = 0.f, st = 0.f;
+  for (int k = threadIdx.x; k < K; k += IB_THREADS) {
+    ss += expf(sr[k] * inv_ts - ms);
+    st += expf((tr[k] - center[k]) * inv_tt - mt);
+  }
+  ss = block_sum(ss, red);
+  st = block_sum(st, red);
+  const float log_ss = logf(ss), inv_ss = 1.0f / ss, inv_st = 1.0f / st;
+  const float g = gscale * w[blockIdx.x];
+  float acc = 0.f;
+  for (int k = threadIdx.x; k < K; k += IB_THREADS) {
+    const float zs = sr[k] * inv_ts - ms;
+    const float tp = expf((tr[k] - center[k]) * inv_tt - mt) * inv_st;
+    acc -= tp * (zs - log_ss);
+    if (ds) ds[base + k] = g * (expf(zs) * inv_ss - tp) * inv_ts;
+  }
+  acc = block_sum(acc, red);
+  if (threadIdx.x == 0) row_loss[blockIdx.x] = acc;
+}
+
+// loss[0] = scale * sum_m w[m] row_loss[m]: thread i adds rows i, i + 256, ... in ascending order, then block_sum (a fixed order).
+__global__ __launch_bounds__(IB_THREADS) void ibot_weighted_sum_kernel(const float* __restrict__ row_loss, const float* __restrict__ w, int M,
+                                                                       float scale, float* __restrict__ loss) {
+  __shared__ float red[16];
+  float a = 0.f;
+  for (int m = threadIdx.x; m < M; m += IB_THREADS) a += w[m] * row_loss[m];
+  a = block_sum(a, red);
+  if (threadIdx.x == 0) loss[0] = a * scale;
+}
+
+// center[k] = center[k] mom + (sum_count[k] / sum_count[K]) (1 - mom): the mean of the masked teacher rows from their column sums and
+// their number (element K, a whole number held in fp32), both possibly summed over ranks.  A count below 1 leaves the centre untouched.
+__global__ __launch_bounds__(IB_THREADS) void ibot_center_ema_kernel(float* __restrict__ c, const float* __restrict__ sum_count, float mom, int K) {
+  const int k = blockIdx.x * IB_THREADS + threadIdx.x;
+  const float n = sum_count[K];
+  if (k < K && n >= 1.0f) c[k] = c[k] * mom + (sum_count[k] / n) * (1.0f - mom);
+}
+
+// ---------------------------------------------------------------- launchers (arguments were validated by the entry points in abi.hip)
+#define IB_LAUNCH_DT(kern, dtype, grid, st, ...)                                                                  \
+  do {                                                                                                            \
+    if ((dtype) == DINOX_F32) hipLaunchKernelGGL((kern<DINOX_F32>), grid, dim3(IB_THREADS), 0, st, __VA_ARGS__);  \
+    else hipLaunchKernelGGL((kern<DINOX_BF16>), grid, dim3(IB_THREADS), 0, st, __VA_ARGS__);                      \
+  } while (0)
+
+int launch_ibot_put_mask(void* patches, const float* mask_token, const int* idx, int M, int64_t rows, int D, int dtype, hipStream_t st) {
+  IB_LAUNCH_DT(ibot_put_mask_kernel, dtype, dim3(ib_grid((int64_t)M * D)), st, patches, mask_token, idx, M, rows, D);
+  return check_launch("ibot_put_mask");
+}
+
+int launch_ibot_put_mask_bwd(void* dpatches, const int* idx, float* dmask, float* ws, int M, int64_t rows, int D, int dtype, hipStream_t st) {
+  const int chunks = (int)ceil_div(M, IBOT_MASK_CHUNK), col_blocks = (int)ceil_div(D, IB_THREADS);
+  IB_LAUNCH_DT(ibot_mask_partial_kernel, dtype, dim3((unsigned)col_blocks, (unsigned)chunks), st, dpatches, idx, ws, M, rows, D);
+  int rc = check_launch("ibot_put_mask_bwd");
+  if (rc) return rc;
+  const dim3 grid((unsigned)col_blocks + ib_grid((int64_t)M * D));
+  IB_LAUNCH_DT(ibot_mask_combine_kernel, dtype, grid, st, dpatches, idx, ws, dmask, M, rows, D, chunks, col_blocks);
+  return check_launch("ibot_put_mask_bwd_combine");
+}
+
+int launch_gather_rows(const float* src, const int* row, void* dst, int64_t M, int64_t src_rows, int D, int64_t dst_row0, int dtype,
+                       hipStream_t st) {
+  IB_LAUNCH_DT(gather_rows_kernel, dtype, dim3(ib_grid(M * D)), st, src, row, dst, M, src_rows, D, dst_row0);
+  return check_launch("gather_rows");
+}
+
+int launch_scatter_add_rows(const void* src, const int* row, float* dst, int64_t M, int64_t dst_rows, int D, int64_t src_row0, int dtype,
+                            hipStream_t st) {
+  IB_LAUNCH_DT(scatter_add_rows_kernel, dtype, dim3(ib_grid(M * D)), st, src, row, dst, M, dst_rows, D, src_row0);
+  return check_launch("scatter_add_rows");
+}
+
+int launch_ibot_ce(const float* s, const float* t, const float* center, const float* w, float inv_ts, float inv_tt, float scale, float gscale,
+                   float* loss, float* ds, float* row_loss, int M, int K, hipStream_t st) {
+  const bool reg = K % 4 == 0 && K <= IBOT_CE_REG_MAX_K && (((uintptr_t)s | (uintptr_t)t | (uintptr_t)center | (uintptr_t)ds) & 15) == 0;
+  const dim3 grid((unsigned)M), block(IB_THREADS);
+  if (reg) {
+    const int K4 = K / 4, nv = (int)ceil_div(K4, IB_THREADS);
+#define IB_CE(NV) hipLaunchKernelGGL((ibot_ce_reg_kernel<NV>), grid, block, 0, st, s, t, center, w, inv_ts, inv_tt, gscale, ds, row_loss, K4)
+    if (nv <= 1) IB_CE(1);
+    else if (nv <= 2) IB_CE(2);
+    else if (nv <= 4) IB_CE(4);
+    else IB_CE(8);
+#undef IB_CE
+  } else {
+    hipLaunchKernelGGL(ibot_ce_scalar_kernel, grid, block, 0, st, s, t, center, w, inv_ts, inv_tt, gscale, ds, row_loss, K);
+  }
+  int rc = check_launch("ibot_ce");
+  if (rc) return rc;
+  hipLaunchKernelGGL(ibot_weighted_sum_kernel, dim3(1), block, 0, st, row_loss, w, M, scale, loss);
+  return check_launch("ibot_ce_sum");
+}
+
+int launch_ibot_center_ema(float* center, const float* sum_count, float momentum, int K, hipStream_t st) {
+  hipLaunchKernelGGL(ibot_center_ema_kernel, dim3((unsigned)ceil_div(K, IB_THREADS)), dim3(IB_THREADS), 0, st, center, sum_count, momentum, K);
+  return check_launch("ibot_center_ema");
+}
+
+}  // namespace dinox

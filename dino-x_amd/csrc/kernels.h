@@ -110,6 +110,19 @@ int launch_mae_loss_fwd(const void* pred, const float* x, const int* ids_restore
 int launch_mae_loss_bwd(const void* pred, const float* x, const int* ids_restore, void* dpred, float gscale, int V, int H, int W, int patch,
                         int Lk, int lead, int dtype, int out_dtype, hipStream_t st);
 
+// ---------------------------------------------------------------- iBOT masked-patch objective (ibot.hip; entry points and argument checks: abi.hip)
+constexpr int IBOT_MASK_CHUNK = 64;        // masked rows per partial sum of put_mask_bwd: ws holds ceil(M / 64) x D floats
+constexpr int IBOT_CE_REG_MAX_K = 8192;    // widest row the register-resident cross-entropy holds: 8 float4 per thread and matrix
+int launch_ibot_put_mask(void* patches, const float* mask_token, const int* idx, int M, int64_t rows, int D, int dtype, hipStream_t st);
+int launch_ibot_put_mask_bwd(void* dpatches, const int* idx, float* dmask, float* ws, int M, int64_t rows, int D, int dtype, hipStream_t st);
+int launch_gather_rows(const float* src, const int* row, void* dst, int64_t M, int64_t src_rows, int D, int64_t dst_row0, int dtype,
+                       hipStream_t st);
+int launch_scatter_add_rows(const void* src, const int* row, float* dst, int64_t M, int64_t dst_rows, int D, int64_t src_row0, int dtype,
+                            hipStream_t st);
+int launch_ibot_ce(const float* s, const float* t, const float* center, const float* w, float inv_ts, float inv_tt, float scale, float gscale,
+                   float* loss, float* ds, float* row_loss, int M, int K, hipStream_t st);
+int launch_ibot_center_ema(float* center, const float* sum_count, float momentum, int K, hipStream_t st);
+
 // ---------------------------------------------------------------- launch glue shared by the NT launchers
 // Activation index of the <OUT, ACT, RES> kernels (gemm_bf16_pp / _pp128 / _areg): the template argument ACT.
 enum { EPI_ACT_PLAIN = 0, EPI_ACT_GELU = 1, EPI_ACT_DGELU = 2 };

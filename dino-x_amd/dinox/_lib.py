@@ -132,6 +132,12 @@ SIGNATURES = {
     "dinox_mae_unshuffle_bwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "dinox_mae_loss_fwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "dinox_mae_loss_bwd": (i32, [vp, vp, vp, vp, f32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "dinox_ibot_put_mask": (i32, [vp, vp, vp, i32, i64, i32, i32, vp]),
+    "dinox_ibot_put_mask_bwd": (i32, [vp, vp, vp, vp, i32, i64, i32, i32, vp]),
+    "dinox_gather_rows": (i32, [vp, vp, vp, i64, i64, i32, i64, i32, vp]),
+    "dinox_scatter_add_rows": (i32, [vp, vp, vp, i64, i64, i32, i64, i32, vp]),
+    "dinox_ibot_ce": (i32, [vp, vp, vp, vp, f32, f32, f32, f32, vp, vp, vp, i32, i32, vp]),
+    "dinox_ibot_center_ema": (i32, [vp, vp, f32, i32, vp]),
     "dinox_attention_rows_ok": (i32, [i32, i32, i32, i32, i32]),
     "dinox_attention_rows": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "dinox_attention_rollout_step_ok": (i32, [i32, i32, i32, i32]),

@@ -23,6 +23,11 @@ form the TAIL of the arena and the optimiser pass runs over the prefix only, so 
 ``.grad is None``).  The logged grad-norm is the reference's: over the ENCODER's gradients (its loop walks ``student.parameters()``,
 and the MAE decoder is not part of ``student``, :1785).  Single rank, eager launches, fp32 image batches only.
 
+``ibot_weight > 0`` (extension, dino only; iBOT / DINOv2): ``step(..., patch_mask=)`` names the patches of the global views that the student
+sees as ``backbone.mask_token``; their final-norm tokens, student and teacher, go through the same heads as the CLS rows (appended to the
+same operands) and ``ops.ibot_ce`` scores them against a patch centre of their own (``ibot_center``).  With the weight 0 -- or nothing
+masked on a step -- the step is launch for launch the one above.
+
 What is different from the reference, by design:
   * parameters, gradients, Adam moments and teacher weights live in flat fp32 arenas, so the grad-norm,
     AdamW and EMA are ONE kernel pass (dinox_adamw_ema) instead of 161 x (.item() + 2 EMA launches); the dW products
@@ -71,6 +76,7 @@ class StepHyperParams:
     centering: str = "ema"           # "ema" (the reference's centre) | "sinkhorn" (DINOv2/v3 Sinkhorn-Knopp targets; extension, dino only)
     sk_iters: int = 3                # Sinkhorn-Knopp iterations (DINOv2: 3)
     simclr_negatives: str = "local"  # "local" (one rank's batch; single rank only) | "global" (the rows of every rank: extension, simclr only)
+    ibot_weight: float = 0.0         # weight of the iBOT masked-patch term (extension, dino only; 0: the step is exactly the one without it)
 
 
 def flatten_parameters(module: torch.nn.Module, align: int = 8, order: Optional[List[torch.nn.Parameter]] = None
@@ -133,12 +139,29 @@ class TrainEngine:
             raise ValueError(f"simclr_negatives must be 'local' or 'global', got {hp.simclr_negatives!r}")
         if hp.simclr_negatives == "global" and hp.loss_type != "simclr":
             raise ValueError(f"simclr_negatives='global' belongs to loss_type='simclr'; loss_type={hp.loss_type!r} has no negatives")
+        if hp.ibot_weight < 0.0:
+            raise ValueError(f"ibot_weight must be >= 0, got {hp.ibot_weight}")
+        self.ibot = hp.ibot_weight > 0.0
+        if self.ibot and hp.loss_type != "dino":
+            raise ValueError(f"ibot_weight > 0 adds the masked-patch term to loss_type='dino' (it shares the DINO head and teacher); "
+                             f"loss_type={hp.loss_type!r} has neither")
+        if self.ibot and use_graph:
+            raise ValueError("ibot_weight > 0 does not run under use_graph: the number of masked patches changes from step to step and a "
+                             "captured step has one fixed layout")
         if hp.loss_type == "mae":
             self._mae_arena(student, teacher, use_graph)
         else:
             self._two_net_arenas(student, teacher, process_group, bucket_bytes)
         dev = self.flat_p.device
         self.center = torch.zeros(1, out_dim, dtype=torch.float32, device=dev)      # (mae never reads it; a checkpoint's "dino_loss" entry holds it)
+        if self.ibot:
+            if not self.manual_top:
+                raise ValueError("ibot_weight > 0 needs the stock DINO head (Linear -> GELU -> Linear with biases): the masked rows join the "
+                                 "CLS rows in the hand-written top of the step, which a replaced head does not take")
+            if any(getattr(m.backbone, "mask_token", None) is None for m in (student, teacher)):
+                raise ValueError("ibot_weight > 0 needs backbones built with mask_token=True (student and teacher share one arena layout)")
+            self.ibot_center = torch.zeros(1, out_dim, dtype=torch.float32, device=dev)     # the patch centre: apart from the CLS centre
+        self._ibot_pending = None        # (column sums + count of this step's masked teacher rows, their all-reduce): awaited in _finish
         self.use_graph = bool(use_graph)
         if self.use_graph and (self.accum != 1 or exchanging(process_group)):
             raise ValueError("use_graph: single rank and accumulation_steps == 1 only")
@@ -245,7 +268,7 @@ class TrainEngine:
 
     # -- one optimiser step ---------------------------------------------------------------------
     def step(self, batch: torch.Tensor, spacing2b: Optional[torch.Tensor] = None, local_batch: Optional[torch.Tensor] = None,
-             local_spacing: Optional[torch.Tensor] = None, mask_noise: Optional[torch.Tensor] = None) -> dict:
+             local_spacing: Optional[torch.Tensor] = None, mask_noise: Optional[torch.Tensor] = None, patch_mask=None) -> dict:
         """batch: (2B,3,H,W) = [view1; view2] on the device; spacing2b: (2B,3) or None.
         local_batch (L*B,3,s,s), view-major, with local_spacing (L*B,3): the multi-crop extension (not in the reference, dino only) --
         the student also sees L smaller crops per sample, which enter the DINO term only (every (teacher view, other student
@@ -253,6 +276,9 @@ class TrainEngine:
         ``loss_type="mae"``: batch (V,3,H,W) fp32 -- every view is one sample, as in the reference (:1725); spacing is ignored there and
         here.  ``mask_noise`` ([V, L] fp32, mae only): the noise whose per-sample order decides which patches are kept; None draws it
         from torch's global device generator.
+        ``patch_mask`` (``ibot_weight > 0`` only): (idx, w, tok) of ``dinox.ibot`` on the device, or a ``dinox.ibot.PatchMask`` -- the masked
+        patches of the global views (flat positions v * P + i, int32, distinct and ascending), their loss weights 1 / n_v (fp32) and their
+        rows v * N + 1 + i of the token matrix (int32).  None or empty: nothing is masked on this step and the term is 0.
         Returns device tensors {loss, dino, gram, koleo, grad_norm_sq} (plus simclr / mae with that ``loss_type``) and the python
         float lr (no sync)."""
         mae = self.hp.loss_type == "mae"          # (refusals come before anything is launched or counted)
@@ -262,8 +288,18 @@ class TrainEngine:
             raise ValueError(self._no_local_crops)
         if mae and isinstance(batch, ops.PatchOperand):
             raise ValueError("loss_type='mae' takes the fp32 image batch (the loss reads its pixels), not a PatchOperand")
+        if patch_mask is not None and not self.ibot:
+            raise ValueError("patch_mask belongs to ibot_weight > 0")
+        if patch_mask is not None:
+            idx, w, tok = patch_mask.triple() if hasattr(patch_mask, "triple") else patch_mask
+            if len(idx) == 0:
+                patch_mask = None
+            else:
+                if not (len(idx) == len(w) == len(tok)) or not all(isinstance(t, torch.Tensor) and t.is_cuda for t in (idx, w, tok)):
+                    raise ValueError("patch_mask must be (idx, w, tok): three device tensors of one length (dinox.ibot.PatchMask.to(device))")
+                patch_mask = (idx, w, tok)
         if not self.use_graph:
-            return self._step_eager(batch, spacing2b, local_batch, local_spacing, mask_noise)
+            return self._step_eager(batch, spacing2b, local_batch, local_spacing, mask_noise, patch_mask=patch_mask)
         return self._step_graph([batch, spacing2b, local_batch, local_spacing])
 
     def _step_graph(self, inputs: list) -> dict:
@@ -296,9 +332,11 @@ class TrainEngine:
         self.last = dict(self._captured, lr=lr)
         return self.last
 
-    def _step_eager(self, batch, spacing2b=None, local_batch=None, local_spacing=None, mask_noise=None, hyper: Optional[torch.Tensor] = None) -> dict:
+    def _step_eager(self, batch, spacing2b=None, local_batch=None, local_spacing=None, mask_noise=None, hyper: Optional[torch.Tensor] = None,
+                    patch_mask=None) -> dict:
         """The skeleton every objective shares.  The objective returns (its scalars by name, batch mean of the teacher output or None, the
         batch mean's pending all-reduce or None)."""
+        self._patch_mask = patch_mask
         lr, last = self._begin()
         scalars, bm, bm_work = self._objective(batch, spacing2b, local_batch, local_spacing, mask_noise)
         return self._finish(lr, last, hyper, scalars, bm, bm_work)
@@ -336,6 +374,12 @@ class TrainEngine:
             bm.div_(self.world)           # (data parallel only)
         if bm is not None:
             ops.center_ema_(self.center.view(-1), bm, hp.center_momentum)
+        if self._ibot_pending is not None:         # the patch centre moves like the CLS centre (untouched when no row was masked anywhere)
+            sum_count, work = self._ibot_pending
+            self._ibot_pending = None
+            if work is not None:
+                work.wait()
+            ops.ibot_center_ema_(self.ibot_center.view(-1), sum_count, hp.center_momentum)
         if self.bucketer is not None:
             self.bucketer.finish()
         self._mark("comm_exposed")        # what of the exchanges did not fit under backward (+ the centre EMA launch)
@@ -373,11 +417,11 @@ class TrainEngine:
                 side.wait_stream(main)
                 with torch.cuda.stream(side), torch.no_grad():
                     t_feats = self.teacher.backbone(batch, spacing=spacing2b)
-                s_feats = self.student.backbone(batch, spacing=spacing2b)
+                s_feats = self._student_forward(batch, spacing2b)
                 main.wait_stream(side)
                 t_feats.record_stream(main)
             else:
-                s_feats = self.student.backbone(batch, spacing=spacing2b)
+                s_feats = self._student_forward(batch, spacing2b)
                 self._mark("fwd_student")
                 with torch.no_grad():
                     t_feats = self.teacher.backbone(batch, spacing=spacing2b)
@@ -387,6 +431,12 @@ class TrainEngine:
             with torch.no_grad():
                 t_out = self.teacher.head(t_feats[:, 0])
             return self._losses_and_backward_autograd(s_feats, t_feats, t_out, batch, local_batch, local_spacing)
+
+    def _student_forward(self, batch, spacing2b):
+        """The student's global views; with a patch mask on this step the masked patches enter as ``backbone.mask_token``."""
+        if self._patch_mask is None:
+            return self.student.backbone(batch, spacing=spacing2b)
+        return self.student.backbone(batch, spacing=spacing2b, patch_idx=self._patch_mask[0])
 
     def _mae_objective(self, batch, spacing2b, local_batch, local_spacing, mask_noise):
         """Forward with random masking, reconstruction loss on the removed patches, backward (no unfold sharing: one net, one forward)."""
@@ -431,24 +481,41 @@ class TrainEngine:
         hp, dt = self.hp, self.compute_dtype
         scale = 1.0 / self.accum
         V = s_feats.shape[0]
+        # iBOT: the M masked patch rows of student and teacher ride at the END of the heads' operands -- one head product each way for CLS,
+        # local-crop and patch rows -- and the cross-entropies see their own rows of the logits.  M = 0 (or the term off): the step below is
+        # launch for launch the one without it.
+        mask = self._patch_mask
+        M = 0 if mask is None else mask[0].numel()
         with torch.no_grad():
             sf = s_feats.detach()
-            t_out, _ = self._head(self.teacher.head, ops.take_rows(t_feats, 0, dt), train=False)
+            t_op = ops.take_rows(t_feats, 0, dt, out_rows=V + M)
+            if M:
+                ops.gather_rows(t_feats, mask[2], dt, out=t_op, out_row0=V)
+            t_all, _ = self._head(self.teacher.head, t_op, train=False)
+            t_out = t_all[:V] if M else t_all
             if local_batch is None:
-                l_feats = None
-                cls = ops.take_rows(sf, 0, dt)
+                l_feats, n_loc = None, 0
+                cls = ops.take_rows(sf, 0, dt, out_rows=V + M)
             else:
                 with torch.enable_grad():
                     l_feats = self.student.backbone(local_batch, spacing=local_spacing)
                 lf = l_feats.detach()
-                cls = ops.take_rows(sf, 0, dt, out_rows=V + lf.shape[0])
+                n_loc = lf.shape[0]
+                cls = ops.take_rows(sf, 0, dt, out_rows=V + n_loc + M)
                 ops.take_rows(lf, 0, dt, out=cls, out_row0=V)
+            if M:
+                ops.gather_rows(sf, mask[2], dt, out=cls, out_row0=V + n_loc)
             s_all, saved = self._head(self.student.head, cls, train=True)
             center = self._target_center(t_out)
+            ds_all = torch.empty_like(s_all) if M else None
+            s_dino, ds_dino = (s_all[:V + n_loc], ds_all[:V + n_loc]) if M else (s_all, None)
             if local_batch is None:
-                l_dino, ds = ops.dino_ce(s_all, t_out, center, hp.student_temp, hp.teacher_temp, True, grad_scale=scale)
+                l_dino, ds = ops.dino_ce(s_dino, t_out, center, hp.student_temp, hp.teacher_temp, True, grad_scale=scale, ds_out=ds_dino)
             else:
-                l_dino, ds = ops.dino_ce_multi(s_all, t_out, center, hp.student_temp, hp.teacher_temp, 2, grad_scale=scale)
+                l_dino, ds = ops.dino_ce_multi(s_dino, t_out, center, hp.student_temp, hp.teacher_temp, 2, grad_scale=scale, ds_out=ds_dino)
+            l_ibot = None
+            if self.ibot:
+                l_ibot = self._ibot_term(s_all, t_all, ds_all, V, n_loc, M, scale)
             # centre EMA after the loss used the old centre; batch mean is global under DP (the centre itself moves after backward,
             # so the exchange runs under the backward pass)
             bm = ops.colmean(t_out)
@@ -467,8 +534,10 @@ class TrainEngine:
             if kstate is not None:
                 l_koleo, ksaved = ops.koleo_end(kstate)
                 ops.axpy_(ds[:V], ops.koleo_bwd(ksaved, hp.koleo_weight * scale), 1.0)      # (ds[:V]: the leading rows, contiguous)
-            dcls = self._student_head_backward(saved, ds)
+            dcls = self._student_head_backward(saved, ds_all if M else ds)
             ops.put_rows_(dfeats, 0, dcls)                                                                            # row 0 (CLS)
+            if M:                                                             # the masked patch rows, on top of what Gram wrote there
+                ops.scatter_add_rows_(dfeats, mask[2], dcls, src_row0=V + n_loc)
             roots, grads = [s_feats], [dfeats]
             if l_feats is not None:
                 dl = torch.empty_like(lf)
@@ -477,9 +546,46 @@ class TrainEngine:
                 roots.append(l_feats)
                 grads.append(dl)
             loss = ops.lincomb3(l_dino, l_gram, l_koleo, hp.gram_weight, hp.koleo_weight)
+            if l_ibot is not None:
+                loss = ops.lincomb3(loss, l_ibot, None, hp.ibot_weight, 0.0)
         self._mark("loss")
         torch.autograd.backward(roots, grads)
-        return {"loss": loss, "dino": l_dino, "gram": l_gram, "koleo": l_koleo}, bm, bm_work
+        scalars = {"loss": loss, "dino": l_dino, "gram": l_gram, "koleo": l_koleo}
+        if self.ibot:
+            scalars["ibot"] = l_ibot                      # (None on a step without masked rows: reported as 0)
+        return scalars, bm, bm_work
+
+    def _ibot_term(self, s_all, t_all, ds_all, V: int, n_loc: int, M: int, scale: float):
+        """The masked-patch cross-entropy on the trailing M rows of the heads' outputs (its gradient into the same rows of ``ds_all``) and the
+        patch centre's bookkeeping: (column sums, count) of the masked teacher rows, all-reduced under data parallelism -- every rank
+        takes part on every step, M differs per rank and may be 0 -- and handed to ``_finish``.  Returns the loss [1], or None at M = 0."""
+        hp = self.hp
+        dp = exchanging(self.group)
+        K = t_all.shape[1]
+        sum_count = None
+        l_ibot = None
+        if M:
+            idx, w_rows, tok = self._patch_mask
+            s_p, t_p = s_all[V + n_loc:], t_all[V:]
+            if hp.centering == "sinkhorn":
+                c_p = ops.sk_center(t_p, hp.teacher_temp, hp.sk_iters, group=self.group)
+            else:
+                c_p = self.ibot_center
+            l_ibot, _, _ = ops.ibot_ce(s_p, t_p, c_p, w_rows, hp.student_temp, hp.teacher_temp, scale=1.0 / V, grad_scale=hp.ibot_weight * scale,
+                                       ds_out=ds_all[V + n_loc:])
+            sum_count = torch.empty(K + 1, dtype=torch.float32, device=t_all.device)
+            ops.colsum(t_p, out=sum_count[:K])
+            count = torch.tensor([float(M)], dtype=torch.float32)          # (a fresh page-locked word per step, like the AdamW scalars)
+            sum_count[K:].copy_(count.pin_memory() if t_all.is_cuda else count, non_blocking=True)
+        elif dp:
+            if hp.centering == "sinkhorn":
+                ops.sk_center_idle(K, hp.sk_iters, self.group, t_all.device)
+            sum_count = torch.empty(K + 1, dtype=torch.float32, device=t_all.device)
+            ops.zero_(sum_count)
+        if sum_count is not None:
+            work = dist.all_reduce(sum_count, op=dist.ReduceOp.SUM, group=self.group, async_op=True) if dp else None
+            self._ibot_pending = (sum_count, work)
+        return l_ibot
 
     def _simclr_objective(self, batch, spacing2b, local_batch, local_spacing, mask_noise):
         """Student forward, student head on the CLS rows, NT-Xent on the two halves of its output (reference :1729-1737) and the backward
@@ -542,8 +648,8 @@ class TrainEngine:
     # -- convenience ------------------------------------------------------------------------------
     def scalars(self) -> dict:
         """Host copies of the last step's scalars (this is the only place that synchronises): what the objective returned (simclr adds
-        the key "simclr", mae "mae"; a dino engine returns exactly the keys it always did, so whatever iterates over them sees no new
-        entry), the grad-norm and the lr."""
+        the key "simclr", mae "mae", ibot_weight > 0 "ibot"; a dino engine without it returns exactly the keys it always did, so whatever
+        iterates over them sees no new entry), the grad-norm and the lr."""
         out = {}
         for k, v in self.last.items():
             if k == "grad_norm_sq":

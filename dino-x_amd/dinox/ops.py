@@ -1603,20 +1603,31 @@ class ScaleEmbedFn(torch.autograd.Function):
                 small_grad(plnb, dlnb), None)
 
 
-def dino_ce(s: Tensor, t: Tensor, center: Tensor, student_temp: float, teacher_temp: float, want_grad: bool, grad_scale: float = 1.0):
+def _ds_buffer(ds_out: Optional[Tensor], like: Tensor) -> Tensor:
+    """The gradient buffer of a cross-entropy: a fresh one, or the caller's rows of a larger buffer (the engine's head backward takes the
+    rows of every term in one operand)."""
+    if ds_out is None:
+        return torch.empty_like(like)
+    assert ds_out.dtype == torch.float32 and ds_out.is_contiguous() and ds_out.shape == like.shape and ds_out.device == like.device
+    return ds_out
+
+
+def dino_ce(s: Tensor, t: Tensor, center: Tensor, student_temp: float, teacher_temp: float, want_grad: bool, grad_scale: float = 1.0,
+            ds_out: Optional[Tensor] = None):
     """Returns (loss[1], ds or None).  s, t: [2B, K]."""
     _need_cuda(s, t, center)
     s, t = _c(s.float()), _c(t.float())
     rows, K = s.shape
     loss = torch.empty(1, dtype=torch.float32, device=s.device)
     row_loss = torch.empty(rows, dtype=torch.float32, device=s.device)
-    ds = torch.empty_like(s) if want_grad else None
+    ds = _ds_buffer(ds_out, s) if want_grad else None
     check(lib.dinox_dino_ce(_p(s), _p(t), _p(_c(center).reshape(-1)), student_temp, teacher_temp, grad_scale, _p(loss), _p(ds), _p(row_loss),
                             rows, K, _stream()), "dinox_dino_ce")
     return loss, ds
 
 
-def dino_ce_multi(s: Tensor, t: Tensor, center: Tensor, student_temp: float, teacher_temp: float, n_global: int, grad_scale: float = 1.0):
+def dino_ce_multi(s: Tensor, t: Tensor, center: Tensor, student_temp: float, teacher_temp: float, n_global: int, grad_scale: float = 1.0,
+                  ds_out: Optional[Tensor] = None):
     """Multi-crop DINO CE (see DinoCEMultiFn): returns (loss[1], ds) with ds already multiplied by grad_scale."""
     _need_cuda(s, t, center)
     sf, tf = _c(s.float()), _c(t.float())
@@ -1625,7 +1636,7 @@ def dino_ce_multi(s: Tensor, t: Tensor, center: Tensor, student_temp: float, tea
     n_views = sf.shape[0] // B
     assert tf.shape[0] == n_global * B and sf.shape[0] == n_views * B and tf.shape[1] == K, (tuple(s.shape), tuple(t.shape), n_global)
     loss = torch.empty(1, dtype=torch.float32, device=sf.device)
-    ds = torch.empty_like(sf)
+    ds = _ds_buffer(ds_out, sf)
     ws = torch.empty((n_views + 2 * n_global) * B, dtype=torch.float32, device=sf.device)
     check(lib.dinox_dino_ce_multi(_p(sf), _p(tf), _p(_c(center).reshape(-1)), student_temp, teacher_temp, grad_scale, _p(loss), _p(ds), _p(ws),
                                   B, n_global, n_views, K, _stream()), "dinox_dino_ce_multi")
@@ -1848,6 +1859,19 @@ def sk_center(t: Tensor, teacher_temp: float, n_iters: int = 3, group=None) -> T
         if n == n_iters:
             return sk_col_lse(gathered, None, 1.0, teacher_temp)                   # c = -tau b = tau lse
         a = sk_row_lse(t, sk_col_lse(gathered, None, 1.0, -1.0), inv, -1.0)
+
+
+def sk_center_idle(K: int, n_iters: int, group, device) -> None:
+    """A rank WITHOUT rows in a data-parallel ``sk_center`` over the global batch (the iBOT patch rows of a step on which this rank masked
+    nothing): it joins the n_iters all-gathers of the column passes with log 0 = -inf in every column, which adds nothing to the other
+    ranks' sums, and computes no centre.  (The -inf vector is one framework fill: this path runs only on a step on which a rank
+    masked nothing, and sk_center's own passes stay free of framework kernels.)"""
+    import torch.distributed as dist
+    world = dist.get_world_size(group)
+    gathered = torch.empty((world, K), dtype=torch.float32, device=device)
+    nothing = torch.full((K,), float("-inf"), dtype=torch.float32, device=device)
+    for _ in range(n_iters):
+        dist.all_gather_into_tensor(gathered, nothing, group=group)
 
 
 def gram_loss_fwd(sf: Tensor, tf: Tensor, dt: torch.dtype):
@@ -2291,6 +2315,173 @@ class MaeLossFn(torch.autograd.Function):
         # the upstream gradient is a device scalar: run with gscale = 1 and scale the result (no host sync)
         d = mae_loss_bwd(ctx.saved, 1.0) * g
         return (d if d.dtype == ctx.pdt else d.to(ctx.pdt)), None, None, None, None, None
+
+
+# ---------------------------------------------------------------- iBOT masked-patch objective (csrc/ibot.hip)
+IBOT_MASK_CHUNK = 64      # csrc/kernels.h: masked rows per partial sum of dinox_ibot_put_mask_bwd
+
+
+def _row_index(idx: Tensor, what: str) -> Tensor:
+    _need_cuda(idx)
+    if idx.dtype != torch.int32 or idx.dim() != 1:
+        raise TypeError(f"{what} must be a 1-D int32 tensor on the device, got {idx.dtype} {tuple(idx.shape)}")
+    return _c(idx)
+
+
+def gather_rows(src: Tensor, row: Tensor, dt: torch.dtype, out: Optional[Tensor] = None, out_row0: int = 0, out_rows: int = 0) -> Tensor:
+    """out[out_row0 + m] = src.view(-1, D)[row[m]] in dt (src fp32 [..., D]; row int32 [M] on the device): ``take_rows`` by index.  An entry
+    outside the rows of src is skipped."""
+    _need_cuda(src)
+    assert src.dtype == torch.float32 and src.is_contiguous() and src.dim() >= 2
+    row = _row_index(row, "row")
+    D, M = src.shape[-1], row.numel()
+    if out is None:
+        out = torch.empty((out_rows or M, D), dtype=dt, device=src.device)
+    assert out.is_contiguous() and out.dtype == dt and out.shape[-1] == D and out_row0 >= 0 and out_row0 + M <= out.numel() // D
+    check(lib.dinox_gather_rows(_p(src), _p(row), _p(out), M, src.numel() // D, D, out_row0, _code(dt), _stream()), "dinox_gather_rows")
+    return out
+
+
+def scatter_add_rows_(dst: Tensor, row: Tensor, src: Tensor, src_row0: int = 0) -> None:
+    """dst.view(-1, D)[row[m]] += src[src_row0 + m]  (dst fp32 [..., D]; src [*, D] fp32 or bf16; the rows must be distinct)."""
+    assert dst.dtype == torch.float32 and dst.is_contiguous() and src.is_contiguous() and dst.shape[-1] == src.shape[-1]
+    row = _row_index(row, "row")
+    D, M = dst.shape[-1], row.numel()
+    assert src_row0 >= 0 and src_row0 + M <= src.numel() // D
+    check(lib.dinox_scatter_add_rows(_p(src), _p(row), _p(dst), M, dst.numel() // D, D, src_row0, _code(src.dtype), _stream()),
+          "dinox_scatter_add_rows")
+
+
+def ibot_put_mask_(patches: Tensor, mask_token: Tensor, idx: Tensor) -> None:
+    """patches[idx[m]] = mask_token (rounded to the dtype of patches [rows, D]), in place."""
+    assert patches.is_contiguous() and patches.dim() == 2 and mask_token.dtype == torch.float32 and mask_token.numel() == patches.shape[1]
+    idx = _row_index(idx, "idx")
+    check(lib.dinox_ibot_put_mask(_p(patches), _p(_c(mask_token)), _p(idx), idx.numel(), patches.shape[0], patches.shape[1],
+                                  _code(patches.dtype), _stream()), "dinox_ibot_put_mask")
+
+
+def ibot_put_mask_bwd_(dpatches: Tensor, idx: Tensor) -> Tensor:
+    """-> dmask_token [1, 1, D] fp32 = sum_m dpatches[idx[m]] (fixed order); those rows of dpatches [rows, D] are then set to 0."""
+    assert dpatches.is_contiguous() and dpatches.dim() == 2
+    idx = _row_index(idx, "idx")
+    M, D = idx.numel(), dpatches.shape[1]
+    dmask = torch.empty((1, 1, D), dtype=torch.float32, device=dpatches.device)
+    ws = torch.empty(((M + IBOT_MASK_CHUNK - 1) // IBOT_MASK_CHUNK, D), dtype=torch.float32, device=dpatches.device)
+    check(lib.dinox_ibot_put_mask_bwd(_p(dpatches), _p(idx), _p(dmask), _p(ws), M, dpatches.shape[0], D, _code(dpatches.dtype), _stream()),
+          "dinox_ibot_put_mask_bwd")
+    return dmask
+
+
+def ibot_ce(s: Tensor, t: Tensor, center: Tensor, w: Tensor, student_temp: float, teacher_temp: float, scale: float = 1.0,
+            want_grad: bool = True, grad_scale: float = 1.0, ds_out: Optional[Tensor] = None):
+    """The masked-patch cross-entropy: s, t [M, K] fp32 (rows of a larger contiguous matrix are fine), center [K], w [M] fp32.
+    Returns (loss[1] = scale * sum_m w[m] row_loss[m], ds or None, row_loss [M]); ds = grad_scale * scale * w[m] * d row_loss[m] / d s[m]."""
+    _need_cuda(s, t, center, w)
+    assert s.dtype == torch.float32 and t.dtype == torch.float32 and s.is_contiguous() and t.is_contiguous() and s.shape == t.shape and s.dim() == 2
+    M, K = s.shape
+    assert w.dtype == torch.float32 and w.is_contiguous() and w.numel() == M and center.numel() == K, (tuple(w.shape), tuple(center.shape), M, K)
+    loss = torch.empty(1, dtype=torch.float32, device=s.device)
+    row_loss = torch.empty(M, dtype=torch.float32, device=s.device)
+    ds = _ds_buffer(ds_out, s) if want_grad else None
+    check(lib.dinox_ibot_ce(_p(s), _p(t), _p(_c(center.float()).reshape(-1)), _p(w), student_temp, teacher_temp, scale, grad_scale, _p(loss),
+                            _p(ds), _p(row_loss), M, K, _stream()), "dinox_ibot_ce")
+    return loss, ds, row_loss
+
+
+def ibot_center_ema_(center: Tensor, sum_count: Tensor, momentum: float) -> None:
+    """center [K] moves towards sum_count[:K] / sum_count[K] (column sums and number of the masked teacher rows); untouched at a count of 0."""
+    assert center.is_contiguous() and center.dtype == torch.float32 and sum_count.dtype == torch.float32 and sum_count.is_contiguous()
+    assert sum_count.numel() == center.numel() + 1
+    check(lib.dinox_ibot_center_ema(_p(center), _p(sum_count), momentum, center.numel(), _stream()), "dinox_ibot_center_ema")
+
+
+class MaskedTokensFn(torch.autograd.Function):
+    """TokensFn with the embedding of the patches ``idx`` (int32 [M], flat positions v P + i, distinct) replaced by ``mask_token``
+    [1, 1, D] after the patch-embedding product and before pos_embed / the scale embedding are added: unfold, patch product,
+    dinox_ibot_put_mask, dinox_tokens_fwd.  Backward: dinox_tokens_bwd, dinox_ibot_put_mask_bwd (the mask token's gradient; the masked rows
+    send nothing into the patch product), then the dW / db products of TokensFn."""
+
+    @staticmethod
+    def forward(ctx, x, pw, pb, cls, pos, regs, scale, patch, idx, mask_token):
+        dt = current_dtype()
+        u = patch_unfold(x, patch, dt)
+        idx = _row_index(idx, "idx")
+        V = x.shape[0]
+        D = pw.shape[0]
+        P = u.shape[0] // V
+        R = 0 if regs is None else regs.shape[1]
+        K0 = 3 * patch * patch
+        wop = weight_operand(pw, dt) if u.shape[1] == K0 else padded_patch_weight(pw, dt, u.shape[1])
+        patches = gemm(u, wop, bias=pb, out_dtype=dt)
+        ibot_put_mask_(patches, mask_token.detach().reshape(-1), idx)
+        tokens = torch.empty((V, 1 + P + R, D), dtype=torch.float32, device=x.device)
+        sc = None if scale is None else _c(scale).reshape(V, D)
+        check(lib.dinox_tokens_fwd(_p(patches), _p(_c(cls)), _p(_c(pos)), _p(None if regs is None else _c(regs)), _p(sc), _p(tokens),
+                                   V, P, R, D, _code(dt), _stream()), "dinox_tokens_fwd")
+        ctx.save_for_backward(u, pw, pb, idx)
+        ctx.small = (cls, pos if isinstance(pos, torch.nn.Parameter) else None, regs, mask_token)
+        grad_sink.use(pw, pb, cls, ctx.small[1], regs, mask_token)
+        ctx.dims, ctx.dt, ctx.has_scale = (V, P, R, D), dt, scale is not None
+        return tokens
+
+    @staticmethod
+    def backward(ctx, dtok):
+        u, pw, pb, idx = ctx.saved_tensors
+        V, P, R, D = ctx.dims
+        dt = ctx.dt
+        dtok = _c(dtok)
+        dev = dtok.device
+        dpatches = torch.empty((V * P, D), dtype=dt, device=dev)
+        dcls = torch.empty((1, 1, D), dtype=torch.float32, device=dev)
+        dpos = torch.empty((1, 1 + P, D), dtype=torch.float32, device=dev)
+        dregs = torch.empty((1, R, D), dtype=torch.float32, device=dev) if R else None
+        dscale = torch.empty((V, 1, D), dtype=torch.float32, device=dev) if ctx.has_scale else None
+        check(lib.dinox_tokens_bwd(_p(dtok), _p(dpatches), _p(dcls), _p(dpos), _p(dregs), _p(dscale), V, P, R, D, _code(dt), _stream()),
+              "dinox_tokens_bwd")
+        dmask = ibot_put_mask_bwd_(dpatches, idx)
+        dw, db = _patch_weight_grad(dpatches, u, pw, pb, D, dev)
+        cls, pos, regs, mask_token = ctx.small
+        return (None, dw, db, small_grad(cls, dcls), small_grad(pos, dpos), small_grad(regs, dregs), dscale, None, None,
+                small_grad(mask_token, dmask))
+
+
+class AnnounceFn(torch.autograd.Function):
+    """Identity on ``x`` that tells the gradient sink, at this point of backward, that ``param`` has its (zero) gradient: the place of
+    ``mask_token`` in a token assembly that masks nothing.  Under data parallelism the ranks exchange a gradient bucket when its last
+    parameter is announced, and all ranks must do so in one order: a rank that masked nothing on a step (and every rank's local crops)
+    announces mask_token here, just ahead of the token assembly's own backward, where MaskedTokensFn announces it on the ranks that
+    did mask -- no other bucket completes in between.  No kernel is launched."""
+
+    @staticmethod
+    def forward(ctx, x, param):
+        ctx.param = param
+        grad_sink.use(param)
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        slot = grad_sink.lookup(ctx.param)
+        if slot is not None:
+            grad_sink.ready(slot)
+        return g, None
+
+
+def _patch_weight_grad(dpatches: Tensor, u: Tensor, pw: Tensor, pb: Optional[Tensor], D: int, dev):
+    """The dW / db products of the patch embedding with the arithmetic of TokensFn.backward (whose text stays as it is)."""
+    K0 = pw[0].numel()
+    if u.shape[1] == K0:
+        return weight_grad(dpatches, u, pw, pb, pb is not None)
+    dbt = torch.empty(D, dtype=torch.float32, device=dev) if pb is not None else None
+    dwp = gemm(dpatches, u, transA=True, transB=True, out_dtype=torch.float32, colsum_out=dbt)
+    sw, sb = grad_sink.lookup(pw), (grad_sink.lookup(pb) if pb is not None else None)
+    if sw is not None and (pb is None or sb is not None):
+        sw[1].grad.view(D, K0).add_(dwp[:, :K0])
+        grad_sink.ready(sw)
+        if pb is not None:
+            axpy_(sb[1].grad.view(-1), dbt, 1.0)
+            grad_sink.ready(sb)
+        return None, None
+    return dwp[:, :K0].reshape(pw.shape).contiguous(), dbt
 
 
 def adamw_hyper(lr: float, beta1: float, beta2: float, step_t: int) -> list:

@@ -534,6 +534,8 @@ def save_checkpoint(path: Path, step: int, student: nn.Module, teacher: nn.Modul
         "rng": _get_rng_state(),
         "config": config_dict(config, getattr(eng, "hp", None)),
     }
+    if getattr(eng, "ibot", False):          # (--ibot-weight only: the mask token travels in the state dicts, the patch centre here)
+        payload["ibot_center"] = eng.ibot_center.detach().cpu().clone()
     torch.save(payload, path)
 
 
@@ -558,6 +560,8 @@ def load_checkpoint(path: Path, student: nn.Module, teacher: nn.Module, eng: Tra
         load_adamw_state_dict(eng, payload["opt"])
     if payload.get("dino_loss") is not None:
         eng.center.copy_(payload["dino_loss"]["center"].to(eng.center.device))
+    if getattr(eng, "ibot", False) and payload.get("ibot_center") is not None:
+        eng.ibot_center.copy_(payload["ibot_center"].to(eng.ibot_center.device))
     if payload.get("rng") is not None:
         _set_rng_state(payload["rng"])
     step = int(payload.get("step", 0))
@@ -696,20 +700,37 @@ def build_simclr_parser() -> argparse.ArgumentParser:
     return ap
 
 
+def build_ibot_parser() -> argparse.ArgumentParser:
+    """The options of the iBOT masked-patch term, a parser of their own like the MAE, centring and SimCLR options (``build_parser()``
+    stays the reference's flag surface plus the general extensions)."""
+    ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    ap.add_argument("--ibot-weight", type=float, default=0.0,
+                    help="Weight of the iBOT masked-patch term (extension, --loss-type dino only; default 0: off, the run is exactly the one "
+                         "without it): masked patches of the global views reach the student as a learned token and must match the teacher's "
+                         "patch tokens through the DINO head; not under --hip-graph")
+    ap.add_argument("--ibot-mask-prob", type=float, default=0.5, help="Probability that a global view is masked (default: 0.5)")
+    ap.add_argument("--ibot-mask-ratio", type=float, nargs=2, default=[0.1, 0.5], metavar=("MIN", "MAX"),
+                    help="A masked view hides a share of its patches drawn uniformly from this range, in BEiT-style blocks (default: 0.1 0.5)")
+    return ap
+
+
 def parse_cli(argv=None) -> argparse.Namespace:
-    """The MAE options (build_mae_parser), the centring options (build_centering_parser) and the SimCLR option (build_simclr_parser)
-    first, everything else through build_parser; one namespace."""
+    """The MAE options (build_mae_parser), the centring options (build_centering_parser), the SimCLR option (build_simclr_parser) and the
+    iBOT options (build_ibot_parser) first, everything else through build_parser; one namespace."""
     mae, rest = build_mae_parser().parse_known_args(argv)
     cen, rest = build_centering_parser().parse_known_args(rest)
     sim, rest = build_simclr_parser().parse_known_args(rest)
+    ibot, rest = build_ibot_parser().parse_known_args(rest)
     ap = build_parser()
     ap.epilog = ("MAE objective: " + " ".join(build_mae_parser().format_help().split()[1:])
                  + "  Teacher centring: " + " ".join(build_centering_parser().format_help().split()[1:])
-                 + "  SimCLR objective: " + " ".join(build_simclr_parser().format_help().split()[1:]))
+                 + "  SimCLR objective: " + " ".join(build_simclr_parser().format_help().split()[1:])
+                 + "  iBOT masked-patch term: " + " ".join(build_ibot_parser().format_help().split()[1:]))
     args = ap.parse_args(rest)
     args.mae_decoder, args.mae_mask_ratio = mae.mae_decoder, mae.mae_mask_ratio
     args.centering, args.sk_iters = cen.centering, cen.sk_iters
     args.simclr_negatives = sim.simclr_negatives
+    args.ibot_weight, args.ibot_mask_prob, args.ibot_mask_ratio = ibot.ibot_weight, ibot.ibot_mask_prob, list(ibot.ibot_mask_ratio)
     return args
 
 
@@ -753,6 +774,7 @@ def check_loss_type(args, world: int = 1) -> None:
         if world > 1:
             raise SystemExit(f"--loss-type mae runs on one GPU only (got {world} ranks): data-parallel MAE is not implemented")
     check_centering(args)
+    check_ibot(args)
     if args.loss_type == "simclr" and args.local_crops:
         raise SystemExit("--loss-type simclr takes the two global views only: drop --local-crops (multi-crop is a DINO-term extension)")
     check_simclr_negatives(args)
@@ -768,6 +790,38 @@ def check_simclr_negatives(args) -> None:
     if args.loss_type != "simclr":
         raise SystemExit(f"--simclr-negatives {args.simclr_negatives} belongs to --loss-type simclr (--loss-type {args.loss_type} has no "
                          "negatives to gather): drop it or train with --loss-type simclr")
+
+
+def ibot_step_mask(args, rank: int, step: int, grid: int, registers: int):
+    """The masked patches of training step ``step`` on ``rank`` (a host ``dinox.ibot.PatchMask``): a function of (--train-seed, rank, step)
+    alone -- a generator of its own per step -- so the view draws of the seed do not move and a resumed run masks what the interrupted
+    one would have."""
+    from dinox.ibot import MaskGenerator
+    g = MaskGenerator((args.train_seed * 1_000_003 + step) * 4099 + rank, grid, registers=registers, mask_prob=args.ibot_mask_prob,
+                      ratio=tuple(args.ibot_mask_ratio))
+    return g.draw(2 * args.batch_size)
+
+
+def check_ibot(args) -> None:
+    """``--ibot-weight`` adds the masked-patch term to the DINO objective: it shares that objective's head and teacher."""
+    weight = getattr(args, "ibot_weight", 0.0)
+    if weight < 0.0:
+        raise SystemExit(f"--ibot-weight must be >= 0, got {weight}")
+    if weight == 0.0:
+        return
+    if args.loss_type != "dino":
+        raise SystemExit(f"--ibot-weight belongs to --loss-type dino (--loss-type {args.loss_type} has no DINO head or teacher for the masked "
+                         "patches): drop it or train with --loss-type dino")
+    if args.hip_graph:
+        raise SystemExit("--ibot-weight does not run under --hip-graph: the number of masked patches changes from step to step and a captured "
+                         "step has one fixed layout")
+    if os.environ.get("DINOX_AUTOGRAD_TOP"):
+        raise SystemExit("--ibot-weight needs the stock DINO head in the hand-written top of the step: unset DINOX_AUTOGRAD_TOP")
+    if not 0.0 <= args.ibot_mask_prob <= 1.0:
+        raise SystemExit(f"--ibot-mask-prob must lie in [0, 1], got {args.ibot_mask_prob}")
+    lo, hi = args.ibot_mask_ratio
+    if not 0.0 < lo <= hi <= 1.0:
+        raise SystemExit(f"--ibot-mask-ratio needs 0 < MIN <= MAX <= 1, got {lo} {hi}")
 
 
 def check_centering(args) -> None:
@@ -792,6 +846,9 @@ def config_dict(config: TrainingConfig, centring=None) -> dict:
     negatives = getattr(centring, "simclr_negatives", "local")
     if negatives != "local":
         d.update(simclr_negatives=negatives)
+    ibot_weight = getattr(centring, "ibot_weight", 0.0)
+    if ibot_weight:
+        d.update(ibot_weight=ibot_weight)
     return d
 
 
@@ -982,6 +1039,8 @@ def _main(argv=None) -> None:
     # ---- model / engine
     vit_kw = dict(img_size=args.img_size, patch=model_cfg.patch, dim=model_cfg.dim, depth=model_cfg.depth, heads=model_cfg.heads,
                   mlp_ratio=model_cfg.mlp_ratio, use_grad_checkpoint=args.grad_checkpoint, scale_aware=args.scale_aware)
+    if args.ibot_weight > 0.0:
+        vit_kw["mask_token"] = True             # (created after the initialiser ran: the initial weights of a seed do not move)
     student = DinoStudentTeacher(PatchViT(**vit_kw), out_dim=model_cfg.out_dim).to(device)
     teacher = DinoStudentTeacher(PatchViT(**vit_kw), out_dim=model_cfg.out_dim).to(device)
     teacher.load_state_dict(student.state_dict())
@@ -989,7 +1048,8 @@ def _main(argv=None) -> None:
                          weight_decay=args.weight_decay, ema=args.ema, teacher_temp=args.teacher_temp, student_temp=args.student_temp,
                          center_momentum=args.center_momentum, gram_weight=args.gram_weight,
                          koleo_weight=args.koleo_weight, loss_type=args.loss_type, mae_mask_ratio=args.mae_mask_ratio,
-                         centering=args.centering, sk_iters=args.sk_iters, simclr_negatives=args.simclr_negatives)
+                         centering=args.centering, sk_iters=args.sk_iters, simclr_negatives=args.simclr_negatives,
+                         ibot_weight=args.ibot_weight)
     if args.hip_graph and (world > 1 or args.accumulation_steps != 1 or args.local_crops):
         raise SystemExit("--hip-graph: single GPU, --accumulation-steps 1 and no --local-crops (the captured step has one fixed batch layout)")
     if device.type == "cuda" and not args.hip_graph and args.streams != "off":
@@ -1019,6 +1079,12 @@ def _main(argv=None) -> None:
         say(f"resumed_from_step={start_step}")
         if loaded and loaded.model and loaded.model.name != model_cfg.name:
             warnings.warn(f"Model config mismatch: checkpoint={loaded.model.name} requested={model_cfg.name}")
+    masker = None
+    if args.ibot_weight > 0.0:
+        def masker(s: int):
+            return ibot_step_mask(args, rank, s, args.img_size // model_cfg.patch, student.backbone.num_registers).to(device)
+        say(f"ibot_weight={args.ibot_weight} mask_prob={args.ibot_mask_prob} mask_ratio={args.ibot_mask_ratio[0]}..{args.ibot_mask_ratio[1]}")
+    ibot_pin = torch.empty(3, dtype=torch.float32).pin_memory() if (masker is not None and device.type == "cuda") else None
     say("tensorboard not installed, skipping TB logging")
 
     stop = _StopFlag()
@@ -1089,7 +1155,7 @@ def _main(argv=None) -> None:
             batch = torch.cat([v.to(device, non_blocking=True) for v in views], 0)
         sp2 = torch.cat([spacing, spacing], 0).to(device, non_blocking=True) if args.scale_aware else None
         _t0 = time.perf_counter()
-        out = eng.step(batch, sp2, loc, spl)
+        out = eng.step(batch, sp2, loc, spl) if masker is None else eng.step(batch, sp2, loc, spl, patch_mask=masker(step))
         _prof["step"] += time.perf_counter() - _t0
         _prof["n"] += 1
         _prof["t1"] = time.time()
@@ -1108,6 +1174,8 @@ def _main(argv=None) -> None:
         if loss_pin is not None:
             slot = step % (LOSS_LAG + 1)
             loss_pin[slot:slot + 1].copy_(loss_t.detach().reshape(1).float(), non_blocking=True)
+            if ibot_pin is not None:        # (this rank's value: the term is logged beside the global loss, not reduced)
+                ibot_pin[slot:slot + 1].copy_(out["ibot"].detach().reshape(1).float(), non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
             cur = (step, (slot, ev), out["lr"])
@@ -1117,14 +1185,15 @@ def _main(argv=None) -> None:
         for (s_, loss_t, lr_) in ([pending.pop(0)] if len(pending) > LOSS_LAG else []):
             loss_val = read_loss(loss_t)
             loss_history.append(loss_val)
+            extra = {"ibot": round(float(ibot_pin[loss_t[0]]), 6)} if ibot_pin is not None else {}     # (its copy precedes the event just waited for)
             if args.log_json is not None and main_rank:
                 with open(args.log_json, "a") as jf:
-                    jf.write(json.dumps({"step": s_, "loss": round(loss_val, 6), "lr": lr_}) + "\n")
+                    jf.write(json.dumps({"step": s_, "loss": round(loss_val, 6), "lr": lr_, **extra}) + "\n")
             now = time.time()
             if now - last_log >= 10.0 or s_ == start_step:
                 sps = (s_ - start_step + 1) / max(now - t0, 1e-6)
-                say(f"step={s_:6d} loss={loss_val:.4f} lr={lr_:.2e} steps/s={sps:.2f} samples/s={sps * cfg.effective_batch_size * world:.1f} "
-                    f"elapsed={now - t0:.1f}s")
+                say(f"step={s_:6d} loss={loss_val:.4f}{''.join(f' {k}={v:.4f}' for k, v in extra.items())} lr={lr_:.2e} steps/s={sps:.2f} "
+                    f"samples/s={sps * cfg.effective_batch_size * world:.1f} elapsed={now - t0:.1f}s")
                 last_log = now
             bad, msg = detect_anomaly(loss_val, loss_history[:-1])
             if bad and ("NaN" in msg or "Inf" in msg):
@@ -1154,9 +1223,10 @@ def _main(argv=None) -> None:
     for s_, loss_t, lr_ in pending:
         loss_val = read_loss(loss_t)
         loss_history.append(loss_val)
+        extra = {"ibot": round(float(ibot_pin[loss_t[0]]), 6)} if ibot_pin is not None else {}
         if args.log_json is not None and main_rank:
             with open(args.log_json, "a") as jf:
-                jf.write(json.dumps({"step": s_, "loss": round(loss_val, 6), "lr": lr_}) + "\n")
+                jf.write(json.dumps({"step": s_, "loss": round(loss_val, 6), "lr": lr_, **extra}) + "\n")
     final_step = step + 1
     if main_rank:
         final = run_dir / f"checkpoint_final_{final_step:08d}.pth"

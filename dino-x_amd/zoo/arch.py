@@ -177,6 +177,7 @@ class PatchViT(nn.Module):
         use_grad_checkpoint: bool = False,
         num_registers: int = 4,
         scale_aware: bool = False,
+        mask_token: bool = False,
     ) -> None:
         super().__init__()
         assert img_size % patch == 0
@@ -203,6 +204,10 @@ class PatchViT(nn.Module):
         if scale_aware:
             nn.init.zeros_(self.scale_embed.mlp[2].weight)
             nn.init.zeros_(self.scale_embed.mlp[2].bias)
+        # iBOT (extension): the learned token masked patches are replaced by.  Created after the initialiser ran and zero-filled, so the
+        # draws -- and with them every other initial weight of a seed -- are those of a model without it.
+        if mask_token:
+            self.mask_token = nn.Parameter(torch.zeros(1, 1, dim))
 
     def _init_weights(self, m: nn.Module) -> None:
         if isinstance(m, nn.Linear):
@@ -218,8 +223,10 @@ class PatchViT(nn.Module):
         if self.num_registers > 0:
             nn.init.trunc_normal_(self.registers, std=0.02)
 
-    def forward(self, x: torch.Tensor, spacing: Optional[torch.Tensor] = None) -> torch.Tensor:
-        return self._forward(x, spacing, None)
+    def forward(self, x: torch.Tensor, spacing: Optional[torch.Tensor] = None, patch_idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``patch_idx`` (int32 [M] on the device, distinct flat patch positions v * P + i; needs ``mask_token=True``): those patches
+        enter as ``mask_token`` instead of their embedding (iBOT masking; training only -- inference never masks)."""
+        return self._forward(x, spacing, None, patch_idx)
 
     def last_attention(self, x: torch.Tensor, spacing: Optional[torch.Tensor] = None, query_tokens=(0,), layer: int = -1):
         """-> (feats, probs): ``feats`` is ``self.forward(x, spacing)`` (the same launches, bit for bit) and ``probs``
@@ -287,7 +294,7 @@ class PatchViT(nn.Module):
             if keep:
                 tap["qkv"].append((qkv, blk.attn.num_heads))
 
-    def _forward(self, x: torch.Tensor, spacing: Optional[torch.Tensor], tap) -> torch.Tensor:
+    def _forward(self, x: torch.Tensor, spacing: Optional[torch.Tensor], tap, patch_idx: Optional[torch.Tensor] = None) -> torch.Tensor:
         g = x.shape[-1] // self.patch
         if x.shape[-2] != x.shape[-1] or x.shape[-1] % self.patch:
             raise ValueError(f"input {tuple(x.shape[-2:])} is not a square multiple of the {self.patch}-pixel patch")
@@ -304,7 +311,18 @@ class PatchViT(nn.Module):
         pos = self.pos_embed
         if g * g != pos.shape[1] - 1:       # extension (multi-crop local views): the reference has one input size only
             pos = ops.interp_pos(pos, g)
-        t = ops.TokensFn.apply(x, self.patch_embed.weight, self.patch_embed.bias, self.cls_token, pos, regs, scale, self.patch)
+        if patch_idx is None:
+            t = ops.TokensFn.apply(x, self.patch_embed.weight, self.patch_embed.bias, self.cls_token, pos, regs, scale, self.patch)
+            mt = getattr(self, "mask_token", None)
+            if mt is not None and mt.requires_grad and torch.is_grad_enabled():
+                t = ops.AnnounceFn.apply(t, mt)          # (nothing masked here: mask_token's zero gradient is announced where a masked assembly would)
+        else:
+            if getattr(self, "mask_token", None) is None:
+                raise ValueError("patch_idx needs a model built with mask_token=True")
+            if patch_idx.numel() == 0:
+                raise ValueError("patch_idx is empty: call forward without it (no kernel is launched over zero rows)")
+            t = ops.MaskedTokensFn.apply(x, self.patch_embed.weight, self.patch_embed.bias, self.cls_token, pos, regs, scale, self.patch,
+                                         patch_idx, self.mask_token)
         chain = (not (self.use_grad_checkpoint and self.training) and type(self.norm) is LayerNorm and len(self.blocks) > 0
                  and all(type(b) is TransformerBlock and b._fusable() for b in self.blocks)
                  and all(b.norm1.eps == self.norm.eps for b in self.blocks))

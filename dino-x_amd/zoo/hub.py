@@ -4,7 +4,8 @@ HuggingFace id, and export it back.  Behaviour mirrors the reference (zoo/hub.py
 * ``load_model(path_or_id, *, device="cpu", config_override=None) -> PatchViT`` in eval mode;
 * ``*.pth`` file  -> training checkpoint (``student``/``model``/bare state dict; config =
   DEFAULT_CONFIG <- ckpt["config"]["model"] <- {img_size, scale_aware} <- override; old keys migrated;
-  ``backbone.`` stripped; ``head.*`` dropped; ``scale_embed.*`` dropped when not scale-aware; strict=False);
+  ``backbone.`` stripped; ``head.*`` and an iBOT run's ``mask_token`` dropped; ``scale_embed.*`` dropped when not scale-aware;
+  strict=False);
 * directory with ``config.json`` -> hub format (``backbone.safetensors`` preferred, else ``backbone.pth``;
   strict=True);
 * anything else -> ``huggingface_hub.snapshot_download`` (needs network);
@@ -105,7 +106,9 @@ def load_from_training_checkpoint(path: Union[str, Path], *, device: Union[str, 
     if any(k.startswith("backbone.") for k in sd):
         sd = _strip_prefix(sd, "backbone.")
     drop = ("head.",) if config.get("scale_aware", False) else ("head.", "scale_embed.")
-    sd = {k: v for k, v in sd.items() if not k.startswith(drop)}
+    # ``mask_token`` (an iBOT run's learned token for masked patches) is a training-only parameter: inference never masks, so the
+    # backbone is built without it and encode() of such a checkpoint equals encode() of the same weights without the key
+    sd = {k: v for k, v in sd.items() if not k.startswith(drop) and k != "mask_token"}
 
     backbone.load_state_dict(sd, strict=False)
     backbone.to(device).eval()

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define DINOX_ABI_VERSION 3   /* 3: + dinox_block_forward / _backward, dinox_gemm_timer_*, dinox_retrieval_* (later also dinox_retrieval_rank_windowed*, dinox_row_dots), dinox_knn_*, dinox_gram_*, dinox_softmax_probe*, dinox_ntxent_* (later also dinox_ntxent_*_rect), dinox_normalize_bwd, dinox_mae_*, dinox_attention_rows*, dinox_attention_rollout_step* (all additive: no entry
+#define DINOX_ABI_VERSION 3   /* 3: + dinox_block_forward / _backward, dinox_gemm_timer_*, dinox_retrieval_* (later also dinox_retrieval_rank_windowed*, dinox_row_dots), dinox_knn_*, dinox_gram_*, dinox_softmax_probe*, dinox_ntxent_* (later also dinox_ntxent_*_rect), dinox_normalize_bwd, dinox_mae_*, dinox_attention_rows*, dinox_attention_rollout_step*, dinox_ibot_*, dinox_gather_rows, dinox_scatter_add_rows (all additive: no entry
                                * of an earlier library changed, so the number callers test, dinox_version() == 3, stays; probe the symbol
                                * to learn whether a given build has the later additions) */
 
@@ -439,6 +439,38 @@ int dinox_mae_loss_fwd(const void* pred, const float* x, const int* ids_restore,
                        int Lk, int lead, int pred_dtype, void* stream);
 int dinox_mae_loss_bwd(const void* pred, const float* x, const int* ids_restore, void* dpred, float gscale, int V, int H, int W, int patch,
                        int Lk, int lead, int pred_dtype, int dpred_dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * iBOT masked-patch objective (extension; iBOT / DINOv2, not in the reference).  idx [M] int32 ON THE DEVICE: distinct flat patch
+ * positions v P + i of the [rows = V P][D] patch-product output.  An entry outside [0, rows) (or [0, src_rows) / [0, dst_rows)) is
+ * skipped: nothing is read or written for it.  fp32 math, fixed summation order, no atomics, no allocation, no synchronisation.
+ *   put_mask:         patches[idx[m]][:] = mask_token [D] fp32, rounded to `dtype`, in place.
+ *   put_mask_bwd:     dmask_token[d] = sum_m dpatches[idx[m]][d], ascending m within chunks of 64 rows, then the chunks in order
+ *                     (ws: ceil(M / 64) * D floats); then those rows of dpatches are set to exactly 0.  M <= 65535 * 64.
+ *   gather_rows:      dst[dst_row0 + m][:] = src[row[m]][:]   (src fp32 [src_rows][D]; dst in dst_dtype): dinox_take_rows by index.
+ *   scatter_add_rows: dst[row[m]][:] += src[src_row0 + m][:]  (dst fp32 [dst_rows][D]); the rows must be distinct.
+ *   ibot_ce:          s, t [M][K] fp32, center [K], w [M]:  p_t[m] = softmax((t[m] - center) / teacher_temp),
+ *                     row_loss[m] = -sum_k p_t[m][k] log_softmax(s[m] / student_temp)[k],   loss[0] = scale * sum_m w[m] row_loss[m]
+ *                     (one workgroup, index order),   ds[m] = grad_scale * scale * w[m] * (softmax(s[m] / student_temp) - p_t[m]) /
+ *                     student_temp, or ds NULL.  ds must not overlap s or t.  Log-sum-exp form: finite inputs give finite outputs.
+ *                     K % 4 == 0, K <= 8192 and 16-byte aligned s, t, center, ds: every row is loaded once and held in registers
+ *                     (each matrix crosses the bus once); anything else takes a scalar kernel that re-reads the row.
+ *   ibot_center_ema:  center[k] = center[k] momentum + (sum_count[k] / sum_count[K]) (1 - momentum): the patch centre from the column
+ *                     sums of the masked teacher rows and their number (sum_count [K + 1] fp32, possibly added up over ranks); a number
+ *                     below 1 leaves the centre untouched.
+ * DINOX_EINVAL before any launch: a null pointer (ds excepted), M < 1, K < 1, D < 1, rows < 1, a temperature <= 0, a dtype other than
+ * DINOX_F32 / DINOX_BF16.
+ * ------------------------------------------------------------------------------------------ */
+int dinox_ibot_put_mask(void* patches, const float* mask_token, const int* idx, int M, int64_t rows, int D, int dtype, void* stream);
+int dinox_ibot_put_mask_bwd(void* dpatches, const int* idx, float* dmask_token, float* ws, int M, int64_t rows, int D, int dtype,
+                            void* stream);
+int dinox_gather_rows(const float* src, const int* row, void* dst, int64_t M, int64_t src_rows, int D, int64_t dst_row0, int dst_dtype,
+                      void* stream);
+int dinox_scatter_add_rows(const void* src, const int* row, float* dst, int64_t M, int64_t dst_rows, int D, int64_t src_row0, int src_dtype,
+                           void* stream);
+int dinox_ibot_ce(const float* s, const float* t, const float* center, const float* w, float student_temp, float teacher_temp, float scale,
+                  float grad_scale, float* loss, float* ds, float* row_loss, int M, int K, void* stream);
+int dinox_ibot_center_ema(float* center, const float* sum_count, float momentum, int K, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Attention rows -- the softmax rows of a few query tokens (CLS, the registers) over all keys, per head: the attention map the
