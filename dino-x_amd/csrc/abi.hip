@@ -316,3 +316,59 @@ extern "C" int dinox_ibot_center_ema(float* center, const float* sum_count, floa
   DX_REQUIRE(center && sum_count && K >= 1, DINOX_EINVAL, "ibot_center_ema: bad arguments");
   return dinox::launch_ibot_center_ema(center, sum_count, momentum, K, dinox::as_stream(stream));
 }
+
+// ---------------------------------------------------------------- LoRA low-rank products (kernels: lora.hip)
+static bool lora_rank_ok(int r) { return r >= 1 && r <= dinox::LORA_MAX_RANK; }
+static bool lora_dim_ok(int d) { return d >= 1 && d <= (1 << 20); }
+static bool lora_rows_ok(int64_t M) { return M >= 1 && M <= 0x7fffffff; }
+
+extern "C" int dinox_lora_down(const void* x, const float* small, float* u, int64_t M, int K, int r, int small_layout, int dtype, void* stream) {
+  DX_REQUIRE(x && small && u, DINOX_EINVAL, "lora_down: null pointer");
+  DX_REQUIRE(mae_dtype_ok(dtype) && (small_layout == 0 || small_layout == 1), DINOX_EINVAL, "lora_down: dtype %d, small_layout %d", dtype,
+             small_layout);
+  DX_REQUIRE(lora_rank_ok(r), DINOX_EINVAL, "lora_down: r=%d (1 <= r <= %d)", r, dinox::LORA_MAX_RANK);
+  DX_REQUIRE(lora_rows_ok(M) && lora_dim_ok(K), DINOX_EINVAL, "lora_down: M=%lld K=%d (1 <= M <= 2^31 - 1; 1 <= K <= 2^20)", (long long)M, K);
+  return dinox::launch_lora_down(x, small, u, M, K, r, small_layout, dtype, dinox::as_stream(stream));
+}
+
+extern "C" int dinox_lora_up(const float* u, const float* small, const float* res, float* t, float s, int64_t M, int N, int r, int small_layout,
+                             void* stream) {
+  DX_REQUIRE(u && small && t, DINOX_EINVAL, "lora_up: null pointer");
+  DX_REQUIRE(small_layout == 0 || small_layout == 1, DINOX_EINVAL, "lora_up: small_layout %d", small_layout);
+  DX_REQUIRE(lora_rank_ok(r), DINOX_EINVAL, "lora_up: r=%d (1 <= r <= %d)", r, dinox::LORA_MAX_RANK);
+  DX_REQUIRE(lora_rows_ok(M) && lora_dim_ok(N) && dinox::lora_up_grid_ok(M, N), DINOX_EINVAL,
+             "lora_up: M=%lld N=%d (1 <= M <= 2^31 - 1; 1 <= N <= 2^20; M N / 4 <= 2^39)", (long long)M, N);
+  return dinox::launch_lora_up(u, small, res, t, s, M, N, r, small_layout, dinox::as_stream(stream));
+}
+
+extern "C" int64_t dinox_lora_grad_ws_bytes(int64_t M, int K, int N, int r) {
+  if (!(lora_rows_ok(M) && lora_dim_ok(K) && lora_dim_ok(N) && lora_rank_ok(r))) return 0;
+  return dinox::lora_grad_chunks(M) * ((int64_t)r * K + (int64_t)N * r) * (int64_t)sizeof(float);
+}
+
+extern "C" int dinox_lora_grad(const void* xl, const void* dy, const float* A, const float* B, float s, float* dA, float* dB, float* ws, int64_t M,
+                               int K, int N, int r, int dtype, void* stream) {
+  DX_REQUIRE(xl && dy && A && B && dA && dB && ws, DINOX_EINVAL, "lora_grad: null pointer");
+  DX_REQUIRE(mae_dtype_ok(dtype), DINOX_EINVAL, "lora_grad: dtype %d", dtype);
+  DX_REQUIRE(lora_rank_ok(r), DINOX_EINVAL, "lora_grad: r=%d (1 <= r <= %d)", r, dinox::LORA_MAX_RANK);
+  DX_REQUIRE(lora_rows_ok(M) && lora_dim_ok(K) && lora_dim_ok(N), DINOX_EINVAL, "lora_grad: M=%lld K=%d N=%d (1 <= M <= 2^31 - 1; 1 <= K, N <= 2^20)",
+             (long long)M, K, N);
+  return dinox::launch_lora_grad(xl, dy, A, B, s, dA, dB, ws, M, K, N, r, dtype, dinox::as_stream(stream));
+}
+
+extern "C" int dinox_lora_dropout(const void* in, void* out, int64_t n, float p, uint64_t seed, uint64_t offset, int dtype, void* stream) {
+  DX_REQUIRE(in && out, DINOX_EINVAL, "lora_dropout: null pointer");
+  DX_REQUIRE(mae_dtype_ok(dtype), DINOX_EINVAL, "lora_dropout: dtype %d", dtype);
+  DX_REQUIRE(p >= 0.f && p < 1.f, DINOX_EINVAL, "lora_dropout: p=%g outside [0, 1)", (double)p);
+  DX_REQUIRE(n >= 1 && n <= ((int64_t)1 << 40), DINOX_EINVAL, "lora_dropout: n=%lld (1 <= n <= 2^40)", (long long)n);
+  return dinox::launch_lora_dropout(in, out, n, p, seed, offset, dtype, dinox::as_stream(stream));
+}
+
+extern "C" int dinox_lora_merge(const float* w, const float* A, const float* B, float* w_out, float s, int sign, int N, int K, int r, void* stream) {
+  DX_REQUIRE(w && A && B && w_out, DINOX_EINVAL, "lora_merge: null pointer");
+  DX_REQUIRE(sign == 1 || sign == -1, DINOX_EINVAL, "lora_merge: sign %d (+1 merges, -1 unmerges)", sign);
+  DX_REQUIRE(lora_rank_ok(r), DINOX_EINVAL, "lora_merge: r=%d (1 <= r <= %d)", r, dinox::LORA_MAX_RANK);
+  DX_REQUIRE(lora_dim_ok(N) && lora_dim_ok(K) && dinox::lora_up_grid_ok(N, K), DINOX_EINVAL, "lora_merge: N=%d K=%d (1 <= N, K <= 2^20)", N, K);
+  // w_out[n][k] = w[n][k] + (sign s) sum_j B[n][j] A[j][k]: the up product with B as its rows and A stored [r][K]
+  return dinox::launch_lora_up(B, A, w, w_out, (float)sign * s, N, K, r, 1, dinox::as_stream(stream));
+}

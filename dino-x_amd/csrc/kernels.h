@@ -123,6 +123,17 @@ int launch_ibot_ce(const float* s, const float* t, const float* center, const fl
                    float* loss, float* ds, float* row_loss, int M, int K, hipStream_t st);
 int launch_ibot_center_ema(float* center, const float* sum_count, float momentum, int K, hipStream_t st);
 
+// ---------------------------------------------------------------- LoRA low-rank products (lora.hip; entry points and argument checks: abi.hip)
+constexpr int LORA_MAX_RANK = 64;          // two 32-wide accumulator blocks per wave; u and v of one row chunk (2 x 128 x r floats) sit in LDS beside a 66 KiB tile
+constexpr int LORA_GRAD_CHUNK = 128;       // rows per partial sum of dinox_lora_grad: ws holds ceil(M / 128) x (r K + N r) floats
+int launch_lora_down(const void* x, const float* S, float* u, int64_t M, int Kd, int r, int layout, int dtype, hipStream_t st);
+bool lora_up_grid_ok(int64_t M, int N);
+int launch_lora_up(const float* u, const float* S, const float* res, float* t, float s, int64_t M, int N, int r, int layout, hipStream_t st);
+int64_t lora_grad_chunks(int64_t M);
+int launch_lora_grad(const void* xl, const void* dy, const float* A, const float* B, float s, float* dA, float* dB, float* ws, int64_t M, int K,
+                     int N, int r, int dtype, hipStream_t st);
+int launch_lora_dropout(const void* in, void* out, int64_t n, float p, uint64_t seed, uint64_t offset, int dtype, hipStream_t st);
+
 // ---------------------------------------------------------------- launch glue shared by the NT launchers
 // Activation index of the <OUT, ACT, RES> kernels (gemm_bf16_pp / _pp128 / _areg): the template argument ACT.
 enum { EPI_ACT_PLAIN = 0, EPI_ACT_GELU = 1, EPI_ACT_DGELU = 2 };

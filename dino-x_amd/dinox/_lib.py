@@ -138,6 +138,12 @@ SIGNATURES = {
     "dinox_scatter_add_rows": (i32, [vp, vp, vp, i64, i64, i32, i64, i32, vp]),
     "dinox_ibot_ce": (i32, [vp, vp, vp, vp, f32, f32, f32, f32, vp, vp, vp, i32, i32, vp]),
     "dinox_ibot_center_ema": (i32, [vp, vp, f32, i32, vp]),
+    "dinox_lora_down": (i32, [vp, vp, vp, i64, i32, i32, i32, i32, vp]),
+    "dinox_lora_up": (i32, [vp, vp, vp, vp, f32, i64, i32, i32, i32, vp]),
+    "dinox_lora_grad_ws_bytes": (i64, [i64, i32, i32, i32]),
+    "dinox_lora_grad": (i32, [vp, vp, vp, vp, f32, vp, vp, vp, i64, i32, i32, i32, i32, vp]),
+    "dinox_lora_dropout": (i32, [vp, vp, i64, f32, C.c_uint64, C.c_uint64, i32, vp]),
+    "dinox_lora_merge": (i32, [vp, vp, vp, vp, f32, i32, i32, i32, i32, vp]),
     "dinox_attention_rows_ok": (i32, [i32, i32, i32, i32, i32]),
     "dinox_attention_rows": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "dinox_attention_rollout_step_ok": (i32, [i32, i32, i32, i32]),

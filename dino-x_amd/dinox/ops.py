@@ -430,10 +430,16 @@ class _WeightCache:
 weight_cache = _WeightCache()
 
 
-def invalidate_weights() -> None:
-    """Drop every cached bf16 weight image.  For callers that modify master weights through raw device pointers (the C ABI's
-    ``dinox_adamw_ema``, a custom optimiser): torch's version counter does not see such writes."""
-    weight_cache.clear()
+def invalidate_weights(params=None) -> None:
+    """Drop every cached bf16 weight image -- or, with ``params``, only the images of those tensors.  For callers that modify master
+    weights through raw device pointers (the C ABI's ``dinox_adamw_ema``, a custom optimiser): torch's version counter does not see
+    such writes."""
+    if params is None:
+        weight_cache.clear()
+        return
+    for p in params:
+        weight_cache.d.pop((id(p), False), None)
+        weight_cache.d.pop((id(p), True), None)
 
 
 def weight_operand(w: Tensor, dt: torch.dtype, transposed=False) -> Tensor:
@@ -1226,6 +1232,156 @@ class LinearFn(torch.autograd.Function):
             db = colsum(dy2)
         dres = dy if ctx.has_res else None
         return dx, dw, db, dres, None
+
+
+# ------------------------------------------------------------------------------------------
+# LoRA: the low-rank side of a wrapped linear layer (csrc/lora.hip)
+# ------------------------------------------------------------------------------------------
+def _lora_small(t: Tensor, what: str) -> Tensor:
+    if t.dtype != torch.float32:
+        raise TypeError(f"{what} must be float32 (the adapter matrices are never rounded), got {t.dtype}")
+    return _c(t.detach())
+
+
+def lora_down(x: Tensor, small: Tensor, layout: int = 0) -> Tensor:
+    """u [M,r] fp32 = x [M,K] . S: layout 0 takes S = A stored [r,K] (u = xl A^T), layout 1 takes S = B stored [K,r] (v = dy B)."""
+    _need_cuda(x, small)
+    x, small = _c(x), _lora_small(small, "lora_down: the small matrix")
+    M, K = x.shape
+    r = small.shape[1] if layout else small.shape[0]
+    assert small.shape == ((K, r) if layout else (r, K)), (tuple(x.shape), tuple(small.shape), layout)
+    u = torch.empty((M, r), dtype=torch.float32, device=x.device)
+    check(lib.dinox_lora_down(_p(x), _p(small), _p(u), M, K, r, int(layout), _code(x.dtype), _stream()), "dinox_lora_down")
+    return u
+
+
+def lora_up(u: Tensor, small: Tensor, s: float, res: Optional[Tensor] = None, layout: int = 0, out: Optional[Tensor] = None) -> Tensor:
+    """t [M,N] fp32 = s u [M,r] . S (+ res): layout 0 takes S = B stored [N,r], layout 1 takes S = A stored [r,N]."""
+    _need_cuda(u, small)
+    u, small = _lora_small(u, "lora_up: u"), _lora_small(small, "lora_up: the small matrix")
+    M, r = u.shape
+    N = small.shape[1] if layout else small.shape[0]
+    assert small.shape == ((r, N) if layout else (N, r)), (tuple(u.shape), tuple(small.shape), layout)
+    if res is not None:
+        assert res.dtype == torch.float32 and res.is_contiguous() and res.numel() == M * N
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=u.device)
+    else:
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == M * N
+    check(lib.dinox_lora_up(_p(u), _p(small), _p(res), _p(out), float(s), M, N, r, int(layout), _stream()), "dinox_lora_up")
+    return out
+
+
+def lora_grad(xl: Tensor, dy: Tensor, A: Tensor, B: Tensor, s: float):
+    """(dA [r,K], dB [N,r]) = (s v^T xl, s dy^T u) with u = xl A^T and v = dy B formed on chip: xl and dy are read once."""
+    _need_cuda(xl, dy, A, B)
+    assert xl.dtype == dy.dtype and xl.dim() == 2 and dy.dim() == 2 and xl.shape[0] == dy.shape[0]
+    xl, dy, A, B = _c(xl), _c(dy), _lora_small(A, "lora_grad: A"), _lora_small(B, "lora_grad: B")
+    M, K = xl.shape
+    N, r = B.shape
+    assert A.shape == (r, K) and dy.shape[1] == N
+    need = lib.dinox_lora_grad_ws_bytes(M, K, N, r)
+    if need <= 0:
+        raise ValueError(f"lora_grad: M={M} K={K} N={N} r={r} outside the kernel's range (1 <= r <= 64)")
+    ws = torch.empty(need // 4, dtype=torch.float32, device=xl.device)
+    dA, dB = torch.empty_like(A), torch.empty_like(B)
+    check(lib.dinox_lora_grad(_p(xl), _p(dy), _p(A), _p(B), float(s), _p(dA), _p(dB), _p(ws), M, K, N, r, _code(xl.dtype), _stream()),
+          "dinox_lora_grad")
+    return dA, dB
+
+
+def lora_dropout(x: Tensor, p: float, seed: int, offset: int, out: Optional[Tensor] = None) -> Tensor:
+    """x keep / (1 - p) with keep recomputed from (seed, offset, flat element index): no mask is stored (include/dinox.h has the hash)."""
+    _need_cuda(x)
+    x = _c(x)
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        assert out.dtype == x.dtype and out.is_contiguous() and out.numel() == x.numel()
+    check(lib.dinox_lora_dropout(_p(x), _p(out), x.numel(), float(p), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), _code(x.dtype),
+                                 _stream()), "dinox_lora_dropout")
+    return out
+
+
+def lora_merge(w: Tensor, A: Tensor, B: Tensor, s: float, sign: int = 1, out: Optional[Tensor] = None) -> Tensor:
+    """W + sign s B A in fp32 (sign -1 takes a merged adapter out again); out may be w itself."""
+    _need_cuda(w, A, B)
+    assert w.dtype == torch.float32 and w.is_contiguous() and w.dim() == 2
+    A, B = _lora_small(A, "lora_merge: A"), _lora_small(B, "lora_merge: B")
+    N, K = w.shape
+    r = A.shape[0]
+    assert A.shape == (r, K) and B.shape == (N, r)
+    if out is None:
+        out = torch.empty_like(w)
+    else:
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == w.shape
+    check(lib.dinox_lora_merge(_p(w), _p(A), _p(B), _p(out), float(s), int(sign), N, K, r, _stream()), "dinox_lora_merge")
+    return out
+
+
+class LoraLinearFn(torch.autograd.Function):
+    """y = x W^T + b + s (xl A^T) B^T (+ residual); xl = dropout(x) when p > 0, else x.  The base product is LinearFn's dinox_gemm call;
+    the low-rank term (plus the residual) reaches it as its fp32 RESIDUAL input, so it meets the base product in fp32 and the sum is
+    rounded once -- it is never folded into a bf16 image of W.  A, B, u and v are fp32 in both modes.  With A None: LinearFn.
+    Saved for backward: xl only if A or B needs a gradient, x2 only if the base weight does (so a frozen base with dropout keeps one
+    activation, not two), and the dropout integers; u is not saved -- dinox_lora_grad forms u and v of a row chunk on chip."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, A, B, s, p, seed, offset, residual, out_dtype):
+        _need_cuda(x, w, A, B)
+        dt = current_dtype()
+        xm = to_mode(x, dt)
+        K, N = xm.shape[-1], w.shape[0]
+        x2 = xm.reshape(-1, K)
+        drop = p > 0.0
+        xl = lora_dropout(x2, p, seed, offset) if drop else x2
+        res2 = None if residual is None else _c(residual).reshape(-1, N)
+        t = lora_up(lora_down(xl, A, 0), B, s, res=res2, layout=0)
+        odt = torch.float32 if residual is not None else (out_dtype or dt)
+        y = gemm(x2, weight_operand(w, dt), bias=b, residual=t, out_dtype=odt)
+        ctx.save_for_backward(x2 if ctx.needs_input_grad[1] else None, xl if (ctx.needs_input_grad[3] or ctx.needs_input_grad[4]) else None,
+                              w, b, A, B)
+        if ctx.needs_input_grad[1]:
+            grad_sink.use(w, b if ctx.needs_input_grad[2] else None)
+        ctx.dt, ctx.has_bias, ctx.has_res, ctx.xshape, ctx.xdtype = dt, b is not None, residual is not None, x.shape, x.dtype
+        ctx.s, ctx.drop = float(s), ((float(p), int(seed), int(offset)) if drop else None)
+        return y.reshape(*x.shape[:-1], N)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, xl, w, b, A, B = ctx.saved_tensors
+        dt, s = ctx.dt, ctx.s
+        dy2 = to_mode(dy.reshape(-1, w.shape[0]), dt)
+        dx = dw = db = dA = dB = None
+        if ctx.needs_input_grad[0]:
+            t = lora_up(lora_down(dy2, B, 1), A, s, layout=1)                                    # s (dy B) A, fp32 [M,K]
+            if ctx.drop is not None:
+                lora_dropout(t, *ctx.drop, out=t)                                               # the forward's mask, recomputed
+            dx = dx_product(dy2, w, dt, residual=t, out_dtype=dt if dt == torch.bfloat16 else ctx.xdtype)
+            if dx.dtype != ctx.xdtype:
+                dx = dx.to(ctx.xdtype)
+            dx = dx.reshape(ctx.xshape)
+        want_db = ctx.has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1]:
+            dw, db = weight_grad(dy2, x2, w, b, want_db)
+        elif want_db:
+            db = colsum(dy2)
+        if ctx.needs_input_grad[3] or ctx.needs_input_grad[4]:
+            dA, dB = lora_grad(xl, dy2, A, B, s)
+        dres = dy if ctx.has_res else None
+        return dx, dw, db, dA, dB, None, None, None, None, dres, None
+
+
+def lora_linear(x: Tensor, w: Tensor, b: Optional[Tensor], A: Optional[Tensor], B: Optional[Tensor], s: float, p: float, seed_offset,
+                residual: Optional[Tensor] = None, out_dtype: Optional[torch.dtype] = None) -> Tensor:
+    """A LoRA-wrapped linear layer.  ``p`` is the dropout probability that applies to THIS call (0 in eval mode); ``seed_offset`` is the
+    (seed, offset) pair the dropout mask is recomputed from.  ``A is None`` is the plain layer, bit for bit ``LinearFn``."""
+    if A is None:
+        return LinearFn.apply(x, w, b, residual, out_dtype)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"lora_linear: dropout probability {p} outside [0, 1)")
+    seed, offset = seed_offset if seed_offset is not None else (0, 0)
+    return LoraLinearFn.apply(x, w, b, A, B, float(s), float(p), int(seed), int(offset), residual, out_dtype)
 
 
 def mlp_forward(x2: Tensor, w1: Tensor, b1: Optional[Tensor], w2: Tensor, b2: Optional[Tensor], residual: Optional[Tensor],

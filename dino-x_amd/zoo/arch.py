@@ -70,7 +70,7 @@ class Attention(nn.Module):
     def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
         qkv = self.qkv(x)                                     # packed [B, N, 3, h, d]; never permuted or copied
         o = ops.AttentionCoreFn.apply(qkv, self.num_heads)    # [B, N, h*d]
-        if type(self.proj) is Linear:
+        if type(self.proj) is Linear or getattr(self.proj, "takes_residual", False):      # (a zoo.peft.LoraLinear adds it in its product too)
             return self.proj(o, residual=residual)
         y = self.proj(o)
         return y if residual is None else residual + y
@@ -89,7 +89,10 @@ class Mlp(nn.Module):
     def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
         if type(self.fc1) is Linear and type(self.fc2) is Linear:
             return ops.MlpFn.apply(x, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, residual, None)
-        y = self.fc2(self.act(self.fc1(x)))
+        h = self.act(self.fc1(x))
+        if type(self.fc2) is Linear or getattr(self.fc2, "takes_residual", False):
+            return self.fc2(h, residual=residual)
+        y = self.fc2(h)
         return y if residual is None else residual + y
 
 

@@ -1,7 +1,8 @@
 """``zoo.hub`` surface: build a PatchViT (HIP engine) from a training checkpoint, a hub directory or a
 HuggingFace id, and export it back.  Behaviour mirrors the reference (zoo/hub.py:74-327):
 
-* ``load_model(path_or_id, *, device="cpu", config_override=None) -> PatchViT`` in eval mode;
+* ``load_model(path_or_id, *, device="cpu", config_override=None) -> PatchViT`` in eval mode (extension: ``adapter=DIR`` puts a
+  stored LoRA adapter on it, ``zoo.peft.load_adapter``);
 * ``*.pth`` file  -> training checkpoint (``student``/``model``/bare state dict; config =
   DEFAULT_CONFIG <- ckpt["config"]["model"] <- {img_size, scale_aware} <- override; old keys migrated;
   ``backbone.`` stripped; ``head.*`` and an iBOT run's ``mask_token`` dropped; ``scale_embed.*`` dropped when not scale-aware;
@@ -143,7 +144,10 @@ def load_from_hub_dir(model_dir: Union[str, Path], *, device: Union[str, torch.d
 
 
 def load_model(model_id_or_path: str, *, device: Union[str, torch.device] = "cpu",
-               config_override: Dict[str, Any] | None = None) -> PatchViT:
+               config_override: Dict[str, Any] | None = None, adapter: Union[str, Path, None] = None) -> PatchViT:
+    if adapter is not None:                 # extension: load_adapter(load_model(...), adapter) in one call
+        from zoo.peft import load_adapter
+        return load_adapter(load_model(model_id_or_path, device=device, config_override=config_override), adapter)
     p = Path(model_id_or_path)
     if p.is_file() and p.suffix == ".pth":
         return load_from_training_checkpoint(p, device=device, config_override=config_override)

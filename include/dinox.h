@@ -738,6 +738,37 @@ int dinox_softmax_probe(const float* x, int64_t ldx, const int32_t* label, int64
                         double* grad, float* prob, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * LoRA: the low-rank side of a wrapped linear layer (kernels: csrc/lora.hip; autograd node: dinox.ops.LoraLinearFn).  One layer is
+ *   y = x W^T + b + s (xl A^T) B^T (+ residual),   x [M][K], W [N][K], A [r][K], B [N][r], s = alpha / r, xl = x or dropout(x).
+ * The base product stays dinox_gemm; the low-rank term reaches it as its fp32 RESIDUAL input, so it is never folded into a bf16 weight.
+ * A, B, u = xl A^T, v = dy B and every sum are fp32; `dtype` is the dtype of the activation operand (DINOX_F32 or DINOX_BF16).
+ * Every entry checks its arguments on the host (DINOX_EINVAL and a message before any launch), allocates nothing, does not synchronise,
+ * uses plain stores only and a fixed summation order: equal inputs give equal bits.  1 <= r <= 64; M, K, N >= 1; M <= 2^31 - 1;
+ * K, N <= 2^20; rows are dense (row stride = row length).
+ *
+ * dinox_lora_down:  u[M][r] (fp32) = x[M][K] . S, one ascending-k chain per lane and a fixed wave tree.  small_layout 0: S is stored [r][K]
+ *   (u = xl A^T with S = A); small_layout 1: S is stored [K][r] (v = dy B with S = B, K standing for the layer's N).
+ * dinox_lora_up:    t[M][N] (fp32) = s . u[M][r] . S (+ res[M][N] fp32, NULL: none; res == t is allowed).  small_layout 0: S is stored [N][r]
+ *   (the forward term, S = B); small_layout 1: S is stored [r][N] (the dX term s (v A), S = A and N standing for the layer's K).
+ * dinox_lora_grad:  dA[r][K] = s v^T xl and dB[N][r] = s dy^T u with u = xl A^T, v = dy B formed on chip, xl and dy read once from memory.
+ *   Workgroup c takes rows [128 c, 128 c + 128), writes its partial sums to ws (dinox_lora_grad_ws_bytes(M, K, N, r) bytes, contents need not
+ *   be initialised); a second launch adds the partials in ascending c and applies s.  Nothing outside dA, dB and that many bytes of ws is written.
+ * dinox_lora_dropout: out[i] = keep(i) ? in[i] / (1 - p) : 0 for i < n, 0 <= p < 1, in == out allowed.  No mask is stored:
+ *   keep(i) = (h(i) >> 8) >= ceil(p 2^24),   h(i) = mix(lo32(i) ^ mix(hi32(i) + key)),
+ *   key = mix(lo32(offset) ^ mix(hi32(offset) + mix(lo32(seed) ^ mix(hi32(seed) + 0x9e3779b9)))),   all in uint32 arithmetic,
+ *   mix(x): x ^= x >> 16; x *= 0x21f0aaad; x ^= x >> 15; x *= 0x735a2d97; x ^= x >> 15.
+ * dinox_lora_merge: w_out[N][K] (fp32) = w[N][K] + sign . s . B A, sign = +1 (merge) or -1 (unmerge); w_out == w is allowed.
+ * ------------------------------------------------------------------------------------------ */
+int dinox_lora_down(const void* x, const float* small, float* u, int64_t M, int K, int r, int small_layout, int dtype, void* stream);
+int dinox_lora_up(const float* u, const float* small, const float* res, float* t, float s, int64_t M, int N, int r, int small_layout,
+                  void* stream);
+int64_t dinox_lora_grad_ws_bytes(int64_t M, int K, int N, int r);
+int dinox_lora_grad(const void* xl, const void* dy, const float* A, const float* B, float s, float* dA, float* dB, float* ws, int64_t M, int K,
+                    int N, int r, int dtype, void* stream);
+int dinox_lora_dropout(const void* in, void* out, int64_t n, float p, uint64_t seed, uint64_t offset, int dtype, void* stream);
+int dinox_lora_merge(const float* w, const float* A, const float* B, float* w_out, float s, int sign, int N, int K, int r, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-launch timing of dinox_gemm (diagnostic; bench.py's roofline object).  Between start and stop every dinox_gemm launch -- also
  * the ones dinox_block_* issue -- is counted per (kernel, shape, epilogue), and one launch in `every` (a fixed hash of the launch
  * counter) is bracketed by a HIP event pair on its stream.  stop synchronises those events and writes one text line per shape into
