@@ -15,7 +15,7 @@
 // K-step ahead into registers and written to the other LDS stage after the MFMAs (one barrier per step).
 // Workgroup ids are remapped so that each XCD walks a contiguous run of tiles: the N-tiles that share an
 // A row-panel hit that XCD's private L2 (cdna_hip_programming.md T1, bijective form).
-#include "common.h"
+#include "small_common.h"
 #include "kernels.h"
 
 namespace dinox {
@@ -537,7 +537,6 @@ static void tn_split_plan(const GemmParams& p, int& splits, int64_t& kps) {
   splits = (int)ceil_div(p.K, kps);
 }
 
-static bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 // Which NT products take the persistent ping-pong kernels (gemm_bf16_pp.hip: 256 x 256 tiles, gemm_bf16_pp128.hip: 256 x 128), and which
 // of the two.  DINOX_NT_PP (read per call, so one process can A/B and the tests can force small shapes onto them): 0 = never; 1 = every

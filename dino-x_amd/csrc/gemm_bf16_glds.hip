@@ -17,7 +17,7 @@
 //     rational erf instead of erff.
 // Envelope: K % 64 == 0, N % 8 == 0, 16-B aligned operands/outputs; anything else takes gemm_bf16_nt.
 
-#include "common.h"
+#include "small_common.h"
 #include "kernels.h"
 
 namespace dinox {
@@ -329,18 +329,17 @@ __global__ __launch_bounds__(256, (GG_BM == 256 ? 2 : (GG_BK == 64 ? 2 : 3))) vo
   }
 }
 
-static bool al16(const void* q) { return (((uintptr_t)q) & 15) == 0; }
 
 bool gemm_bf16_nt_glds_ok(const GemmParams& p) {
   if (p.in_dtype != DINOX_BF16 || p.transA || p.transB) return false;
   if ((p.K % 64) || (p.N & 7) || (p.lda & 7) || (p.ldb & 7) || (p.strideA & 7) || (p.strideB & 7)) return false;
-  if (!al16(p.A) || !al16(p.B) || !al16(p.C)) return false;
+  if (!aligned16(p.A) || !aligned16(p.B) || !aligned16(p.C)) return false;
   const int esz = p.out_dtype == DINOX_BF16 ? 2 : 4;
   if ((p.ldc * esz) & 15 || (p.strideC * esz) & 15) return false;
   if (p.epilogue & DINOX_EPI_ACCUM) return false;
-  if ((p.epilogue & DINOX_EPI_BIAS) && !al16(p.bias)) return false;
-  if ((p.epilogue & DINOX_EPI_RESIDUAL) && (!al16(p.residual) || (p.ldr & 3))) return false;
-  if ((p.epilogue & (DINOX_EPI_GELU | DINOX_EPI_DGELU)) && p.aux && (!al16(p.aux) || ((p.ldaux * esz) & 15))) return false;
+  if ((p.epilogue & DINOX_EPI_BIAS) && !aligned16(p.bias)) return false;
+  if ((p.epilogue & DINOX_EPI_RESIDUAL) && (!aligned16(p.residual) || (p.ldr & 3))) return false;
+  if ((p.epilogue & (DINOX_EPI_GELU | DINOX_EPI_DGELU)) && p.aux && (!aligned16(p.aux) || ((p.ldaux * esz) & 15))) return false;
   if (p.batch > 65535) return false;
   return true;
 }

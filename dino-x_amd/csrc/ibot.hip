@@ -7,17 +7,12 @@
 //     ibot_ce           centring / sharpening cross-entropy of M unpaired rows with per-row weights, loss and d loss / d logits
 // fp32 math.  No float atomics: every sum has a fixed order (stated at each kernel), so a step is bit-reproducible.  Every index read from
 // device memory is range-checked before it becomes an address; an entry outside is skipped.
-#include "common.h"
+#include "small_common.h"
 #include "kernels.h"
 
 namespace dinox {
 
 constexpr int IB_THREADS = 256;
-
-static unsigned ib_grid(int64_t total) {
-  const int64_t b = ceil_div(total, IB_THREADS);
-  return (unsigned)(b < 1 ? 1 : (b < 4096 ? b : 4096));
-}
 
 // ---------------------------------------------------------------- mask token in / out of the patch rows
 template <int DT>
@@ -205,9 +200,7 @@ __global__ __launch_bounds__(IB_THREADS) void ibot_ce_scalar_kernel(const float*
 __global__ __launch_bounds__(IB_THREADS) void ibot_weighted_sum_kernel(const float* __restrict__ row_loss, const float* __restrict__ w, int M,
                                                                        float scale, float* __restrict__ loss) {
   __shared__ float red[16];
-  float a = 0.f;
-  for (int m = threadIdx.x; m < M; m += IB_THREADS) a += w[m] * row_loss[m];
-  a = block_sum(a, red);
+  const float a = block_strided_sum(row_loss, w, M, red);
   if (threadIdx.x == 0) loss[0] = a * scale;
 }
 
@@ -220,42 +213,36 @@ __global__ __launch_bounds__(IB_THREADS) void ibot_center_ema_kernel(float* __re
 }
 
 // ---------------------------------------------------------------- launchers (arguments were validated by the entry points in abi.hip)
-#define IB_LAUNCH_DT(kern, dtype, grid, st, ...)                                                                  \
-  do {                                                                                                            \
-    if ((dtype) == DINOX_F32) hipLaunchKernelGGL((kern<DINOX_F32>), grid, dim3(IB_THREADS), 0, st, __VA_ARGS__);  \
-    else hipLaunchKernelGGL((kern<DINOX_BF16>), grid, dim3(IB_THREADS), 0, st, __VA_ARGS__);                      \
-  } while (0)
-
 int launch_ibot_put_mask(void* patches, const float* mask_token, const int* idx, int M, int64_t rows, int D, int dtype, hipStream_t st) {
-  IB_LAUNCH_DT(ibot_put_mask_kernel, dtype, dim3(ib_grid((int64_t)M * D)), st, patches, mask_token, idx, M, rows, D);
+  DX_LAUNCH_DT(ibot_put_mask_kernel, dtype, dim3(grid_1d((int64_t)M * D, IB_THREADS, 4096)), dim3(IB_THREADS), st, patches, mask_token, idx, M, rows, D);
   return check_launch("ibot_put_mask");
 }
 
 int launch_ibot_put_mask_bwd(void* dpatches, const int* idx, float* dmask, float* ws, int M, int64_t rows, int D, int dtype, hipStream_t st) {
   const int chunks = (int)ceil_div(M, IBOT_MASK_CHUNK), col_blocks = (int)ceil_div(D, IB_THREADS);
-  IB_LAUNCH_DT(ibot_mask_partial_kernel, dtype, dim3((unsigned)col_blocks, (unsigned)chunks), st, dpatches, idx, ws, M, rows, D);
+  DX_LAUNCH_DT(ibot_mask_partial_kernel, dtype, dim3((unsigned)col_blocks, (unsigned)chunks), dim3(IB_THREADS), st, dpatches, idx, ws, M, rows, D);
   int rc = check_launch("ibot_put_mask_bwd");
   if (rc) return rc;
-  const dim3 grid((unsigned)col_blocks + ib_grid((int64_t)M * D));
-  IB_LAUNCH_DT(ibot_mask_combine_kernel, dtype, grid, st, dpatches, idx, ws, dmask, M, rows, D, chunks, col_blocks);
+  const dim3 grid((unsigned)col_blocks + grid_1d((int64_t)M * D, IB_THREADS, 4096));
+  DX_LAUNCH_DT(ibot_mask_combine_kernel, dtype, grid, dim3(IB_THREADS), st, dpatches, idx, ws, dmask, M, rows, D, chunks, col_blocks);
   return check_launch("ibot_put_mask_bwd_combine");
 }
 
 int launch_gather_rows(const float* src, const int* row, void* dst, int64_t M, int64_t src_rows, int D, int64_t dst_row0, int dtype,
                        hipStream_t st) {
-  IB_LAUNCH_DT(gather_rows_kernel, dtype, dim3(ib_grid(M * D)), st, src, row, dst, M, src_rows, D, dst_row0);
+  DX_LAUNCH_DT(gather_rows_kernel, dtype, dim3(grid_1d(M * D, IB_THREADS, 4096)), dim3(IB_THREADS), st, src, row, dst, M, src_rows, D, dst_row0);
   return check_launch("gather_rows");
 }
 
 int launch_scatter_add_rows(const void* src, const int* row, float* dst, int64_t M, int64_t dst_rows, int D, int64_t src_row0, int dtype,
                             hipStream_t st) {
-  IB_LAUNCH_DT(scatter_add_rows_kernel, dtype, dim3(ib_grid(M * D)), st, src, row, dst, M, dst_rows, D, src_row0);
+  DX_LAUNCH_DT(scatter_add_rows_kernel, dtype, dim3(grid_1d(M * D, IB_THREADS, 4096)), dim3(IB_THREADS), st, src, row, dst, M, dst_rows, D, src_row0);
   return check_launch("scatter_add_rows");
 }
 
 int launch_ibot_ce(const float* s, const float* t, const float* center, const float* w, float inv_ts, float inv_tt, float scale, float gscale,
                    float* loss, float* ds, float* row_loss, int M, int K, hipStream_t st) {
-  const bool reg = K % 4 == 0 && K <= IBOT_CE_REG_MAX_K && (((uintptr_t)s | (uintptr_t)t | (uintptr_t)center | (uintptr_t)ds) & 15) == 0;
+  const bool reg = K % 4 == 0 && K <= IBOT_CE_REG_MAX_K && aligned16(s, t, center, ds);
   const dim3 grid((unsigned)M), block(IB_THREADS);
   if (reg) {
     const int K4 = K / 4, nv = (int)ceil_div(K4, IB_THREADS);

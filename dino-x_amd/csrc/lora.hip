@@ -6,25 +6,13 @@
 // load, which is exact, so nothing on the adapter path is rounded to bf16 in either mode; per output element the instruction is one
 // fp32 fma chain in the order its operands are fed.  Activation tiles go through LDS: the global reads are row-contiguous, the operand
 // reads bank-contiguous.
-#include "common.h"
+#include "small_common.h"
 #include "kernels.h"
 
 namespace dinox {
 
-// 4 consecutive elements of an activation row as floats.
-template <int DT>
-__device__ __forceinline__ void ld4(const void* p, int64_t i, float (&v)[4]) {
-  if constexpr (DT == DINOX_F32) {
-    const float4 t = *reinterpret_cast<const float4*>((const float*)p + i);
-    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-  } else {
-    const uint2 t = *reinterpret_cast<const uint2*>((const bf16_t*)p + i);
-    v[0] = __uint_as_float(t.x << 16), v[1] = __uint_as_float(t.x & 0xffff0000u);
-    v[2] = __uint_as_float(t.y << 16), v[3] = __uint_as_float(t.y & 0xffff0000u);
-  }
-}
-
-static bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+// The vector forms read 4 elements of an activation row at once: 8 bytes of bf16, 16 of fp32.
+static bool row_aligned(const void* p, int dtype) { return (reinterpret_cast<uintptr_t>(p) & (dtype == DINOX_BF16 ? 7 : 15)) == 0; }
 
 // ---------------------------------------------------------------- the shared tile machinery: 128 rows x 128 columns of an activation in LDS
 // A workgroup is 256 threads = 4 waves; a lane is (c = lane & 31, h = lane >> 5).  v_mfma_f32_32x32x2_f32: the first operand of lane
@@ -44,18 +32,18 @@ __device__ __forceinline__ void stage_tile(const void* __restrict__ X, int64_t r
 #pragma unroll 4
   for (int p = 0; p < LT_ROWS / 8; ++p) {
     const int m = p * 8 + rr;
-    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    fvec<4> v = vzero<4>();
     if (m < rows && col < C) {
       const int64_t o = (row0 + m) * (int64_t)C + col;
       if (vec) {                                    // C % 4 == 0: col < C means col + 4 <= C
-        ld4<DT>(X, o, v);
+        v = ld_dt<DT, 4>(X, o);
       } else {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-          if (col + i < C) v[i] = elem<DT>::ld(X, o + i);
+          if (col + i < C) v.e[i] = elem<DT>::ld(X, o + i);
       }
     }
-    *reinterpret_cast<f32x4*>(Xs + m * LT_PITCH + 4 * q) = f32x4{v[0], v[1], v[2], v[3]};
+    *reinterpret_cast<f32x4*>(Xs + m * LT_PITCH + 4 * q) = f32x4{v.e[0], v.e[1], v.e[2], v.e[3]};
   }
 }
 
@@ -73,24 +61,24 @@ __device__ __forceinline__ void dot_tile(const float* Xs, const float* __restric
     for (int jb = 0; jb < 2; ++jb) {
       if (jb >= njb) break;
       const int j = 32 * jb + c;
-      float b[4] = {0.f, 0.f, 0.f, 0.f};
+      fvec<4> b = vzero<4>();
       if (j < r && col < C) {
         if constexpr (LAYOUT == 0) {
           if (svec) {
-            ld4<DINOX_F32>(S, (int64_t)j * C + col, b);
+            b = ld_f32<4>(S + (int64_t)j * C + col);
           } else {
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-              if (col + i < C) b[i] = S[(int64_t)j * C + col + i];
+              if (col + i < C) b.e[i] = S[(int64_t)j * C + col + i];
           }
         } else {
 #pragma unroll
           for (int i = 0; i < 4; ++i)
-            if (col + i < C) b[i] = S[(int64_t)(col + i) * r + j];
+            if (col + i < C) b.e[i] = S[(int64_t)(col + i) * r + j];
         }
       }
 #pragma unroll
-      for (int i = 0; i < 4; ++i) acc[jb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[i], acc[jb], 0, 0, 0);
+      for (int i = 0; i < 4; ++i) acc[jb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b.e[i], acc[jb], 0, 0, 0);
     }
   }
 }
@@ -135,7 +123,7 @@ __global__ __launch_bounds__(256) void lora_down_kernel(const void* __restrict__
 }
 
 int launch_lora_down(const void* x, const float* S, float* u, int64_t M, int Kd, int r, int layout, int dtype, hipStream_t st) {
-  const int vec = Kd % 4 == 0 && aligned(x, dtype == DINOX_BF16 ? 8 : 16), svec = layout == 0 && Kd % 4 == 0 && aligned(S, 16);
+  const int vec = Kd % 4 == 0 && row_aligned(x, dtype), svec = layout == 0 && Kd % 4 == 0 && aligned16(S);
   const unsigned grid = (unsigned)ceil_div(M, (int64_t)LT_ROWS);
   const size_t lds = (size_t)LT_FLOATS * sizeof(float);
   auto go = [&](auto dt, auto lay) -> int {
@@ -224,10 +212,10 @@ __global__ __launch_bounds__(256) void lora_up_kernel(const float* __restrict__ 
 bool lora_up_grid_ok(int64_t M, int N) { return ceil_div(ceil_div(M, 4) * (int64_t)N, 256) <= 0x7fffffff; }
 
 int launch_lora_up(const float* u, const float* S, const float* res, float* t, float s, int64_t M, int N, int r, int layout, hipStream_t st) {
-  const bool vec = N % 4 == 0 && aligned(t, 16) && (!res || aligned(res, 16)) && (layout == 0 || aligned(S, 16));
+  const bool vec = N % 4 == 0 && aligned16(t, res) && (layout == 0 || aligned16(S));
   const int64_t items = ceil_div(M, 4) * (int64_t)(vec ? N / 4 : N);
   const unsigned grid = (unsigned)ceil_div(items, 256);
-  const int r4 = layout == 0 && r % 4 == 0 && aligned(S, 16) && aligned(u, 16);
+  const int r4 = layout == 0 && r % 4 == 0 && aligned16(S, u);
   auto go = [&](auto lay, auto v) {
     hipLaunchKernelGGL((lora_up_kernel<decltype(lay)::value, decltype(v)::value>), dim3(grid), dim3(256), 0, st, u, S, res, t, s, M, N, r, r4);
   };
@@ -324,8 +312,7 @@ int64_t lora_grad_chunks(int64_t M) { return ceil_div(M, (int64_t)LORA_GRAD_CHUN
 
 int launch_lora_grad(const void* xl, const void* dy, const float* A, const float* B, float s, float* dA, float* dB, float* ws, int64_t M, int K,
                      int N, int r, int dtype, hipStream_t st) {
-  const size_t op_align = dtype == DINOX_BF16 ? 8 : 16;
-  const int vecK = K % 4 == 0 && aligned(xl, op_align), vecN = N % 4 == 0 && aligned(dy, op_align), avec = K % 4 == 0 && aligned(A, 16);
+  const int vecK = K % 4 == 0 && row_aligned(xl, dtype), vecN = N % 4 == 0 && row_aligned(dy, dtype), avec = K % 4 == 0 && aligned16(A);
   const int64_t chunks = lora_grad_chunks(M), nA = (int64_t)r * K, nB = (int64_t)N * r;
   const size_t lds = ((size_t)LT_FLOATS + (size_t)2 * LT_ROWS * r) * sizeof(float);      // 66 KiB + 1 KiB per rank: 130 KiB at r = 64
   auto go = [&](auto kern) -> int {
@@ -358,18 +345,10 @@ __global__ __launch_bounds__(256) void lora_dropout_kernel(const void* in, void*
   const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
   if (i0 >= n) return;
   if (vec && i0 + 4 <= n) {
-    float v[4];
-    ld4<DT>(in, i0, v);
+    fvec<4> v = ld_dt<DT, 4>(in, i0);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = lora_keep((uint64_t)(i0 + i), key, thr) ? v[i] * scale : 0.f;
-    if constexpr (DT == DINOX_F32) {
-      *reinterpret_cast<float4*>((float*)out + i0) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-      uint2 q;
-      q.x = (uint32_t)f32_to_bf16(v[0]) | ((uint32_t)f32_to_bf16(v[1]) << 16);
-      q.y = (uint32_t)f32_to_bf16(v[2]) | ((uint32_t)f32_to_bf16(v[3]) << 16);
-      *reinterpret_cast<uint2*>((bf16_t*)out + i0) = q;
-    }
+    for (int i = 0; i < 4; ++i) v.e[i] = lora_keep((uint64_t)(i0 + i), key, thr) ? v.e[i] * scale : 0.f;
+    st_dt<DT, 4>(out, i0, v);
   } else {
     for (int64_t i = i0; i < n && i < i0 + 4; ++i)
       elem<DT>::st(out, i, lora_keep((uint64_t)i, key, thr) ? elem<DT>::ld(in, i) * scale : 0.f);
@@ -382,14 +361,12 @@ uint32_t lora_dropout_key(uint64_t seed, uint64_t offset) {
 }
 
 int launch_lora_dropout(const void* in, void* out, int64_t n, float p, uint64_t seed, uint64_t offset, int dtype, hipStream_t st) {
-  const size_t a = dtype == DINOX_BF16 ? 8 : 16;
-  const int vec = aligned(in, a) && aligned(out, a);
+  const int vec = row_aligned(in, dtype) && row_aligned(out, dtype);
   const uint32_t key = lora_dropout_key(seed, offset);
   const uint32_t thr = (uint32_t)ceil((double)p * 16777216.0);          // keep iff the 24-bit draw >= p 2^24
   const float scale = 1.0f / (1.0f - p);
   const unsigned grid = (unsigned)ceil_div(ceil_div(n, 4), 256);
-  if (dtype == DINOX_BF16) hipLaunchKernelGGL((lora_dropout_kernel<DINOX_BF16>), dim3(grid), dim3(256), 0, st, in, out, n, scale, key, thr, vec);
-  else hipLaunchKernelGGL((lora_dropout_kernel<DINOX_F32>), dim3(grid), dim3(256), 0, st, in, out, n, scale, key, thr, vec);
+  DX_LAUNCH_DT(lora_dropout_kernel, dtype, dim3(grid), dim3(256), st, in, out, n, scale, key, thr, vec);
   return check_launch("lora_dropout");
 }
 

@@ -2,7 +2,7 @@
 // Replaces DINOLoss.forward/update_center and compute_gram_anchoring_loss of the reference
 // (scripts/phase5_big_run.py:686-720, 723-739).  Everything here is fp32 (autocast keeps softmax,
 // log_softmax, normalize and mse_loss in fp32 too); the Gram products go through dinox_gemm.
-#include "common.h"
+#include "small_common.h"
 
 namespace dinox {
 
@@ -101,9 +101,7 @@ __global__ __launch_bounds__(CE_THREADS) void dino_ce_multi_kernel(const float* 
 // loss[0] = scale * sum(x[0..n))  -- single workgroup, deterministic order.
 __global__ __launch_bounds__(256) void final_sum_kernel(const float* __restrict__ x, int n, float scale, float* __restrict__ out) {
   __shared__ float red[16];
-  float a = 0.f;
-  for (int i = threadIdx.x; i < n; i += 256) a += x[i];
-  a = block_sum(a, red);
+  const float a = block_strided_sum(x, n, red);
   if (threadIdx.x == 0) out[0] = a * scale;
 }
 
@@ -260,7 +258,7 @@ extern "C" int dinox_dino_ce_multi(const float* s, const float* t, const float* 
 
 extern "C" int dinox_colmean(const float* t, float* out, int rows, int K, void* stream) {
   DX_REQUIRE(t && out && rows > 0 && K > 0, DINOX_EINVAL, "colmean: bad arguments");
-  if (K % 4 == 0 && (((uintptr_t)t | (uintptr_t)out) & 15) == 0)
+  if (K % 4 == 0 && aligned16(t, out))
     hipLaunchKernelGGL(colmean_kernel, dim3((unsigned)ceil_div(K / 4, 64)), dim3(256), 0, as_stream(stream), t, out, rows, K);
   else
     hipLaunchKernelGGL(colmean_scalar_kernel, dim3((unsigned)ceil_div(K, 256)), dim3(256), 0, as_stream(stream), t, out, rows, K);
@@ -279,19 +277,15 @@ extern "C" int dinox_gram_normalize(const float* sfeats, const float* tfeats, vo
   DX_REQUIRE(V > 0 && N > 1 && D > 0, DINOX_EINVAL, "gram_normalize: V=%d N=%d D=%d", V, N, D);
   DX_REQUIRE(out_dtype == DINOX_F32 || out_dtype == DINOX_BF16, DINOX_EINVAL, "gram_normalize: dtype %d", out_dtype);
   const unsigned blocks = (unsigned)ceil_div((int64_t)V * (N - 1), 4);
-  if (out_dtype == DINOX_F32)
-    hipLaunchKernelGGL((gram_normalize_kernel<DINOX_F32>), dim3(blocks), dim3(256), 0, as_stream(stream), sfeats, tfeats, cat, catneg, shat, snorm, V, N, D);
-  else
-    hipLaunchKernelGGL((gram_normalize_kernel<DINOX_BF16>), dim3(blocks), dim3(256), 0, as_stream(stream), sfeats, tfeats, cat, catneg, shat, snorm, V, N, D);
+  DX_LAUNCH_DT(gram_normalize_kernel, out_dtype, dim3(blocks), dim3(256), as_stream(stream), sfeats, tfeats, cat, catneg, shat, snorm, V, N, D);
   return check_launch("gram_normalize");
 }
 
 extern "C" int dinox_sqsum(const float* x, int64_t n, float scale, float* loss, float* ws, void* stream) {
   DX_REQUIRE(x && loss && ws && n > 0, DINOX_EINVAL, "sqsum: bad arguments");
-  int64_t blocks = ceil_div(n, 256 * 8);
-  if (blocks > 1024) blocks = 1024;
+  const unsigned blocks = grid_1d(n, 256 * 8, 1024);
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(sqsum_partial_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, n, ws);
+  hipLaunchKernelGGL(sqsum_partial_kernel, dim3(blocks), dim3(256), 0, st, x, n, ws);
   hipLaunchKernelGGL(final_sum_kernel, dim3(1), dim3(256), 0, st, ws, (int)blocks, scale, loss);
   return check_launch("sqsum");
 }
@@ -303,9 +297,6 @@ extern "C" int dinox_gram_normalize_bwd(const float* dxh, const void* shat, cons
   DX_REQUIRE(V > 0 && N > 1 && D > 0, DINOX_EINVAL, "gram_normalize_bwd: V=%d N=%d D=%d", V, N, D);
   DX_REQUIRE(shat_dtype == DINOX_F32 || shat_dtype == DINOX_BF16, DINOX_EINVAL, "gram_normalize_bwd: dtype %d", shat_dtype);
   const unsigned blocks = (unsigned)ceil_div((int64_t)V * (N - 1), 4);
-  if (shat_dtype == DINOX_F32)
-    hipLaunchKernelGGL((gram_normalize_bwd_kernel<DINOX_F32>), dim3(blocks), dim3(256), 0, as_stream(stream), dxh, shat, snorm, dfeats, V, N, D, accumulate);
-  else
-    hipLaunchKernelGGL((gram_normalize_bwd_kernel<DINOX_BF16>), dim3(blocks), dim3(256), 0, as_stream(stream), dxh, shat, snorm, dfeats, V, N, D, accumulate);
+  DX_LAUNCH_DT(gram_normalize_bwd_kernel, shat_dtype, dim3(blocks), dim3(256), as_stream(stream), dxh, shat, snorm, dfeats, V, N, D, accumulate);
   return check_launch("gram_normalize_bwd");
 }

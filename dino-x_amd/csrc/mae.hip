@@ -8,83 +8,14 @@
 //     loss            mean over removed patches of the mean squared error against pixels read straight from the image
 // All memory-bound.  No float atomics: every sum has a fixed order (the chains are stated at each kernel), so a step is bit-reproducible.
 // Every index read from device memory (ids_keep, ids_restore) is range-checked before it becomes an address.
-#include "common.h"
+#include "small_common.h"
 #include "kernels.h"
 
 namespace dinox {
 
 constexpr int MAE_THREADS = 256;
 
-// ---------------------------------------------------------------- small vector helpers: VW = 1 (any size) or 4 (16-byte fp32 / 8-byte bf16)
-template <int VW>
-struct fvec {
-  float e[VW];
-};
-template <int VW>
-__device__ __forceinline__ fvec<VW> ld_f32(const float* p) {
-  fvec<VW> r;
-  if constexpr (VW == 4) {
-    const float4 q = *reinterpret_cast<const float4*>(p);
-    r.e[0] = q.x; r.e[1] = q.y; r.e[2] = q.z; r.e[3] = q.w;
-  } else {
-    r.e[0] = *p;
-  }
-  return r;
-}
-template <int VW>
-__device__ __forceinline__ void st_f32(float* p, const fvec<VW>& v) {
-  if constexpr (VW == 4) *reinterpret_cast<float4*>(p) = make_float4(v.e[0], v.e[1], v.e[2], v.e[3]);
-  else *p = v.e[0];
-}
-template <int DT, int VW>
-__device__ __forceinline__ fvec<VW> ld_dt(const void* p, int64_t i) {
-  if constexpr (DT == DINOX_F32) {
-    return ld_f32<VW>((const float*)p + i);
-  } else {
-    fvec<VW> r;
-    if constexpr (VW == 4) {
-      const uint2 w = *reinterpret_cast<const uint2*>((const bf16_t*)p + i);
-      r.e[0] = __uint_as_float(w.x << 16); r.e[1] = __uint_as_float(w.x & 0xffff0000u);
-      r.e[2] = __uint_as_float(w.y << 16); r.e[3] = __uint_as_float(w.y & 0xffff0000u);
-    } else {
-      r.e[0] = bf16_to_f32(((const bf16_t*)p)[i]);
-    }
-    return r;
-  }
-}
-template <int DT, int VW>
-__device__ __forceinline__ void st_dt(void* p, int64_t i, const fvec<VW>& v) {
-  if constexpr (DT == DINOX_F32) {
-    st_f32<VW>((float*)p + i, v);
-  } else if constexpr (VW == 4) {
-    uint2 w;
-    w.x = (unsigned)f32_to_bf16(v.e[0]) | ((unsigned)f32_to_bf16(v.e[1]) << 16);
-    w.y = (unsigned)f32_to_bf16(v.e[2]) | ((unsigned)f32_to_bf16(v.e[3]) << 16);
-    *reinterpret_cast<uint2*>((bf16_t*)p + i) = w;
-  } else {
-    ((bf16_t*)p)[i] = f32_to_bf16(v.e[0]);
-  }
-}
-template <int VW>
-__device__ __forceinline__ fvec<VW> vadd(const fvec<VW>& a, const fvec<VW>& b) {
-  fvec<VW> r;
-#pragma unroll
-  for (int i = 0; i < VW; ++i) r.e[i] = a.e[i] + b.e[i];
-  return r;
-}
-template <int VW>
-__device__ __forceinline__ fvec<VW> vzero() {
-  fvec<VW> r;
-#pragma unroll
-  for (int i = 0; i < VW; ++i) r.e[i] = 0.f;
-  return r;
-}
 __device__ __forceinline__ int clamp_idx(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
-
-static unsigned mae_grid(int64_t total) {
-  const int64_t b = ceil_div(total, MAE_THREADS);
-  return (unsigned)(b < 1 ? 1 : (b < 256 * 16 ? b : 256 * 16));
-}
 
 // ---------------------------------------------------------------- mask ids
 // A key whose unsigned order is the order torch.argsort uses: -0 == +0, every NaN equal and above +inf.  With ties broken by index the
@@ -316,9 +247,7 @@ __global__ __launch_bounds__(MAE_THREADS) void mae_loss_rows_kernel(const void* 
 __global__ __launch_bounds__(MAE_THREADS) void mae_loss_mean_kernel(const float* __restrict__ row_loss, int64_t n, float count,
                                                                     float* __restrict__ loss) {
   __shared__ float red[16];
-  float a = 0.f;
-  for (int64_t i = threadIdx.x; i < n; i += MAE_THREADS) a += row_loss[i];
-  a = block_sum(a, red);
+  const float a = block_strided_sum(row_loss, n, red);
   if (threadIdx.x == 0) loss[0] = a / count;
 }
 
@@ -350,21 +279,6 @@ __global__ __launch_bounds__(MAE_THREADS) void mae_loss_bwd_kernel(const void* _
 }
 
 // ---------------------------------------------------------------- launchers (arguments were validated by the entry points in abi.hip)
-static inline bool al16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr, const void* e = nullptr) {
-  return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d | (uintptr_t)e) & 15) == 0;
-}
-
-#define MAE_LAUNCH_DT_VW(kern, dtype, vec, grid, st, ...)                                                                        \
-  do {                                                                                                                           \
-    if ((dtype) == DINOX_F32) {                                                                                                  \
-      if (vec) hipLaunchKernelGGL((kern<DINOX_F32, 4>), grid, dim3(MAE_THREADS), 0, st, __VA_ARGS__);                            \
-      else hipLaunchKernelGGL((kern<DINOX_F32, 1>), grid, dim3(MAE_THREADS), 0, st, __VA_ARGS__);                                \
-    } else {                                                                                                                     \
-      if (vec) hipLaunchKernelGGL((kern<DINOX_BF16, 4>), grid, dim3(MAE_THREADS), 0, st, __VA_ARGS__);                           \
-      else hipLaunchKernelGGL((kern<DINOX_BF16, 1>), grid, dim3(MAE_THREADS), 0, st, __VA_ARGS__);                               \
-    }                                                                                                                            \
-  } while (0)
-
 int launch_mae_mask_ids(const float* noise, int* ids_restore, int* ids_keep, int V, int L, int Lk, hipStream_t st) {
   hipLaunchKernelGGL(mae_mask_ids_kernel, dim3((unsigned)V), dim3(MAE_THREADS), 0, st, noise, ids_restore, ids_keep, L, Lk);
   return check_launch("mae_mask_ids");
@@ -372,43 +286,43 @@ int launch_mae_mask_ids(const float* noise, int* ids_restore, int* ids_keep, int
 
 int launch_mae_gather_unfold(const float* x, const int* ids_keep, void* u, int V, int H, int W, int patch, int Lk, int ld, int dtype,
                              hipStream_t st) {
-  const bool vec = patch % 4 == 0 && ld % 4 == 0 && al16(x, u);
-  const dim3 grid(mae_grid((int64_t)V * Lk * (ld / (vec ? 4 : 1))));
-  MAE_LAUNCH_DT_VW(mae_gather_unfold_kernel, dtype, vec, grid, st, x, ids_keep, u, V, H, W, patch, Lk, ld);
+  const bool vec = patch % 4 == 0 && ld % 4 == 0 && aligned16(x, u);
+  const dim3 grid(grid_1d((int64_t)V * Lk * (ld / (vec ? 4 : 1)), MAE_THREADS, 4096));
+  DX_LAUNCH_DT_VW(mae_gather_unfold_kernel, dtype, vec, grid, dim3(MAE_THREADS), st, x, ids_keep, u, V, H, W, patch, Lk, ld);
   return check_launch("mae_gather_unfold");
 }
 
 int launch_mae_tokens_fwd(const void* patches, const float* cls, const float* pos, const int* ids_keep, float* tok, int V, int L, int Lk,
                           int D, int dtype, hipStream_t st) {
-  const bool vec = D % 4 == 0 && al16(patches, cls, pos, tok);
-  const dim3 grid(mae_grid((int64_t)V * (1 + Lk) * (D / (vec ? 4 : 1))));
-  MAE_LAUNCH_DT_VW(mae_tokens_fwd_kernel, dtype, vec, grid, st, patches, cls, pos, ids_keep, tok, V, L, Lk, D);
+  const bool vec = D % 4 == 0 && aligned16(patches, cls, pos, tok);
+  const dim3 grid(grid_1d((int64_t)V * (1 + Lk) * (D / (vec ? 4 : 1)), MAE_THREADS, 4096));
+  DX_LAUNCH_DT_VW(mae_tokens_fwd_kernel, dtype, vec, grid, dim3(MAE_THREADS), st, patches, cls, pos, ids_keep, tok, V, L, Lk, D);
   return check_launch("mae_tokens_fwd");
 }
 
 int launch_mae_tokens_bwd(const float* dtok, const int* ids_restore, void* dpatches, float* dcls, float* dpos, int V, int L, int Lk, int D,
                           int dtype, hipStream_t st) {
-  const bool vec = D % 4 == 0 && al16(dtok, dpatches, dcls, dpos);
+  const bool vec = D % 4 == 0 && aligned16(dtok, dpatches, dcls, dpos);
   const int DV = D / (vec ? 4 : 1), chunks = (int)ceil_div(DV, MAE_THREADS), param_blocks = (1 + L) * chunks;
-  const dim3 grid((unsigned)param_blocks + mae_grid((int64_t)V * Lk * DV));
-  MAE_LAUNCH_DT_VW(mae_tokens_bwd_kernel, dtype, vec, grid, st, dtok, ids_restore, dpatches, dcls, dpos, V, L, Lk, D, chunks, param_blocks);
+  const dim3 grid((unsigned)param_blocks + grid_1d((int64_t)V * Lk * DV, MAE_THREADS, 4096));
+  DX_LAUNCH_DT_VW(mae_tokens_bwd_kernel, dtype, vec, grid, dim3(MAE_THREADS), st, dtok, ids_restore, dpatches, dcls, dpos, V, L, Lk, D, chunks, param_blocks);
   return check_launch("mae_tokens_bwd");
 }
 
 int launch_mae_unshuffle_fwd(const void* e, const float* mask_token, const float* dpe, const int* ids_restore, float* xd, int V, int L,
                              int Lk, int D, int dtype, hipStream_t st) {
-  const bool vec = D % 4 == 0 && al16(e, mask_token, dpe, xd);
-  const dim3 grid(mae_grid((int64_t)V * (1 + L) * (D / (vec ? 4 : 1))));
-  MAE_LAUNCH_DT_VW(mae_unshuffle_fwd_kernel, dtype, vec, grid, st, e, mask_token, dpe, ids_restore, xd, V, L, Lk, D);
+  const bool vec = D % 4 == 0 && aligned16(e, mask_token, dpe, xd);
+  const dim3 grid(grid_1d((int64_t)V * (1 + L) * (D / (vec ? 4 : 1)), MAE_THREADS, 4096));
+  DX_LAUNCH_DT_VW(mae_unshuffle_fwd_kernel, dtype, vec, grid, dim3(MAE_THREADS), st, e, mask_token, dpe, ids_restore, xd, V, L, Lk, D);
   return check_launch("mae_unshuffle_fwd");
 }
 
 int launch_mae_unshuffle_bwd(const float* g, const int* ids_keep, const int* ids_restore, void* de, float* dmask, float* ws, int V, int L,
                              int Lk, int D, int dtype, hipStream_t st) {
-  const bool vec = D % 4 == 0 && al16(g, de, dmask, ws);
+  const bool vec = D % 4 == 0 && aligned16(g, de, dmask, ws);
   const int DV = D / (vec ? 4 : 1), chunks = (int)ceil_div(DV, MAE_THREADS), part_blocks = V * chunks;
-  const dim3 grid((unsigned)part_blocks + mae_grid((int64_t)V * (1 + Lk) * DV));
-  MAE_LAUNCH_DT_VW(mae_unshuffle_bwd_kernel, dtype, vec, grid, st, g, ids_keep, ids_restore, de, ws, V, L, Lk, D, chunks, part_blocks);
+  const dim3 grid((unsigned)part_blocks + grid_1d((int64_t)V * (1 + Lk) * DV, MAE_THREADS, 4096));
+  DX_LAUNCH_DT_VW(mae_unshuffle_bwd_kernel, dtype, vec, grid, dim3(MAE_THREADS), st, g, ids_keep, ids_restore, de, ws, V, L, Lk, D, chunks, part_blocks);
   int rc = check_launch("mae_unshuffle_bwd");
   if (rc) return rc;
   if (vec) hipLaunchKernelGGL(mae_colsum_rows_kernel<4>, dim3((unsigned)chunks), dim3(MAE_THREADS), 0, st, ws, dmask, V, D);
@@ -419,9 +333,9 @@ int launch_mae_unshuffle_bwd(const float* g, const int* ids_keep, const int* ids
 int launch_mae_loss_fwd(const void* pred, const float* x, const int* ids_restore, float* loss, float* ws, int V, int H, int W, int patch,
                         int Lk, int lead, int dtype, hipStream_t st) {
   const int L = (H / patch) * (W / patch), K = 3 * patch * patch;
-  const bool vec = K % 4 == 0 && al16(pred);
+  const bool vec = K % 4 == 0 && aligned16(pred);
   const dim3 grid((unsigned)((int64_t)V * L));
-  MAE_LAUNCH_DT_VW(mae_loss_rows_kernel, dtype, vec, grid, st, pred, x, ids_restore, ws, H, W, patch, Lk, lead);
+  DX_LAUNCH_DT_VW(mae_loss_rows_kernel, dtype, vec, grid, dim3(MAE_THREADS), st, pred, x, ids_restore, ws, H, W, patch, Lk, lead);
   int rc = check_launch("mae_loss_fwd");
   if (rc) return rc;
   hipLaunchKernelGGL(mae_loss_mean_kernel, dim3(1), dim3(MAE_THREADS), 0, st, ws, (int64_t)V * L, (float)V * (float)(L - Lk), loss);
@@ -438,7 +352,7 @@ static void mae_loss_bwd_vw(bool vec, dim3 grid, hipStream_t st, const void* pre
 int launch_mae_loss_bwd(const void* pred, const float* x, const int* ids_restore, void* dpred, float gscale, int V, int H, int W, int patch,
                         int Lk, int lead, int dtype, int out_dtype, hipStream_t st) {
   const int L = (H / patch) * (W / patch), K = 3 * patch * patch;
-  const bool vec = K % 4 == 0 && al16(pred, dpred);
+  const bool vec = K % 4 == 0 && aligned16(pred, dpred);
   const dim3 grid((unsigned)((int64_t)V * (lead + L)));
   const float scale = (float)((double)gscale * 2.0 / ((double)K * (double)V * (double)(L - Lk)));
   if (dtype == DINOX_F32 && out_dtype == DINOX_F32) mae_loss_bwd_vw<DINOX_F32, DINOX_F32>(vec, grid, st, pred, x, ids_restore, dpred, H, W, patch, Lk, lead, scale);

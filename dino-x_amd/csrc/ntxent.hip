@@ -10,7 +10,7 @@
 // Documented deviation: everything is fp32 in BOTH compute modes (as KoLeo).  Under --amp the reference's autocast runs the
 // similarity matmul in bf16; this engine stays at fp32 there, i.e. closer to the reference's own fp32 step.
 // No float atomics: every sum has a fixed order, so a step is bit-reproducible.
-#include "common.h"
+#include "small_common.h"
 #include "kernels.h"
 
 namespace dinox {
@@ -41,9 +41,11 @@ __global__ __launch_bounds__(NX_THREADS) void ntxent_rows_kernel(const float* __
   }
 }
 
-// loss[0] = (sum_i row_loss[i]) / M, added in index order by one thread; the rows pass through LDS in chunks so that the loads are
-// one coalesced sweep and the serial chain is M dependent adds on LDS reads (M = 512: ~2 us).
-__global__ __launch_bounds__(NX_THREADS) void ntxent_mean_kernel(const float* __restrict__ row_loss, int M, float* __restrict__ loss) {
+// out[0] = (sum_i row_loss[i]) / divisor, added in index order by one thread; the rows pass through LDS in chunks so that the loads are
+// one coalesced sweep and the serial chain is M dependent adds on LDS reads (M = 512: ~2 us).  divisor = M gives the loss; the
+// rectangular form passes 1 (an exact division) for the plain sum: the ranks' sums meet on the host side of the all-gather, which
+// divides by Mg once.
+__global__ __launch_bounds__(NX_THREADS) void ntxent_sum_kernel(const float* __restrict__ row_loss, int M, float divisor, float* __restrict__ out) {
   __shared__ float buf[1024];
   float a = 0.f;
   for (int base = 0; base < M; base += 1024) {
@@ -54,7 +56,7 @@ __global__ __launch_bounds__(NX_THREADS) void ntxent_mean_kernel(const float* __
       for (int t = 0; t < n; ++t) a += buf[t];
     __syncthreads();
   }
-  if (threadIdx.x == 0) loss[0] = a / (float)M;
+  if (threadIdx.x == 0) out[0] = a / divisor;
 }
 
 // W[i][j] = scale * (exp(S_ij/tau - lse_i) + exp(S_ji/tau - lse_j) - [j = p(i)] - [i = p(j)]),  W[i][i] = 0,  scale = g / (M tau).
@@ -115,22 +117,6 @@ __global__ __launch_bounds__(NX_THREADS) void ntxent_rows_rect_kernel(const floa
   }
 }
 
-// loss_sum[0] = sum_i row_loss[i] in index order (ntxent_mean_kernel without the division: the ranks' sums meet on the host side of
-// the all-gather, which divides by Mg once).
-__global__ __launch_bounds__(NX_THREADS) void ntxent_sum_kernel(const float* __restrict__ row_loss, int M, float* __restrict__ loss_sum) {
-  __shared__ float buf[1024];
-  float a = 0.f;
-  for (int base = 0; base < M; base += 1024) {
-    const int n = M - base < 1024 ? M - base : 1024;
-    for (int t = threadIdx.x; t < n; t += NX_THREADS) buf[t] = row_loss[base + t];
-    __syncthreads();
-    if (threadIdx.x == 0)
-      for (int t = 0; t < n; ++t) a += buf[t];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) loss_sum[0] = a;
-}
-
 // W[i][j] = scale * (exp(S_ij/tau - lse_local[i]) + exp(S_ij/tau - lse_all[j]) - 2 [j = p(i)]),  W[i][dg(i)] = 0,  scale = g / (Ml tau).
 // The second term is P_ji: S_ji lives on the rank that owns row j, so S_ij stands in for it (the product is symmetric up to rounding)
 // with the gathered lse of row j; [i = p(j)] = [j = p(i)] for this pairing.  One workgroup per 32 x 32 tile, every element read and
@@ -189,7 +175,7 @@ int launch_ntxent_rows(const float* S, int64_t lds, int M, float inv_tau, float*
   hipLaunchKernelGGL(ntxent_rows_kernel, dim3((unsigned)M), dim3(NX_THREADS), 0, st, S, lds, M, inv_tau, lse, row_loss);
   const int rc = check_launch("ntxent_rows");
   if (rc) return rc;
-  hipLaunchKernelGGL(ntxent_mean_kernel, dim3(1), dim3(NX_THREADS), 0, st, row_loss, M, loss);
+  hipLaunchKernelGGL(ntxent_sum_kernel, dim3(1), dim3(NX_THREADS), 0, st, row_loss, M, (float)M, loss);
   return check_launch("ntxent_rows_mean");
 }
 
@@ -206,7 +192,7 @@ int launch_ntxent_rows_rect(const float* S, int64_t lds, int Ml, int Mg, int row
   hipLaunchKernelGGL(ntxent_rows_rect_kernel, dim3((unsigned)Ml), dim3(NX_THREADS), 0, st, S, lds, Mg, row0, Bl, inv_tau, lse, row_loss);
   const int rc = check_launch("ntxent_rows_rect");
   if (rc) return rc;
-  hipLaunchKernelGGL(ntxent_sum_kernel, dim3(1), dim3(NX_THREADS), 0, st, row_loss, Ml, loss_sum);
+  hipLaunchKernelGGL(ntxent_sum_kernel, dim3(1), dim3(NX_THREADS), 0, st, row_loss, Ml, 1.0f, loss_sum);
   return check_launch("ntxent_rows_rect_sum");
 }
 
@@ -219,7 +205,7 @@ int launch_ntxent_coeff_rect(const float* S, int64_t lds, const float* lse_local
 }
 
 int launch_normalize_bwd(const float* dxh, const float* xh, const float* norm, float* dx, int64_t V, int D, float eps, hipStream_t st) {
-  const bool vec = D % 4 == 0 && (((uintptr_t)dxh | (uintptr_t)xh | (uintptr_t)dx) & 15) == 0;
+  const bool vec = D % 4 == 0 && aligned16(dxh, xh, dx);
   if (vec) hipLaunchKernelGGL(normalize_bwd_kernel<true>, dim3((unsigned)V), dim3(NX_THREADS), 0, st, dxh, xh, norm, dx, D, eps);
   else hipLaunchKernelGGL(normalize_bwd_kernel<false>, dim3((unsigned)V), dim3(NX_THREADS), 0, st, dxh, xh, norm, dx, D, eps);
   return check_launch("normalize_bwd");

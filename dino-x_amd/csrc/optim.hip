@@ -2,7 +2,7 @@
 // Replaces (a) the 155-161 blocking .norm(2).item() calls of the grad-norm loop
 // (scripts/phase5_big_run.py:1784-1789), (b) torch.optim.AdamW.step (:1794) and (c) the per-parameter
 // EMA teacher loop (:1799-1802) with one streaming pass: 5 arenas read, 4 written, 36 B per parameter.
-#include "common.h"
+#include "small_common.h"
 
 namespace dinox {
 
@@ -135,13 +135,6 @@ __global__ __launch_bounds__(256) void gelu_bwd_kernel(const float* __restrict__
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) dx[i] = dy[i] * gelu_erf_grad(x[i]);
 }
 
-static unsigned stream_grid(int64_t n, int per_thread) {
-  int64_t b = ceil_div(n, (int64_t)256 * per_thread);
-  if (b > 2048) b = 2048;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
-
 }  // namespace dinox
 
 using namespace dinox;
@@ -151,9 +144,9 @@ static int adamw_launch(float* p, const float* g, float* m, float* v, float* tea
                         float* gnorm_sq, float* ws, const float* hyper, void* stream) {
   DX_REQUIRE(p && g && m && v && gnorm_sq && ws, DINOX_EINVAL, "adamw_ema: null pointer");
   DX_REQUIRE(n > 0, DINOX_EINVAL, "adamw_ema: n=%lld", (long long)n);
-  DX_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)teacher) & 15) == 0, DINOX_EALIGN,
+  DX_REQUIRE(aligned16(p, g, m, v, teacher), DINOX_EALIGN,
              "adamw_ema: arenas must be 16-byte aligned");
-  const unsigned blocks = stream_grid(n, 4);
+  const unsigned blocks = grid_1d(n, 256 * 4, 2048);
   hipStream_t st = as_stream(stream);
   hipLaunchKernelGGL(adamw_ema_kernel, dim3(blocks), dim3(256), 0, st, p, g, m, v, teacher, n, lr, weight_decay, beta1, beta2,
                      eps, inv_bc1, inv_sqrt_bc2, ema, grad_scale, ws, hyper);
@@ -181,7 +174,7 @@ extern "C" int dinox_adamw_ema_dev(float* p, const float* g, float* m, float* v,
 
 extern "C" int dinox_sumsq(const float* x, int64_t n, float* out, float* ws, void* stream) {
   DX_REQUIRE(x && out && ws && n > 0, DINOX_EINVAL, "sumsq: bad arguments");
-  const unsigned blocks = stream_grid(n, 8);
+  const unsigned blocks = grid_1d(n, 256 * 8, 2048);
   hipStream_t st = as_stream(stream);
   hipLaunchKernelGGL(sumsq_partial, dim3(blocks), dim3(256), 0, st, x, n, ws);
   hipLaunchKernelGGL(sum_parts, dim3(1), dim3(256), 0, st, ws, (int)blocks, out);
@@ -190,7 +183,7 @@ extern "C" int dinox_sumsq(const float* x, int64_t n, float* out, float* ws, voi
 
 extern "C" int dinox_cast_bf16(const float* src, void* dst, int64_t n, void* stream) {
   DX_REQUIRE(src && dst && n > 0, DINOX_EINVAL, "cast_bf16: bad arguments");
-  hipLaunchKernelGGL(cast_bf16_kernel, dim3(stream_grid(n, 4)), dim3(256), 0, as_stream(stream), src, (bf16_t*)dst, n);
+  hipLaunchKernelGGL(cast_bf16_kernel, dim3(grid_1d(n, 256 * 4, 2048)), dim3(256), 0, as_stream(stream), src, (bf16_t*)dst, n);
   return check_launch("cast_bf16");
 }
 
@@ -213,12 +206,12 @@ extern "C" int dinox_cast_transpose_bf16_multi(const float* src_base, void* dst_
 
 extern "C" int dinox_gelu_fwd(const float* x, float* y, int64_t n, void* stream) {
   DX_REQUIRE(x && y && n > 0, DINOX_EINVAL, "gelu_fwd: bad arguments");
-  hipLaunchKernelGGL(gelu_fwd_kernel, dim3(stream_grid(n, 4)), dim3(256), 0, as_stream(stream), x, y, n);
+  hipLaunchKernelGGL(gelu_fwd_kernel, dim3(grid_1d(n, 256 * 4, 2048)), dim3(256), 0, as_stream(stream), x, y, n);
   return check_launch("gelu_fwd");
 }
 
 extern "C" int dinox_gelu_bwd(const float* dy, const float* x, float* dx, int64_t n, void* stream) {
   DX_REQUIRE(dy && x && dx && n > 0, DINOX_EINVAL, "gelu_bwd: bad arguments");
-  hipLaunchKernelGGL(gelu_bwd_kernel, dim3(stream_grid(n, 4)), dim3(256), 0, as_stream(stream), dy, x, dx, n);
+  hipLaunchKernelGGL(gelu_bwd_kernel, dim3(grid_1d(n, 256 * 4, 2048)), dim3(256), 0, as_stream(stream), dy, x, dx, n);
   return check_launch("gelu_bwd");
 }

@@ -7,7 +7,7 @@
 // i.e. the targets dino_ce_kernel already forms from the centre c = -tau b_n.  Everything here is fp32 and max-shifted: no exp of an
 // unshifted logit (at tau = 0.04 exp(z) leaves fp32 at a logit of 3.6).  Every result is a pure function of the inputs: fixed
 // reduction trees, partials met in index order, no atomics.
-#include "common.h"
+#include "small_common.h"
 
 namespace dinox {
 
@@ -144,7 +144,7 @@ static int sk_col_launch(const float* t, const float* a, float inv, float oscale
   const int chunks = sk_chunks(R);
   float* pm = ws;                              // [chunks][K]
   float* ps = ws + (int64_t)chunks * K;        // [chunks][K]
-  if (K % 4 == 0 && (((uintptr_t)t | (uintptr_t)ws) & 15) == 0) {
+  if (K % 4 == 0 && aligned16(t, ws)) {
     const dim3 grid((unsigned)ceil_div(K / 4, 64), (unsigned)chunks);
     if (a) hipLaunchKernelGGL((sk_col_partial_kernel<true>), grid, dim3(SK_THREADS), 0, st, t, a, inv, pm, ps, R, K);
     else hipLaunchKernelGGL((sk_col_partial_kernel<false>), grid, dim3(SK_THREADS), 0, st, t, a, inv, pm, ps, R, K);
@@ -160,7 +160,7 @@ static int sk_col_launch(const float* t, const float* a, float inv, float oscale
 }
 
 static int sk_row_launch(const float* t, const float* b, float inv, float oscale, float* out, int R, int K, hipStream_t st) {
-  const bool vec = K % 4 == 0 && (((uintptr_t)t | (uintptr_t)b) & 15) == 0;
+  const bool vec = K % 4 == 0 && aligned16(t, b);
   const dim3 grid((unsigned)R), block(SK_THREADS);
   if (vec && b) hipLaunchKernelGGL((sk_row_lse_kernel<true, true>), grid, block, 0, st, t, b, inv, oscale, out, K);
   else if (vec) hipLaunchKernelGGL((sk_row_lse_kernel<true, false>), grid, block, 0, st, t, b, inv, oscale, out, K);

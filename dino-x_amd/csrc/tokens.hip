@@ -1,7 +1,7 @@
 // tokens.hip -- patch unfold (im2col for stride==kernel) and token assembly, forward and backward.
 // Replaces the input side of nn.Conv2d(3,D,k=p,s=p) and the flatten/transpose/cat/+pos/+scale/cat
 // sequence of the reference (zoo/arch.py:216-229).  All HBM-bound, coalesced along the innermost axis.
-#include "common.h"
+#include "small_common.h"
 
 namespace dinox {
 
@@ -55,86 +55,43 @@ __global__ __launch_bounds__(256) void unfold_vec8_kernel(const float* __restric
 }
 
 // tokens[v][n][:]:  n=0: cls+pos[0]+scale[v];  1<=n<=P: patches[v][n-1]+pos[n]+scale[v];  n>P: registers[n-1-P]
-template <int DT>
+// One thread per VW consecutive features (VW = 4: D % 4 == 0 and 16-byte aligned operands).
+template <int DT, int VW>
 __global__ __launch_bounds__(256) void tokens_fwd_kernel(const void* __restrict__ patches, const float* __restrict__ cls,
                                                          const float* __restrict__ pos, const float* __restrict__ regs,
                                                          const float* __restrict__ scale, float* __restrict__ tokens,
                                                          int V, int P, int R, int D) {
-  const int N = 1 + P + R;
-  const int64_t total = (int64_t)V * N * D;
+  const int N = 1 + P + R, DV = D / VW;
+  const int64_t total = (int64_t)V * N * DV;
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-    const int dd = (int)(idx % D);
-    const int n = (int)((idx / D) % N);
-    const int64_t v = idx / ((int64_t)D * N);
-    float val;
-    if (n > P) {
-      val = regs[(int64_t)(n - 1 - P) * D + dd];
-    } else {
-      val = (n == 0) ? cls[dd] : elem<DT>::ld(patches, (v * P + (n - 1)) * D + dd);
-      val += pos[(int64_t)n * D + dd];
-      if (scale) val += scale[v * D + dd];
-    }
-    tokens[idx] = val;
-  }
-}
-
-// Vector forms for D % 4 == 0: one thread per 4 consecutive features.
-template <int DT>
-__device__ __forceinline__ float4 ld4(const void* p, int64_t i) {
-  if (DT == DINOX_BF16) {
-    const uint2 w = *reinterpret_cast<const uint2*>((const bf16_t*)p + i);
-    return make_float4(__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xffff0000u), __uint_as_float(w.y << 16), __uint_as_float(w.y & 0xffff0000u));
-  }
-  return *reinterpret_cast<const float4*>((const float*)p + i);
-}
-template <int DT>
-__device__ __forceinline__ void st4(void* p, int64_t i, float4 v) {
-  if (DT == DINOX_BF16) {
-    uint2 w;
-    w.x = (unsigned)f32_to_bf16(v.x) | ((unsigned)f32_to_bf16(v.y) << 16);
-    w.y = (unsigned)f32_to_bf16(v.z) | ((unsigned)f32_to_bf16(v.w) << 16);
-    *reinterpret_cast<uint2*>((bf16_t*)p + i) = w;
-  } else {
-    *reinterpret_cast<float4*>((float*)p + i) = v;
-  }
-}
-__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-
-template <int DT>
-__global__ __launch_bounds__(256) void tokens_fwd_vec4_kernel(const void* __restrict__ patches, const float* __restrict__ cls,
-                                                              const float* __restrict__ pos, const float* __restrict__ regs,
-                                                              const float* __restrict__ scale, float* __restrict__ tokens,
-                                                              int V, int P, int R, int D) {
-  const int N = 1 + P + R, D4 = D / 4;
-  const int64_t total = (int64_t)V * N * D4;
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-    const int dd = (int)(idx % D4) * 4;
-    const int64_t t2 = idx / D4;
+    const int dd = (int)(idx % DV) * VW;
+    const int64_t t2 = idx / DV;
     const int n = (int)(t2 % N);
     const int64_t v = t2 / N;
-    float4 val;
+    fvec<VW> val;
     if (n > P) {
-      val = *reinterpret_cast<const float4*>(regs + (int64_t)(n - 1 - P) * D + dd);
+      val = ld_f32<VW>(regs + (int64_t)(n - 1 - P) * D + dd);
     } else {
-      val = (n == 0) ? *reinterpret_cast<const float4*>(cls + dd) : ld4<DT>(patches, (v * P + (n - 1)) * D + dd);
-      val = add4(val, *reinterpret_cast<const float4*>(pos + (int64_t)n * D + dd));
-      if (scale) val = add4(val, *reinterpret_cast<const float4*>(scale + v * D + dd));
+      val = (n == 0) ? ld_f32<VW>(cls + dd) : ld_dt<DT, VW>(patches, (v * P + (n - 1)) * D + dd);
+      val = vadd<VW>(val, ld_f32<VW>(pos + (int64_t)n * D + dd));
+      if (scale) val = vadd<VW>(val, ld_f32<VW>(scale + v * D + dd));
     }
-    *reinterpret_cast<float4*>(tokens + (v * N + n) * D + dd) = val;
+    st_f32<VW>(tokens + (v * N + n) * D + dd, val);
   }
 }
 
-template <int DT>
-__global__ __launch_bounds__(256) void tokens_bwd_patches_vec4(const float* __restrict__ dt, void* __restrict__ dpatches, int V, int P,
-                                                               int R, int D) {
-  const int N = 1 + P + R, D4 = D / 4;
-  const int64_t total = (int64_t)V * P * D4;
+// dpatches[v][i] = dtokens[v][1+i]  (cast to the GEMM dtype)
+template <int DT, int VW>
+__global__ __launch_bounds__(256) void tokens_bwd_patches_kernel(const float* __restrict__ dt, void* __restrict__ dpatches, int V, int P,
+                                                                 int R, int D) {
+  const int N = 1 + P + R, DV = D / VW;
+  const int64_t total = (int64_t)V * P * DV;
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-    const int dd = (int)(idx % D4) * 4;
-    const int64_t t2 = idx / D4;
+    const int dd = (int)(idx % DV) * VW;
+    const int64_t t2 = idx / DV;
     const int i = (int)(t2 % P);
     const int64_t v = t2 / P;
-    st4<DT>(dpatches, (v * P + i) * D + dd, *reinterpret_cast<const float4*>(dt + (v * N + 1 + i) * D + dd));
+    st_dt<DT, VW>(dpatches, (v * P + i) * D + dd, ld_f32<VW>(dt + (v * N + 1 + i) * D + dd));
   }
 }
 
@@ -144,48 +101,33 @@ __global__ __launch_bounds__(256) void tokens_bwd_patches_vec4(const float* __re
 __global__ __launch_bounds__(256) void tokens_bwd_params_vec4(const float* __restrict__ dt, float* __restrict__ dcls,
                                                               float* __restrict__ dpos, float* __restrict__ dregs, int V, int P, int R,
                                                               int D) {
-  __shared__ float4 part[4][64];
+  __shared__ __attribute__((aligned(16))) float part[4][64][4];
   const int N = 1 + P + R, D4 = D / 4;
   const int n = blockIdx.x, c4 = blockIdx.y * 64 + (threadIdx.x & 63), slice = threadIdx.x >> 6;
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+  fvec<4> s = vzero<4>();
   if (c4 < D4) {
     const float* base = dt + (int64_t)n * D + c4 * 4;
     const int64_t stride = (int64_t)N * D;
     int v = slice;
     for (; v + 12 < V; v += 16) {
-      const float4 a = *reinterpret_cast<const float4*>(base + (int64_t)v * stride);
-      const float4 b = *reinterpret_cast<const float4*>(base + (int64_t)(v + 4) * stride);
-      const float4 c = *reinterpret_cast<const float4*>(base + (int64_t)(v + 8) * stride);
-      const float4 d = *reinterpret_cast<const float4*>(base + (int64_t)(v + 12) * stride);
-      s = add4(s, add4(add4(a, b), add4(c, d)));
+      const fvec<4> a = ld_f32<4>(base + (int64_t)v * stride), b = ld_f32<4>(base + (int64_t)(v + 4) * stride);
+      const fvec<4> c = ld_f32<4>(base + (int64_t)(v + 8) * stride), d = ld_f32<4>(base + (int64_t)(v + 12) * stride);
+      s = vadd<4>(s, vadd<4>(vadd<4>(a, b), vadd<4>(c, d)));
     }
-    for (; v < V; v += 4) s = add4(s, *reinterpret_cast<const float4*>(base + (int64_t)v * stride));
+    for (; v < V; v += 4) s = vadd<4>(s, ld_f32<4>(base + (int64_t)v * stride));
   }
-  part[slice][threadIdx.x & 63] = s;
+  st_f32<4>(part[slice][threadIdx.x & 63], s);
   __syncthreads();
   if (slice == 0 && c4 < D4) {
-    const float4 r = add4(add4(part[0][threadIdx.x], part[1][threadIdx.x]), add4(part[2][threadIdx.x], part[3][threadIdx.x]));
+    const fvec<4> r = vadd<4>(vadd<4>(ld_f32<4>(part[0][threadIdx.x]), ld_f32<4>(part[1][threadIdx.x])),
+                              vadd<4>(ld_f32<4>(part[2][threadIdx.x]), ld_f32<4>(part[3][threadIdx.x])));
     const int dd = c4 * 4;
     if (n > P) {
-      if (dregs) *reinterpret_cast<float4*>(dregs + (int64_t)(n - 1 - P) * D + dd) = r;
+      if (dregs) st_f32<4>(dregs + (int64_t)(n - 1 - P) * D + dd, r);
     } else {
-      *reinterpret_cast<float4*>(dpos + (int64_t)n * D + dd) = r;
-      if (n == 0) *reinterpret_cast<float4*>(dcls + dd) = r;
+      st_f32<4>(dpos + (int64_t)n * D + dd, r);
+      if (n == 0) st_f32<4>(dcls + dd, r);
     }
-  }
-}
-
-// dpatches[v][i] = dtokens[v][1+i]  (cast to the GEMM dtype)
-template <int DT>
-__global__ __launch_bounds__(256) void tokens_bwd_patches(const float* __restrict__ dt, void* __restrict__ dpatches, int V,
-                                                          int P, int R, int D) {
-  const int N = 1 + P + R;
-  const int64_t total = (int64_t)V * P * D;
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-    const int dd = (int)(idx % D);
-    const int i = (int)((idx / D) % P);
-    const int64_t v = idx / ((int64_t)D * P);
-    elem<DT>::st(dpatches, idx, dt[(v * N + 1 + i) * D + dd]);
   }
 }
 
@@ -222,11 +164,6 @@ __global__ __launch_bounds__(256) void tokens_bwd_scale(const float* __restrict_
   dscale[idx] = s;
 }
 
-static unsigned grid_for(int64_t total) {
-  int64_t b = ceil_div(total, 256);
-  return (unsigned)(b < 256 * 16 ? b : 256 * 16);
-}
-
 }  // namespace dinox
 
 using namespace dinox;
@@ -259,11 +196,7 @@ extern "C" int dinox_patch_unfold_ld(const float* x, void* u, int V, int H, int 
              "patch_unfold_ld: V=%d H=%d W=%d patch=%d ld=%d", V, H, W, patch, ld);
   DX_REQUIRE(out_dtype == DINOX_F32 || out_dtype == DINOX_BF16, DINOX_EINVAL, "patch_unfold_ld: dtype %d", out_dtype);
   const int64_t total = (int64_t)V * (H / patch) * (W / patch) * ld;
-  hipStream_t st = as_stream(stream);
-  if (out_dtype == DINOX_F32)
-    hipLaunchKernelGGL((unfold_ld_kernel<DINOX_F32>), dim3(grid_for(total)), dim3(256), 0, st, x, u, V, H, W, patch, ld);
-  else
-    hipLaunchKernelGGL((unfold_ld_kernel<DINOX_BF16>), dim3(grid_for(total)), dim3(256), 0, st, x, u, V, H, W, patch, ld);
+  DX_LAUNCH_DT(unfold_ld_kernel, out_dtype, dim3(grid_1d(total, 256, 4096)), dim3(256), as_stream(stream), x, u, V, H, W, patch, ld);
   return check_launch("patch_unfold_ld");
 }
 
@@ -274,16 +207,10 @@ extern "C" int dinox_patch_unfold(const float* x, void* u, int V, int H, int W, 
   DX_REQUIRE(out_dtype == DINOX_F32 || out_dtype == DINOX_BF16, DINOX_EINVAL, "patch_unfold: dtype %d", out_dtype);
   const int64_t total = (int64_t)V * 3 * H * W;
   hipStream_t st = as_stream(stream);
-  const bool vec = patch % 8 == 0 && (((uintptr_t)x | (uintptr_t)u) & 15) == 0;
-  if (vec) {
-    if (out_dtype == DINOX_F32)
-      hipLaunchKernelGGL((unfold_vec8_kernel<DINOX_F32>), dim3(grid_for(total / 8)), dim3(256), 0, st, x, u, V, H, W, patch);
-    else
-      hipLaunchKernelGGL((unfold_vec8_kernel<DINOX_BF16>), dim3(grid_for(total / 8)), dim3(256), 0, st, x, u, V, H, W, patch);
-  } else if (out_dtype == DINOX_F32)
-    hipLaunchKernelGGL((unfold_kernel<DINOX_F32>), dim3(grid_for(total)), dim3(256), 0, st, x, u, V, H, W, patch);
+  if (patch % 8 == 0 && aligned16(x, u))
+    DX_LAUNCH_DT(unfold_vec8_kernel, out_dtype, dim3(grid_1d(total / 8, 256, 4096)), dim3(256), st, x, u, V, H, W, patch);
   else
-    hipLaunchKernelGGL((unfold_kernel<DINOX_BF16>), dim3(grid_for(total)), dim3(256), 0, st, x, u, V, H, W, patch);
+    DX_LAUNCH_DT(unfold_kernel, out_dtype, dim3(grid_1d(total, 256, 4096)), dim3(256), st, x, u, V, H, W, patch);
   return check_launch("patch_unfold");
 }
 
@@ -295,17 +222,9 @@ extern "C" int dinox_tokens_fwd(const void* patches, const float* cls, const flo
   DX_REQUIRE(patches_dtype == DINOX_F32 || patches_dtype == DINOX_BF16, DINOX_EINVAL, "tokens_fwd: dtype %d", patches_dtype);
   const int64_t total = (int64_t)V * (1 + P + R) * D;
   hipStream_t st = as_stream(stream);
-  const bool vec = D % 4 == 0 && (((uintptr_t)patches | (uintptr_t)cls | (uintptr_t)pos | (uintptr_t)registers | (uintptr_t)scale |
-                                   (uintptr_t)tokens) & 15) == 0;
-  if (vec) {
-    if (patches_dtype == DINOX_F32)
-      hipLaunchKernelGGL((tokens_fwd_vec4_kernel<DINOX_F32>), dim3(grid_for(total / 4)), dim3(256), 0, st, patches, cls, pos, registers, scale, tokens, V, P, R, D);
-    else
-      hipLaunchKernelGGL((tokens_fwd_vec4_kernel<DINOX_BF16>), dim3(grid_for(total / 4)), dim3(256), 0, st, patches, cls, pos, registers, scale, tokens, V, P, R, D);
-  } else if (patches_dtype == DINOX_F32)
-    hipLaunchKernelGGL((tokens_fwd_kernel<DINOX_F32>), dim3(grid_for(total)), dim3(256), 0, st, patches, cls, pos, registers, scale, tokens, V, P, R, D);
-  else
-    hipLaunchKernelGGL((tokens_fwd_kernel<DINOX_BF16>), dim3(grid_for(total)), dim3(256), 0, st, patches, cls, pos, registers, scale, tokens, V, P, R, D);
+  const bool vec = D % 4 == 0 && aligned16(patches, cls, pos, registers, scale, tokens);
+  DX_LAUNCH_DT_VW(tokens_fwd_kernel, patches_dtype, vec, dim3(grid_1d(total / (vec ? 4 : 1), 256, 4096)), dim3(256), st, patches, cls, pos,
+                  registers, scale, tokens, V, P, R, D);
   return check_launch("tokens_fwd");
 }
 
@@ -316,21 +235,14 @@ extern "C" int dinox_tokens_bwd(const float* dtokens, void* dpatches, float* dcl
   DX_REQUIRE(patches_dtype == DINOX_F32 || patches_dtype == DINOX_BF16, DINOX_EINVAL, "tokens_bwd: dtype %d", patches_dtype);
   hipStream_t st = as_stream(stream);
   const int64_t tp = (int64_t)V * P * D;
-  const bool vec = D % 4 == 0 && (((uintptr_t)dtokens | (uintptr_t)dpatches | (uintptr_t)dcls | (uintptr_t)dpos | (uintptr_t)dregs) & 15) == 0;
-  if (vec) {
-    if (patches_dtype == DINOX_F32)
-      hipLaunchKernelGGL((tokens_bwd_patches_vec4<DINOX_F32>), dim3(grid_for(tp / 4)), dim3(256), 0, st, dtokens, dpatches, V, P, R, D);
-    else
-      hipLaunchKernelGGL((tokens_bwd_patches_vec4<DINOX_BF16>), dim3(grid_for(tp / 4)), dim3(256), 0, st, dtokens, dpatches, V, P, R, D);
+  const bool vec = D % 4 == 0 && aligned16(dtokens, dpatches, dcls, dpos, dregs);
+  DX_LAUNCH_DT_VW(tokens_bwd_patches_kernel, patches_dtype, vec, dim3(grid_1d(tp / (vec ? 4 : 1), 256, 4096)), dim3(256), st, dtokens, dpatches,
+                  V, P, R, D);
+  if (vec)
     hipLaunchKernelGGL(tokens_bwd_params_vec4, dim3((unsigned)(1 + P + R), (unsigned)ceil_div(D / 4, 64)), dim3(256), 0, st, dtokens, dcls, dpos, dregs,
                        V, P, R, D);
-  } else {
-    if (patches_dtype == DINOX_F32)
-      hipLaunchKernelGGL((tokens_bwd_patches<DINOX_F32>), dim3(grid_for(tp)), dim3(256), 0, st, dtokens, dpatches, V, P, R, D);
-    else
-      hipLaunchKernelGGL((tokens_bwd_patches<DINOX_BF16>), dim3(grid_for(tp)), dim3(256), 0, st, dtokens, dpatches, V, P, R, D);
+  else
     hipLaunchKernelGGL(tokens_bwd_params, dim3((unsigned)ceil_div((int64_t)(1 + P + R) * D, 256)), dim3(256), 0, st, dtokens, dcls, dpos, dregs, V, P, R, D);
-  }
   if (dscale)
     hipLaunchKernelGGL(tokens_bwd_scale, dim3((unsigned)ceil_div((int64_t)V * D, 256)), dim3(256), 0, st, dtokens, dscale, V, P, R, D);
   return check_launch("tokens_bwd");

@@ -67,6 +67,25 @@ def test_ntxent_kernels_match_reference_and_oracle(dx, gold, oracle, tag):
     assert row_err(dz3, 0.25 * o_dz)[0] <= 1e-3
 
 
+def test_ntxent_second_ragged_chunk_of_the_row_sum(dx):
+    """B = 513, D = 32: M = 1026 rows, so the row-loss sum (ntxent_sum_kernel, 1024 rows of LDS per pass) takes a second pass of
+    2 rows -- no fixture is that large, the input is drawn here from a fixed seed.  Loss and gradient against the float64 oracle at the
+    bar of the cases above, through the square path (the mean form: divisor M) and, force_rect=True, the rectangular one (the sum
+    form: divisor 1, the host divides)."""
+    ops, _ = dx
+    z = torch.randn(1026, 32, generator=torch.Generator().manual_seed(513))
+    o_loss, o_dz = NX.ntxent(z.numpy(), 0.1)
+    for rect in (False, True):
+        loss, saved = ops.ntxent_fwd(z.to(DEV), 0.1, force_rect=rect)
+        dz = ops.ntxent_bwd(saved, 1.0).cpu().numpy()
+        loss = float(loss)
+        assert np.isfinite(loss) and np.isfinite(dz).all()
+        e_row, e_zero = row_err(dz, o_dz)
+        print(f"M=1026 {'rect' if rect else 'square'}: loss rel err {abs(loss - o_loss) / abs(o_loss):.2e}, worst gradient row {e_row:.2e}")
+        assert abs(loss - o_loss) <= 1e-3 * abs(o_loss)
+        assert e_row <= 1e-3 and e_zero == 0.0
+
+
 @pytest.mark.parametrize("tag", ["b33", "b130", "adv"])
 def test_ntxent_is_bit_reproducible(dx, gold, tag):
     ops, _ = dx
