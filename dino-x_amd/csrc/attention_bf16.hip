@@ -1,103 +1,44 @@
-// attention_bf16.hip -- MFMA flash-style attention core for head_dim 64 on gfx950 (bf16 in, fp32 softmax).
+// attention_bf16.hip -- MFMA attention for head size 64 and sequences whose whole K and V (or Q and dO) fit in LDS (bf16 in, fp32
+// softmax).  Token counts on this path are small (201 at /16, 261 at /14): a head's image is 28 KiB at N = 201, and one wave can hold
+// a full 32-query score strip in registers, so the forward needs no online-softmax rescaling.  The image layout, the fragment
+// readers and the accumulator helpers are in attention_common.h (conventions in its header); longer sequences and other head
+// sizes run attention_flash.hip.  nblk = ceil(N / 32); one wave per 32 tokens everywhere.
 //
-// Token counts on this path are small (201 at /16, 261 at /14), so a whole head's K and V (or Q and dO)
-// fit in LDS (28 KiB each at N=201) and one wave can hold a full 32-query score strip in registers:
-// the forward needs no online-softmax rescaling.  All three kernels use ONE LDS image layout that
-// serves both row reads (ds_read_b128, MFMA A operands) and transposed reads (ds_read_b64_tr_b16, MFMA B
-// operands whose reduction index runs down the rows) without bank conflicts -- the 8-row x 32-column
-// sub-tile image of cdna_hip_programming.md T10(a), adapted to 64-column (128-B) rows.
+//   kernel                      launcher picks it when                                      forced by
+//   attn_fwd_bf16_persist<NKT>  launch_attention_bf16_fwd: nblk <= 7 (N <= 224: four images    (default)
+//                               and the waves' staging tiles fit 160 KiB of LDS).  NKT = 7,
+//                               1, 2: one pass at exactly that nblk; NKT = 0: two passes,
+//                               nblk = 3 .. 6
+//   attn_fwd_bf16<NKT>          the same launcher otherwise (N <= 288), NKT = 2, 4, 7, 9    DINOX_ATTN_NO_PERSIST=1 (A/B only)
+//   attn_bwd_fused_bf16         launch_attention_bf16_bwd: nblk <= 7 (N <= 224)             (default)
+//   attn_bwd_dq_bf16 +          the same launcher otherwise (N <= 544)                      DINOX_ATTN_BWD_SPLIT=1
+//   attn_bwd_dkv_bf16
+//   attn_qkv_fused_fwd<7>       launch_attention_qkv_fused_fwd: 192 < N <= 224              DINOX_QKV_FUSED = 0 never, 1 at every width
+//                               (attention_qkv_fused_ok); called by the block plan of       (read by the block plan, block.hip)
+//                               block.hip for no-grad forwards, by default at widths <= 512
 //
-// Score tiles are computed TRANSPOSED (S^T = K . Q^T: keys in the accumulator rows, queries on the lanes)
-// so that softmax statistics are lane-local and the accumulator can be re-used directly as the A operand
-// of the next product (P^T)^T . V  /  (dS^T)^T . K  with no lane movement (guide section 3, "An accumulator
-// tile as the next MFMA's operand"); the other operand is fetched in the matching permuted k order.
-//
-//   fwd   : attn_fwd_bf16_persist: persistent workgroups, one (image, head) per iteration, the NEXT head's K,V image
-//           streamed into the second LDS buffer by LDS-DMA (buffer_load ... lds, swizzle on the source address) while this
-//           one computes; one wave per 32 queries.  Up to 7 key tiles (N <= 224): S^T of the whole strip stays in
-//           registers (one pass: max, exp, sum, O = P V); more keys: two passes over the key tiles.  Writes lse.
-//           attn_fwd_bf16<NKT> is the non-persistent two-pass form (DINOX_ATTN_NO_PERSIST=1, A/B only).
-//   bwd dQ: one wave per 32 queries.   K,V images by LDS-DMA; streams key tiles: S^T, dP^T = V . dO^T, dS^T -> dQ += dS K;
-//           writes delta = rowsum(dO o O) to the workspace for the dKV kernel.
-//   bwd dKV: one wave per 32 keys.     Q,dO images by LDS-DMA, lse/delta in LDS; streams query tiles: S = Q . K^T,
-//           dP = dO . V^T -> dV += P^T dO, dK += dS^T Q.
-// (two backward kernels recompute S/dP once more than a single fused pass would: 7 instead of 5 tile
-//  products, traded for no cross-wave reduction of dQ; attention is ~8 % of the block's FLOPs.)
+//   persistent forward : one workgroup per CU walks (image, head) pairs; the NEXT pair's K, V images stream into the second LDS
+//           buffer by LDS-DMA (buffer_load ... lds, swizzle on the source address) while this one computes.  Writes lse.
+//   split backward, dQ : K, V images by LDS-DMA; streams key tiles: S^T, dP^T = V . dO^T, dS^T -> dQ += dS K; writes
+//           delta = rowsum(dO o O) to the workspace for the dKV kernel.
+//   split backward, dKV: Q, dO images by LDS-DMA, lse / delta in LDS; streams query tiles: S = Q . K^T, dP = dO . V^T ->
+//           dV += P^T dO, dK += dS^T Q.  (The two kernels recompute S / dP once more than one pass would: 7 instead of 5 tile
+//           products, traded for no cross-wave reduction of dQ.)
+//   fused backward     : both phases from one residency of a pair's data, every load under the other phase's arithmetic.
+//   qkv-fused forward  : qkv projection and attention of a pair in one launch; the packed qkv tensor never reaches HBM.
 
-#include "common.h"
+#include "attention_common.h"
 #include "kernels.h"
-#include <type_traits>
 
 namespace dinox {
 
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-constexpr int AT_D = 64;
-
-// byte offset of 16-B chunk ch (0..7) of row r in a [rows][64 bf16] image
-__device__ __forceinline__ int img_off(int r, int ch) {
-  return 1024 * (r >> 3) + 512 * (ch >> 2) + 64 * (r & 7) + 16 * ((ch & 3) ^ ((r >> 2) & 3));
-}
-
-// Cooperative load of `rows_pad` rows x 64 bf16 (rows >= n_valid are zero) from a strided global matrix.
-__device__ __forceinline__ void load_image(char* __restrict__ img, const bf16_t* __restrict__ src, int64_t row_stride,
-                                           int n_valid, int rows_pad) {
-  for (int idx = threadIdx.x; idx < rows_pad * 8; idx += blockDim.x) {
-    const int r = idx >> 3, ch = idx & 7;
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if (r < n_valid) v = *reinterpret_cast<const uint4*>(src + (int64_t)r * row_stride + ch * 8);
-    *reinterpret_cast<uint4*>(img + img_off(r, ch)) = v;
-  }
-}
-
-// A-operand fragment (standard k order): lane (row = l&31, hl = l>>5) gets img[row0 + row][16*ks + 8*hl + j], j<8.
-__device__ __forceinline__ bf16x8 frag_rows(const char* __restrict__ img, int row0, int ks, int lane) {
-  return *reinterpret_cast<const bf16x8*>(img + img_off(row0 + (lane & 31), 2 * ks + (lane >> 5)));
-}
-
-// B-operand fragment in the PERMUTED k order that matches an accumulator tile used as the A operand:
-// lane (col = l&31, hl = l>>5), element j  <-  img[row0 + 16*s + 8*(j>>2) + 4*hl + (j&3)][d0 + col].
-__device__ __forceinline__ bf16x8 frag_tr_perm(const char* __restrict__ img, int row0, int s, int d0, int lane) {
-  const int i = lane & 15, g = lane >> 4;
-  const int q4 = i >> 2, p = i & 3, hl = g >> 1;
-  const int ch = (d0 >> 3) + 2 * (g & 1) + (p >> 1);
-  const int r0 = row0 + 16 * s + 4 * hl + q4;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + img_off(r0, ch) + 8 * (p & 1)));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + img_off(r0 + 8, ch) + 8 * (p & 1)));
-  s16x8 v;
-  v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-  v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-  return __builtin_bit_cast(bf16x8, v);
-}
-
-// accumulator registers [8s, 8s+8) -> bf16 A fragment of k-step s
-__device__ __forceinline__ bf16x8 acc_as_a(const f32x16& x, int s) {
-  bf16x8 a;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) a[j] = (__bf16)x[8 * s + j];
-  return a;
-}
-
-// row index inside a 32-row accumulator tile held by register e of lane-half hl
-__device__ __forceinline__ int acc_row(int e, int hl) { return (e & 3) + 8 * (e >> 2) + 4 * hl; }
-
-// 4 fragments (ks = 0..3) of one 64-element global row: lane (row = l&31, hl) takes d = 16*ks + 8*hl + j
-__device__ __forceinline__ void load_row_frags(bf16x8 (&f)[4], const bf16_t* __restrict__ rowp, int lane) {
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) f[ks] = *reinterpret_cast<const bf16x8*>(rowp + 16 * ks + 8 * (lane >> 5));
-}
-
-__device__ __forceinline__ void zero16(f32x16& x) {
-#pragma unroll
-  for (int e = 0; e < 16; ++e) x[e] = 0.f;
-}
-
 // store a 32x32 accumulator tile (rows = tokens row0.., cols = d0..) as bf16 rows of a strided matrix
 __device__ __forceinline__ void store_tile(bf16_t* __restrict__ dst, int64_t row_stride, int row0, int n_valid, int d0,
-                                           const f32x16& x, float scale, int lane) {
+                                           const f32x16& x, int lane) {
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
     const int r = row0 + acc_row(e, lane >> 5);
-    if (r < n_valid) dst[(int64_t)r * row_stride + d0 + (lane & 31)] = f32_to_bf16(x[e] * scale);
+    if (r < n_valid) dst[(int64_t)r * row_stride + d0 + (lane & 31)] = f32_to_bf16(x[e]);
   }
 }
 
@@ -147,8 +88,8 @@ __global__ __launch_bounds__(512) void attn_fwd_bf16(const bf16_t* __restrict__ 
   char* kimg = smem;
   char* vimg = smem + npad * 128;
   float* inv_s = reinterpret_cast<float*>(smem + 2 * npad * 128) + wv * 32;   // per-wave 1/rowsum, query-indexed
-  load_image(kimg, base + C, rs, N, npad);
-  load_image(vimg, base + 2 * C, rs, N, npad);
+  load_image<AT_D>(kimg, base + C, rs, 0, npad, N, AT_D);
+  load_image<AT_D>(vimg, base + 2 * C, rs, 0, npad, N, AT_D);
   __syncthreads();
   const int qb = blockIdx.y * nw + wv;
   if (qb * 32 >= N) return;
@@ -156,7 +97,7 @@ __global__ __launch_bounds__(512) void attn_fwd_bf16(const bf16_t* __restrict__ 
   int qrow = q0 + (lane & 31);
   if (qrow >= N) qrow = N - 1;                                      // clamp: computed, never stored
   bf16x8 qf[4];
-  load_row_frags(qf, base + (int64_t)qrow * rs, lane);
+  load_row_frags<AT_D>(qf, base + (int64_t)qrow * rs, AT_D, lane);
 
   float mx = -INFINITY;
 #pragma unroll 1
@@ -165,7 +106,7 @@ __global__ __launch_bounds__(512) void attn_fwd_bf16(const bf16_t* __restrict__ 
     zero16(s);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks)
-      s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows(kimg, kt * 32, ks, lane), qf[ks], s, 0, 0, 0);
+      s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<AT_D>(kimg, kt * 32, ks, lane), qf[ks], s, 0, 0, 0);
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const int key = kt * 32 + acc_row(e, hl);
@@ -184,7 +125,7 @@ __global__ __launch_bounds__(512) void attn_fwd_bf16(const bf16_t* __restrict__ 
     zero16(s);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks)
-      s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows(kimg, kt * 32, ks, lane), qf[ks], s, 0, 0, 0);
+      s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<AT_D>(kimg, kt * 32, ks, lane), qf[ks], s, 0, 0, 0);
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const int key = kt * 32 + acc_row(e, hl);
@@ -197,7 +138,7 @@ __global__ __launch_bounds__(512) void attn_fwd_bf16(const bf16_t* __restrict__ 
       const bf16x8 pa = acc_as_a(s, ss);
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt)
-        oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa, frag_tr_perm(vimg, kt * 32, ss, dt * 32, lane), oacc[dt], 0, 0, 0);
+        oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa, frag_tr_perm<AT_D>(vimg, kt * 32, ss, dt * 32, lane), oacc[dt], 0, 0, 0);
     }
   }
   sum += __shfl_xor(sum, 32, 64);
@@ -219,62 +160,11 @@ __global__ __launch_bounds__(512) void attn_fwd_bf16(const bf16_t* __restrict__ 
     }
   }
   bf16_t* ob = o + (int64_t)b * N * C + hh * AT_D;
-  store_tile(ob, C, q0, N, 0, oacc[0], 1.0f, lane);
-  store_tile(ob, C, q0, N, 32, oacc[1], 1.0f, lane);
-}
-
-// Per-lane constant parts of the fragment addresses.  Tile t of an image starts 4096 B after tile t-1 (32 rows = four 1-KiB
-// row groups; the swizzle terms depend on the row inside the tile only), so address = table entry + 4096*t.
-struct RowAddr {            // A-operand row reads: entry ks
-  int off[4];
-  __device__ __forceinline__ void init(int lane) {
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) off[ks] = img_off(lane & 31, 2 * ks + (lane >> 5));
-  }
-};
-struct TrAddr {             // permuted-k transposed reads: entry [ss][dt][lo/hi]
-  int off[2][2][2];
-  __device__ __forceinline__ void init(int lane) {
-    const int i = lane & 15, g = lane >> 4, q4 = i >> 2, pp = i & 3;
-#pragma unroll
-    for (int ss = 0; ss < 2; ++ss)
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt) {
-        const int ch = (dt * 32 >> 3) + 2 * (g & 1) + (pp >> 1);
-        const int r0 = 16 * ss + 4 * (g >> 1) + q4;
-        off[ss][dt][0] = img_off(r0, ch) + 8 * (pp & 1);
-        off[ss][dt][1] = img_off(r0 + 8, ch) + 8 * (pp & 1);
-      }
-  }
-};
-__device__ __forceinline__ bf16x8 rd_rows(const char* img, const RowAddr& a, int ks, int t) {
-  return *reinterpret_cast<const bf16x8*>(img + a.off[ks] + t * 4096);
-}
-__device__ __forceinline__ bf16x8 rd_tr(const char* img, const TrAddr& a, int ss, int dt, int t) {
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + a.off[ss][dt][0] + t * 4096));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + a.off[ss][dt][1] + t * 4096));
-  s16x8 v;
-  v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-  v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-  return __builtin_bit_cast(bf16x8, v);
-}
-
-// Two transposed 8-byte LDS reads -> one B fragment.  The __restrict__ parameters are not decoration: after inlining they give the
-// two reads alias-scope metadata, and hipcc's waitcnt insertion only falls back to "wait for every LDS-DMA in flight" (vmcnt(0),
-// which in the persistent forward kernel means the NEXT pair's images, requested a moment earlier) for LDS reads that carry none.
-__device__ __forceinline__ bf16x8 rd_tr_pair(const char* __restrict__ p0, const char* __restrict__ p1) {
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p0);
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p1);
-  s16x8 v;
-  v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-  v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-  return __builtin_bit_cast(bf16x8, v);
+  store_tile(ob, C, q0, N, 0, oacc[0], lane);
+  store_tile(ob, C, q0, N, 32, oacc[1], lane);
 }
 
 // ------------------------------------------------------------------------------------------ forward, persistent
-typedef __attribute__((address_space(3))) void at_lds_void;
-typedef __attribute__((address_space(1))) const void at_gbl_void;
-
 // LDS-DMA of one [npad][64] image: wave-instruction `blk` fills rows 8*blk .. 8*blk+7 (1 KiB, lane-linear destination); the
 // img_off() placement is produced by permuting the per-lane SOURCE address.  Rows >= n_valid re-read row n_valid-1 (finite
 // data; every consumer masks those keys/queries), so no address leaves the tensor.
@@ -361,11 +251,9 @@ __global__ __launch_bounds__(512) void attn_fwd_bf16_persist(const bf16_t* __res
     if (nxt < npairs) q_dma(nxt);
     const char* kimg = smem + (2 * buf) * img_bytes;
     const char* vimg = kimg + img_bytes;
-    const int b = pair / heads, hh = pair % heads;
-    // One query block of this pair.  DEFER (the wave's last block, always executed so that the pending tile is redefined in every
-    // iteration and is never live across another block's arithmetic): keep the normalised tile for the next iteration's stores.
-    auto do_block = [&](int qb, auto defer_c) {
-      constexpr bool DEFER = decltype(defer_c)::value;
+    // One query block of this pair; its normalised tile is kept for the next iteration's stores (the pending tile is redefined in
+    // every iteration and is never live across another block's arithmetic).
+    auto do_block = [&](int qb) {
       const int q0 = qb * 32;
       // Key tile kt sits 4096 B after tile kt-1 in the image (32 rows = four 1-KiB row groups, swizzle terms unchanged), so
       // every fragment address is a per-lane constant plus kt*4096: computed once here, not per tile.
@@ -498,20 +386,15 @@ __global__ __launch_bounds__(512) void attn_fwd_bf16_persist(const bf16_t* __res
         }
       }
       __builtin_amdgcn_wave_barrier();
-      if (DEFER) {                                        // the wave's last (for N <= 256: only) block of this pair: stored next iteration
-        pend[0] = oacc[0];
-        pend[1] = oacc[1];
-        pend_lse = lse_q;
-        pend_pair = pair;
-        pend_q0 = q0;
-      } else {
-        if (hl == 0 && q0 + lane < N) lse[((int64_t)b * heads + hh) * N + q0 + lane] = lse_q;
-        store_block(o + (int64_t)b * N * C + hh * AT_D, C, q0, N, oacc[0], oacc[1], st_scratch, lane);
-      }
+      pend[0] = oacc[0];
+      pend[1] = oacc[1];
+      pend_lse = lse_q;
+      pend_pair = pair;
+      pend_q0 = q0;
     };
     // One query block per wave: the launcher guarantees nblk <= nw (its LDS budget admits at most 7 blocks).  A wave walking
     // several blocks would store through st_scratch while q_dma(nxt) streams the next pair's Q block into it.
-    do_block(wv, std::true_type{});
+    do_block(wv);
   }
   store_pending();
 }
@@ -542,9 +425,9 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_bf16(const bf16_t* __restrict
   if (qrow >= N) qrow = N - 1;
   const int64_t orow = ((int64_t)b * N + qrow) * C + hh * AT_D;
   bf16x8 qf[4], dof[4], of[4];
-  load_row_frags(qf, base + (int64_t)qrow * rs, lane);
-  load_row_frags(dof, d_o + orow, lane);
-  load_row_frags(of, o + orow, lane);
+  load_row_frags<AT_D>(qf, base + (int64_t)qrow * rs, AT_D, lane);
+  load_row_frags<AT_D>(dof, d_o + orow, AT_D, lane);
+  load_row_frags<AT_D>(of, o + orow, AT_D, lane);
   const float L = lse[((int64_t)b * heads + hh) * N + qrow];
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
@@ -596,8 +479,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_bf16(const bf16_t* __restrict
   // (direct stores: staging them through the images' LDS needs a workgroup barrier first, and waves that finish early then wait
   //  instead of storing under the others' arithmetic -- measured 4 % slower for the two backward kernels together)
   bf16_t* dqb = dqkv + (int64_t)b * N * rs + hh * AT_D;
-  store_tile(dqb, rs, q0, N, 0, dq[0], 1.0f, lane);
-  store_tile(dqb, rs, q0, N, 32, dq[1], 1.0f, lane);
+  store_tile(dqb, rs, q0, N, 0, dq[0], lane);
+  store_tile(dqb, rs, q0, N, 32, dq[1], lane);
   }   // active
 }
 
@@ -630,8 +513,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_bf16(const bf16_t* __restric
   int krow = k0 + (lane & 31);
   if (krow >= N) krow = N - 1;
   bf16x8 kf[4], vf[4];
-  load_row_frags(kf, base + (int64_t)krow * rs + C, lane);
-  load_row_frags(vf, base + (int64_t)krow * rs + 2 * C, lane);
+  load_row_frags<AT_D>(kf, base + (int64_t)krow * rs + C, AT_D, lane);
+  load_row_frags<AT_D>(vf, base + (int64_t)krow * rs + 2 * C, AT_D, lane);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();                                                   // DMA pieces + the LDS statistics of every wave
   const bool active = kb * 32 < N;                                   // wave-uniform
@@ -680,10 +563,10 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_bf16(const bf16_t* __restric
   }
   bf16_t* dkb = dqkv + (int64_t)b * N * rs + hh * AT_D + C;
   bf16_t* dvb = dkb + C;
-  store_tile(dkb, rs, k0, N, 0, dk[0], 1.0f, lane);
-  store_tile(dkb, rs, k0, N, 32, dk[1], 1.0f, lane);
-  store_tile(dvb, rs, k0, N, 0, dv[0], 1.0f, lane);
-  store_tile(dvb, rs, k0, N, 32, dv[1], 1.0f, lane);
+  store_tile(dkb, rs, k0, N, 0, dk[0], lane);
+  store_tile(dkb, rs, k0, N, 32, dk[1], lane);
+  store_tile(dvb, rs, k0, N, 0, dv[0], lane);
+  store_tile(dvb, rs, k0, N, 32, dv[1], lane);
   }   // active
 }
 
@@ -741,9 +624,9 @@ __global__ __launch_bounds__(448) void attn_bwd_fused_bf16(const bf16_t* __restr
   bf16x8 qf[4], dof[4], of[4];
   float L = 0.f;
   auto load_rows = [&](int pr) {
-    load_row_frags(qf, qkv_of(pr) + (int64_t)trow * rs, lane);
-    load_row_frags(dof, d_o + do_of(pr) + (int64_t)trow * C, lane);
-    load_row_frags(of, o + do_of(pr) + (int64_t)trow * C, lane);
+    load_row_frags<AT_D>(qf, qkv_of(pr) + (int64_t)trow * rs, AT_D, lane);
+    load_row_frags<AT_D>(dof, d_o + do_of(pr) + (int64_t)trow * C, AT_D, lane);
+    load_row_frags<AT_D>(of, o + do_of(pr) + (int64_t)trow * C, AT_D, lane);
     L = lse[(int64_t)pr * N + trow];                                          // (pair index = b * heads + h)
   };
   RowAddr ra;
@@ -813,8 +696,7 @@ __global__ __launch_bounds__(448) void attn_bwd_fused_bf16(const bf16_t* __restr
         const bf16x8 a = acc_as_a(st, ss);
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt)
-          dq[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, rd_tr_pair(kimg + ta.off[ss][dt][0] + kt * 4096, kimg + ta.off[ss][dt][1] + kt * 4096),
-                                                           dq[dt], 0, 0, 0);
+          dq[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, rd_tr(kimg, ta, ss, dt, kt), dq[dt], 0, 0, 0);
       }
     }
     // softmax scale, once per output element instead of once per score (sc = 1/8 at head size 64: exact, the result is bit for bit the same)
@@ -875,10 +757,8 @@ __global__ __launch_bounds__(448) void attn_bwd_fused_bf16(const bf16_t* __restr
         const bf16x8 pa = acc_as_a(st, ss), da = acc_as_a(dp, ss);
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt) {
-          dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa, rd_tr_pair(doimg + ta.off[ss][dt][0] + qt * 4096, doimg + ta.off[ss][dt][1] + qt * 4096),
-                                                           dv[dt], 0, 0, 0);
-          dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da, rd_tr_pair(qimg + ta.off[ss][dt][0] + qt * 4096, qimg + ta.off[ss][dt][1] + qt * 4096),
-                                                           dk[dt], 0, 0, 0);
+          dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa, rd_tr(doimg, ta, ss, dt, qt), dv[dt], 0, 0, 0);
+          dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da, rd_tr(qimg, ta, ss, dt, qt), dk[dt], 0, 0, 0);
         }
       }
     }
@@ -906,7 +786,8 @@ __global__ __launch_bounds__(448) void attn_bwd_fused_bf16(const bf16_t* __restr
 //                by LDS-DMA in a two-slot ring, one barrier per step;
 //   hand-over    q -> the wave's 32-row image in its staging tile, k / v -> rows 32 w .. of the K / V images, in the layout the
 //                attention kernels read (img_off); optionally the packed qkv rows leave for HBM too (qkv_out != null);
-//   attention    exactly attn_fwd_bf16_persist's one-pass block (S^T strip in registers, lane-local softmax, P as the next A operand).
+//   attention    exactly attn_fwd_bf16_persist's one-pass block (S^T strip in registers, lane-local softmax, P as the next A operand):
+//                a second copy of that text, held to it bit for bit by test_fused_qkv_attention_equals_the_forward_on_its_own_rows.
 // The pairs of one image are kept on one XCD (its six heads run side by side: the token rows come out of that XCD's L2, the weights
 // -- 0.9 MB for all heads -- stay there).
 // MEASURED (tools/qkv_attn_bench.py): correct, and NOT faster than the two launches it replaces -- 219-227 us against
@@ -1127,12 +1008,6 @@ __global__ __launch_bounds__(NKT * 64) void attn_qkv_fused_fwd(const bf16_t* __r
 }
 
 // ------------------------------------------------------------------------------------------ launchers
-// Workgroups of a persistent attention kernel that fit one CU: 160 KiB of LDS, and 8 waves (the kernels sit at ~250 registers: two per SIMD).
-static int persist_wgs_per_cu(size_t lds_bytes, int waves) {
-  const int by_lds = (int)((size_t)160 * 1024 / (lds_bytes ? lds_bytes : 1)), by_waves = 8 / (waves > 0 ? waves : 1);
-  const int n = by_lds < by_waves ? by_lds : by_waves;
-  return n < 1 ? 1 : n;
-}
 static void geometry(int N, int& nblk, int& nwg, int& waves) {
   nblk = (N + 31) / 32;
   nwg = (nblk + 7) / 8;
@@ -1155,10 +1030,7 @@ int launch_attention_bf16_fwd(const void* qkv, void* o, float* lse, int B, int N
     static const bool off = knob_set("DINOX_ATTN_NO_PERSIST");
     if (lds <= 160 * 1024 && !off && nblk <= nw) {          // one query block per wave (the kernel relies on it)
       const int npairs = B * heads;
-      // resident workgroups: one per CU at 7 blocks (201 tokens); short sequences (the 41-token local crops: two waves, 41 KiB) get as many as
-      // LDS and two waves per SIMD allow -- with one the chip ran half a wave per SIMD (113 us for 5 GFLOP at N = 41)
-      const int per_cu = persist_wgs_per_cu(lds, nw);
-      const int nwgp = npairs < 256 * per_cu ? npairs : 256 * per_cu;
+      const int nwgp = persist_grid(npairs, lds, nw);
 #define PFWD(NKT)                                                                                                                  \
   do {                                                                                                                             \
     if (int rc = allow_lds(attn_fwd_bf16_persist<NKT>, lds)) return fail(rc, "attention_fwd: cannot reserve %zu B of LDS", lds);   \
@@ -1193,8 +1065,7 @@ int launch_attention_qkv_fused_fwd(const void* x, const void* w, const float* bi
   constexpr int NKT = 7;
   const size_t lds = (size_t)2 * NKT * 32 * 128 + 2 * QA_WSLOT + (size_t)NKT * 2 * QA_XSLOT + (size_t)NKT * ST_BYTES + NKT * 32 * sizeof(float) + 192 * sizeof(float);
   if (int rc = allow_lds(attn_qkv_fused_fwd<NKT>, lds)) return fail(rc, "qkv_attention_fwd: cannot reserve %zu B of LDS", lds);
-  const int64_t npairs = (int64_t)B * heads;
-  const int nwg = npairs < 256 ? (int)npairs : 256;
+  const int nwg = persist_grid((int64_t)B * heads, lds, NKT);       // (its LDS admits one workgroup per CU)
   hipLaunchKernelGGL((attn_qkv_fused_fwd<NKT>), dim3(nwg), dim3(NKT * 64), lds, st, (const bf16_t*)x, (const bf16_t*)w, bias, (bf16_t*)o,
                      (bf16_t*)qkv_out, lse, B, N, heads, D, 1.0f / sqrtf((float)d));
   return check_launch("qkv_attention_fwd");
@@ -1213,8 +1084,7 @@ int launch_attention_bf16_bwd(const void* d_o, const void* qkv, const void* o, c
     static const bool split = knob_set("DINOX_ATTN_BWD_SPLIT");
     if (nblk <= 7 && ldsf <= 160 * 1024 && !split) {
       const int npairs = B * heads;
-      const int per_cu = persist_wgs_per_cu(ldsf, nblk);
-      const int nwgp = npairs < 256 * per_cu ? npairs : 256 * per_cu;
+      const int nwgp = persist_grid(npairs, ldsf, nblk);
       if (int rc = allow_lds(attn_bwd_fused_bf16, ldsf)) return fail(rc, "attention_bwd: cannot reserve %zu B of LDS", ldsf);
       hipLaunchKernelGGL(attn_bwd_fused_bf16, dim3(nwgp), dim3(nblk * 64), ldsf, st, (const bf16_t*)d_o, (const bf16_t*)qkv, (const bf16_t*)o, lse,
                          (bf16_t*)dqkv, N, heads, nblk, sc, npairs);

@@ -3,10 +3,7 @@
 // 1408 / 16 = 88 per head, /root/reference scripts/phase5_big_run.py:212-220), on the same packed qkv [B, N, 3, heads, d] layout.
 // Before round 3 such shapes ran the exact-fp32 product form (1/16-rate matrix instructions, [B, N, N] fp32 score buffers in HBM).
 //
-// Same conventions as attention_bf16.hip (read its header first): v_mfma_f32_32x32x16_bf16; score tiles computed TRANSPOSED
-// (S^T = K . Q^T: keys in the accumulator rows, a query per lane) so that softmax statistics are lane-local and the accumulator is
-// the next product's A operand as it stands; ONE LDS image layout for row reads (ds_read_b128) and transposed reads
-// (ds_read_b64_tr_b16).  What is new:
+// Same conventions, image layout and fragment helpers as attention_bf16.hip: all of them in attention_common.h.  What differs:
 //   * head size DH = 64 / 96 / 128 columns per image row (88 runs as 96: the missing columns are zero in Q, K, V, dO, so they add
 //     nothing to a product and their outputs are not stored); d % 8 == 0;
 //   * K / V (forward, dQ) and Q / dO (dK, dV) move through LDS in CHUNKS of 64 rows, so the sequence length is unbounded;
@@ -14,77 +11,12 @@
 //     some row's maximum really moved -- after the first few tiles it rarely does).
 // Replaces F.scaled_dot_product_attention (reference zoo/arch.py:51) and its backward.
 
-#include "common.h"
+#include "attention_common.h"
 #include "kernels.h"
 
 namespace dinox {
 
-typedef __attribute__((address_space(3))) s16x4 fl_lds_s16x4;
 constexpr int FL_KC = 64;                                     // rows of a chunk
-
-// byte offset of 16-B chunk ch (0 .. DH/8 - 1) of row r in a [rows][DH bf16] image: 8-row x 32-column sub-tiles of 512 B
-template <int DH>
-__device__ __forceinline__ int fl_off(int r, int ch) {
-  return (DH * 16) * (r >> 3) + 512 * (ch >> 2) + 64 * (r & 7) + 16 * ((ch & 3) ^ ((r >> 2) & 3));
-}
-
-// rows [row0, row0 + FL_KC) of a strided global matrix -> image rows 0 .. FL_KC - 1 (rows >= n_valid and columns >= d are zero)
-template <int DH>
-__device__ __forceinline__ void fl_load_chunk(char* __restrict__ img, const bf16_t* __restrict__ src, int64_t row_stride, int row0, int n_valid, int d) {
-  constexpr int CH = DH / 8;
-  for (int idx = threadIdx.x; idx < FL_KC * CH; idx += blockDim.x) {
-    const int r = idx / CH, ch = idx - r * CH;
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if (row0 + r < n_valid && ch * 8 < d) v = *reinterpret_cast<const uint4*>(src + (int64_t)(row0 + r) * row_stride + ch * 8);
-    *reinterpret_cast<uint4*>(img + fl_off<DH>(r, ch)) = v;
-  }
-}
-
-// A-operand fragment (standard k order): lane (row = l & 31, hl = l >> 5) gets img[row0 + row][16 ks + 8 hl + j], j < 8
-template <int DH>
-__device__ __forceinline__ bf16x8 fl_rows(const char* __restrict__ img, int row0, int ks, int lane) {
-  return *reinterpret_cast<const bf16x8*>(img + fl_off<DH>(row0 + (lane & 31), 2 * ks + (lane >> 5)));
-}
-
-// B-operand fragment in the PERMUTED k order of an accumulator tile used as the A operand:
-// lane (col = l & 31, hl = l >> 5), element j  <-  img[row0 + 16 s + 8 (j >> 2) + 4 hl + (j & 3)][d0 + col]
-template <int DH>
-__device__ __forceinline__ bf16x8 fl_tr(const char* __restrict__ img, int row0, int s, int d0, int lane) {
-  const int i = lane & 15, g = lane >> 4;
-  const int q4 = i >> 2, p = i & 3, hl = g >> 1;
-  const int ch = (d0 >> 3) + 2 * (g & 1) + (p >> 1);
-  const int r0 = row0 + 16 * s + 4 * hl + q4;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((fl_lds_s16x4*)(img + fl_off<DH>(r0, ch) + 8 * (p & 1)));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((fl_lds_s16x4*)(img + fl_off<DH>(r0 + 8, ch) + 8 * (p & 1)));
-  s16x8 v;
-  v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-  v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-  return __builtin_bit_cast(bf16x8, v);
-}
-
-__device__ __forceinline__ bf16x8 fl_acc_as_a(const f32x16& x, int s) {
-  bf16x8 a;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) a[j] = (__bf16)x[8 * s + j];
-  return a;
-}
-__device__ __forceinline__ int fl_acc_row(int e, int hl) { return (e & 3) + 8 * (e >> 2) + 4 * hl; }
-__device__ __forceinline__ void fl_zero(f32x16& x) {
-#pragma unroll
-  for (int e = 0; e < 16; ++e) x[e] = 0.f;
-}
-
-// DH / 16 fragments of one global row of d valid elements: lane (hl) takes columns 16 ks + 8 hl .. + 7 (zero past d)
-template <int DH>
-__device__ __forceinline__ void fl_row_frags(bf16x8 (&f)[DH / 16], const bf16_t* __restrict__ rowp, int d, int lane) {
-#pragma unroll
-  for (int ks = 0; ks < DH / 16; ++ks) {
-    const int c = 16 * ks + 8 * (lane >> 5);
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if (c < d) v = *reinterpret_cast<const uint4*>(rowp + c);
-    f[ks] = __builtin_bit_cast(bf16x8, v);
-  }
-}
 
 // A 32-row x DH-column block of fp32 accumulators (DH / 32 tiles of 32 x 32: rows = tokens, a column per lane) -> bf16 rows of a
 // strided matrix, through a per-wave LDS scratch of 32 rows x (2 DH + 16) bytes: re-read by rows, a lane stores 16-byte pieces and
@@ -97,7 +29,7 @@ __device__ __forceinline__ void fl_store_block(bf16_t* __restrict__ dst, int64_t
 #pragma unroll
   for (int t = 0; t < DH / 32; ++t)
 #pragma unroll
-    for (int e = 0; e < 16; ++e) *reinterpret_cast<bf16_t*>(scratch + fl_acc_row(e, hl) * ROWB + (t * 32 + col) * 2) = f32_to_bf16(x[t][e]);
+    for (int e = 0; e < 16; ++e) *reinterpret_cast<bf16_t*>(scratch + acc_row(e, hl) * ROWB + (t * 32 + col) * 2) = f32_to_bf16(x[t][e]);
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   for (int idx = lane; idx < 32 * CH; idx += 64) {
@@ -131,17 +63,17 @@ __global__ __launch_bounds__(256, 2) void attn_flash_fwd(const bf16_t* __restric
   int qrow = q0 + (lane & 31);
   if (qrow >= N) qrow = N - 1;
   bf16x8 qf[KS];
-  fl_row_frags<DH>(qf, base + (int64_t)qrow * rs, d, lane);
+  load_row_frags<DH>(qf, base + (int64_t)qrow * rs, d, lane);
   const float c2 = sc * 1.4426950408889634f;
   float m2 = -INFINITY, l = 0.f;
   f32x16 oacc[DT];
 #pragma unroll
-  for (int t = 0; t < DT; ++t) fl_zero(oacc[t]);
+  for (int t = 0; t < DT; ++t) zero16(oacc[t]);
 
   for (int kc0 = 0; kc0 < N; kc0 += FL_KC) {
     __syncthreads();                                                 // every wave is done with the previous chunk
-    fl_load_chunk<DH>(kimg, base + C, rs, kc0, N, d);
-    fl_load_chunk<DH>(vimg, base + 2 * C, rs, kc0, N, d);
+    load_image<DH>(kimg, base + C, rs, kc0, FL_KC, N, d);
+    load_image<DH>(vimg, base + 2 * C, rs, kc0, FL_KC, N, d);
     __syncthreads();
     if (!active) continue;
 #pragma unroll
@@ -149,13 +81,13 @@ __global__ __launch_bounds__(256, 2) void attn_flash_fwd(const bf16_t* __restric
       const int key0 = kc0 + kt * 32;
       if (key0 >= N) break;                                          // (uniform)
       f32x16 st;
-      fl_zero(st);
+      zero16(st);
 #pragma unroll
-      for (int ks = 0; ks < KS; ++ks) st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fl_rows<DH>(kimg, kt * 32, ks, lane), qf[ks], st, 0, 0, 0);
+      for (int ks = 0; ks < KS; ++ks) st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<DH>(kimg, kt * 32, ks, lane), qf[ks], st, 0, 0, 0);
       float tmax = -INFINITY;
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const bool ok = key0 + fl_acc_row(e, hl) < N;
+        const bool ok = key0 + acc_row(e, hl) < N;
         st[e] = ok ? st[e] * c2 : -INFINITY;
         tmax = fmaxf(tmax, st[e]);
       }
@@ -189,9 +121,9 @@ __global__ __launch_bounds__(256, 2) void attn_flash_fwd(const bf16_t* __restric
       }
 #pragma unroll
       for (int ss = 0; ss < 2; ++ss) {
-        const bf16x8 pa = fl_acc_as_a(st, ss);
+        const bf16x8 pa = acc_as_a(st, ss);
 #pragma unroll
-        for (int t = 0; t < DT; ++t) oacc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa, fl_tr<DH>(vimg, kt * 32, ss, t * 32, lane), oacc[t], 0, 0, 0);
+        for (int t = 0; t < DT; ++t) oacc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa, frag_tr_perm<DH>(vimg, kt * 32, ss, t * 32, lane), oacc[t], 0, 0, 0);
       }
     }
   }
@@ -237,12 +169,12 @@ __global__ __launch_bounds__(256, 2) void attn_flash_bwd_dq(const bf16_t* __rest
   if (qrow >= N) qrow = N - 1;
   const int64_t orow = ((int64_t)b * N + qrow) * C + hh * d;
   bf16x8 qf[KS], dof[KS];
-  fl_row_frags<DH>(qf, base + (int64_t)qrow * rs, d, lane);
-  fl_row_frags<DH>(dof, d_o + orow, d, lane);
+  load_row_frags<DH>(qf, base + (int64_t)qrow * rs, d, lane);
+  load_row_frags<DH>(dof, d_o + orow, d, lane);
   float delta = 0.f;
   {
     bf16x8 of[KS];
-    fl_row_frags<DH>(of, o + orow, d, lane);
+    load_row_frags<DH>(of, o + orow, d, lane);
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
@@ -253,11 +185,11 @@ __global__ __launch_bounds__(256, 2) void attn_flash_bwd_dq(const bf16_t* __rest
   const float L2 = lse[((int64_t)b * heads + hh) * N + qrow] * 1.4426950408889634f, c2 = sc * 1.4426950408889634f;
   f32x16 dq[DT];
 #pragma unroll
-  for (int t = 0; t < DT; ++t) fl_zero(dq[t]);
+  for (int t = 0; t < DT; ++t) zero16(dq[t]);
   for (int kc0 = 0; kc0 < N; kc0 += FL_KC) {
     __syncthreads();
-    fl_load_chunk<DH>(kimg, base + C, rs, kc0, N, d);
-    fl_load_chunk<DH>(vimg, base + 2 * C, rs, kc0, N, d);
+    load_image<DH>(kimg, base + C, rs, kc0, FL_KC, N, d);
+    load_image<DH>(vimg, base + 2 * C, rs, kc0, FL_KC, N, d);
     __syncthreads();
     if (!active) continue;
 #pragma unroll
@@ -265,23 +197,23 @@ __global__ __launch_bounds__(256, 2) void attn_flash_bwd_dq(const bf16_t* __rest
       const int key0 = kc0 + kt * 32;
       if (key0 >= N) break;
       f32x16 st, dp;
-      fl_zero(st);
-      fl_zero(dp);
+      zero16(st);
+      zero16(dp);
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
-        st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fl_rows<DH>(kimg, kt * 32, ks, lane), qf[ks], st, 0, 0, 0);
-        dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fl_rows<DH>(vimg, kt * 32, ks, lane), dof[ks], dp, 0, 0, 0);
+        st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<DH>(kimg, kt * 32, ks, lane), qf[ks], st, 0, 0, 0);
+        dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<DH>(vimg, kt * 32, ks, lane), dof[ks], dp, 0, 0, 0);
       }
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const float pv = __builtin_amdgcn_exp2f(st[e] * c2 - L2);
-        st[e] = key0 + fl_acc_row(e, hl) < N ? pv * (dp[e] - delta) * sc : 0.f;           // dS^T (scaled)
+        st[e] = key0 + acc_row(e, hl) < N ? pv * (dp[e] - delta) * sc : 0.f;           // dS^T (scaled)
       }
 #pragma unroll
       for (int ss = 0; ss < 2; ++ss) {
-        const bf16x8 a = fl_acc_as_a(st, ss);
+        const bf16x8 a = acc_as_a(st, ss);
 #pragma unroll
-        for (int t = 0; t < DT; ++t) dq[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, fl_tr<DH>(kimg, kt * 32, ss, t * 32, lane), dq[t], 0, 0, 0);
+        for (int t = 0; t < DT; ++t) dq[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, frag_tr_perm<DH>(kimg, kt * 32, ss, t * 32, lane), dq[t], 0, 0, 0);
       }
     }
   }
@@ -312,19 +244,19 @@ __global__ __launch_bounds__(256, 2) void attn_flash_bwd_dkv(const bf16_t* __res
   int krow = k0 + (lane & 31);
   if (krow >= N) krow = N - 1;
   bf16x8 kf[KS], vf[KS];
-  fl_row_frags<DH>(kf, base + (int64_t)krow * rs + C, d, lane);
-  fl_row_frags<DH>(vf, base + (int64_t)krow * rs + 2 * C, d, lane);
+  load_row_frags<DH>(kf, base + (int64_t)krow * rs + C, d, lane);
+  load_row_frags<DH>(vf, base + (int64_t)krow * rs + 2 * C, d, lane);
   const float c2 = sc * 1.4426950408889634f;
   f32x16 dk[DT], dv[DT];
 #pragma unroll
   for (int t = 0; t < DT; ++t) {
-    fl_zero(dk[t]);
-    fl_zero(dv[t]);
+    zero16(dk[t]);
+    zero16(dv[t]);
   }
   for (int qc0 = 0; qc0 < N; qc0 += FL_KC) {
     __syncthreads();
-    fl_load_chunk<DH>(qimg, base, rs, qc0, N, d);
-    fl_load_chunk<DH>(doimg, dob, C, qc0, N, d);
+    load_image<DH>(qimg, base, rs, qc0, FL_KC, N, d);
+    load_image<DH>(doimg, dob, C, qc0, FL_KC, N, d);
     if (threadIdx.x < FL_KC) {
       const int q = qc0 + threadIdx.x;
       const int64_t si = ((int64_t)b * heads + hh) * N + q;
@@ -337,12 +269,12 @@ __global__ __launch_bounds__(256, 2) void attn_flash_bwd_dkv(const bf16_t* __res
     for (int qt = 0; qt < FL_KC / 32; ++qt) {
       if (qc0 + qt * 32 >= N) break;
       f32x16 st, dp;
-      fl_zero(st);
-      fl_zero(dp);
+      zero16(st);
+      zero16(dp);
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
-        st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fl_rows<DH>(qimg, qt * 32, ks, lane), kf[ks], st, 0, 0, 0);      // S[q][key]
-        dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fl_rows<DH>(doimg, qt * 32, ks, lane), vf[ks], dp, 0, 0, 0);     // dP[q][key]
+        st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<DH>(qimg, qt * 32, ks, lane), kf[ks], st, 0, 0, 0);      // S[q][key]
+        dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<DH>(doimg, qt * 32, ks, lane), vf[ks], dp, 0, 0, 0);     // dP[q][key]
       }
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
@@ -360,11 +292,11 @@ __global__ __launch_bounds__(256, 2) void attn_flash_bwd_dkv(const bf16_t* __res
       }
 #pragma unroll
       for (int ss = 0; ss < 2; ++ss) {
-        const bf16x8 pa = fl_acc_as_a(st, ss), da = fl_acc_as_a(dp, ss);
+        const bf16x8 pa = acc_as_a(st, ss), da = acc_as_a(dp, ss);
 #pragma unroll
         for (int t = 0; t < DT; ++t) {
-          dv[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa, fl_tr<DH>(doimg, qt * 32, ss, t * 32, lane), dv[t], 0, 0, 0);
-          dk[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da, fl_tr<DH>(qimg, qt * 32, ss, t * 32, lane), dk[t], 0, 0, 0);
+          dv[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa, frag_tr_perm<DH>(doimg, qt * 32, ss, t * 32, lane), dv[t], 0, 0, 0);
+          dk[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da, frag_tr_perm<DH>(qimg, qt * 32, ss, t * 32, lane), dk[t], 0, 0, 0);
         }
       }
     }

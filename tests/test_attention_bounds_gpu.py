@@ -108,6 +108,23 @@ def test_fused_qkv_attention_within_elementwise_bounds(ops, B, N, case):
     AB.check_forward(o, lse, fb, h, f"fused qkv+attention {(B, N, h, D)} {case}")
 
 
+@pytest.mark.parametrize("B,N,heads,D", [(2, 201, 6, 384), (2, 193, 2, 96)])
+def test_fused_qkv_attention_equals_the_forward_on_its_own_rows(ops, B, N, heads, D):
+    """The attention phase of dinox_qkv_attention_fwd is, by its own comment, exactly the persistent forward's one-pass block: the two
+    are separate copies of that text, and this pins them together.  dinox_attention_fwd on the qkv rows the fused kernel handed over
+    gives the same o and lse bit for bit (7 key tiles, padded last tile: 201 and 193 tokens)."""
+    C = heads * 64
+    assert ops.qkv_attention_ok(B, N, heads, D, C)
+    g = torch.Generator().manual_seed(N + D)
+    x = (torch.randn(B, N, D, generator=g) * 0.7).bfloat16().to(DEV)
+    w = (torch.randn(3 * C, D, generator=g) * (1.5 / D ** 0.5)).bfloat16().to(DEV)
+    o, qkv, lse = ops.qkv_attention(x, w, None, heads, want_qkv=True, want_lse=True)
+    o2, lse2 = ops.attention_fwd(qkv, heads)
+    torch.cuda.synchronize()
+    assert torch.equal(o, o2), f"o: {int((o != o2).sum())} of {o.numel()} elements differ"
+    assert torch.equal(lse, lse2), f"lse: {int((lse != lse2).sum())} of {lse.numel()} elements differ"
+
+
 # ------------------------------------------------------------------------------------------ padding
 GUARD = 4096          # elements on either side of every output (a multiple of 8: the 16-byte alignment of the kernels holds)
 
