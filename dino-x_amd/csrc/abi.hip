@@ -317,6 +317,50 @@ extern "C" int dinox_ibot_center_ema(float* center, const float* sum_count, floa
   return dinox::launch_ibot_center_ema(center, sum_count, momentum, K, dinox::as_stream(stream));
 }
 
+// ---------------------------------------------------------------- dense segmentation loss (kernels: segloss.hip)
+// 0, or the error code after the message is set.  B g^2 cells and B S^2 pixels stay far inside int64 and the grids inside 2^31 - 1.
+static int seg_geometry(const char* who, int64_t B, int g, int u, int C) {
+  DX_REQUIRE(B >= 1 && B <= (1 << 20) && g >= 1 && g <= 4096, DINOX_EINVAL, "%s: B=%lld g=%d (1 <= B <= 2^20; 1 <= g <= 4096)", who, (long long)B, g);
+  DX_REQUIRE(u >= 1 && u <= dinox::SEG_MAX_UPSAMPLE, DINOX_EINVAL, "%s: u=%d (1 <= u <= %d)", who, u, dinox::SEG_MAX_UPSAMPLE);
+  DX_REQUIRE(C >= 2, DINOX_EINVAL, "%s: C=%d (2 <= C <= %d)", who, C, dinox::SEG_MAX_CLASSES);
+  DX_REQUIRE(C <= dinox::SEG_MAX_CLASSES, DINOX_EUNSUPPORTED, "%s: C=%d classes: at most %d are held in registers", who, C, dinox::SEG_MAX_CLASSES);
+  DX_REQUIRE(B * g * g <= ((int64_t)1 << 32), DINOX_EINVAL, "%s: B g^2 = %lld cells (at most 2^32)", who, (long long)(B * g * g));
+  return 0;
+}
+
+extern "C" int64_t dinox_seg_loss_ws_bytes(int64_t B, int g, int u, int C) {
+  if (B < 1 || B > (1 << 20) || g < 1 || g > 4096 || u < 1 || u > dinox::SEG_MAX_UPSAMPLE || C < 2 || C > dinox::SEG_MAX_CLASSES ||
+      B * g * g > ((int64_t)1 << 32))
+    return 0;
+  return dinox::seg_loss_ws_bytes(B, g, C);
+}
+
+extern "C" int dinox_seg_loss_fwd(const float* z, const uint8_t* y, float* loss, float* stats, int64_t* nv, void* ws, int64_t B, int g, int u, int C,
+                                  int c0, float w_ce, float w_dice, void* stream) {
+  DX_REQUIRE(z && y && loss && stats && nv && ws, DINOX_EINVAL, "seg_loss_fwd: null pointer");
+  const int rc = seg_geometry("seg_loss_fwd", B, g, u, C);
+  if (rc) return rc;
+  DX_REQUIRE(c0 == 0 || c0 == 1, DINOX_EINVAL, "seg_loss_fwd: c0=%d (0: every class in the Dice term, 1: without class 0)", c0);
+  return dinox::launch_seg_loss_fwd(z, y, loss, stats, nv, ws, B, g, u, C, c0, w_ce, w_dice, dinox::as_stream(stream));
+}
+
+extern "C" int dinox_seg_loss_bwd(const float* z, const uint8_t* y, const float* stats, const int64_t* nv, float* dz, void* ws, int64_t B, int g,
+                                  int u, int C, int c0, float w_ce, float w_dice, float grad_scale, void* stream) {
+  DX_REQUIRE(z && y && stats && nv && dz && ws, DINOX_EINVAL, "seg_loss_bwd: null pointer");
+  const int rc = seg_geometry("seg_loss_bwd", B, g, u, C);
+  if (rc) return rc;
+  DX_REQUIRE(c0 == 0 || c0 == 1, DINOX_EINVAL, "seg_loss_bwd: c0=%d (0: every class in the Dice term, 1: without class 0)", c0);
+  return dinox::launch_seg_loss_bwd(z, y, stats, nv, dz, ws, B, g, u, C, c0, w_ce, w_dice, grad_scale, dinox::as_stream(stream));
+}
+
+extern "C" int dinox_seg_predict(const float* z, const uint8_t* y, uint8_t* pred, int64_t* counts, int64_t B, int g, int u, int C, void* stream) {
+  DX_REQUIRE(z && pred, DINOX_EINVAL, "seg_predict: null pointer");
+  DX_REQUIRE((y == nullptr) == (counts == nullptr), DINOX_EINVAL, "seg_predict: labels and counts come together (both or neither)");
+  const int rc = seg_geometry("seg_predict", B, g, u, C);
+  if (rc) return rc;
+  return dinox::launch_seg_predict(z, y, pred, counts, B, g, u, C, dinox::as_stream(stream));
+}
+
 // ---------------------------------------------------------------- LoRA low-rank products (kernels: lora.hip)
 static bool lora_rank_ok(int r) { return r >= 1 && r <= dinox::LORA_MAX_RANK; }
 static bool lora_dim_ok(int d) { return d >= 1 && d <= (1 << 20); }

@@ -134,6 +134,17 @@ int launch_lora_grad(const void* xl, const void* dy, const float* A, const float
                      int N, int r, int dtype, hipStream_t st);
 int launch_lora_dropout(const void* in, void* out, int64_t n, float p, uint64_t seed, uint64_t offset, int dtype, hipStream_t st);
 
+// ---------------------------------------------------------------- dense segmentation loss (segloss.hip; entry points and argument checks: abi.hip)
+constexpr int SEG_MAX_CLASSES = 64;        // the C logits of a pixel, its softmax and two C-wide accumulators live in a lane's registers
+constexpr int SEG_MAX_UPSAMPLE = 32;       // a cell (the pixels that share their four taps) is at most 1.5 u = 48 columns: one wave row
+constexpr int SEG_FWD_CELLS = 8;           // cells per partial sum of dinox_seg_loss_fwd
+int64_t seg_loss_ws_bytes(int64_t B, int g, int C);
+int launch_seg_loss_fwd(const float* z, const uint8_t* y, float* loss, float* stats, int64_t* nv, void* ws, int64_t B, int g, int u, int C, int c0,
+                        float w_ce, float w_dice, hipStream_t st);
+int launch_seg_loss_bwd(const float* z, const uint8_t* y, const float* stats, const int64_t* nv, float* dz, void* ws, int64_t B, int g, int u, int C,
+                        int c0, float w_ce, float w_dice, float gscale, hipStream_t st);
+int launch_seg_predict(const float* z, const uint8_t* y, uint8_t* pred, int64_t* counts, int64_t B, int g, int u, int C, hipStream_t st);
+
 // ---------------------------------------------------------------- launch glue shared by the NT launchers
 // Activation index of the <OUT, ACT, RES> kernels (gemm_bf16_pp / _pp128 / _areg): the template argument ACT.
 enum { EPI_ACT_PLAIN = 0, EPI_ACT_GELU = 1, EPI_ACT_DGELU = 2 };

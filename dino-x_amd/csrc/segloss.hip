@@ -1,0 +1,407 @@
+// segloss.hip -- dense segmentation loss on patch logits: bilinear upsampling (align_corners = False), softmax, cross-entropy and soft Dice,
+// their gradient, and the arg-max prediction, without a full-resolution logit tensor in memory in either direction (entry points and
+// argument checks: abi.hip; definitions: include/dinox.h).
+//
+// Layout.  The S x S pixels of an image fall into g x g CELLS: cell (cy, cx) holds the pixels whose upper-left tap is patch (cy, cx), i.e.
+// rows [lo(cy), lo(cy + 1)) and columns [lo(cx), lo(cx + 1)) with lo(0) = 0, lo(k) = k u + u / 2, lo(g) = S.  Every pixel of a cell
+// interpolates the same four patches, so a WAVE takes a cell: it reads the four logit rows once (wave-uniform addresses), a lane keeps one
+// pixel column (its x weights fold the rows into two C-vectors in registers) and walks down the cell's rows, 64 / width rows per step.
+// Per pixel the C logits, the softmax and every per-class term live in registers.  A cell is at most 48 x 48 pixels (u <= 32).
+// Sums: a lane adds its pixels in row order, the wave adds its lanes by the xor butterfly, partial sums go to the workspace with plain
+// stores and a second launch adds them in ascending order -- no floating-point atomics anywhere.  The label and prediction COUNTS are
+// integers and use integer atomics (LDS; global for dinox_seg_predict's int64 counts).
+// A label is compared with class numbers and 255 only; it never becomes an address beyond a [0, C) slot of an LDS counter.
+#include "small_common.h"
+#include "kernels.h"
+
+namespace dinox {
+
+constexpr int SEG_WAVES = 4;                      // waves (= cells in flight) per workgroup
+
+__device__ __forceinline__ int seg_lo(int k, int g, int u, int S) { return k <= 0 ? 0 : (k >= g ? S : k * u + u / 2); }
+
+// weight of the second tap at pixel coordinate x of cell index k: frac((x + 0.5) / u - 0.5) as (2 x + 1 - u - 2 u k) / (2 u), 0 where the
+// source coordinate is clamped at 0 or where the second tap is clamped onto the first (k = g - 1: both weights go to the one patch).
+__device__ __forceinline__ float seg_w1(int x, int k, int g, int u, float inv2u) {
+  const int t = 2 * x + 1 - u;
+  return (k + 1 < g && t > 0) ? (float)(t - 2 * u * k) * inv2u : 0.f;
+}
+
+// Pixel column of `lane` in a cell of column index cx: the lanes run along the cell's rows, 64 / width rows at a time.
+__device__ __forceinline__ int seg_lane_x(int cx, int g, int u, int lane) {
+  const int xlo = seg_lo(cx, g, u, g * u), cw = seg_lo(cx + 1, g, u, g * u) - xlo;
+  return xlo + lane % cw;
+}
+
+// Calls f(ok, lab, wy0, wy1, l, Y, X) for the pixels of `cell`, this lane's column from the top row down; l[c] = the interpolated logit.
+// Every lane of the wave makes every call (ok = false where the lane has no pixel), so f may use wave-wide operations.
+// y == nullptr: lab = 255 everywhere.  ywide: u % 8 == 0 and y 4-byte aligned -- every fourth lane reads four labels in one 32-bit load.
+template <int CP, typename F>
+__device__ __forceinline__ void seg_cell_pixels(const float* __restrict__ z, const uint8_t* __restrict__ y, int g, int u, int C, float inv2u, int ywide,
+                                                int64_t cell, int lane, F&& f) {
+  const int S = g * u;
+  const int cx = (int)(cell % g), cy = (int)((cell / g) % g);
+  const int64_t b = cell / ((int64_t)g * g);
+  const int xlo = seg_lo(cx, g, u, S), xhi = seg_lo(cx + 1, g, u, S), ylo = seg_lo(cy, g, u, S), yhi = seg_lo(cy + 1, g, u, S);
+  const int cw = xhi - xlo, R = 64 / cw;          // 1 <= cw <= 48
+  const int r0 = lane / cw, X = seg_lane_x(cx, g, u, lane);
+  const bool live = r0 < R;
+  const float wx1 = seg_w1(X, cx, g, u, inv2u), wx0 = 1.f - wx1;
+  const int cx1 = cx + 1 < g ? cx + 1 : cx, cy1 = cy + 1 < g ? cy + 1 : cy;
+  const float* z00 = z + ((b * g + cy) * g + cx) * C;
+  const float* z01 = z + ((b * g + cy) * g + cx1) * C;
+  const float* z10 = z + ((b * g + cy1) * g + cx) * C;
+  const float* z11 = z + ((b * g + cy1) * g + cx1) * C;
+  float zx0[CP], zx1[CP];
+#pragma unroll
+  for (int c = 0; c < CP; ++c) {
+    const bool in = c < C;
+    zx0[c] = in ? wx0 * z00[c] + wx1 * z01[c] : 0.f;
+    zx1[c] = in ? wx0 * z10[c] + wx1 * z11[c] : 0.f;
+  }
+  const uint8_t* yb = y ? y + b * (int64_t)S * S : nullptr;
+  for (int Y0 = ylo; Y0 < yhi; Y0 += R) {          // wave-uniform trip count
+    const int Y = Y0 + r0;
+    const bool ok = live && Y < yhi;
+    int lab = 255;
+    if (yb) {
+      if (ywide) {
+        unsigned w = 0;
+        if (ok && (lane & 3) == 0) w = *reinterpret_cast<const unsigned*>(yb + (int64_t)Y * S + X);
+        w = __shfl(w, lane & ~3, 64);
+        lab = ok ? (int)((w >> (8 * (lane & 3))) & 255u) : 255;
+      } else if (ok) {
+        lab = yb[(int64_t)Y * S + X];
+      }
+    }
+    const float wy1 = seg_w1(Y, cy, g, u, inv2u), wy0 = 1.f - wy1;
+    float l[CP];
+#pragma unroll
+    for (int c = 0; c < CP; ++c) l[c] = wy0 * zx0[c] + wy1 * zx1[c];
+    f(ok, lab, wy0, wy1, l, Y, X);
+  }
+}
+
+// l -> p = softmax(l) in place over c < C; returns max and the sum of exp(l - max).
+template <int CP>
+__device__ __forceinline__ void seg_softmax(float (&l)[CP], int C, float& m, float& sum) {
+  m = l[0];
+#pragma unroll
+  for (int c = 1; c < CP; ++c)
+    if (c < C) m = fmaxf(m, l[c]);
+  sum = 0.f;
+#pragma unroll
+  for (int c = 0; c < CP; ++c) {
+    l[c] = c < C ? expf(l[c] - m) : 0.f;
+    sum += l[c];
+  }
+  const float inv = 1.f / sum;
+#pragma unroll
+  for (int c = 0; c < CP; ++c) l[c] *= inv;
+}
+
+// ---------------------------------------------------------------- forward: partial sums of SEG_FWD_CELLS cells per wave
+// wsf[part][1 + 2 C] = (sum of lse - l_y, P[C], I[C]); wsi[part][C + 2] = (Y[C], valid pixels, labels outside [0, C) other than 255).
+template <int CP>
+__global__ __launch_bounds__(64 * SEG_WAVES) void seg_fwd_partial_kernel(const float* __restrict__ z, const uint8_t* __restrict__ y, float* __restrict__ wsf,
+                                                                         unsigned* __restrict__ wsi, int g, int u, int C, float inv2u, int ywide,
+                                                                         int64_t ncell, int64_t nparts) {
+  __shared__ unsigned cnt[SEG_WAVES][CP + 2];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t part = (int64_t)blockIdx.x * SEG_WAVES + wave;
+  for (int i = lane; i < CP + 2; i += 64) cnt[wave][i] = 0;
+  __syncthreads();
+  float P[CP], I[CP], ce = 0.f;
+#pragma unroll
+  for (int c = 0; c < CP; ++c) P[c] = I[c] = 0.f;
+  if (part < nparts) {
+    const int64_t c_end = (part + 1) * SEG_FWD_CELLS < ncell ? (part + 1) * SEG_FWD_CELLS : ncell;
+    for (int64_t cell = part * SEG_FWD_CELLS; cell < c_end; ++cell)
+      seg_cell_pixels<CP>(z, y, g, u, C, inv2u, ywide, cell, lane, [&](bool ok, int lab, float, float, float(&l)[CP], int, int) {
+        if (!ok || lab == 255) return;
+        if (lab >= C) {
+          atomicAdd(&cnt[wave][CP + 1], 1u);
+          return;
+        }
+        float ly = 0.f;
+#pragma unroll
+        for (int c = 0; c < CP; ++c) ly = lab == c ? l[c] : ly;
+        float m, sum;
+        seg_softmax<CP>(l, C, m, sum);
+        ce += (logf(sum) + m) - ly;
+#pragma unroll
+        for (int c = 0; c < CP; ++c) {
+          P[c] += l[c];
+          I[c] += lab == c ? l[c] : 0.f;
+        }
+        atomicAdd(&cnt[wave][lab], 1u);
+        atomicAdd(&cnt[wave][CP], 1u);
+      });
+  }
+  ce = wave_sum(ce);
+  float outP = 0.f, outI = 0.f;                   // lane c keeps class c's sums: one coalesced store each
+#pragma unroll
+  for (int c = 0; c < CP; ++c) {
+    const float p = wave_sum(P[c]), i = wave_sum(I[c]);
+    if (lane == c) outP = p, outI = i;
+  }
+  __syncthreads();                                // the LDS counters of every wave are complete
+  if (part < nparts) {
+    float* wf = wsf + part * (1 + 2 * C);
+    unsigned* wi = wsi + part * (C + 2);
+    if (lane == 0) wf[0] = ce;
+    if (lane < C) {
+      wf[1 + lane] = outP;
+      wf[1 + C + lane] = outI;
+      wi[lane] = cnt[wave][lane];
+    }
+    if (lane == 0) wi[C] = cnt[wave][CP], wi[C + 1] = cnt[wave][CP + 1];
+  }
+}
+
+// One workgroup: the partial sums in a fixed order (lane i takes parts i, i + 64, ..., then the butterfly), then the losses.
+__global__ __launch_bounds__(256) void seg_fwd_final_kernel(const float* __restrict__ wsf, const unsigned* __restrict__ wsi, float* __restrict__ loss,
+                                                            float* __restrict__ stats, int64_t* __restrict__ nv, int C, int c0, float w_ce,
+                                                            float w_dice, int64_t nparts) {
+  __shared__ float sf[1 + 2 * 64];
+  __shared__ double si[64 + 2];
+  __shared__ float dc[64];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nf = 1 + 2 * C, ni = C + 2;
+  for (int q = wave; q < nf + ni; q += 4) {
+    if (q < nf) {
+      float a = 0.f;
+      for (int64_t p = lane; p < nparts; p += 64) a += wsf[p * nf + q];
+      a = wave_sum(a);
+      if (lane == 0) sf[q] = a;
+    } else {
+      double a = 0.0;                             // counts: exact in double
+      for (int64_t p = lane; p < nparts; p += 64) a += (double)wsi[p * ni + (q - nf)];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+      if (lane == 0) si[q - nf] = a;
+    }
+  }
+  __syncthreads();
+  const double nvd = si[C];
+  const int c = threadIdx.x;
+  if (c < C) {
+    const float Pc = sf[1 + c], Ic = sf[1 + C + c], Yc = (float)si[c];
+    stats[c] = nvd > 0 ? Ic : 0.f;
+    stats[C + c] = nvd > 0 ? Pc : 0.f;
+    stats[2 * C + c] = Yc;
+    dc[c] = (2.f * Ic + 1.f) / ((Pc + Yc) + 1.f);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    nv[0] = (int64_t)nvd;
+    nv[1] = (int64_t)si[C + 1];
+    float ce = 0.f, dice = 0.f;
+    if (nvd > 0) {
+      ce = sf[0] / (float)nvd;
+      float d = 0.f;
+      for (int k = c0; k < C; ++k) d += dc[k];
+      dice = 1.f - d / (float)(C - c0);
+    }
+    loss[0] = w_ce * ce + w_dice * dice;
+    loss[1] = ce;
+    loss[2] = dice;
+  }
+}
+
+// ---------------------------------------------------------------- backward: per cell, the four taps' sums of W(p, tap) G_p
+// wsb[cell][4][C]: tap (ty, tx) at index 2 ty + tx; a clamped second tap carries weight 0 (its weight went to the first).
+template <int CP>
+__global__ __launch_bounds__(64 * SEG_WAVES) void seg_bwd_cells_kernel(const float* __restrict__ z, const uint8_t* __restrict__ y,
+                                                                       const float* __restrict__ stats, const int64_t* __restrict__ nv,
+                                                                       float* __restrict__ wsb, int g, int u, int C, int c0, float w_ce, float w_dice,
+                                                                       float inv2u, int ywide, int64_t ncell) {
+  __shared__ float al[CP], be[CP];                // w_dice a_pc = be[c] + [y_p = c] al[c]
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (threadIdx.x < CP) {
+    const int c = threadIdx.x;
+    float a = 0.f, bt = 0.f;
+    if (c >= c0 && c < C) {
+      const float k = w_dice / (float)(C - c0);
+      const float den = (stats[C + c] + stats[2 * C + c]) + 1.f, num = 2.f * stats[c] + 1.f;
+      a = -2.f * k / den;
+      bt = k * num / (den * den);
+    }
+    al[c] = a;
+    be[c] = bt;
+  }
+  __syncthreads();
+  const int64_t cell = (int64_t)blockIdx.x * SEG_WAVES + wave;
+  if (cell >= ncell) return;                      // no barrier below
+  const int64_t nvv = nv[0];
+  const float kce = nvv > 0 ? w_ce / (float)nvv : 0.f;
+  float T0[CP], T1[CP];
+#pragma unroll
+  for (int c = 0; c < CP; ++c) T0[c] = T1[c] = 0.f;
+  seg_cell_pixels<CP>(z, y, g, u, C, inv2u, ywide, cell, lane, [&](bool ok, int lab, float wy0, float wy1, float(&l)[CP], int, int) {
+    if (!ok || lab >= C) return;
+    float m, sum;
+    seg_softmax<CP>(l, C, m, sum);
+    float dot = 0.f;
+#pragma unroll
+    for (int c = 0; c < CP; ++c) dot += l[c] * (be[c] + (lab == c ? al[c] : 0.f));
+#pragma unroll
+    for (int c = 0; c < CP; ++c) {
+      const bool hit = lab == c;
+      const float G = kce * (l[c] - (hit ? 1.f : 0.f)) + l[c] * ((be[c] + (hit ? al[c] : 0.f)) - dot);
+      T0[c] += wy0 * G;
+      T1[c] += wy1 * G;
+    }
+  });
+  const int cx = (int)(cell % g);
+  const float wx1 = seg_w1(seg_lane_x(cx, g, u, lane), cx, g, u, inv2u), wx0 = 1.f - wx1;      // the lane's column weights, as in seg_cell_pixels
+  float out[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int c = 0; c < CP; ++c) {
+    if (c < C) {                                  // uniform
+      const float s00 = wave_sum(wx0 * T0[c]), s01 = wave_sum(wx1 * T0[c]), s10 = wave_sum(wx0 * T1[c]), s11 = wave_sum(wx1 * T1[c]);
+      if (lane == c) out[0] = s00, out[1] = s01, out[2] = s10, out[3] = s11;
+    }
+  }
+  if (lane < C) {
+    float* w = wsb + cell * 4 * C;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) w[t * C + lane] = out[t];
+  }
+}
+
+// dz[b][jy][jx][c] = gscale (t00(jy, jx) + t01(jy, jx - 1) + t10(jy - 1, jx) + t11(jy - 1, jx - 1)), absent cells left out, in that order.
+__global__ __launch_bounds__(256) void seg_bwd_gather_kernel(const float* __restrict__ wsb, float* __restrict__ dz, float gscale, int g, int C,
+                                                             int64_t total) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int c = (int)(i % C);
+  const int64_t cell = i / C;
+  const int jx = (int)(cell % g), jy = (int)((cell / g) % g);
+  float a = wsb[cell * 4 * C + c];
+  if (jx > 0) a += wsb[(cell - 1) * 4 * C + C + c];
+  if (jy > 0) a += wsb[(cell - g) * 4 * C + 2 * C + c];
+  if (jx > 0 && jy > 0) a += wsb[(cell - g - 1) * 4 * C + 3 * C + c];
+  dz[i] = gscale * a;
+}
+
+// ---------------------------------------------------------------- predict: arg-max label map and the confusion counts
+template <int CP>
+__global__ __launch_bounds__(64 * SEG_WAVES) void seg_predict_kernel(const float* __restrict__ z, const uint8_t* __restrict__ y, uint8_t* __restrict__ pred,
+                                                                     unsigned long long* __restrict__ counts, int g, int u, int C, float inv2u,
+                                                                     int ywide, int pwide, int64_t ncell) {
+  __shared__ unsigned cnt[SEG_WAVES][3 * CP + 1];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, S = g * u;
+  const int64_t cell = (int64_t)blockIdx.x * SEG_WAVES + wave;
+  for (int i = lane; i < 3 * CP + 1; i += 64) cnt[wave][i] = 0;
+  __syncthreads();
+  if (cell < ncell) {
+    uint8_t* pb = pred + (cell / ((int64_t)g * g)) * (int64_t)S * S;
+    seg_cell_pixels<CP>(z, y, g, u, C, inv2u, ywide, cell, lane, [&](bool ok, int lab, float, float, float(&l)[CP], int Y, int X) {
+      int best = 0;
+      float bv = l[0];
+#pragma unroll
+      for (int c = 1; c < CP; ++c)
+        if (c < C && l[c] > bv) bv = l[c], best = c;
+      if (pwide) {                                // four lanes' bytes leave as one 32-bit store
+        unsigned w = (unsigned)best << (8 * (lane & 3));
+        w |= __shfl_xor(w, 1, 64);
+        w |= __shfl_xor(w, 2, 64);
+        if (ok && (lane & 3) == 0) *reinterpret_cast<unsigned*>(pb + (int64_t)Y * S + X) = w;
+      } else if (ok) {
+        pb[(int64_t)Y * S + X] = (uint8_t)best;
+      }
+      if (!ok || lab == 255) return;
+      if (lab >= C) {
+        atomicAdd(&cnt[wave][3 * CP], 1u);
+        return;
+      }
+      if (best == lab) atomicAdd(&cnt[wave][best], 1u);
+      atomicAdd(&cnt[wave][CP + best], 1u);
+      atomicAdd(&cnt[wave][2 * CP + lab], 1u);
+    });
+  }
+  __syncthreads();
+  if (cell < ncell && counts) {
+    if (lane < C)
+#pragma unroll
+      for (int t = 0; t < 3; ++t)
+        if (cnt[wave][t * CP + lane]) atomicAdd(&counts[t * C + lane], (unsigned long long)cnt[wave][t * CP + lane]);
+    if (lane == 0 && cnt[wave][3 * CP]) atomicAdd(&counts[3 * C], (unsigned long long)cnt[wave][3 * CP]);
+  }
+}
+
+// ---------------------------------------------------------------- host
+static int seg_cp(int C) { return C <= 4 ? 4 : C <= 8 ? 8 : C <= 16 ? 16 : C <= 32 ? 32 : 64; }
+
+// f(std::integral_constant<int, CP>) for the register width that holds C classes
+template <typename F>
+static inline void seg_by_width(int C, F&& f) {
+  switch (seg_cp(C)) {
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    case 16: f(std::integral_constant<int, 16>{}); break;
+    case 32: f(std::integral_constant<int, 32>{}); break;
+    default: f(std::integral_constant<int, 64>{}); break;
+  }
+}
+
+static int seg_wide(const void* p, int u) { return u % 8 == 0 && (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
+
+int64_t seg_fwd_parts(int64_t B, int g) { return ceil_div(B * g * g, (int64_t)SEG_FWD_CELLS); }
+
+int64_t seg_loss_ws_bytes(int64_t B, int g, int C) {
+  const int64_t ncell = B * g * g, parts = seg_fwd_parts(B, g);
+  const int64_t fwd = parts * (1 + 2 * C) * 4 + parts * (C + 2) * 4, bwd = ncell * 4 * C * 4;
+  return fwd > bwd ? fwd : bwd;
+}
+
+int launch_seg_loss_fwd(const float* z, const uint8_t* y, float* loss, float* stats, int64_t* nv, void* ws, int64_t B, int g, int u, int C, int c0,
+                        float w_ce, float w_dice, hipStream_t st) {
+  const int64_t ncell = B * g * g, parts = seg_fwd_parts(B, g);
+  float* wsf = (float*)ws;
+  unsigned* wsi = (unsigned*)(wsf + parts * (1 + 2 * C));
+  const unsigned grid = (unsigned)ceil_div(parts, (int64_t)SEG_WAVES);
+  const float inv2u = 1.0f / (float)(2 * u);
+  seg_by_width(C, [&](auto cp) {
+    hipLaunchKernelGGL((seg_fwd_partial_kernel<decltype(cp)::value>), dim3(grid), dim3(64 * SEG_WAVES), 0, st, z, y, wsf, wsi, g, u, C, inv2u,
+                       seg_wide(y, u), ncell, parts);
+  });
+  int rc = check_launch("seg_loss_fwd (partials)");
+  if (rc) return rc;
+  hipLaunchKernelGGL(seg_fwd_final_kernel, dim3(1), dim3(256), 0, st, wsf, wsi, loss, stats, nv, C, c0, w_ce, w_dice, parts);
+  return check_launch("seg_loss_fwd (sum)");
+}
+
+int launch_seg_loss_bwd(const float* z, const uint8_t* y, const float* stats, const int64_t* nv, float* dz, void* ws, int64_t B, int g, int u, int C,
+                        int c0, float w_ce, float w_dice, float gscale, hipStream_t st) {
+  const int64_t ncell = B * g * g;
+  float* wsb = (float*)ws;
+  const unsigned grid = (unsigned)ceil_div(ncell, (int64_t)SEG_WAVES);
+  const float inv2u = 1.0f / (float)(2 * u);
+  seg_by_width(C, [&](auto cp) {
+    hipLaunchKernelGGL((seg_bwd_cells_kernel<decltype(cp)::value>), dim3(grid), dim3(64 * SEG_WAVES), 0, st, z, y, stats, nv, wsb, g, u, C, c0, w_ce,
+                       w_dice, inv2u, seg_wide(y, u), ncell);
+  });
+  int rc = check_launch("seg_loss_bwd (cells)");
+  if (rc) return rc;
+  const int64_t total = ncell * C;
+  hipLaunchKernelGGL(seg_bwd_gather_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, st, wsb, dz, gscale, g, C, total);
+  return check_launch("seg_loss_bwd (gather)");
+}
+
+int launch_seg_predict(const float* z, const uint8_t* y, uint8_t* pred, int64_t* counts, int64_t B, int g, int u, int C, hipStream_t st) {
+  const int64_t ncell = B * g * g;
+  if (counts) {
+    const hipError_t e = hipMemsetAsync(counts, 0, (size_t)(3 * C + 1) * sizeof(int64_t), st);
+    if (e != hipSuccess) return fail((int)e, "seg_predict: hipMemsetAsync: %s", hipGetErrorString(e));
+  }
+  const unsigned grid = (unsigned)ceil_div(ncell, (int64_t)SEG_WAVES);
+  const float inv2u = 1.0f / (float)(2 * u);
+  seg_by_width(C, [&](auto cp) {
+    hipLaunchKernelGGL((seg_predict_kernel<decltype(cp)::value>), dim3(grid), dim3(64 * SEG_WAVES), 0, st, z, y, pred, (unsigned long long*)counts, g, u,
+                       C, inv2u, y ? seg_wide(y, u) : 0, seg_wide(pred, u), ncell);
+  });
+  return check_launch("seg_predict");
+}
+
+}  // namespace dinox

@@ -144,6 +144,10 @@ SIGNATURES = {
     "dinox_lora_grad": (i32, [vp, vp, vp, vp, f32, vp, vp, vp, i64, i32, i32, i32, i32, vp]),
     "dinox_lora_dropout": (i32, [vp, vp, i64, f32, C.c_uint64, C.c_uint64, i32, vp]),
     "dinox_lora_merge": (i32, [vp, vp, vp, vp, f32, i32, i32, i32, i32, vp]),
+    "dinox_seg_loss_ws_bytes": (i64, [i64, i32, i32, i32]),
+    "dinox_seg_loss_fwd": (i32, [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, f32, vp]),
+    "dinox_seg_loss_bwd": (i32, [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, f32, f32, vp]),
+    "dinox_seg_predict": (i32, [vp, vp, vp, vp, i64, i32, i32, i32, vp]),
     "dinox_attention_rows_ok": (i32, [i32, i32, i32, i32, i32]),
     "dinox_attention_rows": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "dinox_attention_rollout_step_ok": (i32, [i32, i32, i32, i32]),

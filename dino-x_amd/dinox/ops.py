@@ -2956,3 +2956,115 @@ def softmax_probe(x: Tensor, label: Tensor, theta: Tensor, *, want_grad: bool = 
     check(lib.dinox_softmax_probe(_p(x), x.stride(0), _p(label), N, D, C, _p(theta), _p(loss), _p(grad), _p(prob), _p(ws), _stream()),
           "dinox_softmax_probe")
     return loss, grad, prob
+
+
+# ------------------------------------------------------------------------------------------
+# dense segmentation on patch logits (csrc/segloss.hip)
+# ------------------------------------------------------------------------------------------
+SEG_MAX_CLASSES = 64
+SEG_MAX_UPSAMPLE = 32
+SEG_IGNORE = 255
+
+
+def _seg_geometry(name: str, z: Tensor, u: int):
+    """(B, g, C) of patch logits z [B, g^2, C] for an integer upsampling factor u; ValueError for anything the kernels do not take."""
+    if not isinstance(z, Tensor) or z.dim() != 3 or not z.is_floating_point():
+        raise ValueError(f"{name}: patch logits must be a floating-point [B, P, C] tensor, got {_describe(z)}")
+    B, P, C = z.shape
+    g = math.isqrt(P)
+    if B < 1 or P < 1 or g * g != P:
+        raise ValueError(f"{name}: P = {P} patches are not a square grid (z is {tuple(z.shape)})")
+    if isinstance(u, bool) or not isinstance(u, int) or not 1 <= u <= SEG_MAX_UPSAMPLE:
+        raise ValueError(f"{name}: the upsampling factor must be an integer in [1, {SEG_MAX_UPSAMPLE}], got {u!r}")
+    if not 2 <= C <= SEG_MAX_CLASSES:
+        raise ValueError(f"{name}: C must lie in [2, {SEG_MAX_CLASSES}], got {C}")
+    return B, g, C
+
+
+def _seg_labels(name: str, y, B: int, g: int, z: Tensor) -> int:
+    """The upsampling factor u of a uint8 label map [B, S, S] with S = g u."""
+    if not isinstance(y, Tensor) or y.dtype != torch.uint8 or y.dim() != 3 or y.shape[0] != B or y.shape[1] != y.shape[2]:
+        raise ValueError(f"{name}: labels must be uint8 [{B}, S, S] (255 = ignore), got {_describe(y)}")
+    S = y.shape[1]
+    if S < g or S % g or S // g > SEG_MAX_UPSAMPLE:
+        raise ValueError(f"{name}: label side {S} is not {g} patches times an integer factor in [1, {SEG_MAX_UPSAMPLE}]")
+    if y.device != z.device:
+        raise ValueError(f"{name}: logits on {z.device}, labels on {y.device}")
+    return S // g
+
+
+def _seg_refuse_bad_labels(name: str, bad: int, C: int) -> None:
+    if bad:
+        raise ValueError(f"{name}: {bad} label(s) are >= C = {C} and not {SEG_IGNORE} (ignore)")
+
+
+def seg_loss_fwd(z: Tensor, y: Tensor, w_ce: float = 1.0, w_dice: float = 1.0, c0: int = 0):
+    """Cross-entropy + soft Dice of the patch logits z [B, g^2, C] against the uint8 label map y [B, S, S] (S = g u, 255 = ignore) at full
+    resolution, the logits upsampled bilinearly (align_corners=False) inside the kernel (include/dinox.h has the definitions).  Returns
+    (loss[3] = (L, CE, Dice) fp32 on the device, stats [3, C] = (I, P, Y), saved); seg_loss_bwd(saved, gscale) gives d(gscale L)/dz.
+    A label >= C other than 255 raises ValueError (one device read of two integers)."""
+    B, g, C = _seg_geometry("seg_loss", z, 1)
+    u = _seg_labels("seg_loss", y, B, g, z)
+    if c0 not in (0, 1):
+        raise ValueError(f"seg_loss: c0 must be 0 or 1, got {c0!r}")
+    _need_cuda(z, y)
+    z, y = _c(z.float()), _c(y)
+    dev = z.device
+    loss = torch.empty(3, dtype=torch.float32, device=dev)
+    stats = torch.empty((3, C), dtype=torch.float32, device=dev)
+    nv = torch.empty(2, dtype=torch.int64, device=dev)
+    ws = torch.empty(int(lib.dinox_seg_loss_ws_bytes(B, g, u, C)) // 4, dtype=torch.float32, device=dev)
+    check(lib.dinox_seg_loss_fwd(_p(z), _p(y), _p(loss), _p(stats), _p(nv), _p(ws), B, g, u, C, int(c0), float(w_ce), float(w_dice), _stream()),
+          "dinox_seg_loss_fwd")
+    _seg_refuse_bad_labels("seg_loss", int(nv[1]), C)
+    return loss, stats, (z, y, stats, nv, ws, (B, g, u, C, int(c0), float(w_ce), float(w_dice)))
+
+
+def seg_loss_bwd(saved, gscale: float = 1.0) -> Tensor:
+    """dz [B, g^2, C] fp32 = d(gscale L)/dz: each patch gathers the pixels it was interpolated into, in a fixed order."""
+    z, y, stats, nv, ws, (B, g, u, C, c0, w_ce, w_dice) = saved
+    dz = torch.empty_like(z)
+    check(lib.dinox_seg_loss_bwd(_p(z), _p(y), _p(stats), _p(nv), _p(dz), _p(ws), B, g, u, C, c0, w_ce, w_dice, float(gscale), _stream()),
+          "dinox_seg_loss_bwd")
+    return dz
+
+
+class SegLossFn(torch.autograd.Function):
+    """(z, y, w_ce, w_dice, c0) -> (L, CE, Dice) as 0-d tensors; the backward takes the upstream gradient of L only (CE and Dice are
+    reported values).  z of any floating dtype is cast to fp32."""
+
+    @staticmethod
+    def forward(ctx, z, y, w_ce=1.0, w_dice=1.0, c0=0):
+        loss, _, saved = seg_loss_fwd(z, y, w_ce, w_dice, c0)
+        ctx.saved, ctx.zdt = saved, z.dtype
+        total, ce, dice = (loss[i].clone() for i in range(3))
+        ctx.mark_non_differentiable(ce, dice)
+        return total, ce, dice
+
+    @staticmethod
+    def backward(ctx, g, *_reported):
+        # the upstream gradient is a device scalar: run with gscale = 1 and scale the small [B, P, C] result (no host sync)
+        d = seg_loss_bwd(ctx.saved, 1.0) * g
+        return (d if d.dtype == ctx.zdt else d.to(ctx.zdt)), None, None, None, None
+
+
+def seg_predict(z: Tensor, u: int, labels: Optional[Tensor] = None):
+    """Label map of the patch logits z [B, g^2, C] at S = g u: pred uint8 [B, S, S] = argmax of the bilinearly upsampled logits (lowest
+    index on an exact tie).  With ``labels`` (uint8 [B, S, S], 255 = ignore) returns (pred, counts): counts int64 [3, C] = true positives,
+    predicted pixels and labelled pixels per class over the valid pixels (dinox.segment turns them into Dice / IoU / accuracy)."""
+    B, g, C = _seg_geometry("seg_predict", z, u)
+    if labels is not None and _seg_labels("seg_predict", labels, B, g, z) != u:
+        raise ValueError(f"seg_predict: labels {tuple(labels.shape)} do not have side g u = {g * u}")
+    _need_cuda(z, labels)
+    z = _c(z.float())
+    dev = z.device
+    pred = torch.empty((B, g * u, g * u), dtype=torch.uint8, device=dev)
+    counts = None
+    if labels is not None:
+        labels = _c(labels)
+        counts = torch.empty(3 * C + 1, dtype=torch.int64, device=dev)
+    check(lib.dinox_seg_predict(_p(z), _p(labels), _p(pred), _p(counts), B, g, u, C, _stream()), "dinox_seg_predict")
+    if counts is None:
+        return pred
+    _seg_refuse_bad_labels("seg_predict", int(counts[3 * C]), C)
+    return pred, counts[:3 * C].view(3, C)

@@ -1,0 +1,348 @@
+#!/usr/bin/env python3
+"""Dense segmentation fine-tuning of a DINO-X backbone on the HIP engine: a linear head on the patch tokens, cross-entropy + soft Dice.
+
+    python scripts/finetune_segmentation.py --backbone runs/x/hub-export/ --train-csv train.csv --val-csv val.csv \\
+        --num-classes 3 --rank 0 --epochs 50 --output seg/x/                       # --rank 0: frozen backbone, linear probe
+    python scripts/finetune_segmentation.py --backbone runs/x/hub-export/ --synthetic 48 --num-classes 3 --epochs 3 --output /tmp/s
+
+CSV columns: image_path,mask_path[,spacing_x,spacing_y,spacing_z].  The mask is an 8-bit single-channel PNG of class indices, 255 = ignore.
+Image and mask get the same random-resized crop window and the same flip (image bicubic, mask nearest); validation takes the centre crop
+of both.  The loss and the validation metrics run at full resolution inside csrc/segloss.hip (ops.SegLossFn, ops.seg_predict): the
+[B, P, C] patch logits are the only logits in memory.  Optimiser, schedule, pixel reading and the adapter come from finetune_lora.py.
+Written to --output whenever the early-stopping metric improves: the adapter files (rank > 0), seg_head.pth, finetune_config.json and,
+with --unfreeze-blocks, unfrozen_blocks.pth; dinox.segment.load_segmenter puts them back together.
+"""
+from __future__ import annotations
+
+import argparse
+import csv
+import json
+import logging
+import math
+import random
+import sys
+import time
+from dataclasses import asdict, dataclass
+from pathlib import Path
+from typing import List, Optional, Tuple
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+_HERE = Path(__file__).resolve().parent
+for _p in (_HERE.parent, _HERE):
+    if str(_p) not in sys.path:
+        sys.path.insert(0, str(_p))
+
+import finetune_lora as fl  # noqa: E402
+from dinox import ops, segment as SG  # noqa: E402
+from zoo.hub import load_model  # noqa: E402
+from zoo.peft import apply_lora, save_adapter  # noqa: E402
+
+log = logging.getLogger("finetune_segmentation")
+
+IGNORE = ops.SEG_IGNORE
+
+
+# ------------------------------------------------------------------------------------------ records, paired transforms
+@dataclass
+class MaskedRow(fl.LabeledRow):
+    mask_path: Path = Path()
+
+
+def read_csv(path: Path) -> List[MaskedRow]:
+    with open(path, newline="") as f:
+        rd = csv.DictReader(f)
+        cols = rd.fieldnames or []
+        lacking = {"image_path", "mask_path"} - set(cols)
+        if lacking:
+            raise ValueError(f"{path}: column(s) {sorted(lacking)} missing (found {cols})")
+        sp = all(c in cols for c in ("spacing_x", "spacing_y", "spacing_z"))
+        rows = []
+        for n, rec in enumerate(rd, 2):
+            try:
+                spacing = tuple(float(rec[c]) for c in ("spacing_x", "spacing_y", "spacing_z")) if sp else (1.0, 1.0, 1.0)
+                rows.append(MaskedRow(Path(rec["image_path"]), 0.0, spacing, sp, Path(rec["mask_path"])))
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"{path}, line {n}: {e}") from e
+    return rows
+
+
+def _resize_mask(m: torch.Tensor, h: int, w: int) -> torch.Tensor:
+    if m.shape[-2:] == (h, w):
+        return m
+    return F.interpolate(m[None, None].float(), size=(h, w), mode="nearest")[0, 0].to(torch.uint8)
+
+
+def _crop_window(h: int, w: int, gen: torch.Generator, scale=(0.7, 1.0), ratio=(3 / 4, 4 / 3)) -> Optional[Tuple[int, int, int, int]]:
+    """(top, left, height, width) drawn as finetune_lora.random_resized_crop draws it; None after ten misses."""
+    for _ in range(10):
+        area = h * w * float(torch.empty(1).uniform_(scale[0], scale[1], generator=gen))
+        asp = math.exp(float(torch.empty(1).uniform_(math.log(ratio[0]), math.log(ratio[1]), generator=gen)))
+        cw, ch = int(round(math.sqrt(area * asp))), int(round(math.sqrt(area / asp)))
+        if 0 < cw <= w and 0 < ch <= h:
+            return int(torch.randint(0, h - ch + 1, (1,), generator=gen)), int(torch.randint(0, w - cw + 1, (1,), generator=gen)), ch, cw
+    return None
+
+
+def _center_pair(x: torch.Tensor, m: torch.Tensor, size: int):
+    h, w = x.shape[-2:]
+    k = size / min(h, w)
+    nh, nw = max(size, round(h * k)), max(size, round(w * k))
+    x, m = fl._resize(x, nh, nw), _resize_mask(m, nh, nw)
+    t, l = (nh - size) // 2, (nw - size) // 2
+    return x[:, t:t + size, l:l + size], m[t:t + size, l:l + size]
+
+
+def paired_transform(x: torch.Tensor, m: torch.Tensor, size: int, gen: torch.Generator, augment: bool):
+    """image [3, H, W] in [0, 1] and mask uint8 [H, W] -> (normalised image [3, size, size], mask uint8 [size, size]).  ``augment``: one
+    random-resized crop window and one horizontal flip for both; otherwise the centre crop of both.  The image is resized bicubic, the
+    mask nearest, so the mask holds only values of the source mask."""
+    if x.shape[-2:] != m.shape[-2:]:
+        raise ValueError(f"image {tuple(x.shape[-2:])} and mask {tuple(m.shape[-2:])} differ in size")
+    if augment:
+        win = _crop_window(x.shape[-2], x.shape[-1], gen)
+        if win is None:
+            x, m = _center_pair(x, m, size)
+        else:
+            t, l, ch, cw = win
+            x, m = fl._resize(x[:, t:t + ch, l:l + cw], size, size), _resize_mask(m[t:t + ch, l:l + cw], size, size)
+        if float(torch.rand(1, generator=gen)) < 0.5:
+            x, m = x.flip(-1), m.flip(-1)
+    else:
+        x, m = _center_pair(x, m, size)
+    return fl.normalize(x).contiguous(), m.contiguous()
+
+
+class MaskedImages(fl.LabeledImages):
+    """(image [3, S, S], spacing [3], mask uint8 [S, S]) per row; the pixel reading is finetune_lora's."""
+
+    def read_mask(self, row: MaskedRow) -> torch.Tensor:
+        from PIL import Image
+        p = row.mask_path if row.mask_path.is_absolute() or self.root is None else self.root / row.mask_path
+        a = np.asarray(Image.open(p))
+        if a.ndim != 2 or a.dtype != np.uint8:
+            raise ValueError(f"{p}: the mask must be an 8-bit single-channel image of class indices (got {a.dtype}, shape {a.shape})")
+        return torch.from_numpy(a.copy())
+
+    def __getitem__(self, i: int):
+        row = self.rows[i]
+        x, m = paired_transform(self.pixels(row)[None].expand(3, -1, -1), self.read_mask(row), self.img_size, self.gen, self.augment)
+        return x, torch.tensor(row.spacing, dtype=torch.float32), m
+
+
+class SyntheticMasks(fl.LabeledImages):
+    """``n`` seeded images whose labels can be read off the pixels: noise around 0.2 (class 0) and C - 1 rectangles of rising brightness
+    (classes 1 .. C - 1, later ones on top); the four left-most columns are marked 255 (ignore)."""
+
+    def __init__(self, n: int, img_size: int, num_classes: int, seed: int, first: int = 0, augment: bool = False) -> None:
+        super().__init__([], img_size, "float01", augment=augment, seed=seed + 1 + first)
+        g = torch.Generator().manual_seed(seed * 7919 + 17)
+        total, S = first + n, img_size
+        img = 0.2 + 0.1 * (torch.rand((total, S, S), generator=g) - 0.5)
+        noise = torch.rand((total, S, S), generator=g)
+        mask = torch.zeros((total, S, S), dtype=torch.uint8)
+        for c in range(1, num_classes):
+            h = torch.randint(S // 4, S // 2 + 1, (total, 2), generator=g)
+            t = (torch.rand((total, 2), generator=g) * (S - h)).long()
+            for i in range(total):
+                ys, xs = slice(int(t[i, 0]), int(t[i, 0] + h[i, 0])), slice(int(t[i, 1]), int(t[i, 1] + h[i, 1]))
+                img[i, ys, xs] = 0.2 + 0.7 * c / (num_classes - 1) + 0.1 * (noise[i, ys, xs] - 0.5)
+                mask[i, ys, xs] = c
+        mask[:, :, :4] = IGNORE
+        self.images, self.masks = img.clamp(0, 1)[first:, None], mask[first:]
+        self.spacings = 0.5 + torch.rand((total, 3), generator=g)[first:]
+
+    def __len__(self) -> int:
+        return self.images.shape[0]
+
+    def __getitem__(self, i: int):
+        x, m = paired_transform(self.images[i].expand(3, -1, -1), self.masks[i], self.img_size, self.gen, self.augment)
+        return x, self.spacings[i], m
+
+
+# ------------------------------------------------------------------------------------------ epochs, saving
+@dataclass
+class SegConfig(fl.FinetuneConfig):
+    ce_weight: float = 1.0
+    dice_weight: float = 1.0
+    dice_c0: int = 0
+    ignore_index: int = IGNORE
+    best_dice_per_class: Optional[List[float]] = None
+
+
+def _batches(loader, device, scale_aware):
+    for x, sp, m in loader:
+        yield x.to(device), (sp.to(device) if scale_aware else None), m.to(device)
+
+
+def train_epoch(model, loader, opt: fl.ArenaAdamW, sched, device, scale_aware, amp, w_ce, w_dice, c0) -> float:
+    model.train()
+    tot, n = 0.0, 0
+    for x, sp, m in _batches(loader, device, scale_aware):
+        opt.zero_grad()
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+            logits = model(x, spacing=sp)
+        loss, _, _ = ops.SegLossFn.apply(logits, m, w_ce, w_dice, c0)
+        loss.backward()
+        opt.step(sched(opt.t))
+        tot, n = tot + float(loss.detach()), n + 1
+    return tot / max(n, 1)
+
+
+@torch.no_grad()
+def validate(model, loader, device, scale_aware, amp, w_ce, w_dice, c0):
+    """-> (mean loss, metrics, counts int64 [3, C] on the host, label maps uint8 [n, S, S] on the host)."""
+    model.eval()
+    tot, n, counts, preds = 0.0, 0, None, []
+    for x, sp, m in _batches(loader, device, scale_aware):
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+            logits = model(x, spacing=sp)
+        tot, n = tot + float(ops.seg_loss_fwd(logits, m, w_ce, w_dice, c0)[0][0]), n + 1
+        pred, cnt = ops.seg_predict(logits, model.patch, m)
+        counts = cnt.clone() if counts is None else counts + cnt
+        preds.append(pred.cpu())
+    counts = counts.cpu()
+    metrics = {"loss": tot / max(n, 1), "mean_dice": SG.mean_dice(counts, skip_background=bool(c0)), "miou": SG.miou(counts),
+               "pixel_accuracy": SG.pixel_accuracy(counts)}
+    return metrics["loss"], metrics, counts, torch.cat(preds)
+
+
+def save_segmenter(model: SG.SegModel, vit: nn.Module, output_dir: Path, config: SegConfig) -> None:
+    output_dir = Path(output_dir)
+    output_dir.mkdir(parents=True, exist_ok=True)
+    if config.rank > 0:
+        save_adapter(model.backbone, output_dir)
+    torch.save({k: v.detach().cpu().clone() for k, v in model.head.state_dict().items()}, output_dir / SG.HEAD_FILE)
+    if config.unfreeze_blocks > 0:
+        state = {}
+        for i in fl.unfrozen_block_range(len(vit.blocks), config.unfreeze_blocks):
+            for name, p in vit.blocks[i].named_parameters():
+                if ".lora_" not in name:
+                    state[f"blocks.{i}.{name}"] = p.detach().cpu().clone()
+        torch.save(state, output_dir / SG.BLOCKS_FILE)
+    (output_dir / SG.CONFIG_FILE).write_text(json.dumps(asdict(config), indent=2, default=str))
+
+
+# ------------------------------------------------------------------------------------------ command line
+def build_parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(description="Segmentation fine-tuning of a DINO-X backbone (linear head on the patch tokens)",
+                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    base = {a.dest: a for a in fl.build_parser()._actions}
+    for dest in ("backbone", "device", "train_csv", "val_csv", "synthetic", "data_root", "input_format", "window_level", "window_width",
+                 "num_classes", "rank", "alpha", "lora_dropout", "epochs", "batch_size", "lr", "weight_decay", "warmup_epochs", "patience"):
+        ap._add_action(base[dest])                           # the very flags of finetune_lora.py: names, types, defaults, help
+    ap.add_argument("--es-metric", default="loss", choices=["loss", "mean_dice"], help="'loss' (lower is better) or 'mean_dice' (higher is better)")
+    for dest in ("num_workers", "no_amp", "seed", "unfreeze_blocks", "backbone_lr", "output"):
+        ap._add_action(base[dest])
+    ap.add_argument("--ce-weight", type=float, default=1.0, help="weight of the cross-entropy term")
+    ap.add_argument("--dice-weight", type=float, default=1.0, help="weight of the soft Dice term")
+    ap.add_argument("--dice-skip-background", action="store_true", help="leave class 0 out of the Dice term (c0 = 1)")
+    ap.add_argument("--ignore-index", type=int, default=IGNORE, help="label value left out of loss and metrics; only 255 is supported")
+    return ap
+
+
+def run(args: argparse.Namespace) -> dict:
+    """One run -> {"config": SegConfig, "val_pred": the best epoch's validation label maps uint8 [n, S, S] (host), "val_dataset": the
+    validation set}."""
+    ap = build_parser()
+    if args.ignore_index != IGNORE:
+        ap.error(f"--ignore-index {args.ignore_index}: only {IGNORE} is supported (the kernels compare labels with that value)")
+    if not 2 <= args.num_classes <= ops.SEG_MAX_CLASSES:
+        ap.error(f"--num-classes {args.num_classes}: the segmentation kernels take 2 to {ops.SEG_MAX_CLASSES} classes")
+    if not args.synthetic and (args.train_csv is None or args.val_csv is None):
+        ap.error("--train-csv and --val-csv are required unless --synthetic N is given")
+    device = torch.device(args.device)
+    amp = not args.no_amp and device.type == "cuda"
+    if args.seed is not None:
+        random.seed(args.seed)
+        np.random.seed(args.seed)
+        torch.manual_seed(args.seed)
+    seed = args.seed if args.seed is not None else 0
+    c0 = 1 if args.dice_skip_background else 0
+
+    backbone = load_model(args.backbone, device=str(device))
+    scale_aware, dim, img = backbone.scale_aware, backbone.dim, backbone.img_size
+    if backbone.patch > ops.SEG_MAX_UPSAMPLE:
+        ap.error(f"patch size {backbone.patch}: the segmentation kernels upsample by at most {ops.SEG_MAX_UPSAMPLE}")
+    if args.synthetic:
+        n_val = max(args.synthetic // 4, 1)
+        n_train = args.synthetic - n_val
+        train_ds = SyntheticMasks(n_train, img, args.num_classes, seed, first=0, augment=True)
+        val_ds = SyntheticMasks(n_val, img, args.num_classes, seed, first=n_train, augment=False)
+        workers = 0
+    else:
+        rows_t, rows_v = read_csv(args.train_csv), read_csv(args.val_csv)
+        if scale_aware and not rows_t[0].has_spacing:
+            log.warning("scale-aware backbone, but the CSV has no spacing_x/y/z columns: 1 mm is assumed everywhere")
+        kw = dict(input_format=args.input_format, window_level=args.window_level, window_width=args.window_width, data_root=args.data_root)
+        train_ds = MaskedImages(rows_t, img, augment=True, seed=seed + 1, **kw)
+        val_ds = MaskedImages(rows_v, img, augment=False, **kw)
+        workers = args.num_workers
+    gen = torch.Generator().manual_seed(seed)
+    train_loader = torch.utils.data.DataLoader(train_ds, batch_size=args.batch_size, shuffle=True, drop_last=True, num_workers=workers,
+                                               generator=gen)
+    val_loader = torch.utils.data.DataLoader(val_ds, batch_size=args.batch_size, shuffle=False, num_workers=workers)
+    if len(train_loader) == 0:
+        ap.error(f"{len(train_ds)} training samples do not fill one batch of {args.batch_size}")
+
+    if args.rank > 0:
+        backbone = apply_lora(backbone, rank=args.rank, alpha=args.alpha, dropout=args.lora_dropout)
+        vit = backbone.base_model.model
+    else:                                                    # linear probe: no adapter, nothing of the backbone trains
+        vit = backbone
+        for p in vit.parameters():
+            p.requires_grad = False
+    base_params: List[nn.Parameter] = []
+    for i in fl.unfrozen_block_range(len(vit.blocks), args.unfreeze_blocks):
+        for p in vit.blocks[i].parameters():
+            if not p.requires_grad:
+                p.requires_grad = True
+                base_params.append(p)
+    frozen = args.rank == 0 and not base_params
+    model = SG.SegModel(backbone, SG.SegHead(dim, args.num_classes), frozen_backbone=frozen).to(device)
+    base_ids = {id(p) for p in base_params}
+    fast = [p for p in backbone.parameters() if p.requires_grad and id(p) not in base_ids] + list(model.head.parameters())
+    log.info("%d adapter + %d unfrozen + %d head parameters train%s", sum(p.numel() for p in fast) - sum(p.numel() for p in model.head.parameters()),
+             sum(p.numel() for p in base_params), sum(p.numel() for p in model.head.parameters()), " (backbone under no_grad)" if frozen else "")
+    opt = fl.ArenaAdamW([(fast, args.lr), (base_params, args.backbone_lr)], args.weight_decay)
+    steps, warm = args.epochs * len(train_loader), args.warmup_epochs * len(train_loader)
+
+    cfg = SegConfig(backbone=str(args.backbone), task="segmentation", num_classes=args.num_classes, rank=args.rank, alpha=args.alpha, lr=args.lr,
+                    epochs=args.epochs, batch_size=args.batch_size, input_format=args.input_format, scale_aware=scale_aware,
+                    train_samples=len(train_ds), val_samples=len(val_ds), seed=args.seed, unfreeze_blocks=args.unfreeze_blocks,
+                    backbone_lr=args.backbone_lr if args.unfreeze_blocks > 0 else None, ce_weight=args.ce_weight, dice_weight=args.dice_weight,
+                    dice_c0=c0, ignore_index=args.ignore_index)
+    higher = args.es_metric != "loss"
+    best, stale, t0, best_pred = (-math.inf if higher else math.inf), 0, time.time(), None
+    for epoch in range(1, args.epochs + 1):
+        tr = train_epoch(model, train_loader, opt, lambda s: fl.lr_factor(s, warm, steps), device, scale_aware, amp, args.ce_weight,
+                         args.dice_weight, c0)
+        vl, metrics, counts, preds = validate(model, val_loader, device, scale_aware, amp, args.ce_weight, args.dice_weight, c0)
+        cfg.train_loss_history.append(tr)
+        log.info("epoch %d/%d  train %.4f  %s", epoch, args.epochs, tr, "  ".join(f"{k} {v:.4f}" for k, v in metrics.items()))
+        cur = metrics[args.es_metric] if higher else vl
+        if (cur > best) if higher else (cur < best):
+            best, stale, best_pred = cur, 0, preds
+            cfg.best_epoch, cfg.best_val_loss, cfg.best_val_metrics = epoch, vl, metrics
+            cfg.best_dice_per_class = SG.dice_per_class(counts).tolist()
+            save_segmenter(model, vit, args.output, cfg)
+        else:
+            stale += 1
+            if stale >= args.patience:
+                log.info("no improvement for %d epochs: stopping at epoch %d", stale, epoch)
+                break
+    log.info("done in %.1f s: best epoch %d, val loss %.4f", time.time() - t0, cfg.best_epoch, cfg.best_val_loss)
+    return {"config": cfg, "val_pred": best_pred, "val_dataset": val_ds}
+
+
+def main(argv=None) -> SegConfig:
+    args = build_parser().parse_args(argv)
+    logging.basicConfig(level=logging.INFO, format="%(asctime)s [%(levelname)s] %(message)s", datefmt="%H:%M:%S")
+    return run(args)["config"]
+
+
+if __name__ == "__main__":
+    main()

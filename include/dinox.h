@@ -769,6 +769,42 @@ int dinox_lora_dropout(const void* in, void* out, int64_t n, float p, uint64_t s
 int dinox_lora_merge(const float* w, const float* A, const float* B, float* w_out, float s, int sign, int N, int K, int r, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Dense segmentation loss on patch logits (kernels: csrc/segloss.hip; autograd node: dinox.ops.SegLossFn).  A linear head gives one
+ * logit row per patch; the loss is taken at full resolution, and no tensor of B C S^2 elements is written in either direction.
+ *   z[B][P][C]  fp32, dense, P = g^2, patch i = gy g + gx.  2 <= C <= 64 (C > 64: DINOX_EUNSUPPORTED; C < 2: DINOX_EINVAL).
+ *   y[B][S][S]  uint8, S = g u, 1 <= u <= 32 (the patch size).  255 = ignore.  Any other value >= C is an argument error: such a pixel
+ *               is left out like an ignored one (a label is only ever compared, never an address), and the calls COUNT them -- nv[1] of
+ *               the forward, counts[3 C] of predict -- for the caller to refuse.
+ *   l_p[c]      bilinear upsampling, align_corners = False: along x the source coordinate is s = max((x + 0.5) / u - 0.5, 0),
+ *               x0 = floor(s), x1 = min(x0 + 1, g - 1), the weight of x1 is s - x0; y alike; l_p is the 4-tap interpolation of z.
+ *   p_p = softmax(l_p) (max subtracted);  Nv = number of pixels with y_p != 255 (and < C);
+ *   CE = (1 / Nv) sum_valid (lse(l_p) - l_p[y_p]);
+ *   I_c = sum_valid p_pc [y_p = c],  P_c = sum_valid p_pc,  Y_c = sum_valid [y_p = c]   (over the whole batch);
+ *   D_c = (2 I_c + 1) / (P_c + Y_c + 1);   Dice = 1 - mean_{c >= c0} D_c,  c0 in {0, 1} (1: the background class is left out);
+ *   L = w_ce CE + w_dice Dice.   Nv = 0: every loss is 0 and every gradient exactly 0.
+ *   G_pc = (w_ce / Nv)(p_pc - [y_p = c]) + w_dice p_pc (a_pc - sum_k p_pk a_pk),
+ *   a_pc = -(1 / (C - c0)) (2 [y_p = c](P_c + Y_c + 1) - (2 I_c + 1)) / (P_c + Y_c + 1)^2 for c >= c0, 0 below;  G = 0 at ignored pixels;
+ *   dz[b][j][c] = grad_scale sum_p W(p, j) G_pc,  W(p, j) = the bilinear weight of patch j at pixel p.
+ * Every entry checks its arguments on the host (a message before any launch), allocates nothing and does not synchronise.  Floating-point
+ * sums have a fixed order (per lane, wave butterfly, partial sums in the workspace added in ascending order by a second launch): equal
+ * inputs give equal bits.  Integer counts use integer atomics.  1 <= B <= 2^20, 1 <= g <= 4096, B g^2 <= 2^32.
+ *
+ * dinox_seg_loss_ws_bytes: bytes of workspace for forward and backward (a pure function of the sizes; 0 for sizes the calls refuse; contents
+ *   need not be initialised; 4-byte aligned).
+ * dinox_seg_loss_fwd: loss[3] = (L, CE, Dice) fp32, stats[3][C] = (I, P, Y) fp32, nv[2] = (Nv, number of labels >= C other than 255).
+ * dinox_seg_loss_bwd: dz[B][P][C] fp32 from z, y and the forward's stats and nv (device pointers; nothing crosses to the host).
+ * dinox_seg_predict:  pred[B][S][S] uint8 = argmax_c l_p[c], the lowest index on an exact tie.  y != NULL (then counts != NULL, and both or
+ *   neither): counts[3 C + 1] int64 = per class the true positives, the predicted pixels and the labelled pixels over the valid pixels,
+ *   then the number of labels >= C other than 255.  counts is zeroed on the stream first.
+ * ------------------------------------------------------------------------------------------ */
+int64_t dinox_seg_loss_ws_bytes(int64_t B, int g, int u, int C);
+int dinox_seg_loss_fwd(const float* z, const uint8_t* y, float* loss, float* stats, int64_t* nv, void* ws, int64_t B, int g, int u, int C,
+                       int c0, float w_ce, float w_dice, void* stream);
+int dinox_seg_loss_bwd(const float* z, const uint8_t* y, const float* stats, const int64_t* nv, float* dz, void* ws, int64_t B, int g, int u,
+                       int C, int c0, float w_ce, float w_dice, float grad_scale, void* stream);
+int dinox_seg_predict(const float* z, const uint8_t* y, uint8_t* pred, int64_t* counts, int64_t B, int g, int u, int C, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-launch timing of dinox_gemm (diagnostic; bench.py's roofline object).  Between start and stop every dinox_gemm launch -- also
  * the ones dinox_block_* issue -- is counted per (kernel, shape, epilogue), and one launch in `every` (a fixed hash of the launch
  * counter) is bracketed by a HIP event pair on its stream.  stop synchronises those events and writes one text line per shape into
