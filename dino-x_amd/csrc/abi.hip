@@ -361,6 +361,31 @@ extern "C" int dinox_seg_predict(const float* z, const uint8_t* y, uint8_t* pred
   return dinox::launch_seg_predict(z, y, pred, counts, B, g, u, C, dinox::as_stream(stream));
 }
 
+// ---------------------------------------------------------------- surface distances of two label maps (kernels: surfdist.hip)
+// B C 2 H workgroups (the row launch) stay inside 2^30 and every plane index inside int64.
+static bool surface_sizes_ok(int64_t B, int H, int W, int C) {
+  return B >= 1 && B <= (1 << 20) && H >= 1 && H <= dinox::SURF_MAX_SIDE && W >= 1 && W <= dinox::SURF_MAX_SIDE && C >= 2 && C <= dinox::SEG_MAX_CLASSES &&
+         B * C * 2 * H <= ((int64_t)1 << 30);
+}
+
+extern "C" int64_t dinox_surface_ws_bytes(int64_t B, int H, int W, int C) {
+  return surface_sizes_ok(B, H, W, C) ? dinox::surface_ws_bytes(B, H, W, C) : 0;
+}
+
+extern "C" int dinox_surface_stats(const uint8_t* pred, const uint8_t* gt, const float* spacing, const float* tol, int64_t* counts, float* values,
+                                   int64_t* bad, void* ws, int64_t B, int H, int W, int C, int T, int q_num, int q_den, void* stream) {
+  DX_REQUIRE(pred && gt && spacing && tol && counts && values && bad && ws, DINOX_EINVAL, "surface_stats: null pointer");
+  DX_REQUIRE(H >= 1 && H <= dinox::SURF_MAX_SIDE && W >= 1 && W <= dinox::SURF_MAX_SIDE, DINOX_EINVAL, "surface_stats: H=%d W=%d (1 <= H, W <= %d)", H, W,
+             dinox::SURF_MAX_SIDE);
+  DX_REQUIRE(C >= 2 && C <= dinox::SEG_MAX_CLASSES, DINOX_EINVAL, "surface_stats: C=%d (2 <= C <= %d)", C, dinox::SEG_MAX_CLASSES);
+  DX_REQUIRE(surface_sizes_ok(B, H, W, C), DINOX_EINVAL, "surface_stats: B=%lld (B >= 1 and B C 2 H <= 2^30; evaluate a longer batch in pieces)",
+             (long long)B);
+  DX_REQUIRE(T >= 1 && T <= dinox::SURF_MAX_TOL, DINOX_EINVAL, "surface_stats: T=%d tolerances (1 <= T <= %d)", T, dinox::SURF_MAX_TOL);
+  for (int t = 0; t < T; ++t) DX_REQUIRE(tol[t] >= 0.f && tol[t] <= 3.0e38f, DINOX_EINVAL, "surface_stats: tolerance %d is %g (finite and >= 0)", t, (double)tol[t]);
+  DX_REQUIRE(q_num > 0 && q_num <= q_den, DINOX_EINVAL, "surface_stats: quantile %d/%d (0 < q_num <= q_den)", q_num, q_den);
+  return dinox::launch_surface_stats(pred, gt, spacing, tol, counts, values, bad, ws, B, H, W, C, T, q_num, q_den, dinox::as_stream(stream));
+}
+
 // ---------------------------------------------------------------- LoRA low-rank products (kernels: lora.hip)
 static bool lora_rank_ok(int r) { return r >= 1 && r <= dinox::LORA_MAX_RANK; }
 static bool lora_dim_ok(int d) { return d >= 1 && d <= (1 << 20); }

@@ -145,6 +145,13 @@ int launch_seg_loss_bwd(const float* z, const uint8_t* y, const float* stats, co
                         int c0, float w_ce, float w_dice, float gscale, hipStream_t st);
 int launch_seg_predict(const float* z, const uint8_t* y, uint8_t* pred, int64_t* counts, int64_t B, int g, int u, int C, hipStream_t st);
 
+// ---------------------------------------------------------------- surface distances of two label maps (surfdist.hip; entry point and argument checks: abi.hip)
+constexpr int SURF_MAX_SIDE = 1024;        // a row of squared column distances (4 KiB) sits in LDS; a column distance fits uint16 beside its sentinel
+constexpr int SURF_MAX_TOL = 8;            // tolerance counters per lane, in registers
+int64_t surface_ws_bytes(int64_t B, int H, int W, int C);
+int launch_surface_stats(const uint8_t* pred, const uint8_t* gt, const float* spacing, const float* tol, int64_t* counts, float* values, int64_t* bad,
+                         void* ws, int64_t B, int H, int W, int C, int T, int q_num, int q_den, hipStream_t st);
+
 // ---------------------------------------------------------------- launch glue shared by the NT launchers
 // Activation index of the <OUT, ACT, RES> kernels (gemm_bf16_pp / _pp128 / _areg): the template argument ACT.
 enum { EPI_ACT_PLAIN = 0, EPI_ACT_GELU = 1, EPI_ACT_DGELU = 2 };

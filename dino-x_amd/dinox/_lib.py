@@ -148,6 +148,8 @@ SIGNATURES = {
     "dinox_seg_loss_fwd": (i32, [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, f32, vp]),
     "dinox_seg_loss_bwd": (i32, [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, f32, f32, vp]),
     "dinox_seg_predict": (i32, [vp, vp, vp, vp, i64, i32, i32, i32, vp]),
+    "dinox_surface_ws_bytes": (i64, [i64, i32, i32, i32]),
+    "dinox_surface_stats": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp]),
     "dinox_attention_rows_ok": (i32, [i32, i32, i32, i32, i32]),
     "dinox_attention_rows": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "dinox_attention_rollout_step_ok": (i32, [i32, i32, i32, i32]),

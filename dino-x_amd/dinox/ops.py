@@ -3068,3 +3068,81 @@ def seg_predict(z: Tensor, u: int, labels: Optional[Tensor] = None):
         return pred
     _seg_refuse_bad_labels("seg_predict", int(counts[3 * C]), C)
     return pred, counts[:3 * C].view(3, C)
+
+
+# ------------------------------------------------------------------------------------------
+# surface distances between two label maps (csrc/surfdist.hip)
+# ------------------------------------------------------------------------------------------
+SURFACE_MAX_SIDE = 1024
+SURFACE_MAX_TOLERANCES = 8
+SURFACE_WS_CAP = 256 << 20      # bytes of workspace per call: a longer batch is evaluated in pieces (a single image may exceed it)
+
+
+def _surface_maps(pred, labels):
+    """(B, H, W) of two uint8 label maps [B, H, W] on one device; ValueError for anything the kernel does not take."""
+    for what, t in (("pred", pred), ("labels", labels)):
+        if not isinstance(t, Tensor) or t.dtype != torch.uint8 or t.dim() != 3:
+            raise ValueError(f"surface_stats: {what} must be uint8 [B, H, W], got {_describe(t)}")
+    if pred.shape != labels.shape:
+        raise ValueError(f"surface_stats: pred {tuple(pred.shape)} and labels {tuple(labels.shape)} differ in shape")
+    if pred.device != labels.device:
+        raise ValueError(f"surface_stats: pred on {pred.device}, labels on {labels.device}")
+    B, H, W = pred.shape
+    if B < 1 or not (1 <= H <= SURFACE_MAX_SIDE and 1 <= W <= SURFACE_MAX_SIDE):
+        raise ValueError(f"surface_stats: maps must be [B >= 1, H, W] with 1 <= H, W <= {SURFACE_MAX_SIDE}, got {tuple(pred.shape)}")
+    return B, H, W
+
+
+def _surface_spacing(spacing, B: int, device) -> Tensor:
+    """spacing [B, 2] = (s_y, s_x) in mm per pixel -> fp32 on ``device``; every entry finite and > 0."""
+    sp = torch.as_tensor(spacing)
+    if sp.dim() != 2 or tuple(sp.shape) != (B, 2) or sp.is_complex() or sp.dtype == torch.bool:
+        raise ValueError(f"surface_stats: spacing must be [{B}, 2] = (s_y, s_x) in mm per pixel, got {_describe(sp)}")
+    sp = sp.to(device=device, dtype=torch.float32)
+    if not bool((torch.isfinite(sp) & (sp > 0)).all()):
+        raise ValueError("surface_stats: every spacing must be finite and > 0")
+    return _c(sp)
+
+
+def surface_stats(pred: Tensor, labels: Tensor, spacing, num_classes: int, tolerances=(1.0,), q=(95, 100)):
+    """Directed surface-distance statistics of two uint8 label maps [B, H, W] (labels: 255 = ignore) in mm, spacing [B, 2] = (s_y, s_x)
+    per image (include/dinox.h has the definitions).  Returns (counts int64 [B, C, 2, 1 + T] = (n, within tolerance t), values fp32
+    [B, C, 2, 3] = (sum, max, q[0]/q[1] nearest-rank quantile)), both on the device; direction 0 runs from the border of ``pred`` to the
+    border of ``labels``, direction 1 the other way.  dinox.segment.surface_metrics forms HD95 / ASSD / NSD from them.  The batch is cut
+    so that one call's workspace stays under SURFACE_WS_CAP; the results do not depend on the cut.  A label >= C other than 255 in
+    ``labels``, or any value >= C in ``pred``, raises ValueError (one device read of two integers)."""
+    B, H, W = _surface_maps(pred, labels)
+    C = num_classes
+    if isinstance(C, bool) or not isinstance(C, int) or not 2 <= C <= SEG_MAX_CLASSES:
+        raise ValueError(f"surface_stats: num_classes must be an integer in [2, {SEG_MAX_CLASSES}], got {C!r}")
+    try:
+        tol = [float(t) for t in tolerances]
+    except TypeError as e:
+        raise ValueError(f"surface_stats: tolerances must be a sequence of numbers, got {tolerances!r}") from e
+    if not 1 <= len(tol) <= SURFACE_MAX_TOLERANCES or not all(math.isfinite(t) and t >= 0 for t in tol):
+        raise ValueError(f"surface_stats: 1 to {SURFACE_MAX_TOLERANCES} tolerances in mm, finite and >= 0, got {tolerances!r}")
+    if (not isinstance(q, (tuple, list)) or len(q) != 2 or any(isinstance(v, bool) or not isinstance(v, int) for v in q)
+            or not 0 < q[0] <= q[1] or q[1] >= 1 << 31):
+        raise ValueError(f"surface_stats: q must be two integers (q_num, q_den) with 0 < q_num <= q_den, got {q!r}")
+    _need_cuda(pred, labels)
+    dev = pred.device
+    sp = _surface_spacing(spacing, B, dev)
+    pred, labels = _c(pred), _c(labels)
+    T = len(tol)
+    tol_host = (_lib.f32 * T)(*tol)                         # a host array: the entry reads it during the call
+    counts = torch.empty((B, C, 2, 1 + T), dtype=torch.int64, device=dev)
+    values = torch.empty((B, C, 2, 3), dtype=torch.float32, device=dev)
+    per_image = int(lib.dinox_surface_ws_bytes(1, H, W, C))
+    step = max(1, min(B, SURFACE_WS_CAP // per_image))
+    while step > 1 and not lib.dinox_surface_ws_bytes(step, H, W, C):      # the launch grids bound the images per call as well
+        step //= 2
+    ws = torch.empty(per_image * step // 4, dtype=torch.float32, device=dev)
+    bad = torch.zeros((-(-B // step), 2), dtype=torch.int64, device=dev)
+    for i, b0 in enumerate(range(0, B, step)):
+        n = min(step, B - b0)
+        check(lib.dinox_surface_stats(_p(pred[b0:]), _p(labels[b0:]), _p(sp[b0:]), tol_host, _p(counts[b0:]), _p(values[b0:]), _p(bad[i]), _p(ws),
+                                      n, H, W, C, T, int(q[0]), int(q[1]), _stream()), "dinox_surface_stats")
+    nbad = bad.sum(0).tolist()
+    if nbad[0] or nbad[1]:
+        raise ValueError(f"surface_stats: {nbad[0]} value(s) of pred are >= C = {C}, {nbad[1]} label(s) are >= C and not {SEG_IGNORE} (ignore)")
+    return counts, values

@@ -6,7 +6,8 @@
 
 The head's [B, P, C] logits are all that exists in memory; the upsampling to S = g * patch happens inside the loss / predict kernels.
 ``load_segmenter`` puts back what scripts/finetune_segmentation.py wrote.  The metric helpers take the int64 counts [3, C] of
-``ops.seg_predict`` (true positives, predicted pixels, labelled pixels per class, over the valid pixels).
+``ops.seg_predict`` (true positives, predicted pixels, labelled pixels per class, over the valid pixels); ``surface_metrics`` and
+``SurfaceAccumulator`` turn ``ops.surface_stats`` (csrc/surfdist.hip) into HD95 / ASSD / surface Dice in mm.
 """
 from __future__ import annotations
 
@@ -138,6 +139,64 @@ def miou(counts, skip_background: bool = False) -> float:
 def pixel_accuracy(counts) -> float:
     tp, _, yc = _rows(counts)
     return float(tp.sum() / yc.sum()) if float(yc.sum()) > 0 else 0.0
+
+
+# ------------------------------------------------------------------------------------------ boundary metrics from ops.surface_stats
+def surface_metrics(counts, values, spacing, shape) -> dict:
+    """HD95, HD, ASSD and NSD per image and class from ``ops.surface_stats``'s outputs: counts [B, C, 2, 1 + T], values [B, C, 2, 3],
+    spacing [B, 2] = (s_y, s_x) in mm per pixel, shape = (H, W) of the label maps.  Returns float64 tensors on the host:
+    {"hd95", "hd", "assd": [B, C], "nsd": [B, C, T]} ("hd95" is whatever quantile surface_stats was asked for; 95/100 by default).
+    A class with neither border in an image is absent there: NaN.  A class with exactly one (missed or hallucinated) takes the image
+    diagonal sqrt((s_y H)^2 + (s_x W)^2) for the distance metrics and 0 for NSD."""
+    c, v = torch.as_tensor(counts).double().cpu(), torch.as_tensor(values).double().cpu()
+    if c.dim() != 4 or c.shape[2] != 2 or c.shape[3] < 2 or v.shape != c.shape[:3] + (3,):
+        raise ValueError(f"surface_metrics: counts must be [B, C, 2, 1 + T] and values [B, C, 2, 3], got {tuple(c.shape)} and {tuple(v.shape)}")
+    sp = torch.as_tensor(spacing).double().cpu()
+    if sp.shape != (c.shape[0], 2):
+        raise ValueError(f"surface_metrics: spacing must be [{c.shape[0]}, 2] = (s_y, s_x), got {tuple(sp.shape)}")
+    H, W = shape
+    diag = torch.sqrt((sp[:, 0] * H) ** 2 + (sp[:, 1] * W) ** 2)[:, None].expand(-1, c.shape[1])
+    nA, nG = c[:, :, 0, 0], c[:, :, 1, 0]
+    absent, one = (nA == 0) & (nG == 0), (nA == 0) != (nG == 0)
+    den = (nA + nG).clamp(min=1)
+    nan = torch.full_like(den, float("nan"))
+
+    def pick(x):
+        return torch.where(absent, nan, torch.where(one, diag, x))
+
+    nsd = (c[:, :, 0, 1:] + c[:, :, 1, 1:]) / den[..., None]
+    nsd = torch.where(absent[..., None], nan[..., None], torch.where(one[..., None], torch.zeros_like(nsd), nsd))
+    return {"hd95": pick(torch.maximum(v[:, :, 0, 2], v[:, :, 1, 2])), "hd": pick(torch.maximum(v[:, :, 0, 1], v[:, :, 1, 1])),
+            "assd": pick((v[:, :, 0, 0] + v[:, :, 1, 0]) / den), "nsd": nsd}
+
+
+class SurfaceAccumulator:
+    """Per-class dataset means of ``surface_metrics``' per-image figures over a stream of batches.  A class's score is the mean over the
+    images in which it is not absent; ``result()`` reports that number of images beside it (a class absent everywhere scores NaN over 0)."""
+
+    def __init__(self, num_classes: int, num_tolerances: int) -> None:
+        self.C, self.T = num_classes, num_tolerances
+        self.images = torch.zeros(num_classes, dtype=torch.int64)
+        self.sums = {"hd95": torch.zeros(num_classes, dtype=torch.float64), "hd": torch.zeros(num_classes, dtype=torch.float64),
+                     "assd": torch.zeros(num_classes, dtype=torch.float64), "nsd": torch.zeros((num_classes, num_tolerances), dtype=torch.float64)}
+
+    def update(self, metrics: dict) -> None:
+        hd = metrics["hd95"]
+        if hd.dim() != 2 or hd.shape[1] != self.C or metrics["nsd"].shape != hd.shape + (self.T,):
+            raise ValueError(f"SurfaceAccumulator: expected [B, {self.C}] metrics with {self.T} tolerance(s), got {tuple(hd.shape)} and "
+                             f"{tuple(metrics['nsd'].shape)}")
+        present = ~torch.isnan(hd)
+        self.images += present.sum(0)
+        for k, s in self.sums.items():
+            s += torch.nan_to_num(metrics[k].double(), nan=0.0).sum(0)
+
+    def result(self) -> dict:
+        """{"hd95", "hd", "assd": [C], "nsd": [C, T], "images": int64 [C]}: float64 means, NaN where a class was in no image."""
+        n = self.images.double()
+        out = {k: torch.where((n > 0).reshape([-1] + [1] * (s.dim() - 1)), s / n.clamp(min=1).reshape([-1] + [1] * (s.dim() - 1)),
+                              torch.full_like(s, float("nan"))) for k, s in self.sums.items()}
+        out["images"] = self.images.clone()
+        return out
 
 
 # ------------------------------------------------------------------------------------------ what finetune_segmentation.py wrote

@@ -1,0 +1,172 @@
+#!/usr/bin/env python3
+"""Evaluate a fine-tuned segmenter: overlap scores and boundary metrics in millimetres, all of it on the device.
+
+    python scripts/evaluate_segmentation.py --backbone runs/x/hub-export/ --segmenter seg/x/ --val-csv val.csv --out seg_eval.json
+    python scripts/evaluate_segmentation.py --backbone runs/x/hub-export/ --segmenter /tmp/s --synthetic 48 --out /tmp/s/seg_eval.json
+
+``--segmenter`` is the directory scripts/finetune_segmentation.py wrote (dinox.segment.load_segmenter puts it back together); the CSV has
+that script's columns: image_path,mask_path[,spacing_x,spacing_y,spacing_z].  Per class and as means over the present classes the JSON
+holds Dice and IoU (ops.seg_predict's counts over the whole set) and HD95, ASSD and the surface Dice (NSD) at every ``--tolerance-mm``
+(ops.surface_stats, csrc/surfdist.hip; dinox.segment.surface_metrics), each with the number of images behind it.
+
+Spacing.  The boundary metrics are measured on the grid the model predicts on: the centre crop resizes an h x w slice to nh x nw before
+cropping, so a pixel of the label map is (spacing_y h / nh, spacing_x w / nw) mm, not the CSV's value; ``--synthetic`` maps are never
+resized and keep their own spacings.  The backbone still sees the CSV's spacing, as in training.
+Per image a class absent from both maps is left out; one present in exactly one of them scores the image diagonal (HD95, ASSD) and 0 (NSD).
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import logging
+import sys
+from pathlib import Path
+
+import torch
+
+_HERE = Path(__file__).resolve().parent
+for _p in (_HERE.parent, _HERE):
+    if str(_p) not in sys.path:
+        sys.path.insert(0, str(_p))
+
+import finetune_lora as fl  # noqa: E402
+import finetune_segmentation as fs  # noqa: E402
+from dinox import ops, segment as SG  # noqa: E402
+
+log = logging.getLogger("evaluate_segmentation")
+
+SPACING_CONVENTION = ("mm per pixel of the evaluated label map as (s_y, s_x): the CSV's (spacing_y h / nh, spacing_x w / nw) for an h x w "
+                      "slice resized to nh x nw before the centre crop; --synthetic maps keep their own (spacing_y, spacing_x)")
+
+
+def resize_factors(h: int, w: int, size: int):
+    """(h / nh, w / nw) of finetune_segmentation._center_pair: the shorter side goes to ``size``, neither side below it."""
+    k = size / min(h, w)
+    return h / max(size, round(h * k)), w / max(size, round(w * k))
+
+
+class EvalImages(fs.MaskedImages):
+    """MaskedImages (centre crop) that also returns the spacing of the evaluated grid, (s_y, s_x) in mm per label-map pixel."""
+
+    def __getitem__(self, i: int):
+        row = self.rows[i]
+        px, m = self.pixels(row), self.read_mask(row)
+        x, m = fs.paired_transform(px[None].expand(3, -1, -1), m, self.img_size, self.gen, False)
+        fy, fx = resize_factors(px.shape[-2], px.shape[-1], self.img_size)
+        return x, torch.tensor(row.spacing, dtype=torch.float32), m, torch.tensor([row.spacing[1] * fy, row.spacing[0] * fx], dtype=torch.float32)
+
+
+class EvalSynthetic(fs.SyntheticMasks):
+    """SyntheticMasks with the (s_y, s_x) of its own spacings: the maps are generated at the evaluated size."""
+
+    def __getitem__(self, i: int):
+        x, sp, m = super().__getitem__(i)
+        return x, sp, m, torch.stack([sp[1], sp[0]])
+
+
+def build_parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(description="Dice / IoU and HD95 / ASSD / surface Dice in mm of a fine-tuned segmenter",
+                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    base = {a.dest: a for a in fl.build_parser()._actions}
+    ap._add_action(base["backbone"])
+    ap.add_argument("--segmenter", required=True, type=Path, metavar="DIR", help="output directory of finetune_segmentation.py")
+    ap._add_action(base["device"])
+    ap.add_argument("--val-csv", type=Path, default=None, help="required unless --synthetic")
+    ap.add_argument("--synthetic", type=int, default=0, metavar="N", help="the validation quarter of finetune_segmentation.py --synthetic N")
+    for dest in ("data_root", "input_format", "window_level", "window_width", "batch_size", "num_workers", "no_amp"):
+        ap._add_action(base[dest])
+    ap.add_argument("--seed", type=int, default=0, help="seed of the --synthetic set (the fine-tuning run's --seed)")
+    ap.add_argument("--tolerance-mm", type=float, action="append", default=None, metavar="MM",
+                    help="surface Dice tolerance in mm; repeatable (default: 1.0 and 2.0)")
+    ap.add_argument("--out", type=Path, default=Path("seg_eval.json"))
+    return ap
+
+
+def _floats(t: torch.Tensor):
+    """Nested lists with None for NaN (JSON has no NaN)."""
+    return [_floats(v) for v in t] if t.dim() else (None if bool(torch.isnan(t)) else float(t))
+
+
+def _mean_present(t: torch.Tensor):
+    keep = ~torch.isnan(t)
+    return float(t[keep].mean()) if bool(keep.any()) else None
+
+
+@torch.no_grad()
+def evaluate(model: SG.SegModel, loader, device, amp: bool, tolerances, num_classes: int) -> dict:
+    """One pass: the [3, C] overlap counts of the whole set and the per-class surface means.  -> the report dict (no file is written)."""
+    acc = SG.SurfaceAccumulator(num_classes, len(tolerances))
+    counts, n = None, 0
+    for x, sp, m, grid_sp in loader:
+        x, m = x.to(device), m.to(device)
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+            logits = model(x, spacing=sp.to(device) if model.scale_aware else None)
+        pred, cnt = ops.seg_predict(logits, model.patch, m)
+        counts = cnt.clone() if counts is None else counts + cnt
+        sc, sv = ops.surface_stats(pred, m, grid_sp, num_classes, tolerances=tolerances)
+        acc.update(SG.surface_metrics(sc, sv, grid_sp, tuple(m.shape[-2:])))
+        n += x.shape[0]
+    counts = counts.cpu()
+    res = acc.result()
+    dice, iou = SG.dice_per_class(counts), SG.iou_per_class(counts)
+    per_class = {"dice": _floats(dice), "iou": _floats(iou), "hd95_mm": _floats(res["hd95"]), "assd_mm": _floats(res["assd"]),
+                 "nsd": {f"{t:g}": _floats(res["nsd"][:, i]) for i, t in enumerate(tolerances)}, "surface_images": res["images"].tolist(),
+                 "overlap_images": n}
+    mean = {"dice": SG.mean_dice(counts), "iou": SG.miou(counts), "hd95_mm": _mean_present(res["hd95"]), "assd_mm": _mean_present(res["assd"]),
+            "nsd": {f"{t:g}": _mean_present(res["nsd"][:, i]) for i, t in enumerate(tolerances)},
+            "classes": int((res["images"] > 0).sum())}
+    return {"images": n, "num_classes": num_classes, "tolerances_mm": list(tolerances), "quantile": "95/100 (nearest rank)",
+            "spacing": SPACING_CONVENTION, "pixel_accuracy": SG.pixel_accuracy(counts), "per_class": per_class, "mean": mean}
+
+
+def run(args: argparse.Namespace) -> dict:
+    ap = build_parser()
+    device = torch.device(args.device)
+    if device.type != "cuda":
+        raise SystemExit(f"this engine computes on MI355X only: --device {args.device} requested (no CPU compute path)")
+    if not args.synthetic and args.val_csv is None:
+        ap.error("--val-csv is required unless --synthetic N is given")
+    if args.val_csv is not None and not args.synthetic and not Path(args.val_csv).is_file():
+        ap.error(f"--val-csv {args.val_csv}: no such file")
+    tolerances = tuple(args.tolerance_mm) if args.tolerance_mm else (1.0, 2.0)
+    if len(tolerances) > ops.SURFACE_MAX_TOLERANCES or any(not t >= 0 or t == float("inf") for t in tolerances):
+        ap.error(f"--tolerance-mm: 1 to {ops.SURFACE_MAX_TOLERANCES} finite values >= 0, got {list(tolerances)}")
+    cfg_file = Path(args.segmenter) / SG.CONFIG_FILE
+    if not cfg_file.is_file():
+        ap.error(f"--segmenter {args.segmenter}: no {SG.CONFIG_FILE} (not an output directory of finetune_segmentation.py)")
+    cfg = json.loads(cfg_file.read_text())
+    if cfg.get("task") != "segmentation":
+        ap.error(f"--segmenter {args.segmenter}: task {cfg.get('task')!r} is not 'segmentation'")
+    if not torch.cuda.is_available():
+        raise SystemExit("this engine computes on MI355X only: no CUDA/HIP device available")
+    model = SG.load_segmenter(args.backbone, args.segmenter, device)
+    C, img = cfg["num_classes"], model.img_size
+    if args.synthetic:
+        n_val = max(args.synthetic // 4, 1)
+        ds = EvalSynthetic(n_val, img, C, args.seed, first=args.synthetic - n_val, augment=False)
+        workers = 0
+    else:
+        rows = fs.read_csv(args.val_csv)
+        if not rows[0].has_spacing:
+            log.warning("the CSV has no spacing_x/y/z columns: 1 mm per source pixel is assumed, so the mm figures are in source pixels")
+        ds = EvalImages(rows, img, input_format=args.input_format, window_level=args.window_level, window_width=args.window_width,
+                        augment=False, data_root=args.data_root)
+        workers = args.num_workers
+    loader = torch.utils.data.DataLoader(ds, batch_size=args.batch_size, shuffle=False, num_workers=workers)
+    report = evaluate(model, loader, device, not args.no_amp, tolerances, C)
+    report["segmenter"], report["backbone"] = str(args.segmenter), str(args.backbone)
+    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    Path(args.out).write_text(json.dumps(report, indent=2))
+    log.info("%d images: mean Dice %.4f, HD95 %s mm, ASSD %s mm -> %s", report["images"], report["mean"]["dice"], report["mean"]["hd95_mm"],
+             report["mean"]["assd_mm"], args.out)
+    return report
+
+
+def main(argv=None) -> dict:
+    args = build_parser().parse_args(argv)
+    logging.basicConfig(level=logging.INFO, format="%(asctime)s [%(levelname)s] %(message)s", datefmt="%H:%M:%S")
+    return run(args)
+
+
+if __name__ == "__main__":
+    main()

@@ -805,6 +805,41 @@ int dinox_seg_loss_bwd(const float* z, const uint8_t* y, const float* stats, con
 int dinox_seg_predict(const float* z, const uint8_t* y, uint8_t* pred, int64_t* counts, int64_t B, int g, int u, int C, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Surface distances between two label maps, in mm (kernels: csrc/surfdist.hip; dinox.ops.surface_stats, dinox.segment.surface_metrics).
+ *   pred[B][H][W], gt[B][H][W]  uint8, dense, 1 <= H, W <= 1024 (rectangular maps are fine: nothing here knows a patch grid), B >= 1 and
+ *               B C 2 H <= 2^30.  Classes 0 .. C - 1, 2 <= C <= 64.  gt == 255 is ignore.  A pred value >= C, or a gt value >= C other
+ *               than 255, is an argument error: it belongs to no class (a label is only ever compared, never an address) and the call
+ *               COUNTS them -- bad[0] for pred, bad[1] for gt -- for the caller to refuse.
+ *   spacing[B][2]  fp32 on the device, (s_y, s_x) in mm per pixel of each image, finite and > 0.
+ *   Sets, per image b and class c:  A = {p : gt_p != 255 and pred_p = c},  G = {p : gt_p = c}; an ignored pixel is in neither.
+ *   Border dX of a set X: the pixels of X with at least one of their four edge neighbours outside X; a neighbour outside the image is
+ *               outside X (X and not binary_erosion(X) with the 4-connected cross).
+ *   d(p, Y) = min over q in Y of sqrt((s_y (p_y - q_y))^2 + (s_x (p_x - q_x))^2).
+ *   Directed surface distances: D_AG = {d(p, dG) : p in dA} (direction 0), D_GA = {d(p, dA) : p in dG} (direction 1).
+ *   Per (b, c, direction):  n = the number of border pixels on the query side; the sum and the maximum of the distances; the k-th smallest
+ *               distance, k = ceil(n q_num / q_den) in integer arithmetic (nearest rank; 0 < q_num <= q_den, e.g. 95 / 100; n = 20 gives
+ *               k = 19); for each of T tolerances tol_t (1 <= T <= 8, mm, finite, >= 0) the number of distances <= tol_t.
+ *               If either border is empty the three floats and the T tolerance counts are 0; n of the two directions says which side was.
+ *   HD95 = max of the two quantiles, HD = max of the two maxima, ASSD = (sum_AG + sum_GA) / (n_A + n_G),
+ *   NSD(tol) = (within_AG + within_GA) / (n_A + n_G) are formed by the caller (dinox.segment.surface_metrics).
+ * An exact separable distance transform: a column scan (vertical distance in pixels to the nearest border pixel of the column), a row
+ * minimum over (s_x (x - x'))^2 + (s_y d)^2 at the border pixels only, then per (b, c, direction) a reduction and a radix select on the
+ * fp32 bit patterns.  A distance is sqrt(fl(fl(s_x k)^2 + fl(s_y m)^2)), every operation rounded once: within 3 * 2^-24 of the exact
+ * one, relatively.  The sum has a fixed order (per lane, wave butterfly, per-wave partials in ascending order); maximum, counts and
+ * the select are integer work: equal inputs give equal bits, and an image's outputs do not depend on the rest of the batch.
+ * The entry checks its arguments on the host (a message before any launch), allocates nothing and does not synchronise.
+ *
+ * dinox_surface_ws_bytes: bytes of workspace, 12 B C H W (a pure function of the sizes; 0 for sizes the call refuses; contents need not
+ *   be initialised; 4-byte aligned).
+ * dinox_surface_stats: counts[B][C][2][1 + T] int64 = (n, within tol_0 .. tol_{T-1}); values[B][C][2][3] fp32 = (sum, max, quantile);
+ *   bad[2] int64, zeroed on the stream first.  tol is a HOST array of T floats, read during the call; every other pointer is a device
+ *   pointer.
+ * ------------------------------------------------------------------------------------------ */
+int64_t dinox_surface_ws_bytes(int64_t B, int H, int W, int C);
+int dinox_surface_stats(const uint8_t* pred, const uint8_t* gt, const float* spacing, const float* tol, int64_t* counts, float* values,
+                        int64_t* bad, void* ws, int64_t B, int H, int W, int C, int T, int q_num, int q_den, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-launch timing of dinox_gemm (diagnostic; bench.py's roofline object).  Between start and stop every dinox_gemm launch -- also
  * the ones dinox_block_* issue -- is counted per (kernel, shape, epilogue), and one launch in `every` (a fixed hash of the launch
  * counter) is bracketed by a HIP event pair on its stream.  stop synchronises those events and writes one text line per shape into
