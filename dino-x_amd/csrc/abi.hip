@@ -386,6 +386,50 @@ extern "C" int dinox_surface_stats(const uint8_t* pred, const uint8_t* gt, const
   return dinox::launch_surface_stats(pred, gt, spacing, tol, counts, values, bad, ws, B, H, W, C, T, q_num, q_den, dinox::as_stream(stream));
 }
 
+// ---------------------------------------------------------------- connected components of a label map (kernels: cclabel.hip)
+// B H W < 2^31: every pixel index of an image fits int32 (and 20 bits: H, W <= 1024), every batch offset int64.
+static bool cc_sizes_ok(int64_t B, int H, int W, int C) {
+  return B >= 1 && B < ((int64_t)1 << 31) && H >= 1 && H <= dinox::CC_MAX_SIDE && W >= 1 && W <= dinox::CC_MAX_SIDE && C >= 2 &&
+         C <= dinox::SEG_MAX_CLASSES && B * H * W < ((int64_t)1 << 31);
+}
+
+#define DX_CC_SIZES(what)                                                                                                                        \
+  do {                                                                                                                                           \
+    DX_REQUIRE(H >= 1 && H <= dinox::CC_MAX_SIDE && W >= 1 && W <= dinox::CC_MAX_SIDE, DINOX_EINVAL, what ": H=%d W=%d (1 <= H, W <= %d)", H, W, \
+               dinox::CC_MAX_SIDE);                                                                                                              \
+    DX_REQUIRE(C >= 2 && C <= dinox::SEG_MAX_CLASSES, DINOX_EINVAL, what ": C=%d (2 <= C <= %d)", C, dinox::SEG_MAX_CLASSES);                     \
+    DX_REQUIRE(cc_sizes_ok(B, H, W, C), DINOX_EINVAL, what ": B=%lld (B >= 1 and B H W < 2^31; cut a longer batch in pieces)", (long long)B);     \
+  } while (0)
+
+extern "C" int64_t dinox_cc_ws_bytes(int64_t B, int H, int W, int C) { return cc_sizes_ok(B, H, W, C) ? dinox::cc_ws_bytes(B, H, W, C) : 0; }
+
+extern "C" int dinox_cc_label(const uint8_t* labels, const uint8_t* mask, int32_t* comp, int32_t* area, int64_t* ncomp, int64_t* bad, void* ws, int64_t B,
+                              int H, int W, int C, int connectivity, void* stream) {
+  DX_REQUIRE(labels && comp && area && ncomp && bad && ws, DINOX_EINVAL, "cc_label: null pointer");
+  DX_CC_SIZES("cc_label");
+  DX_REQUIRE(connectivity == 4 || connectivity == 8, DINOX_EINVAL, "cc_label: connectivity=%d (4 or 8)", connectivity);
+  return dinox::launch_cc_label(labels, mask, comp, area, ncomp, bad, ws, B, H, W, C, connectivity, dinox::as_stream(stream));
+}
+
+extern "C" int dinox_cc_filter(const uint8_t* labels, const int32_t* comp, const int32_t* area, const int32_t* min_px, const uint8_t* y, uint8_t* out,
+                               int64_t* counts, void* ws, int64_t B, int H, int W, int C, int c0, int keep_largest, void* stream) {
+  DX_REQUIRE(labels && comp && area && out && ws, DINOX_EINVAL, "cc_filter: null pointer");
+  DX_REQUIRE((y == nullptr) == (counts == nullptr), DINOX_EINVAL, "cc_filter: y and counts go together (both or neither)");
+  DX_CC_SIZES("cc_filter");
+  DX_REQUIRE(c0 >= 0 && c0 <= C, DINOX_EINVAL, "cc_filter: c0=%d (0 <= c0 <= C = %d)", c0, C);
+  return dinox::launch_cc_filter(labels, comp, area, min_px, y, out, counts, ws, B, H, W, C, c0, keep_largest ? 1 : 0, dinox::as_stream(stream));
+}
+
+extern "C" int dinox_cc_match(const uint8_t* pred, const int32_t* pred_comp, const int32_t* pred_area, const uint8_t* gt, const int32_t* gt_comp,
+                              const int32_t* gt_area, const int32_t* min_px, int64_t* counts, void* ws, int64_t B, int H, int W, int C, int t_num,
+                              int t_den, void* stream) {
+  DX_REQUIRE(pred && pred_comp && pred_area && gt && gt_comp && gt_area && counts && ws, DINOX_EINVAL, "cc_match: null pointer");
+  DX_CC_SIZES("cc_match");
+  DX_REQUIRE(t_den > 0 && t_den < (1 << 20) && t_num >= 0 && t_num <= t_den, DINOX_EINVAL,
+             "cc_match: overlap %d/%d (0 <= t_num <= t_den, 0 < t_den < 2^20)", t_num, t_den);
+  return dinox::launch_cc_match(pred, pred_comp, pred_area, gt, gt_comp, gt_area, min_px, counts, ws, B, H, W, C, t_num, t_den, dinox::as_stream(stream));
+}
+
 // ---------------------------------------------------------------- LoRA low-rank products (kernels: lora.hip)
 static bool lora_rank_ok(int r) { return r >= 1 && r <= dinox::LORA_MAX_RANK; }
 static bool lora_dim_ok(int d) { return d >= 1 && d <= (1 << 20); }

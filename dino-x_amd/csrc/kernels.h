@@ -152,6 +152,17 @@ int64_t surface_ws_bytes(int64_t B, int H, int W, int C);
 int launch_surface_stats(const uint8_t* pred, const uint8_t* gt, const float* spacing, const float* tol, int64_t* counts, float* values, int64_t* bad,
                          void* ws, int64_t B, int H, int W, int C, int T, int q_num, int q_den, hipStream_t st);
 
+// ---------------------------------------------------------------- connected components of a label map (cclabel.hip; entry points and argument checks: abi.hip)
+constexpr int CC_MAX_SIDE = 1024;          // a root index y W + x and an area both fit 20 bits beside each other in the 64-bit tie key
+int64_t cc_ws_bytes(int64_t B, int H, int W, int C);
+int launch_cc_label(const uint8_t* labels, const uint8_t* mask, int32_t* comp, int32_t* area, int64_t* ncomp, int64_t* bad, void* ws, int64_t B, int H,
+                    int W, int C, int conn, hipStream_t st);
+int launch_cc_filter(const uint8_t* labels, const int32_t* comp, const int32_t* area, const int32_t* min_px, const uint8_t* y, uint8_t* out,
+                     int64_t* counts, void* ws, int64_t B, int H, int W, int C, int c0, int keep_largest, hipStream_t st);
+int launch_cc_match(const uint8_t* pred, const int32_t* pred_comp, const int32_t* pred_area, const uint8_t* gt, const int32_t* gt_comp,
+                    const int32_t* gt_area, const int32_t* min_px, int64_t* counts, void* ws, int64_t B, int H, int W, int C, int t_num, int t_den,
+                    hipStream_t st);
+
 // ---------------------------------------------------------------- launch glue shared by the NT launchers
 // Activation index of the <OUT, ACT, RES> kernels (gemm_bf16_pp / _pp128 / _areg): the template argument ACT.
 enum { EPI_ACT_PLAIN = 0, EPI_ACT_GELU = 1, EPI_ACT_DGELU = 2 };

@@ -150,7 +150,11 @@ SIGNATURES = {
     "dinox_seg_predict": (i32, [vp, vp, vp, vp, i64, i32, i32, i32, vp]),
     "dinox_surface_ws_bytes": (i64, [i64, i32, i32, i32]),
     "dinox_surface_stats": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp]),
-    "dinox_attention_rows_ok": (i32, [i32, i32, i32, i32, i32]),
+    "dinox_cc_ws_bytes": (i64, [i64, i32, i32, i32]),
+    "dinox_cc_label": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp]),
+    "dinox_cc_filter": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp]),
+    "dinox_cc_match": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp]),
+    "dinox_attention_rows_ok":(i32, [i32, i32, i32, i32, i32]),
     "dinox_attention_rows": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "dinox_attention_rollout_step_ok": (i32, [i32, i32, i32, i32]),
     "dinox_attention_rollout_step": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp]),

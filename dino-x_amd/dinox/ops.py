@@ -3146,3 +3146,177 @@ def surface_stats(pred: Tensor, labels: Tensor, spacing, num_classes: int, toler
     if nbad[0] or nbad[1]:
         raise ValueError(f"surface_stats: {nbad[0]} value(s) of pred are >= C = {C}, {nbad[1]} label(s) are >= C and not {SEG_IGNORE} (ignore)")
     return counts, values
+
+
+# ------------------------------------------------------------------------------------------
+# connected components of a label map: labelling, clean-up, lesion-wise counts (csrc/cclabel.hip)
+# ------------------------------------------------------------------------------------------
+CC_MAX_SIDE = 1024
+CC_WS_CAP = 256 << 20           # bytes of workspace per call: a longer batch is labelled in pieces (images are independent)
+
+
+def _cc_int(v) -> bool:
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+def _cc_maps(fn: str, named, num_classes, connectivity):
+    """(B, H, W) of uint8 maps [B, H, W] of one shape on one device (``named``: (name, tensor or None) pairs; None is skipped);
+    ValueError for anything the kernels do not take."""
+    first = None
+    for what, t in named:
+        if t is None:
+            continue
+        if not isinstance(t, Tensor) or t.dtype != torch.uint8 or t.dim() != 3:
+            raise ValueError(f"{fn}: {what} must be uint8 [B, H, W], got {_describe(t)}")
+        if first is None:
+            first = (what, t)
+        elif t.shape != first[1].shape:
+            raise ValueError(f"{fn}: {first[0]} {tuple(first[1].shape)} and {what} {tuple(t.shape)} differ in shape")
+        elif t.device != first[1].device:
+            raise ValueError(f"{fn}: {first[0]} on {first[1].device}, {what} on {t.device}")
+    B, H, W = first[1].shape
+    if B < 1 or not (1 <= H <= CC_MAX_SIDE and 1 <= W <= CC_MAX_SIDE):
+        raise ValueError(f"{fn}: maps must be [B >= 1, H, W] with 1 <= H, W <= {CC_MAX_SIDE}, got {tuple(first[1].shape)}")
+    if not _cc_int(num_classes) or not 2 <= num_classes <= SEG_MAX_CLASSES:
+        raise ValueError(f"{fn}: num_classes must be an integer in [2, {SEG_MAX_CLASSES}], got {num_classes!r}")
+    if not _cc_int(connectivity) or connectivity not in (4, 8):
+        raise ValueError(f"{fn}: connectivity must be 4 or 8, got {connectivity!r}")
+    return B, H, W
+
+
+def _cc_min_px(fn: str, min_px, B: int):
+    """None, one integer or B integers (a sequence or an integer tensor), each in [0, 2^31) -> None or an int32 tensor [B] on the host."""
+    if min_px is None:
+        return None
+    if _cc_int(min_px):
+        min_px = [min_px] * B
+    t = min_px if isinstance(min_px, Tensor) else None
+    if t is None:
+        try:
+            vals = list(min_px)
+        except TypeError as e:
+            raise ValueError(f"{fn}: min_px must be None, an integer or {B} integers, got {min_px!r}") from e
+        if not all(_cc_int(v) for v in vals):
+            raise ValueError(f"{fn}: min_px must be None, an integer or {B} integers, got {min_px!r}")
+        if len(vals) != B or not all(0 <= v < 1 << 31 for v in vals):
+            raise ValueError(f"{fn}: min_px must hold {B} value(s) in [0, 2^31), got {min_px!r}")
+        return torch.tensor(vals, dtype=torch.int32)
+    if t.dtype not in (torch.int32, torch.int64) or tuple(t.shape) != (B,):
+        raise ValueError(f"{fn}: min_px must be None, an integer or {B} integers, got {_describe(t)}")
+    if not bool(((t >= 0) & (t < 1 << 31)).all()):
+        raise ValueError(f"{fn}: min_px must hold {B} value(s) in [0, 2^31)")
+    return t.to(torch.int32)
+
+
+def _cc_step(B: int, H: int, W: int, C: int) -> int:
+    """Images per call: the workspace under CC_WS_CAP (one image may exceed it) and the sizes inside what the entries take."""
+    step = max(1, min(B, CC_WS_CAP // int(lib.dinox_cc_ws_bytes(1, H, W, C))))
+    while step > 1 and not lib.dinox_cc_ws_bytes(step, H, W, C):
+        step //= 2
+    return step
+
+
+def _cc_ws(step: int, H: int, W: int, C: int, dev) -> Tensor:
+    return torch.empty(int(lib.dinox_cc_ws_bytes(step, H, W, C)) // 8, dtype=torch.int64, device=dev)
+
+
+def _cc_label_into(labels, mask, C, conn, ws, step):
+    """(comp, area, ncomp, bad [chunks]) of contiguous device maps, nothing read back."""
+    B, H, W = labels.shape
+    dev = labels.device
+    comp = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+    area = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+    ncomp = torch.empty((B, C), dtype=torch.int64, device=dev)
+    bad = torch.zeros(-(-B // step), dtype=torch.int64, device=dev)
+    for i, b0 in enumerate(range(0, B, step)):
+        check(lib.dinox_cc_label(_p(labels[b0:]), None if mask is None else _p(mask[b0:]), _p(comp[b0:]), _p(area[b0:]), _p(ncomp[b0:]), _p(bad[i:]),
+                                 _p(ws), min(step, B - b0), H, W, C, conn, _stream()), "dinox_cc_label")
+    return comp, area, ncomp, bad
+
+
+def _cc_refuse(fn: str, what: str, bad: int, C: int) -> None:
+    if bad:
+        raise ValueError(f"{fn}: {bad} value(s) of {what} are >= C = {C} and not {SEG_IGNORE}")
+
+
+def cc_label(labels: Tensor, num_classes: int, connectivity: int = 8, mask: Optional[Tensor] = None):
+    """Connected components of a uint8 label map [B, H, W], every class in one pass (include/dinox.h has the definitions).  Returns
+    (comp int32 [B, H, W]: the index y W + x of the component's first pixel in raster order, -1 where the pixel is in none; area int32
+    [B, H, W]: the pixel count at that root pixel, 0 elsewhere; ncomp int64 [B, C]), all on the device.  A pixel with ``mask == 255`` or
+    a label of 255 is in no component; any other label >= C raises ValueError (one device read).  ``connectivity`` 4 joins pixels that
+    share an edge, 8 also those that share a corner.  The batch is cut so that one call's workspace stays under CC_WS_CAP; the results
+    do not depend on the cut."""
+    B, H, W = _cc_maps("cc_label", (("labels", labels), ("mask", mask)), num_classes, connectivity)
+    _need_cuda(labels, mask)
+    labels, mask = _c(labels), None if mask is None else _c(mask)
+    step = _cc_step(B, H, W, num_classes)
+    comp, area, ncomp, bad = _cc_label_into(labels, mask, num_classes, connectivity, _cc_ws(step, H, W, num_classes, labels.device), step)
+    _cc_refuse("cc_label", "labels", int(bad.sum()), num_classes)
+    return comp, area, ncomp
+
+
+def cc_filter(labels: Tensor, num_classes: int, *, min_px=None, keep_largest: bool = False, first_class: int = 1, connectivity: int = 8,
+              mask: Optional[Tensor] = None, targets: Optional[Tensor] = None):
+    """Clean-up of a uint8 label map [B, H, W]: ``out`` equals ``labels`` where the pixel's component is kept and is 0 elsewhere.  Classes
+    below ``first_class`` are always kept; a component of another class is kept iff its area >= min_px[b] (None: 1; one integer or B of
+    them) and, with ``keep_largest``, it is the largest of its (image, class) -- equal areas: the one whose first pixel comes first.
+    With ``targets`` (uint8, 255 = ignore) returns (out, counts int64 [3, C]) with ops.seg_predict's counts of ``out`` against them.
+    Labels internally (``connectivity``, ``mask``: see cc_label); bad values raise ValueError after one device read."""
+    B, H, W = _cc_maps("cc_filter", (("labels", labels), ("mask", mask), ("targets", targets)), num_classes, connectivity)
+    C = num_classes
+    if not _cc_int(first_class) or not 0 <= first_class <= C:
+        raise ValueError(f"cc_filter: first_class must be an integer in [0, {C}], got {first_class!r}")
+    if not isinstance(keep_largest, (bool, int)):
+        raise ValueError(f"cc_filter: keep_largest must be a bool, got {keep_largest!r}")
+    mp = _cc_min_px("cc_filter", min_px, B)
+    _need_cuda(labels, mask, targets)
+    dev = labels.device
+    labels, mask, targets = _c(labels), None if mask is None else _c(mask), None if targets is None else _c(targets)
+    mp = None if mp is None else mp.to(dev)
+    step = _cc_step(B, H, W, C)
+    ws = _cc_ws(step, H, W, C, dev)
+    comp, area, _, bad = _cc_label_into(labels, mask, C, connectivity, ws, step)
+    out = torch.empty_like(labels)
+    counts = None if targets is None else torch.empty((-(-B // step), 3 * C + 1), dtype=torch.int64, device=dev)
+    for i, b0 in enumerate(range(0, B, step)):
+        check(lib.dinox_cc_filter(_p(labels[b0:]), _p(comp[b0:]), _p(area[b0:]), None if mp is None else _p(mp[b0:]),
+                                  None if targets is None else _p(targets[b0:]), _p(out[b0:]), None if counts is None else _p(counts[i]), _p(ws),
+                                  min(step, B - b0), H, W, C, first_class, int(bool(keep_largest)), _stream()), "dinox_cc_filter")
+    if counts is None:
+        _cc_refuse("cc_filter", "labels", int(bad.sum()), C)
+        return out
+    counts = counts.sum(0)
+    nbad = torch.stack([bad.sum(), counts[3 * C]]).tolist()
+    _cc_refuse("cc_filter", "labels", nbad[0], C)
+    _seg_refuse_bad_labels("cc_filter", nbad[1], C)
+    return out, counts[:3 * C].view(3, C)
+
+
+def lesion_counts(pred: Tensor, labels: Tensor, num_classes: int, *, connectivity: int = 8, overlap=(0, 1), min_px=None) -> Tensor:
+    """Lesion-wise detection counts of a prediction against a ground truth, both uint8 [B, H, W] (labels: 255 = ignore):
+    int64 [B, C, 4] = (n_gt, n_gt_hit, n_pred, n_pred_hit) on the device.  The components of ``pred`` are taken over the pixels
+    ``labels`` does not ignore.  A component is hit iff the pixels of it where pred == labels number >= 1 and >= overlap[0] / overlap[1]
+    of its area (integers, 0 <= num <= den < 2^20; (0, 1): any overlap).  Components under min_px[b] pixels are no lesions on their side.
+    dinox.segment.lesion_metrics turns the counts into sensitivity, precision, F1 and false positives per image."""
+    B, H, W = _cc_maps("lesion_counts", (("pred", pred), ("labels", labels)), num_classes, connectivity)
+    C = num_classes
+    if (not isinstance(overlap, (tuple, list)) or len(overlap) != 2 or not all(_cc_int(v) for v in overlap)
+            or not (0 <= overlap[0] <= overlap[1] and 0 < overlap[1] < 1 << 20)):
+        raise ValueError(f"lesion_counts: overlap must be two integers (num, den) with 0 <= num <= den and 0 < den < 2^20, got {overlap!r}")
+    mp = _cc_min_px("lesion_counts", min_px, B)
+    _need_cuda(pred, labels)
+    dev = pred.device
+    pred, labels = _c(pred), _c(labels)
+    mp = None if mp is None else mp.to(dev)
+    step = _cc_step(B, H, W, C)
+    ws = _cc_ws(step, H, W, C, dev)
+    pc, pa, _, pbad = _cc_label_into(pred, labels, C, connectivity, ws, step)
+    gc, ga, _, gbad = _cc_label_into(labels, None, C, connectivity, ws, step)
+    counts = torch.empty((B, C, 4), dtype=torch.int64, device=dev)
+    for b0 in range(0, B, step):
+        check(lib.dinox_cc_match(_p(pred[b0:]), _p(pc[b0:]), _p(pa[b0:]), _p(labels[b0:]), _p(gc[b0:]), _p(ga[b0:]), None if mp is None else _p(mp[b0:]),
+                                 _p(counts[b0:]), _p(ws), min(step, B - b0), H, W, C, int(overlap[0]), int(overlap[1]), _stream()), "dinox_cc_match")
+    nbad = torch.stack([pbad.sum(), gbad.sum()]).tolist()
+    _cc_refuse("lesion_counts", "pred", nbad[0], C)
+    _cc_refuse("lesion_counts", "labels", nbad[1], C)
+    return counts

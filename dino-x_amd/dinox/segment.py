@@ -7,11 +7,14 @@
 The head's [B, P, C] logits are all that exists in memory; the upsampling to S = g * patch happens inside the loss / predict kernels.
 ``load_segmenter`` puts back what scripts/finetune_segmentation.py wrote.  The metric helpers take the int64 counts [3, C] of
 ``ops.seg_predict`` (true positives, predicted pixels, labelled pixels per class, over the valid pixels); ``surface_metrics`` and
-``SurfaceAccumulator`` turn ``ops.surface_stats`` (csrc/surfdist.hip) into HD95 / ASSD / surface Dice in mm.
+``SurfaceAccumulator`` turn ``ops.surface_stats`` (csrc/surfdist.hip) into HD95 / ASSD / surface Dice in mm; ``postprocess`` cleans a
+label map by connected components and ``lesion_metrics`` / ``LesionAccumulator`` turn ``ops.lesion_counts`` (csrc/cclabel.hip) into
+lesion-wise sensitivity, precision, F1 and false positives per image.
 """
 from __future__ import annotations
 
 import json
+import math
 from pathlib import Path
 from typing import Literal, Optional, Tuple, Union
 
@@ -80,10 +83,15 @@ class SegModel(nn.Module):
 
 def segment(model: SegModel, image: np.ndarray, pixel_spacing: Tuple[float, float] = (1.0, 1.0), slice_thickness: float = 1.0, *,
             input_format: Literal["hu_float", "hu16_png", "windowed_float"] = "hu_float", hu_level: float = 40.0, hu_width: float = 400.0,
-            device: Union[str, torch.device, None] = None, preprocess: Literal["host", "device", "auto"] = "host") -> np.ndarray:
+            device: Union[str, torch.device, None] = None, preprocess: Literal["host", "device", "auto"] = "host",
+            keep_largest: bool = False, min_area_mm2: float = 0.0, connectivity: int = 8) -> np.ndarray:
     """Label map of one image: uint8 (S, S) with S = model.img_size, the arg-max of the upsampled patch logits.  Preprocessing, argument
     checking and the spacing convention are those of ``zoo.encode`` (its ``_batch``), so a stored head sees what ``encode()`` sees.
-    Honours an ambient ``torch.autocast`` as ``encode`` does."""
+    Honours an ambient ``torch.autocast`` as ``encode`` does.
+
+    ``keep_largest`` / ``min_area_mm2`` > 0 clean the map with ``postprocess`` before it leaves the device (with the defaults nothing
+    changes).  The area is measured on the model's grid: ``pixel_spacing`` is (mm per source pixel along x, along y), as for ``encode``,
+    and the h x w image is resized to S x S, so a pixel of the label map is (s_y, s_x) = (pixel_spacing[1] h / S, pixel_spacing[0] w / S) mm."""
     from zoo.encode import _batch
     if device is None:
         device = next(model.parameters()).device
@@ -93,7 +101,14 @@ def segment(model: SegModel, image: np.ndarray, pixel_spacing: Tuple[float, floa
         spacing = torch.tensor([[pixel_spacing[0], pixel_spacing[1], slice_thickness]], dtype=torch.float32, device=device)
     with torch.no_grad():
         logits = model(x, spacing=spacing)
-    return ops.seg_predict(logits, model.patch)[0].cpu().numpy()
+    pred = ops.seg_predict(logits, model.patch)
+    if keep_largest or min_area_mm2 > 0:
+        arr = np.asarray(image)
+        h, w = arr.shape[1:] if arr.ndim == 3 and arr.shape[2] != 3 else arr.shape[:2]
+        S = model.img_size
+        pred = postprocess(pred, model.head.num_classes, [[pixel_spacing[1] * h / S, pixel_spacing[0] * w / S]], keep_largest=keep_largest,
+                           min_area_mm2=min_area_mm2, connectivity=connectivity)
+    return pred[0].cpu().numpy()
 
 
 # ------------------------------------------------------------------------------------------ metrics from the int64 counts [3, C]
@@ -197,6 +212,84 @@ class SurfaceAccumulator:
                               torch.full_like(s, float("nan"))) for k, s in self.sums.items()}
         out["images"] = self.images.clone()
         return out
+
+
+# ------------------------------------------------------------------------------------------ components: clean-up and lesion-wise metrics
+def min_component_px(min_area_mm2: float, spacing, B: int) -> list:
+    """min_px[b] = ceil(min_area_mm2 / (s_y s_x)) per image, in float64 on the host: the smallest pixel count whose area reaches
+    ``min_area_mm2``.  ``spacing``: [B, 2] = (s_y, s_x) in mm per pixel of the label map (one pair serves every image; None: 1 mm)."""
+    a = float(min_area_mm2)
+    if not (a >= 0 and math.isfinite(a)):
+        raise ValueError(f"min_area_mm2 must be finite and >= 0, got {min_area_mm2!r}")
+    sp = torch.ones((B, 2), dtype=torch.float64) if spacing is None else torch.as_tensor(spacing).double().cpu()
+    if sp.shape == (2,):
+        sp = sp[None].expand(B, 2)
+    if sp.shape != (B, 2) or not bool((torch.isfinite(sp) & (sp > 0)).all()):
+        raise ValueError(f"spacing must be [{B}, 2] = (s_y, s_x) in mm per pixel, finite and > 0, got {spacing!r}")
+    px = [math.ceil(a / (float(s[0]) * float(s[1]))) for s in sp]
+    if max(px) >= 1 << 31:
+        raise ValueError(f"min_area_mm2 = {a} is {max(px)} pixels at this spacing: no map is that large")
+    return px
+
+
+def postprocess(label_map: torch.Tensor, num_classes: int, spacing=None, *, keep_largest: bool = False, min_area_mm2: float = 0.0,
+                connectivity: int = 8) -> torch.Tensor:
+    """The usual clean-up of uint8 label maps [B, H, W] on the device (``ops.cc_filter``, csrc/cclabel.hip): per image and class >= 1 drop
+    the connected components under ``min_area_mm2`` and, with ``keep_largest``, every component but the largest (equal areas: the one
+    whose first pixel comes first in raster order); dropped pixels become background (0), the background itself is left alone.
+    ``spacing`` is the (s_y, s_x) mm per pixel of the label map's grid that ``surface_metrics`` takes, [B, 2] (one pair serves all
+    images, None means 1 mm): a component is kept iff its pixel count >= min_px[b] = ceil(min_area_mm2 / (s_y s_x)), computed in
+    float64 on the host, i.e. iff its area in mm^2 reaches ``min_area_mm2`` (0 removes nothing)."""
+    if not isinstance(label_map, torch.Tensor) or label_map.dim() != 3:
+        raise ValueError(f"postprocess: label_map must be uint8 [B, H, W], got {type(label_map).__name__}")
+    return ops.cc_filter(label_map, num_classes, min_px=min_component_px(min_area_mm2, spacing, label_map.shape[0]), keep_largest=keep_largest,
+                         connectivity=connectivity)
+
+
+LESION_COUNTS = ("n_gt", "n_gt_hit", "n_pred", "n_pred_hit")
+
+
+def lesion_metrics(counts, images: Optional[int] = None) -> dict:
+    """Lesion-wise detection scores from ``ops.lesion_counts``' int64 [B, C, 4] = (n_gt, n_gt_hit, n_pred, n_pred_hit): summed over the
+    images, then per class sensitivity n_gt_hit / n_gt, precision n_pred_hit / n_pred, F1 2 P R / (P + R) and false positives per image
+    (n_pred - n_pred_hit) / images, float64 [C] on the host, NaN where the denominator is 0; beside them the four summed counts (int64
+    [C]) and "images".  Counts already summed, [C, 4], need ``images``."""
+    c = torch.as_tensor(counts).cpu()
+    if c.dim() == 3 and c.shape[2] == 4 and images is None:
+        images = c.shape[0]
+    if c.dim() == 3 and c.shape[2] == 4:
+        c = c.sum(0)
+    if c.dim() != 2 or c.shape[1] != 4 or images is None or c.dtype.is_floating_point:
+        raise ValueError(f"lesion_metrics: counts must be integers [B, C, 4], or [C, 4] with images given, got {tuple(c.shape)} {c.dtype}")
+    c = c.to(torch.int64)
+    n_gt, gt_hit, n_pred, pred_hit = (c[:, i].double() for i in range(4))
+    nan = torch.full_like(n_gt, float("nan"))
+    sens = torch.where(n_gt > 0, gt_hit / n_gt.clamp(min=1), nan)
+    prec = torch.where(n_pred > 0, pred_hit / n_pred.clamp(min=1), nan)
+    den = prec + sens
+    f1 = torch.where(den > 0, 2 * prec * sens / torch.where(den > 0, den, torch.ones_like(den)), nan)
+    fp = (n_pred - pred_hit) / images if images > 0 else nan
+    out = {"sensitivity": sens, "precision": prec, "f1": f1, "fp_per_image": fp, "images": int(images)}
+    out.update({k: c[:, i].clone() for i, k in enumerate(LESION_COUNTS)})
+    return out
+
+
+class LesionAccumulator:
+    """Sums ``ops.lesion_counts`` over a stream of batches; ``result()`` is ``lesion_metrics`` of the whole set."""
+
+    def __init__(self, num_classes: int) -> None:
+        self.C, self.images = num_classes, 0
+        self.counts = torch.zeros((num_classes, 4), dtype=torch.int64)
+
+    def update(self, counts) -> None:
+        c = torch.as_tensor(counts).cpu()
+        if c.dim() != 3 or tuple(c.shape[1:]) != (self.C, 4) or c.dtype.is_floating_point:
+            raise ValueError(f"LesionAccumulator: expected integer counts [B, {self.C}, 4], got {tuple(c.shape)} {c.dtype}")
+        self.counts += c.to(torch.int64).sum(0)
+        self.images += c.shape[0]
+
+    def result(self) -> dict:
+        return lesion_metrics(self.counts, images=self.images)
 
 
 # ------------------------------------------------------------------------------------------ what finetune_segmentation.py wrote

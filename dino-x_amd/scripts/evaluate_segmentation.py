@@ -13,6 +13,13 @@ Spacing.  The boundary metrics are measured on the grid the model predicts on: t
 cropping, so a pixel of the label map is (spacing_y h / nh, spacing_x w / nw) mm, not the CSV's value; ``--synthetic`` maps are never
 resized and keep their own spacings.  The backbone still sees the CSV's spacing, as in training.
 Per image a class absent from both maps is left out; one present in exactly one of them scores the image diagonal (HD95, ASSD) and 0 (NSD).
+
+Components (csrc/cclabel.hip; all opt-in, without these flags the report is what it was).  ``--keep-largest`` / ``--min-component-mm2 A``
+clean the predicted map first (dinox.segment.postprocess's rule, the area on the evaluated grid's spacing); every score of the report is
+then taken on the cleaned map and a "postprocess" object records the settings.  ``--lesion-metrics`` adds a "lesion" object: per class and
+as means over the foreground classes that have a value, lesion-wise sensitivity, precision, F1 and false positives per image, with the
+summed counts; a lesion is a connected component (``--connectivity``) of at least ``--min-component-mm2``, hit when at least
+``--lesion-overlap`` of it (to 1/1000; 0: any pixel) is matched by the other map.
 """
 from __future__ import annotations
 
@@ -79,6 +86,15 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--tolerance-mm", type=float, action="append", default=None, metavar="MM",
                     help="surface Dice tolerance in mm; repeatable (default: 1.0 and 2.0)")
     ap.add_argument("--out", type=Path, default=Path("seg_eval.json"))
+    ap.add_argument("--lesion-metrics", action="store_true",
+                    help="add lesion-wise sensitivity, precision, F1 and false positives per image (connected components, csrc/cclabel.hip)")
+    ap.add_argument("--lesion-overlap", type=float, default=0.0, metavar="F",
+                    help="a lesion is hit when at least this fraction of it is matched (taken to 1/1000; 0: any overlap)")
+    ap.add_argument("--connectivity", type=int, choices=(4, 8), default=8, help="neighbourhood of a connected component")
+    ap.add_argument("--keep-largest", action="store_true", help="score the map with only the largest component of every class >= 1 kept")
+    ap.add_argument("--min-component-mm2", type=float, default=0.0, metavar="A",
+                    help="score the map with the components of the classes >= 1 under A mm^2 removed; with --lesion-metrics also the "
+                         "smallest ground-truth component that counts as a lesion")
     return ap
 
 
@@ -92,17 +108,38 @@ def _mean_present(t: torch.Tensor):
     return float(t[keep].mean()) if bool(keep.any()) else None
 
 
+def lesion_report(res: dict, connectivity: int, overlap, min_area_mm2: float) -> dict:
+    """The "lesion" object of the report from LesionAccumulator.result(); the means run over the foreground classes (>= 1) that have a
+    value (a class with no ground-truth lesion has no sensitivity, one never predicted no precision)."""
+    scores = ("sensitivity", "precision", "f1", "fp_per_image")
+    per_class = {k: _floats(res[k]) for k in scores}
+    per_class.update({k: res[k].tolist() for k in SG.LESION_COUNTS})
+    mean = {k: _mean_present(res[k][1:]) for k in scores}
+    mean["classes"] = int((~torch.isnan(res["f1"][1:])).sum())
+    return {"connectivity": connectivity, "overlap": f"{overlap[0]}/{overlap[1]}", "min_area_mm2": min_area_mm2, "images": res["images"],
+            "per_class": per_class, "mean": mean}
+
+
 @torch.no_grad()
-def evaluate(model: SG.SegModel, loader, device, amp: bool, tolerances, num_classes: int) -> dict:
-    """One pass: the [3, C] overlap counts of the whole set and the per-class surface means.  -> the report dict (no file is written)."""
+def evaluate(model: SG.SegModel, loader, device, amp: bool, tolerances, num_classes: int, *, lesion=None, post=None) -> dict:
+    """One pass: the [3, C] overlap counts of the whole set and the per-class surface means.  -> the report dict (no file is written).
+    ``post``: None or {"keep_largest", "min_area_mm2", "connectivity"} -- every score is then taken on the cleaned map (ops.cc_filter; the
+    area on the evaluated grid's spacing).  ``lesion``: None or {"connectivity", "overlap": (num, den), "min_area_mm2"} -- adds "lesion"."""
     acc = SG.SurfaceAccumulator(num_classes, len(tolerances))
+    les = SG.LesionAccumulator(num_classes) if lesion else None
     counts, n = None, 0
     for x, sp, m, grid_sp in loader:
         x, m = x.to(device), m.to(device)
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
             logits = model(x, spacing=sp.to(device) if model.scale_aware else None)
         pred, cnt = ops.seg_predict(logits, model.patch, m)
+        if post:
+            pred, cnt = ops.cc_filter(pred, num_classes, min_px=SG.min_component_px(post["min_area_mm2"], grid_sp, pred.shape[0]),
+                                      keep_largest=post["keep_largest"], connectivity=post["connectivity"], targets=m)
         counts = cnt.clone() if counts is None else counts + cnt
+        if lesion:
+            les.update(ops.lesion_counts(pred, m, num_classes, connectivity=lesion["connectivity"], overlap=lesion["overlap"],
+                                         min_px=SG.min_component_px(lesion["min_area_mm2"], grid_sp, pred.shape[0])))
         sc, sv = ops.surface_stats(pred, m, grid_sp, num_classes, tolerances=tolerances)
         acc.update(SG.surface_metrics(sc, sv, grid_sp, tuple(m.shape[-2:])))
         n += x.shape[0]
@@ -115,8 +152,13 @@ def evaluate(model: SG.SegModel, loader, device, amp: bool, tolerances, num_clas
     mean = {"dice": SG.mean_dice(counts), "iou": SG.miou(counts), "hd95_mm": _mean_present(res["hd95"]), "assd_mm": _mean_present(res["assd"]),
             "nsd": {f"{t:g}": _mean_present(res["nsd"][:, i]) for i, t in enumerate(tolerances)},
             "classes": int((res["images"] > 0).sum())}
-    return {"images": n, "num_classes": num_classes, "tolerances_mm": list(tolerances), "quantile": "95/100 (nearest rank)",
-            "spacing": SPACING_CONVENTION, "pixel_accuracy": SG.pixel_accuracy(counts), "per_class": per_class, "mean": mean}
+    report = {"images": n, "num_classes": num_classes, "tolerances_mm": list(tolerances), "quantile": "95/100 (nearest rank)",
+              "spacing": SPACING_CONVENTION, "pixel_accuracy": SG.pixel_accuracy(counts), "per_class": per_class, "mean": mean}
+    if post:
+        report["postprocess"] = dict(post)
+    if lesion:
+        report["lesion"] = lesion_report(les.result(), lesion["connectivity"], lesion["overlap"], lesion["min_area_mm2"])
+    return report
 
 
 def run(args: argparse.Namespace) -> dict:
@@ -131,6 +173,17 @@ def run(args: argparse.Namespace) -> dict:
     tolerances = tuple(args.tolerance_mm) if args.tolerance_mm else (1.0, 2.0)
     if len(tolerances) > ops.SURFACE_MAX_TOLERANCES or any(not t >= 0 or t == float("inf") for t in tolerances):
         ap.error(f"--tolerance-mm: 1 to {ops.SURFACE_MAX_TOLERANCES} finite values >= 0, got {list(tolerances)}")
+    if not 0.0 <= args.lesion_overlap <= 1.0:
+        ap.error(f"--lesion-overlap: a fraction in [0, 1], got {args.lesion_overlap}")
+    if not 0.0 <= args.min_component_mm2 < float("inf"):
+        ap.error(f"--min-component-mm2: a finite area >= 0, got {args.min_component_mm2}")
+    post = None
+    if args.keep_largest or args.min_component_mm2 > 0:
+        post = {"keep_largest": bool(args.keep_largest), "min_area_mm2": float(args.min_component_mm2), "connectivity": args.connectivity}
+    lesion = None
+    if args.lesion_metrics:
+        lesion = {"connectivity": args.connectivity, "overlap": (round(1000 * args.lesion_overlap), 1000),
+                  "min_area_mm2": float(args.min_component_mm2)}
     cfg_file = Path(args.segmenter) / SG.CONFIG_FILE
     if not cfg_file.is_file():
         ap.error(f"--segmenter {args.segmenter}: no {SG.CONFIG_FILE} (not an output directory of finetune_segmentation.py)")
@@ -153,7 +206,7 @@ def run(args: argparse.Namespace) -> dict:
                         augment=False, data_root=args.data_root)
         workers = args.num_workers
     loader = torch.utils.data.DataLoader(ds, batch_size=args.batch_size, shuffle=False, num_workers=workers)
-    report = evaluate(model, loader, device, not args.no_amp, tolerances, C)
+    report = evaluate(model, loader, device, not args.no_amp, tolerances, C, lesion=lesion, post=post)
     report["segmenter"], report["backbone"] = str(args.segmenter), str(args.backbone)
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     Path(args.out).write_text(json.dumps(report, indent=2))

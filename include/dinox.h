@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define DINOX_ABI_VERSION 3   /* 3: + dinox_block_forward / _backward, dinox_gemm_timer_*, dinox_retrieval_* (later also dinox_retrieval_rank_windowed*, dinox_row_dots), dinox_knn_*, dinox_gram_*, dinox_softmax_probe*, dinox_ntxent_* (later also dinox_ntxent_*_rect), dinox_normalize_bwd, dinox_mae_*, dinox_attention_rows*, dinox_attention_rollout_step*, dinox_ibot_*, dinox_gather_rows, dinox_scatter_add_rows (all additive: no entry
+#define DINOX_ABI_VERSION 3   /* 3: + dinox_block_forward / _backward, dinox_gemm_timer_*, dinox_retrieval_* (later also dinox_retrieval_rank_windowed*, dinox_row_dots), dinox_knn_*, dinox_gram_*, dinox_softmax_probe*, dinox_ntxent_* (later also dinox_ntxent_*_rect), dinox_normalize_bwd, dinox_mae_*, dinox_attention_rows*, dinox_attention_rollout_step*, dinox_ibot_*, dinox_gather_rows, dinox_scatter_add_rows, dinox_seg_*, dinox_surface_*, dinox_cc_* (all additive: no entry
                                * of an earlier library changed, so the number callers test, dinox_version() == 3, stays; probe the symbol
                                * to learn whether a given build has the later additions) */
 
@@ -838,6 +838,59 @@ int dinox_seg_predict(const float* z, const uint8_t* y, uint8_t* pred, int64_t* 
 int64_t dinox_surface_ws_bytes(int64_t B, int H, int W, int C);
 int dinox_surface_stats(const uint8_t* pred, const uint8_t* gt, const float* spacing, const float* tol, int64_t* counts, float* values,
                         int64_t* bad, void* ws, int64_t B, int H, int W, int C, int T, int q_num, int q_den, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Connected components of a label map: labelling, clean-up and lesion-wise matching (kernels: csrc/cclabel.hip; dinox.ops.cc_label,
+ * cc_filter, lesion_counts; dinox.segment.postprocess, lesion_metrics).
+ *   labels[B][H][W]  uint8, dense, 1 <= H, W <= 1024 (rectangular is fine), B >= 1 and B H W < 2^31.  Classes 0 .. C - 1, 2 <= C <= 64.
+ *   mask[B][H][W]    uint8 or NULL.  A pixel whose mask value is 255 belongs to no component (pass the ground truth to restrict a
+ *               prediction to the pixels the ground truth does not ignore: the set A of the surface-distance section).
+ *   A pixel whose label is >= C belongs to no component.  255 in labels is simply such a pixel; any other value >= C at a pixel the mask
+ *               does not exclude is an argument error, which the call COUNTS (bad[0]) for the caller to refuse: a label is only ever
+ *               compared, never an address.
+ *   Neighbours: connectivity 4, the pixels that share an edge; connectivity 8, an edge or a corner.  Two pixels are joined when they are
+ *               neighbours, both belong to a component and carry the same class value.  A component is a maximal joined set.  Every class is
+ *               labelled in the one pass, background (class 0) included.
+ *   Canonical form: comp[B][H][W] int32 = the linear index y W + x, inside its image, of the component's first pixel in raster order (its
+ *               smallest index, its ROOT), -1 where the pixel is in no component.  It is unique, so two labellings compare bit for bit.
+ *               area[B][H][W] int32 = the component's pixel count at its root pixel, 0 everywhere else.
+ *               ncomp[B][C] int64 = the number of components per image and class.
+ *   Filter: out[B][H][W] uint8 = labels where the pixel's component is kept, 0 where it is removed or the pixel is in none.  Classes below
+ *               c0 (0 <= c0 <= C; 1 keeps the background whatever its shape) are always kept.  A component of a class >= c0 is kept iff its
+ *               area >= min_px[b] and, with keep_largest != 0, it is also the largest of its (image, class).  Tie rule: of components with
+ *               equal area the one with the SMALLEST root index is the largest (one 64-bit maximum over area << 20 | (2^20 - 1 - root)).
+ *               The largest is chosen among all components of the class, whatever min_px says.  min_px: device int32 [B], or NULL for 1.
+ *               y != NULL (then counts != NULL, both or neither): counts[3 C + 1] int64 of out against y, exactly dinox_seg_predict's:
+ *               per class the true positives, the predicted pixels and the labelled pixels over the pixels with y != 255, then the
+ *               number of y values >= C other than 255 (such a pixel counts nowhere else).  Zeroed on the stream first.
+ *   Match: a prediction and a ground truth with the comp / area of each, the prediction labelled with mask = gt.  Every pixel p with
+ *               pred_p = gt_p = c inside a component on both sides adds 1 to `inter` of its pred component and of its gt component.
+ *               A component with area < min_px[b] is not a lesion on its side; its pixels still count as overlap for the other side.
+ *               Hit criterion, per component: inter >= 1 and inter t_den >= t_num area, in int64; 0 <= t_num <= t_den, 0 < t_den < 2^20;
+ *               t_num = 0: any overlap.  counts[B][C][4] int64 = (n_gt, n_gt_hit, n_pred, n_pred_hit), zeroed on the stream first.
+ *               The criterion is per component: no pair table.  Sensitivity = n_gt_hit / n_gt, precision = n_pred_hit / n_pred
+ *               (dinox.segment.lesion_metrics).
+ * Labelling is union-find with parent <= child throughout, so a root is its component's smallest index: a workgroup per 32 x 32 tile in
+ * LDS, then a launch that unites across tile edges (and corners for connectivity 8) with agent-scope atomics on the parent array, then a
+ * launch that gives every pixel its root and counts.  No loop waits for another wave: each is bounded by strictly decreasing indices or
+ * by the 64 lanes of a wave.  All of it is integer work: equal inputs give equal bits, and an image's outputs do not depend on the batch.
+ * Every entry checks its arguments on the host (a message before any launch), allocates nothing, reads nothing back and does not
+ * synchronise.
+ *
+ * dinox_cc_ws_bytes: bytes of workspace for any of the three calls, 8 B H W + 8 B C (a pure function of the sizes; 0 for sizes the calls
+ *   refuse; contents need not be initialised; 8-byte aligned).
+ * dinox_cc_label: connectivity 4 or 8; bad[1] int64, zeroed on the stream first.
+ * dinox_cc_filter: comp / area as dinox_cc_label wrote them for `labels` (same mask, same connectivity).
+ * dinox_cc_match: pred_comp / pred_area from dinox_cc_label(pred, mask = gt), gt_comp / gt_area from dinox_cc_label(gt, mask = NULL).
+ * ------------------------------------------------------------------------------------------ */
+int64_t dinox_cc_ws_bytes(int64_t B, int H, int W, int C);
+int dinox_cc_label(const uint8_t* labels, const uint8_t* mask, int32_t* comp, int32_t* area, int64_t* ncomp, int64_t* bad, void* ws, int64_t B,
+                   int H, int W, int C, int connectivity, void* stream);
+int dinox_cc_filter(const uint8_t* labels, const int32_t* comp, const int32_t* area, const int32_t* min_px, const uint8_t* y, uint8_t* out,
+                    int64_t* counts, void* ws, int64_t B, int H, int W, int C, int c0, int keep_largest, void* stream);
+int dinox_cc_match(const uint8_t* pred, const int32_t* pred_comp, const int32_t* pred_area, const uint8_t* gt, const int32_t* gt_comp,
+                   const int32_t* gt_area, const int32_t* min_px, int64_t* counts, void* ws, int64_t B, int H, int W, int C, int t_num, int t_den,
+                   void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Per-launch timing of dinox_gemm (diagnostic; bench.py's roofline object).  Between start and stop every dinox_gemm launch -- also
