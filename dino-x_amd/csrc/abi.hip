@@ -430,6 +430,52 @@ extern "C" int dinox_cc_match(const uint8_t* pred, const int32_t* pred_comp, con
   return dinox::launch_cc_match(pred, pred_comp, pred_area, gt, gt_comp, gt_area, min_px, counts, ws, B, H, W, C, t_num, t_den, dinox::as_stream(stream));
 }
 
+// ---------------------------------------------------------------- connected components of one label volume (kernels: cclabel3d.hip)
+// Z H W <= 2^30: every voxel index and every area fits int32.
+static bool cc3d_sizes_ok(int64_t Z, int H, int W, int C) {
+  return Z >= 1 && Z <= dinox::CC3D_MAX_VOXELS && H >= 1 && H <= dinox::CC_MAX_SIDE && W >= 1 && W <= dinox::CC_MAX_SIDE && C >= 2 &&
+         C <= dinox::SEG_MAX_CLASSES && Z * H * W <= dinox::CC3D_MAX_VOXELS;
+}
+
+#define DX_CC3D_SIZES(what)                                                                                                                      \
+  do {                                                                                                                                           \
+    DX_REQUIRE(H >= 1 && H <= dinox::CC_MAX_SIDE && W >= 1 && W <= dinox::CC_MAX_SIDE, DINOX_EINVAL, what ": H=%d W=%d (1 <= H, W <= %d)", H, W, \
+               dinox::CC_MAX_SIDE);                                                                                                              \
+    DX_REQUIRE(C >= 2 && C <= dinox::SEG_MAX_CLASSES, DINOX_EINVAL, what ": C=%d (2 <= C <= %d)", C, dinox::SEG_MAX_CLASSES);                     \
+    DX_REQUIRE(cc3d_sizes_ok(Z, H, W, C), DINOX_EINVAL, what ": Z=%lld (Z >= 1 and Z H W <= 2^30; label a longer series in pieces)", (long long)Z); \
+  } while (0)
+
+extern "C" int64_t dinox_cc3d_ws_bytes(int64_t Z, int H, int W, int C) { return cc3d_sizes_ok(Z, H, W, C) ? dinox::cc3d_ws_bytes(Z, H, W, C) : 0; }
+
+extern "C" int dinox_cc3d_label(const uint8_t* labels, const uint8_t* mask, int32_t* comp, int32_t* area, int64_t* ncomp, int64_t* bad, void* ws, int64_t Z,
+                                int H, int W, int C, int connectivity, void* stream) {
+  DX_REQUIRE(labels && comp && area && ncomp && bad && ws, DINOX_EINVAL, "cc3d_label: null pointer");
+  DX_CC3D_SIZES("cc3d_label");
+  DX_REQUIRE(connectivity == 6 || connectivity == 18 || connectivity == 26, DINOX_EINVAL, "cc3d_label: connectivity=%d (6, 18 or 26)", connectivity);
+  return dinox::launch_cc3d_label(labels, mask, comp, area, ncomp, bad, ws, Z, H, W, C, connectivity, dinox::as_stream(stream));
+}
+
+extern "C" int dinox_cc3d_filter(const uint8_t* labels, const int32_t* comp, const int32_t* area, int min_vox, const uint8_t* y, uint8_t* out,
+                                 int64_t* counts, void* ws, int64_t Z, int H, int W, int C, int c0, int keep_largest, void* stream) {
+  DX_REQUIRE(labels && comp && area && out && ws, DINOX_EINVAL, "cc3d_filter: null pointer");
+  DX_REQUIRE((y == nullptr) == (counts == nullptr), DINOX_EINVAL, "cc3d_filter: y and counts go together (both or neither)");
+  DX_CC3D_SIZES("cc3d_filter");
+  DX_REQUIRE(min_vox >= 0, DINOX_EINVAL, "cc3d_filter: min_vox=%d (>= 0)", min_vox);
+  DX_REQUIRE(c0 >= 0 && c0 <= C, DINOX_EINVAL, "cc3d_filter: c0=%d (0 <= c0 <= C = %d)", c0, C);
+  return dinox::launch_cc3d_filter(labels, comp, area, min_vox, y, out, counts, ws, Z, H, W, C, c0, keep_largest ? 1 : 0, dinox::as_stream(stream));
+}
+
+extern "C" int dinox_cc3d_match(const uint8_t* pred, const int32_t* pred_comp, const int32_t* pred_area, const uint8_t* gt, const int32_t* gt_comp,
+                                const int32_t* gt_area, int min_vox, int64_t* counts, void* ws, int64_t Z, int H, int W, int C, int t_num, int t_den,
+                                void* stream) {
+  DX_REQUIRE(pred && pred_comp && pred_area && gt && gt_comp && gt_area && counts && ws, DINOX_EINVAL, "cc3d_match: null pointer");
+  DX_CC3D_SIZES("cc3d_match");
+  DX_REQUIRE(min_vox >= 0, DINOX_EINVAL, "cc3d_match: min_vox=%d (>= 0)", min_vox);
+  DX_REQUIRE(t_den > 0 && t_den < (1 << 20) && t_num >= 0 && t_num <= t_den, DINOX_EINVAL,
+             "cc3d_match: overlap %d/%d (0 <= t_num <= t_den, 0 < t_den < 2^20)", t_num, t_den);
+  return dinox::launch_cc3d_match(pred, pred_comp, pred_area, gt, gt_comp, gt_area, min_vox, counts, ws, Z, H, W, C, t_num, t_den, dinox::as_stream(stream));
+}
+
 // ---------------------------------------------------------------- LoRA low-rank products (kernels: lora.hip)
 static bool lora_rank_ok(int r) { return r >= 1 && r <= dinox::LORA_MAX_RANK; }
 static bool lora_dim_ok(int d) { return d >= 1 && d <= (1 << 20); }

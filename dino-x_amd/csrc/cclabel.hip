@@ -19,90 +19,19 @@
 // wave: what other waves do can only lower parents, which shortens the walks.  No flag, no grid barrier, no host round trip, no
 // floating point: equal inputs give equal bits, and an image's outputs do not depend on what else is in the batch.
 // A label is compared with class numbers and 255 only; it indexes nothing before `< C` has been tested.
-#include "small_common.h"
-#include "kernels.h"
+//
+// The primitives (cc_find, cc_unite, cc_wave_add, cc_class) and the constants live in cc_common.h.  The launches are grouped into the stages
+// cc_run_planes / cc_run_flatten / cc_run_filter / cc_run_match, which cclabel3d.hip runs again on a volume: there the B images are the
+// slices of one array, `volume` makes launches 1 and 2 write volume-wide indices into ONE parent array, and the per-pixel stages see the
+// volume as a single array of Z H W elements.
+#include "cc_common.h"
 
 namespace dinox {
-
-constexpr int CC_TILE = 32;                        // tile side: 1024 local parents (4 KiB) + 1 KiB of classes in LDS
-constexpr int CC_TPX = CC_TILE * CC_TILE;
-constexpr int CC_THREADS = 256;                    // four pixels of a tile, or of a chunk, per thread
-constexpr int CC_CHUNK = 4 * CC_THREADS;           // pixels of one image per work item of the per-pixel kernels
-constexpr int CC_NONE = 255;                       // class of a pixel in no component
-constexpr int64_t CC_GRID_CAP = 1 << 20;           // workgroups per launch; the kernels stride over what is left
-constexpr int CC_KEY_BITS = 20;                    // root < 2^20 and area <= 2^20: area << 20 | (2^20 - 1 - root) orders "larger, then lower root"
-
-#define CC_AGENT __HIP_MEMORY_SCOPE_AGENT
-#define CC_WG __HIP_MEMORY_SCOPE_WORKGROUP
-
-template <int SCOPE>
-__device__ __forceinline__ int cc_ld(int* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, SCOPE);
-}
-template <int SCOPE>
-__device__ __forceinline__ int cc_min(int* p, int v) {
-  return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, SCOPE);
-}
-
-// Root of x, halving the path on the way (a parent is only ever replaced by a smaller member of the same component).
-// Ends: the loop runs only while p < x (unsigned: a negative p stops it too) and then x = p, so x falls strictly.
-template <int SCOPE>
-__device__ __forceinline__ int cc_find(int* L, int x) {
-  int p = cc_ld<SCOPE>(L + x);
-  while ((unsigned)p < (unsigned)x) {
-    const int gp = cc_ld<SCOPE>(L + p);
-    if ((unsigned)gp < (unsigned)p) cc_min<SCOPE>(L + x, gp);
-    x = p;
-    p = gp;
-  }
-  return x;
-}
-
-// Join the components of a and b: the larger root gets the smaller as its parent.  If another wave re-parented that root first, the
-// atomicMin returns what it wrote (old < a): L[a] is now min(old, b), and old and b are still to be joined -- the next pass.
-// Ends: a pass that does not return replaces a by old < a while b does not rise; both are >= 0.
-template <int SCOPE>
-__device__ __forceinline__ void cc_unite(int* L, int a, int b) {
-  for (;;) {
-    a = cc_find<SCOPE>(L, a);
-    b = cc_find<SCOPE>(L, b);
-    if (a == b) return;
-    if (a < b) {
-      const int t = a;
-      a = b;
-      b = t;
-    }
-    const int old = cc_min<SCOPE>(L + a, b);
-    if (old >= a) return;                           // a was still a root (old == a; parent <= child rules out old > a)
-    a = old;
-  }
-}
-
-// base[key] += the number of lanes of this wave with `todo` and this key, one atomic per distinct key.  All 64 lanes call it together.
-// Ends: uniform control flow; every pass clears at least bit `src` of rem.
-__device__ __forceinline__ void cc_wave_add(int* base, int key, bool todo) {
-  const int lane = (int)(threadIdx.x & 63);
-  unsigned long long rem = __ballot(todo);
-  while (rem) {
-    const int src = __ffsll((long long)rem) - 1;
-    const int lead = __shfl(key, src);
-    const unsigned long long m = __ballot(todo && key == lead);
-    if (lane == src) atomicAdd(base + lead, (int)__popcll(m));
-    rem &= ~m;
-  }
-}
-
-// Class of pixel i of one image: 0 .. C - 1, or CC_NONE (masked out, 255, or a bad value).
-__device__ __forceinline__ int cc_class(const uint8_t* __restrict__ lab, const uint8_t* __restrict__ msk, int64_t i, int C) {
-  if (msk && msk[i] == 255) return CC_NONE;
-  const int v = lab[i];
-  return v < C ? v : CC_NONE;
-}
 
 // ---------------------------------------------------------------- 1: union-find of one tile in LDS
 __global__ __launch_bounds__(CC_THREADS) void cc_tile_kernel(const uint8_t* __restrict__ labels, const uint8_t* __restrict__ mask, int* __restrict__ parent,
                                                              int* __restrict__ area, unsigned long long* __restrict__ bad, int H, int W, int C, int conn,
-                                                             int ntx, int nty, int64_t ntiles) {
+                                                             int volume, int ntx, int nty, int64_t ntiles) {
   __shared__ int par[CC_TPX];
   __shared__ uint8_t cls[CC_TPX];
   const int64_t hw = (int64_t)H * W;
@@ -147,7 +76,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_tile_kernel(const uint8_t* __re
       int r = -1;
       if (cls[l] != CC_NONE) {
         const int rl = cc_find<CC_WG>(par, l);
-        r = (y0 + rl / CC_TILE) * W + x0 + rl % CC_TILE;
+        r = (volume ? (int)img : 0) + (y0 + rl / CC_TILE) * W + x0 + rl % CC_TILE;   // volume: B H W <= 2^30
       }
       parent[img + (int64_t)y * W + x] = r;
     }
@@ -162,7 +91,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_tile_kernel(const uint8_t* __re
 // north, north-west and north-east neighbours and unites with those in ANOTHER tile; a pair seen from two candidate sets is united twice,
 // which changes nothing.
 __global__ __launch_bounds__(CC_THREADS) void cc_border_kernel(const uint8_t* __restrict__ labels, const uint8_t* __restrict__ mask, int* parent, int H,
-                                                               int W, int C, int conn, int nA, int nB, int per, int64_t total) {
+                                                               int W, int C, int conn, int volume, int nA, int nB, int per, int64_t total) {
   const int64_t hw = (int64_t)H * W;
   for (int64_t it = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x; it < total; it += (int64_t)gridDim.x * CC_THREADS) {
     const int64_t img = (it / per) * hw;
@@ -178,17 +107,18 @@ __global__ __launch_bounds__(CC_THREADS) void cc_border_kernel(const uint8_t* __
     }
     const uint8_t* lab = labels + img;
     const uint8_t* msk = mask ? mask + img : nullptr;
-    int* L = parent + img;
+    int* L = volume ? parent : parent + img;
     const int i = y * W + x;
+    const int g = (volume ? (int)img : 0) + i;      // the pixel as launch 1 numbered it
     const int c = cc_class(lab, msk, i, C);
     if (c == CC_NONE) continue;
     const bool w = x > 0 && cc_class(lab, msk, i - 1, C) == c, n = y > 0 && cc_class(lab, msk, i - W, C) == c;
     const bool xedge = x % CC_TILE == 0, yedge = y % CC_TILE == 0;
-    if (w && xedge) cc_unite<CC_AGENT>(L, i, i - 1);
-    if (n && yedge) cc_unite<CC_AGENT>(L, i, i - W);
+    if (w && xedge) cc_unite<CC_AGENT>(L, g, g - 1);
+    if (n && yedge) cc_unite<CC_AGENT>(L, g, g - W);
     if (conn == 8 && y > 0 && !n) {
-      if (x > 0 && !w && (xedge || yedge) && cc_class(lab, msk, i - W - 1, C) == c) cc_unite<CC_AGENT>(L, i, i - W - 1);
-      if (x + 1 < W && (x % CC_TILE == CC_TILE - 1 || yedge) && cc_class(lab, msk, i - W + 1, C) == c) cc_unite<CC_AGENT>(L, i, i - W + 1);
+      if (x > 0 && !w && (xedge || yedge) && cc_class(lab, msk, i - W - 1, C) == c) cc_unite<CC_AGENT>(L, g, g - W - 1);
+      if (x + 1 < W && (x % CC_TILE == CC_TILE - 1 || yedge) && cc_class(lab, msk, i - W + 1, C) == c) cc_unite<CC_AGENT>(L, g, g - W + 1);
     }
   }
 }
@@ -224,22 +154,24 @@ __global__ __launch_bounds__(CC_THREADS) void cc_flatten_kernel(const uint8_t* _
 
 // ---------------------------------------------------------------- filter: the largest component per (image, class), then the kept pixels
 __global__ __launch_bounds__(CC_THREADS) void cc_best_kernel(const uint8_t* __restrict__ labels, const int* __restrict__ area,
-                                                             unsigned long long* __restrict__ best, int64_t hw, int C, int c0, int64_t total) {
+                                                             unsigned long long* __restrict__ best, int64_t hw, int C, int c0, int key_bits,
+                                                             int64_t total) {
   for (int64_t g = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x; g < total; g += (int64_t)gridDim.x * CC_THREADS) {
     const int a = area[g];
     if (a <= 0) continue;                           // not a root
     const int c = labels[g];
     if (c < c0 || c >= C) continue;
     const unsigned long long root = (unsigned long long)(g % hw);
-    atomicMax(&best[(g / hw) * C + c], ((unsigned long long)a << CC_KEY_BITS) | (((1ull << CC_KEY_BITS) - 1) - root));
+    atomicMax(&best[(g / hw) * C + c], ((unsigned long long)a << key_bits) | (((1ull << key_bits) - 1) - root));
   }
 }
 
 __global__ __launch_bounds__(CC_THREADS) void cc_filter_kernel(const uint8_t* __restrict__ labels, const int* __restrict__ comp, const int* __restrict__ area,
-                                                               const int* __restrict__ min_px, const unsigned long long* __restrict__ best,
+                                                               const int* __restrict__ min_px, int min_all, const unsigned long long* __restrict__ best,
                                                                const uint8_t* __restrict__ y, uint8_t* __restrict__ out,
                                                                unsigned long long* __restrict__ counts, int64_t hw, int C, int c0, int keep_largest,
-                                                               int64_t nchunk, int64_t nitems) {
+                                                               int key_bits, int64_t nchunk, int64_t nitems) {
+  const int kmask = (int)((1ull << key_bits) - 1);  // key_bits <= 31
   constexpr int CP = SEG_MAX_CLASSES;
   __shared__ unsigned cnt[3 * CP + 1];               // true positives, predicted, labelled per class; bad values of y
   for (int64_t item = blockIdx.x; item < nitems; item += gridDim.x) {
@@ -249,7 +181,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_filter_kernel(const uint8_t* __
       for (int t = threadIdx.x; t < 3 * CP + 1; t += CC_THREADS) cnt[t] = 0;
       __syncthreads();
     }
-    const int mp = min_px ? min_px[b] : 1;
+    const int mp = min_px ? min_px[b] : min_all;
 #pragma unroll
     for (int j = 0; j < CC_CHUNK / CC_THREADS; ++j) {
       const int i = i0 + j * CC_THREADS + (int)threadIdx.x;
@@ -260,7 +192,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_filter_kernel(const uint8_t* __
         bool keep = c < c0;
         if (!keep) {
           keep = area[img + r] >= mp;
-          if (keep && keep_largest) keep = (int)(best[b * C + c] & ((1u << CC_KEY_BITS) - 1)) == (1 << CC_KEY_BITS) - 1 - r;
+          if (keep && keep_largest) keep = (int)(best[b * C + c] & (unsigned long long)kmask) == kmask - r;
         }
         o = keep ? c : 0;
       }
@@ -313,7 +245,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_inter_kernel(const uint8_t* __r
 // counts[B][C][4] = (n_gt, n_gt_hit, n_pred, n_pred_hit): roots with area >= min_px; hit: inter >= 1 and inter t_den >= t_num area.
 __global__ __launch_bounds__(CC_THREADS) void cc_count_kernel(const uint8_t* __restrict__ pred, const int* __restrict__ parea, const uint8_t* __restrict__ gt,
                                                               const int* __restrict__ garea, const int* __restrict__ ip, const int* __restrict__ ig,
-                                                              const int* __restrict__ min_px, unsigned long long* __restrict__ counts, int64_t hw, int C,
+                                                              const int* __restrict__ min_px, int min_all, unsigned long long* __restrict__ counts, int64_t hw, int C,
                                                               int t_num, int t_den, int64_t nchunk, int64_t nitems) {
   __shared__ unsigned cnt[4 * SEG_MAX_CLASSES];
   for (int64_t item = blockIdx.x; item < nitems; item += gridDim.x) {
@@ -321,7 +253,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_count_kernel(const uint8_t* __r
     const int i0 = (int)(item % nchunk) * CC_CHUNK;
     cnt[threadIdx.x] = 0;                           // 256 threads, 4 * 64 counters
     __syncthreads();
-    const int mp = min_px ? min_px[b] : 1;
+    const int mp = min_px ? min_px[b] : min_all;
 #pragma unroll
     for (int j = 0; j < CC_CHUNK / CC_THREADS; ++j) {
       const int i = i0 + j * CC_THREADS + (int)threadIdx.x;
@@ -350,79 +282,97 @@ static_assert((int64_t)CC_MAX_SIDE * CC_MAX_SIDE <= (1 << CC_KEY_BITS), "root an
 // label: parent [B][H][W] int32.  filter: best [B][C] uint64.  match: ip, ig [B][H][W] int32 each.
 int64_t cc_ws_bytes(int64_t B, int H, int W, int C) { return 8 * B * (int64_t)H * W + 8 * B * C; }
 
-static int cc_zero(void* p, int64_t bytes, hipStream_t st, const char* what) {
-  const hipError_t e = hipMemsetAsync(p, 0, (size_t)bytes, st);
-  return e == hipSuccess ? 0 : fail((int)e, "%s: hipMemsetAsync: %s", what, hipGetErrorString(e));
+static int cc_check(const char* what, const char* stage) {
+  char msg[96];
+  snprintf(msg, sizeof msg, "%s (%s)", what, stage);
+  return check_launch(msg);
 }
 
-int launch_cc_label(const uint8_t* labels, const uint8_t* mask, int32_t* comp, int32_t* area, int64_t* ncomp, int64_t* bad, void* ws, int64_t B, int H,
-                    int W, int C, int conn, hipStream_t st) {
-  const int64_t hw = (int64_t)H * W;
-  int* parent = (int*)ws;
-  int rc = cc_zero(bad, sizeof(int64_t), st, "cc_label");
-  if (rc) return rc;
-  rc = cc_zero(ncomp, B * C * (int64_t)sizeof(int64_t), st, "cc_label");
+int cc_run_planes(const uint8_t* labels, const uint8_t* mask, int* parent, int32_t* area, int64_t* bad, int64_t B, int H, int W, int C, int conn, int volume,
+                  hipStream_t st, const char* what) {
+  int rc = cc_zero(bad, sizeof(int64_t), st, what);
   if (rc) return rc;
   const int ntx = (int)ceil_div(W, CC_TILE), nty = (int)ceil_div(H, CC_TILE);
   const int64_t ntiles = B * ntx * nty;
   hipLaunchKernelGGL(cc_tile_kernel, dim3(grid_1d(ntiles, 1, CC_GRID_CAP)), dim3(CC_THREADS), 0, st, labels, mask, parent, area, (unsigned long long*)bad, H,
-                     W, C, conn, ntx, nty, ntiles);
-  rc = check_launch("cc_label (tiles)");
+                     W, C, conn, volume, ntx, nty, ntiles);
+  rc = cc_check(what, "tiles");
   if (rc) return rc;
   const int nA = (nty - 1) * W, nB = (ntx - 1) * H, per = nA + nB + (conn == 8 ? nB : 0);
   if (per > 0) {
     const int64_t total = B * per;
-    hipLaunchKernelGGL(cc_border_kernel, dim3(grid_1d(total, CC_THREADS, CC_GRID_CAP)), dim3(CC_THREADS), 0, st, labels, mask, parent, H, W, C, conn, nA, nB,
-                       per, total);
-    rc = check_launch("cc_label (borders)");
+    hipLaunchKernelGGL(cc_border_kernel, dim3(grid_1d(total, CC_THREADS, CC_GRID_CAP)), dim3(CC_THREADS), 0, st, labels, mask, parent, H, W, C, conn, volume,
+                       nA, nB, per, total);
+    rc = cc_check(what, "borders");
+  }
+  return rc;
+}
+
+int cc_run_flatten(const uint8_t* labels, int* parent, int32_t* comp, int32_t* area, int64_t* ncomp, int64_t B, int64_t n, int C, hipStream_t st,
+                   const char* what) {
+  const int64_t nchunk = ceil_div(n, CC_CHUNK), nitems = B * nchunk;
+  hipLaunchKernelGGL(cc_flatten_kernel, dim3(grid_1d(nitems, 1, CC_GRID_CAP)), dim3(CC_THREADS), 0, st, labels, parent, comp, area,
+                     (unsigned long long*)ncomp, n, C, nchunk, nitems);
+  return cc_check(what, "flatten");
+}
+
+int cc_run_filter(const uint8_t* labels, const int32_t* comp, const int32_t* area, const int32_t* min_px, int min_all, const uint8_t* y, uint8_t* out,
+                  int64_t* counts, void* ws, int64_t B, int64_t n, int C, int c0, int keep_largest, int key_bits, hipStream_t st, const char* what) {
+  unsigned long long* best = (unsigned long long*)ws;
+  int rc;
+  if (y) {
+    rc = cc_zero(counts, (3 * C + 1) * (int64_t)sizeof(int64_t), st, what);
     if (rc) return rc;
   }
-  const int64_t nchunk = ceil_div(hw, CC_CHUNK), nitems = B * nchunk;
-  hipLaunchKernelGGL(cc_flatten_kernel, dim3(grid_1d(nitems, 1, CC_GRID_CAP)), dim3(CC_THREADS), 0, st, labels, parent, comp, area,
-                     (unsigned long long*)ncomp, hw, C, nchunk, nitems);
-  return check_launch("cc_label (flatten)");
+  if (keep_largest) {
+    rc = cc_zero(best, B * C * (int64_t)sizeof(int64_t), st, what);
+    if (rc) return rc;
+    hipLaunchKernelGGL(cc_best_kernel, dim3(grid_1d(B * n, CC_THREADS, CC_GRID_CAP)), dim3(CC_THREADS), 0, st, labels, area, best, n, C, c0, key_bits, B * n);
+    rc = cc_check(what, "largest");
+    if (rc) return rc;
+  }
+  const int64_t nchunk = ceil_div(n, CC_CHUNK), nitems = B * nchunk;
+  hipLaunchKernelGGL(cc_filter_kernel, dim3(grid_1d(nitems, 1, CC_GRID_CAP)), dim3(CC_THREADS), 0, st, labels, comp, area, min_px, min_all, best, y, out,
+                     (unsigned long long*)counts, n, C, c0, keep_largest, key_bits, nchunk, nitems);
+  return check_launch(what);
+}
+
+int cc_run_match(const uint8_t* pred, const int32_t* pred_comp, const int32_t* pred_area, const uint8_t* gt, const int32_t* gt_comp, const int32_t* gt_area,
+                 const int32_t* min_px, int min_all, int64_t* counts, void* ws, int64_t B, int64_t n, int C, int t_num, int t_den, hipStream_t st,
+                 const char* what) {
+  int* ip = (int*)ws;
+  int* ig = ip + B * n;
+  int rc = cc_zero(ws, 2 * B * n * (int64_t)sizeof(int), st, what);
+  if (rc) return rc;
+  rc = cc_zero(counts, B * C * 4 * (int64_t)sizeof(int64_t), st, what);
+  if (rc) return rc;
+  const int64_t nchunk = ceil_div(n, CC_CHUNK), nitems = B * nchunk;
+  const unsigned grid = grid_1d(nitems, 1, CC_GRID_CAP);
+  hipLaunchKernelGGL(cc_inter_kernel, dim3(grid), dim3(CC_THREADS), 0, st, pred, pred_comp, gt, gt_comp, ip, ig, n, nchunk, nitems);
+  rc = cc_check(what, "overlap");
+  if (rc) return rc;
+  hipLaunchKernelGGL(cc_count_kernel, dim3(grid), dim3(CC_THREADS), 0, st, pred, pred_area, gt, gt_area, ip, ig, min_px, min_all,
+                     (unsigned long long*)counts, n, C, t_num, t_den, nchunk, nitems);
+  return cc_check(what, "counts");
+}
+
+int launch_cc_label(const uint8_t* labels, const uint8_t* mask, int32_t* comp, int32_t* area, int64_t* ncomp, int64_t* bad, void* ws, int64_t B, int H,
+                    int W, int C, int conn, hipStream_t st) {
+  int rc = cc_zero(ncomp, B * C * (int64_t)sizeof(int64_t), st, "cc_label");
+  if (rc) return rc;
+  rc = cc_run_planes(labels, mask, (int*)ws, area, bad, B, H, W, C, conn, 0, st, "cc_label");
+  return rc ? rc : cc_run_flatten(labels, (int*)ws, comp, area, ncomp, B, (int64_t)H * W, C, st, "cc_label");
 }
 
 int launch_cc_filter(const uint8_t* labels, const int32_t* comp, const int32_t* area, const int32_t* min_px, const uint8_t* y, uint8_t* out,
                      int64_t* counts, void* ws, int64_t B, int H, int W, int C, int c0, int keep_largest, hipStream_t st) {
-  const int64_t hw = (int64_t)H * W;
-  unsigned long long* best = (unsigned long long*)ws;
-  int rc;
-  if (y) {
-    rc = cc_zero(counts, (3 * C + 1) * (int64_t)sizeof(int64_t), st, "cc_filter");
-    if (rc) return rc;
-  }
-  if (keep_largest) {
-    rc = cc_zero(best, B * C * (int64_t)sizeof(int64_t), st, "cc_filter");
-    if (rc) return rc;
-    hipLaunchKernelGGL(cc_best_kernel, dim3(grid_1d(B * hw, CC_THREADS, CC_GRID_CAP)), dim3(CC_THREADS), 0, st, labels, area, best, hw, C, c0, B * hw);
-    rc = check_launch("cc_filter (largest)");
-    if (rc) return rc;
-  }
-  const int64_t nchunk = ceil_div(hw, CC_CHUNK), nitems = B * nchunk;
-  hipLaunchKernelGGL(cc_filter_kernel, dim3(grid_1d(nitems, 1, CC_GRID_CAP)), dim3(CC_THREADS), 0, st, labels, comp, area, min_px, best, y, out,
-                     (unsigned long long*)counts, hw, C, c0, keep_largest, nchunk, nitems);
-  return check_launch("cc_filter");
+  return cc_run_filter(labels, comp, area, min_px, 1, y, out, counts, ws, B, (int64_t)H * W, C, c0, keep_largest, CC_KEY_BITS, st, "cc_filter");
 }
 
 int launch_cc_match(const uint8_t* pred, const int32_t* pred_comp, const int32_t* pred_area, const uint8_t* gt, const int32_t* gt_comp,
                     const int32_t* gt_area, const int32_t* min_px, int64_t* counts, void* ws, int64_t B, int H, int W, int C, int t_num, int t_den,
                     hipStream_t st) {
-  const int64_t hw = (int64_t)H * W;
-  int* ip = (int*)ws;
-  int* ig = ip + B * hw;
-  int rc = cc_zero(ws, 2 * B * hw * (int64_t)sizeof(int), st, "cc_match");
-  if (rc) return rc;
-  rc = cc_zero(counts, B * C * 4 * (int64_t)sizeof(int64_t), st, "cc_match");
-  if (rc) return rc;
-  const int64_t nchunk = ceil_div(hw, CC_CHUNK), nitems = B * nchunk;
-  const unsigned grid = grid_1d(nitems, 1, CC_GRID_CAP);
-  hipLaunchKernelGGL(cc_inter_kernel, dim3(grid), dim3(CC_THREADS), 0, st, pred, pred_comp, gt, gt_comp, ip, ig, hw, nchunk, nitems);
-  rc = check_launch("cc_match (overlap)");
-  if (rc) return rc;
-  hipLaunchKernelGGL(cc_count_kernel, dim3(grid), dim3(CC_THREADS), 0, st, pred, pred_area, gt, gt_area, ip, ig, min_px, (unsigned long long*)counts, hw, C,
-                     t_num, t_den, nchunk, nitems);
-  return check_launch("cc_match (counts)");
+  return cc_run_match(pred, pred_comp, pred_area, gt, gt_comp, gt_area, min_px, 1, counts, ws, B, (int64_t)H * W, C, t_num, t_den, st, "cc_match");
 }
 
 }  // namespace dinox

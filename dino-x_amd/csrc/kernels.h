@@ -163,6 +163,16 @@ int launch_cc_match(const uint8_t* pred, const int32_t* pred_comp, const int32_t
                     const int32_t* gt_area, const int32_t* min_px, int64_t* counts, void* ws, int64_t B, int H, int W, int C, int t_num, int t_den,
                     hipStream_t st);
 
+// ---------------------------------------------------------------- connected components of one label volume (cclabel3d.hip on cclabel.hip's stages; abi.hip)
+constexpr int64_t CC3D_MAX_VOXELS = (int64_t)1 << 30;   // every voxel index and every area fits int32, and 31 bits of the 64-bit tie key
+int64_t cc3d_ws_bytes(int64_t Z, int H, int W, int C);
+int launch_cc3d_label(const uint8_t* labels, const uint8_t* mask, int32_t* comp, int32_t* area, int64_t* ncomp, int64_t* bad, void* ws, int64_t Z, int H,
+                      int W, int C, int conn, hipStream_t st);
+int launch_cc3d_filter(const uint8_t* labels, const int32_t* comp, const int32_t* area, int min_vox, const uint8_t* y, uint8_t* out, int64_t* counts,
+                       void* ws, int64_t Z, int H, int W, int C, int c0, int keep_largest, hipStream_t st);
+int launch_cc3d_match(const uint8_t* pred, const int32_t* pred_comp, const int32_t* pred_area, const uint8_t* gt, const int32_t* gt_comp,
+                      const int32_t* gt_area, int min_vox, int64_t* counts, void* ws, int64_t Z, int H, int W, int C, int t_num, int t_den, hipStream_t st);
+
 // ---------------------------------------------------------------- launch glue shared by the NT launchers
 // Activation index of the <OUT, ACT, RES> kernels (gemm_bf16_pp / _pp128 / _areg): the template argument ACT.
 enum { EPI_ACT_PLAIN = 0, EPI_ACT_GELU = 1, EPI_ACT_DGELU = 2 };

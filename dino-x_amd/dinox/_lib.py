@@ -154,6 +154,10 @@ SIGNATURES = {
     "dinox_cc_label": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp]),
     "dinox_cc_filter": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp]),
     "dinox_cc_match": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp]),
+    "dinox_cc3d_ws_bytes": (i64, [i64, i32, i32, i32]),
+    "dinox_cc3d_label": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp]),
+    "dinox_cc3d_filter": (i32, [vp, vp, vp, i32, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp]),
+    "dinox_cc3d_match": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, vp, i64, i32, i32, i32, i32, i32, vp]),
     "dinox_attention_rows_ok":(i32, [i32, i32, i32, i32, i32]),
     "dinox_attention_rows": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "dinox_attention_rollout_step_ok": (i32, [i32, i32, i32, i32]),

@@ -3153,21 +3153,23 @@ def surface_stats(pred: Tensor, labels: Tensor, spacing, num_classes: int, toler
 # ------------------------------------------------------------------------------------------
 CC_MAX_SIDE = 1024
 CC_WS_CAP = 256 << 20           # bytes of workspace per call: a longer batch is labelled in pieces (images are independent)
+CC3D_MAX_VOXELS = 1 << 30       # one volume is labelled whole: every voxel index and every area fits int32
 
 
 def _cc_int(v) -> bool:
     return isinstance(v, int) and not isinstance(v, bool)
 
 
-def _cc_maps(fn: str, named, num_classes, connectivity):
+def _cc_maps(fn: str, named, num_classes, connectivity, volume: bool = False):
     """(B, H, W) of uint8 maps [B, H, W] of one shape on one device (``named``: (name, tensor or None) pairs; None is skipped);
-    ValueError for anything the kernels do not take."""
+    ValueError for anything the kernels do not take.  ``volume``: (Z, H, W) of one volume [Z, H, W] and its connectivities."""
+    lead, conns, said = ("Z", (6, 18, 26), "6, 18 or 26") if volume else ("B", (4, 8), "4 or 8")
     first = None
     for what, t in named:
         if t is None:
             continue
         if not isinstance(t, Tensor) or t.dtype != torch.uint8 or t.dim() != 3:
-            raise ValueError(f"{fn}: {what} must be uint8 [B, H, W], got {_describe(t)}")
+            raise ValueError(f"{fn}: {what} must be uint8 [{lead}, H, W], got {_describe(t)}")
         if first is None:
             first = (what, t)
         elif t.shape != first[1].shape:
@@ -3176,11 +3178,13 @@ def _cc_maps(fn: str, named, num_classes, connectivity):
             raise ValueError(f"{fn}: {first[0]} on {first[1].device}, {what} on {t.device}")
     B, H, W = first[1].shape
     if B < 1 or not (1 <= H <= CC_MAX_SIDE and 1 <= W <= CC_MAX_SIDE):
-        raise ValueError(f"{fn}: maps must be [B >= 1, H, W] with 1 <= H, W <= {CC_MAX_SIDE}, got {tuple(first[1].shape)}")
+        raise ValueError(f"{fn}: maps must be [{lead} >= 1, H, W] with 1 <= H, W <= {CC_MAX_SIDE}, got {tuple(first[1].shape)}")
+    if volume and B * H * W > CC3D_MAX_VOXELS:
+        raise ValueError(f"{fn}: a volume holds at most 2^30 voxels, got {tuple(first[1].shape)}")
     if not _cc_int(num_classes) or not 2 <= num_classes <= SEG_MAX_CLASSES:
         raise ValueError(f"{fn}: num_classes must be an integer in [2, {SEG_MAX_CLASSES}], got {num_classes!r}")
-    if not _cc_int(connectivity) or connectivity not in (4, 8):
-        raise ValueError(f"{fn}: connectivity must be 4 or 8, got {connectivity!r}")
+    if not _cc_int(connectivity) or connectivity not in conns:
+        raise ValueError(f"{fn}: connectivity must be {said}, got {connectivity!r}")
     return B, H, W
 
 
@@ -3319,4 +3323,105 @@ def lesion_counts(pred: Tensor, labels: Tensor, num_classes: int, *, connectivit
     nbad = torch.stack([pbad.sum(), gbad.sum()]).tolist()
     _cc_refuse("lesion_counts", "pred", nbad[0], C)
     _cc_refuse("lesion_counts", "labels", nbad[1], C)
+    return counts
+
+
+# ------------------------------------------------------------------------------------------
+# connected components of one label volume (csrc/cclabel3d.hip on the stages of csrc/cclabel.hip)
+# ------------------------------------------------------------------------------------------
+def _cc3d_min_vox(fn: str, min_vox) -> int:
+    if min_vox is None:
+        return 1
+    if not _cc_int(min_vox) or not 0 <= min_vox < 1 << 31:
+        raise ValueError(f"{fn}: min_vox must be None or an integer in [0, 2^31), got {min_vox!r}")
+    return min_vox
+
+
+def _cc3d_ws(Z: int, H: int, W: int, C: int, dev) -> Tensor:
+    return torch.empty(int(lib.dinox_cc3d_ws_bytes(Z, H, W, C)) // 8, dtype=torch.int64, device=dev)
+
+
+def _cc3d_label_into(volume, mask, C, conn, ws):
+    """(comp, area, ncomp, bad [1]) of a contiguous device volume, nothing read back."""
+    Z, H, W = volume.shape
+    dev = volume.device
+    comp = torch.empty((Z, H, W), dtype=torch.int32, device=dev)
+    area = torch.empty((Z, H, W), dtype=torch.int32, device=dev)
+    ncomp = torch.empty(C, dtype=torch.int64, device=dev)
+    bad = torch.zeros(1, dtype=torch.int64, device=dev)
+    check(lib.dinox_cc3d_label(_p(volume), None if mask is None else _p(mask), _p(comp), _p(area), _p(ncomp), _p(bad), _p(ws), Z, H, W, C, conn,
+                               _stream()), "dinox_cc3d_label")
+    return comp, area, ncomp, bad
+
+
+def cc_label_3d(volume: Tensor, num_classes: int, connectivity: int = 26, mask: Optional[Tensor] = None):
+    """Connected components of ONE uint8 label volume [Z, H, W], every class in one pass (include/dinox.h has the definitions).  Returns
+    (comp int32 [Z, H, W]: the index (z H + y) W + x of the component's first voxel in raster order, -1 where the voxel is in none; area
+    int32 [Z, H, W]: the voxel count at that root, 0 elsewhere; ncomp int64 [C]), all on the device.  A voxel with ``mask == 255`` or a
+    label of 255 is in no component; any other label >= C raises ValueError (one device read).  ``connectivity`` 6 joins voxels that share
+    a face, 18 also those that share an edge, 26 also those that share a corner.  At most 2^30 voxels, 1 <= H, W <= 1024."""
+    Z, H, W = _cc_maps("cc_label_3d", (("volume", volume), ("mask", mask)), num_classes, connectivity, volume=True)
+    _need_cuda(volume, mask)
+    volume, mask = _c(volume), None if mask is None else _c(mask)
+    comp, area, ncomp, bad = _cc3d_label_into(volume, mask, num_classes, connectivity, _cc3d_ws(Z, H, W, num_classes, volume.device))
+    _cc_refuse("cc_label_3d", "volume", int(bad.sum()), num_classes)
+    return comp, area, ncomp
+
+
+def cc_filter_3d(volume: Tensor, num_classes: int, *, min_vox=None, keep_largest: bool = False, first_class: int = 1, connectivity: int = 26,
+                 mask: Optional[Tensor] = None, targets: Optional[Tensor] = None):
+    """Clean-up of one uint8 label volume [Z, H, W]: ``out`` equals ``volume`` where the voxel's component is kept and is 0 elsewhere.
+    Classes below ``first_class`` are always kept; a component of another class is kept iff its voxel count >= min_vox (None: 1) and,
+    with ``keep_largest``, it is the largest of its class in the whole volume -- equal counts: the one whose first voxel comes first.
+    With ``targets`` (uint8, 255 = ignore) returns (out, counts int64 [3, C]) with ops.seg_predict's counts of ``out`` against them.
+    Labels internally (``connectivity``, ``mask``: see cc_label_3d); bad values raise ValueError after one device read."""
+    Z, H, W = _cc_maps("cc_filter_3d", (("volume", volume), ("mask", mask), ("targets", targets)), num_classes, connectivity, volume=True)
+    C = num_classes
+    if not _cc_int(first_class) or not 0 <= first_class <= C:
+        raise ValueError(f"cc_filter_3d: first_class must be an integer in [0, {C}], got {first_class!r}")
+    if not isinstance(keep_largest, (bool, int)):
+        raise ValueError(f"cc_filter_3d: keep_largest must be a bool, got {keep_largest!r}")
+    mv = _cc3d_min_vox("cc_filter_3d", min_vox)
+    _need_cuda(volume, mask, targets)
+    dev = volume.device
+    volume, mask, targets = _c(volume), None if mask is None else _c(mask), None if targets is None else _c(targets)
+    ws = _cc3d_ws(Z, H, W, C, dev)
+    comp, area, _, bad = _cc3d_label_into(volume, mask, C, connectivity, ws)
+    out = torch.empty_like(volume)
+    counts = None if targets is None else torch.empty(3 * C + 1, dtype=torch.int64, device=dev)
+    check(lib.dinox_cc3d_filter(_p(volume), _p(comp), _p(area), mv, None if targets is None else _p(targets), _p(out),
+                                None if counts is None else _p(counts), _p(ws), Z, H, W, C, first_class, int(bool(keep_largest)), _stream()),
+          "dinox_cc3d_filter")
+    if counts is None:
+        _cc_refuse("cc_filter_3d", "volume", int(bad.sum()), C)
+        return out
+    nbad = torch.stack([bad.sum(), counts[3 * C]]).tolist()
+    _cc_refuse("cc_filter_3d", "volume", nbad[0], C)
+    _seg_refuse_bad_labels("cc_filter_3d", nbad[1], C)
+    return out, counts[:3 * C].view(3, C)
+
+
+def lesion_counts_3d(pred: Tensor, labels: Tensor, num_classes: int, *, connectivity: int = 26, overlap=(0, 1), min_vox=None) -> Tensor:
+    """Lesion-wise detection counts of one predicted volume against its ground truth, both uint8 [Z, H, W] (labels: 255 = ignore):
+    int64 [C, 4] = (n_gt, n_gt_hit, n_pred, n_pred_hit) on the device, a lesion being a 3-D component.  The components of ``pred`` are taken
+    over the voxels ``labels`` does not ignore.  The hit rule and ``overlap`` are lesion_counts'; components under ``min_vox`` voxels are
+    no lesions on their side.  dinox.segment.CaseAccumulator sums the counts over cases."""
+    Z, H, W = _cc_maps("lesion_counts_3d", (("pred", pred), ("labels", labels)), num_classes, connectivity, volume=True)
+    C = num_classes
+    if (not isinstance(overlap, (tuple, list)) or len(overlap) != 2 or not all(_cc_int(v) for v in overlap)
+            or not (0 <= overlap[0] <= overlap[1] and 0 < overlap[1] < 1 << 20)):
+        raise ValueError(f"lesion_counts_3d: overlap must be two integers (num, den) with 0 <= num <= den and 0 < den < 2^20, got {overlap!r}")
+    mv = _cc3d_min_vox("lesion_counts_3d", min_vox)
+    _need_cuda(pred, labels)
+    dev = pred.device
+    pred, labels = _c(pred), _c(labels)
+    ws = _cc3d_ws(Z, H, W, C, dev)
+    pc, pa, _, pbad = _cc3d_label_into(pred, labels, C, connectivity, ws)
+    gc, ga, _, gbad = _cc3d_label_into(labels, None, C, connectivity, ws)
+    counts = torch.empty((C, 4), dtype=torch.int64, device=dev)
+    check(lib.dinox_cc3d_match(_p(pred), _p(pc), _p(pa), _p(labels), _p(gc), _p(ga), mv, _p(counts), _p(ws), Z, H, W, C, int(overlap[0]),
+                               int(overlap[1]), _stream()), "dinox_cc3d_match")
+    nbad = torch.stack([pbad.sum(), gbad.sum()]).tolist()
+    _cc_refuse("lesion_counts_3d", "pred", nbad[0], C)
+    _cc_refuse("lesion_counts_3d", "labels", nbad[1], C)
     return counts

@@ -9,7 +9,9 @@ The head's [B, P, C] logits are all that exists in memory; the upsampling to S =
 ``ops.seg_predict`` (true positives, predicted pixels, labelled pixels per class, over the valid pixels); ``surface_metrics`` and
 ``SurfaceAccumulator`` turn ``ops.surface_stats`` (csrc/surfdist.hip) into HD95 / ASSD / surface Dice in mm; ``postprocess`` cleans a
 label map by connected components and ``lesion_metrics`` / ``LesionAccumulator`` turn ``ops.lesion_counts`` (csrc/cclabel.hip) into
-lesion-wise sensitivity, precision, F1 and false positives per image.
+lesion-wise sensitivity, precision, F1 and false positives per image.  For a whole series: ``segment_volume`` (one trip to the device,
+the chunk loop of ``zoo.encode.encode_volume``), ``postprocess_volume`` and ``ops.lesion_counts_3d`` on 3-D components
+(csrc/cclabel3d.hip), ``resample_labels_nearest`` for the ground truth and ``CaseAccumulator`` for per-case scores.
 """
 from __future__ import annotations
 
@@ -109,6 +111,36 @@ def segment(model: SegModel, image: np.ndarray, pixel_spacing: Tuple[float, floa
         pred = postprocess(pred, model.head.num_classes, [[pixel_spacing[1] * h / S, pixel_spacing[0] * w / S]], keep_largest=keep_largest,
                            min_area_mm2=min_area_mm2, connectivity=connectivity)
     return pred[0].cpu().numpy()
+
+
+def segment_volume(model: SegModel, volume: np.ndarray, spacing: Tuple[float, float, float] = (1.0, 1.0, 1.0), *,
+                   input_format: Literal["hu_float", "hu16_png", "windowed_float"] = "hu_float", hu_level: float = 40.0, hu_width: float = 400.0,
+                   context: Literal["neighbours", "replicate"] = "neighbours", batch_size: int = 64,
+                   device: Union[str, torch.device, None] = None, keep_largest: bool = False, min_volume_mm3: float = 0.0,
+                   connectivity: int = 26) -> np.ndarray:
+    """Label volume of a ``(Z, H, W)`` series: uint8 (Z, S, S) with S = model.img_size.  The volume crosses to the device once and is
+    preprocessed and forwarded in chunks of ``batch_size`` slices exactly as ``zoo.encode.encode_volume`` does it (``context``: the 2.5D
+    stack of a slice); every chunk's patch logits go through ``ops.seg_predict`` into one device buffer, which is copied back once.
+    ``spacing = (sx, sy, sz)`` in mm holds for the whole series.  Honours an ambient ``torch.autocast`` as ``segment`` does.
+
+    ``keep_largest`` / ``min_volume_mm3`` > 0 clean the volume with ``postprocess_volume`` (3-D components, ``connectivity`` 6, 18 or 26)
+    before it leaves the device.  The voxel of the label grid follows ``segment``'s convention: the h x w planes are resized to S x S, so
+    it measures (s_z, s_y, s_x) = (spacing[2], spacing[1] h / S, spacing[0] w / S) mm."""
+    from zoo.encode import forward_volume_chunks
+    min_component_vox(min_volume_mm3)               # refuses a negative or non-finite volume before any work is done
+    if connectivity not in (6, 18, 26):
+        raise ValueError(f"segment_volume: connectivity must be 6, 18 or 26, got {connectivity!r}")
+    S, out = model.img_size, None
+    for ch, logits in forward_volume_chunks(model, volume, spacing, input_format=input_format, hu_level=hu_level, hu_width=hu_width,
+                                            context=context, z_stride=1, batch_size=batch_size, device=device):
+        if out is None:
+            out = torch.empty((np.asarray(volume).shape[0], S, S), dtype=torch.uint8, device=logits.device)
+        out[ch[0]:ch[0] + len(ch)] = ops.seg_predict(logits, model.patch)
+    if keep_largest or min_volume_mm3 > 0:
+        _, h, w = np.asarray(volume).shape
+        out = postprocess_volume(out, model.head.num_classes, (spacing[2], spacing[1] * h / S, spacing[0] * w / S), keep_largest=keep_largest,
+                                 min_volume_mm3=min_volume_mm3, connectivity=connectivity)
+    return out.cpu().numpy()
 
 
 # ------------------------------------------------------------------------------------------ metrics from the int64 counts [3, C]
@@ -246,6 +278,47 @@ def postprocess(label_map: torch.Tensor, num_classes: int, spacing=None, *, keep
                          connectivity=connectivity)
 
 
+def min_component_vox(min_volume_mm3: float, voxel_mm=None) -> int:
+    """ceil(min_volume_mm3 / (s_z s_y s_x)) in float64 on the host: the smallest voxel count whose volume reaches ``min_volume_mm3``.
+    ``voxel_mm``: (s_z, s_y, s_x) in mm per voxel of the label volume (None: 1 mm)."""
+    v = float(min_volume_mm3)
+    if not (v >= 0 and math.isfinite(v)):
+        raise ValueError(f"min_volume_mm3 must be finite and >= 0, got {min_volume_mm3!r}")
+    sp = torch.ones(3, dtype=torch.float64) if voxel_mm is None else torch.as_tensor(voxel_mm).double().cpu()
+    if sp.shape != (3,) or not bool((torch.isfinite(sp) & (sp > 0)).all()):
+        raise ValueError(f"voxel_mm must be (s_z, s_y, s_x) in mm per voxel, finite and > 0, got {voxel_mm!r}")
+    vox = math.ceil(v / (float(sp[0]) * float(sp[1]) * float(sp[2])))
+    if vox >= 1 << 31:
+        raise ValueError(f"min_volume_mm3 = {v} is {vox} voxels at this spacing: no volume is that large")
+    return vox
+
+
+def postprocess_volume(label_volume: torch.Tensor, num_classes: int, voxel_mm=None, *, keep_largest: bool = False, min_volume_mm3: float = 0.0,
+                       connectivity: int = 26) -> torch.Tensor:
+    """``postprocess`` for one uint8 label volume [Z, H, W] on the device (``ops.cc_filter_3d``, csrc/cclabel3d.hip): per class >= 1 drop
+    the 3-D connected components under ``min_volume_mm3`` and, with ``keep_largest``, every component but the largest of the whole volume
+    (equal counts: the one whose first voxel comes first); dropped voxels become background (0).  ``voxel_mm`` is the (s_z, s_y, s_x) mm
+    per voxel of the label grid (None: 1 mm): a component is kept iff its voxel count >= ``min_component_vox(min_volume_mm3, voxel_mm)``."""
+    if not isinstance(label_volume, torch.Tensor) or label_volume.dim() != 3:
+        raise ValueError(f"postprocess_volume: label_volume must be uint8 [Z, H, W], got {type(label_volume).__name__}")
+    return ops.cc_filter_3d(label_volume, num_classes, min_vox=min_component_vox(min_volume_mm3, voxel_mm), keep_largest=keep_largest,
+                            connectivity=connectivity)
+
+
+def resample_labels_nearest(labels_zhw, S: int) -> np.ndarray:
+    """Ground truth (Z, H, W) on the model's S x S grid, slice by slice: output pixel (i, j) takes source pixel
+    (min(floor((i + 0.5) H / S), H - 1), min(floor((j + 0.5) W / S), W - 1)).  No value is ever mixed, so 255 (ignore) is preserved."""
+    lab = np.asarray(labels_zhw)
+    if lab.ndim != 3 or lab.dtype != np.uint8 or min(lab.shape) < 1:
+        raise ValueError(f"resample_labels_nearest: labels must be uint8 (Z, H, W), got {lab.dtype} {lab.shape}")
+    if int(S) != S or S < 1:
+        raise ValueError(f"resample_labels_nearest: S must be an integer >= 1, got {S!r}")
+    _, H, W = lab.shape
+    iy = np.minimum(((2 * np.arange(S, dtype=np.int64) + 1) * H) // (2 * int(S)), H - 1)     # floor((i + 0.5) H / S) in integers
+    ix = np.minimum(((2 * np.arange(S, dtype=np.int64) + 1) * W) // (2 * int(S)), W - 1)
+    return np.ascontiguousarray(lab[:, iy[:, None], ix[None, :]])
+
+
 LESION_COUNTS = ("n_gt", "n_gt_hit", "n_pred", "n_pred_hit")
 
 
@@ -290,6 +363,36 @@ class LesionAccumulator:
 
     def result(self) -> dict:
         return lesion_metrics(self.counts, images=self.images)
+
+
+class CaseAccumulator:
+    """Scores over cases (volumes).  Per case: the overlap counts [3, C] of ``ops.cc_filter_3d(..., targets=)`` / ``ops.seg_predict`` summed
+    over the case, and the lesion counts [C, 4] of ``ops.lesion_counts_3d``.  ``result()``: "dice" = per class the mean of the per-case
+    Dice over the cases where the class occurs in the prediction or the labels (NaN where in none), "cases" = that number of cases per
+    class (int64 [C]), and "lesions" = ``lesion_metrics`` of the summed lesion counts with images = the number of cases, so its
+    "fp_per_image" is false positives per case."""
+
+    def __init__(self, num_classes: int) -> None:
+        self.C, self.n = num_classes, 0
+        self.dice_sum = torch.zeros(num_classes, dtype=torch.float64)
+        self.cases = torch.zeros(num_classes, dtype=torch.int64)
+        self.lesions = torch.zeros((num_classes, 4), dtype=torch.int64)
+
+    def update(self, counts, lesion_counts) -> None:
+        c, l = torch.as_tensor(counts).cpu(), torch.as_tensor(lesion_counts).cpu()
+        if tuple(c.shape) != (3, self.C) or tuple(l.shape) != (self.C, 4) or c.dtype.is_floating_point or l.dtype.is_floating_point:
+            raise ValueError(f"CaseAccumulator: expected integer counts [3, {self.C}] and lesion counts [{self.C}, 4], got {tuple(c.shape)} {c.dtype} "
+                             f"and {tuple(l.shape)} {l.dtype}")
+        present = (c[1] + c[2]) > 0
+        self.dice_sum += torch.where(present, dice_per_class(c), torch.zeros(self.C, dtype=torch.float64))
+        self.cases += present.to(torch.int64)
+        self.lesions += l.to(torch.int64)
+        self.n += 1
+
+    def result(self) -> dict:
+        n = self.cases.double()
+        dice = torch.where(n > 0, self.dice_sum / n.clamp(min=1), torch.full_like(n, float("nan")))
+        return {"dice": dice, "cases": self.cases.clone(), "lesions": lesion_metrics(self.lesions, images=self.n)}
 
 
 # ------------------------------------------------------------------------------------------ what finetune_segmentation.py wrote

@@ -1,0 +1,165 @@
+#!/usr/bin/env python3
+"""Segment whole CT series with a fine-tuned segmenter, clean the result by 3-D connected components and score it per case.
+
+    python scripts/segment_volume.py --backbone runs/x/hub-export/ --segmenter seg/x/ --volume series.npy --spacing 0.8 0.8 2.5 --out labels.npy
+    python scripts/segment_volume.py --backbone B --segmenter S --volume a.npy --labels a_gt.npy --volume b.npy --labels b_gt.npy \\
+        --spacing 0.8 0.8 2.5 --keep-largest --min-component-mm3 50 --out labels.npy --report cases.json
+
+``--volume`` is a .npy file holding a (Z, H, W) series; the label volume written to ``--out`` is uint8 (Z, S, S) on the model's grid
+(dinox.segment.segment_volume: one trip to the device, chunks of ``--batch-size`` slices).  With several ``--volume`` the outputs are
+``--out`` with ``_0``, ``_1``, ... before the suffix.  ``--keep-largest`` / ``--min-component-mm3 V`` clean every class >= 1 by 3-D components
+(csrc/cclabel3d.hip; ``--connectivity`` 6, 18 or 26; the voxel is that of the label grid, see segment_volume).
+
+``--labels`` (one per ``--volume``, in order) holds the ground truth, uint8 with 255 = ignore: (Z, S, S) is taken as is, (Z, H, W) of the
+series is resampled to the grid by dinox.segment.resample_labels_nearest.  ``--report`` then gets, per class, the mean over cases of the
+per-case Dice and the lesion-wise sensitivity, precision, F1 and false positives per case (dinox.segment.CaseAccumulator); a lesion is a
+3-D component of at least ``--min-component-mm3``, hit when at least ``--lesion-overlap`` of it (to 1/1000; 0: any voxel) is matched.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import logging
+import sys
+from pathlib import Path
+
+import numpy as np
+import torch
+
+_HERE = Path(__file__).resolve().parent
+for _p in (_HERE.parent, _HERE):
+    if str(_p) not in sys.path:
+        sys.path.insert(0, str(_p))
+
+import finetune_lora as fl  # noqa: E402
+from evaluate_segmentation import _floats, _mean_present  # noqa: E402
+from dinox import ops, segment as SG  # noqa: E402
+
+log = logging.getLogger("segment_volume")
+
+
+def build_parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(description="Label volumes of whole series, 3-D clean-up and per-case scores",
+                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    base = {a.dest: a for a in fl.build_parser()._actions}
+    ap._add_action(base["backbone"])
+    ap.add_argument("--segmenter", required=True, type=Path, metavar="DIR", help="output directory of finetune_segmentation.py")
+    ap._add_action(base["device"])
+    ap.add_argument("--volume", required=True, type=Path, action="append", help=".npy file holding a (Z, H, W) series; repeatable")
+    ap.add_argument("--spacing", type=float, nargs=3, required=True, metavar=("SX", "SY", "SZ"),
+                    help="mm per source pixel in x and y and the slice spacing, for every --volume")
+    ap.add_argument("--out", required=True, type=Path, help="output .npy: uint8 (Z, S, S)")
+    for dest in ("input_format", "window_level", "window_width"):
+        ap._add_action(base[dest])
+    ap.add_argument("--context", default="neighbours", choices=("neighbours", "replicate"), help="the 2.5D stack of a slice")
+    ap.add_argument("--batch-size", type=int, default=64, help="slices per forward")
+    ap._add_action(base["no_amp"])
+    ap.add_argument("--keep-largest", action="store_true", help="keep only the largest 3-D component of every class >= 1")
+    ap.add_argument("--min-component-mm3", type=float, default=0.0, metavar="V",
+                    help="remove the 3-D components of the classes >= 1 under V mm^3; with --labels also the smallest component that counts as a lesion")
+    ap.add_argument("--connectivity", type=int, choices=(6, 18, 26), default=26, help="neighbourhood of a 3-D connected component")
+    ap.add_argument("--labels", type=Path, action="append", default=None, help=".npy ground truth of the --volume in the same position; repeatable")
+    ap.add_argument("--lesion-overlap", type=float, default=0.0, metavar="F",
+                    help="a lesion is hit when at least this fraction of it is matched (taken to 1/1000; 0: any overlap)")
+    ap.add_argument("--report", type=Path, default=None, help="JSON of the per-case scores (needs --labels)")
+    return ap
+
+
+def check_args(ap: argparse.ArgumentParser, args: argparse.Namespace) -> None:
+    """The argument errors that need no file and no device."""
+    if not 0.0 <= args.min_component_mm3 < float("inf"):
+        ap.error(f"--min-component-mm3: a finite volume >= 0, got {args.min_component_mm3}")
+    if not 0.0 <= args.lesion_overlap <= 1.0:
+        ap.error(f"--lesion-overlap: a fraction in [0, 1], got {args.lesion_overlap}")
+    if args.labels is not None and len(args.labels) != len(args.volume):
+        ap.error(f"--labels: one per --volume, got {len(args.labels)} for {len(args.volume)} volume(s)")
+    if args.report is not None and args.labels is None:
+        ap.error("--report needs --labels")
+    if args.batch_size < 1:
+        ap.error(f"--batch-size: an integer >= 1, got {args.batch_size}")
+    if any(not 0.0 < s < float("inf") for s in args.spacing):
+        ap.error(f"--spacing: three finite values > 0, got {args.spacing}")
+
+
+def grid_labels(ap: argparse.ArgumentParser, path: Path, vol_shape, S: int) -> np.ndarray:
+    """The ground truth of one case on the (Z, S, S) grid."""
+    gt = np.load(path)
+    Z = vol_shape[0]
+    if gt.dtype != np.uint8 or gt.ndim != 3:
+        ap.error(f"--labels {path}: uint8 (Z, H, W) or (Z, S, S) expected, got {gt.dtype} {gt.shape}")
+    if gt.shape == (Z, S, S):
+        return gt
+    if gt.shape == tuple(vol_shape):
+        return SG.resample_labels_nearest(gt, S)
+    ap.error(f"--labels {path}: shape {gt.shape} is neither the series' {tuple(vol_shape)} nor the label grid's {(Z, S, S)}")
+
+
+def case_report(res: dict, args: argparse.Namespace, overlap) -> dict:
+    """The report of CaseAccumulator.result(); the means run over the foreground classes (>= 1) that have a value."""
+    les = res["lesions"]
+    scores = ("sensitivity", "precision", "f1")
+    per_class = {"dice": _floats(res["dice"]), "dice_cases": res["cases"].tolist(), "fp_per_case": _floats(les["fp_per_image"])}
+    per_class.update({k: _floats(les[k]) for k in scores})
+    per_class.update({k: les[k].tolist() for k in SG.LESION_COUNTS})
+    mean = {"dice": _mean_present(res["dice"][1:]), "fp_per_case": _mean_present(les["fp_per_image"][1:])}
+    mean.update({k: _mean_present(les[k][1:]) for k in scores})
+    return {"cases": les["images"], "connectivity": args.connectivity, "overlap": f"{overlap[0]}/{overlap[1]}",
+            "min_volume_mm3": float(args.min_component_mm3), "keep_largest": bool(args.keep_largest), "per_class": per_class, "mean": mean}
+
+
+def run(args: argparse.Namespace):
+    ap = build_parser()
+    check_args(ap, args)
+    device = torch.device(args.device)
+    if device.type != "cuda":
+        raise SystemExit(f"this engine computes on MI355X only: --device {args.device} requested (no CPU compute path)")
+    for f in list(args.volume) + list(args.labels or []):
+        if not Path(f).is_file():
+            ap.error(f"{f}: no such file")
+    if not torch.cuda.is_available():
+        raise SystemExit("this engine computes on MI355X only: no CUDA/HIP device available")
+    model = SG.load_segmenter(args.backbone, args.segmenter, device)
+    C, S = model.head.num_classes, model.img_size
+    overlap = (round(1000 * args.lesion_overlap), 1000)
+    acc = SG.CaseAccumulator(C) if args.labels else None
+    sx, sy, sz = args.spacing
+    for i, vpath in enumerate(args.volume):
+        vol = np.load(vpath)
+        if vol.ndim != 3:
+            ap.error(f"--volume {vpath}: a (Z, H, W) array expected, got {vol.shape}")
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=not args.no_amp):
+            pred = SG.segment_volume(model, vol, (sx, sy, sz), input_format=args.input_format, hu_level=args.window_level,
+                                     hu_width=args.window_width, context=args.context, batch_size=args.batch_size, device=device,
+                                     keep_largest=args.keep_largest, min_volume_mm3=args.min_component_mm3, connectivity=args.connectivity)
+        out = args.out if len(args.volume) == 1 else args.out.with_name(f"{args.out.stem}_{i}{args.out.suffix}")
+        Path(out).parent.mkdir(parents=True, exist_ok=True)
+        np.save(out, pred)
+        log.info("%s: %s -> %s", vpath, tuple(vol.shape), out)
+        if acc is None:
+            continue
+        gt = torch.from_numpy(grid_labels(ap, args.labels[i], vol.shape, S)).to(device)
+        p = torch.from_numpy(pred).to(device)
+        voxel = (sz, sy * vol.shape[1] / S, sx * vol.shape[2] / S)
+        mv = SG.min_component_vox(args.min_component_mm3, voxel)
+        _, cnt = ops.cc_filter_3d(p, C, first_class=C, connectivity=args.connectivity, targets=gt)      # first_class = C: keeps all, counts only
+        acc.update(cnt, ops.lesion_counts_3d(p, gt, C, connectivity=args.connectivity, overlap=overlap, min_vox=mv))
+    if acc is None:
+        return None
+    report = case_report(acc.result(), args, overlap)
+    report["segmenter"], report["backbone"] = str(args.segmenter), str(args.backbone)
+    if args.report is not None:
+        Path(args.report).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.report).write_text(json.dumps(report, indent=2))
+    log.info("%d case(s): mean Dice %s, sensitivity %s, false positives per case %s", report["cases"], report["mean"]["dice"],
+             report["mean"]["sensitivity"], report["mean"]["fp_per_case"])
+    return report
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    logging.basicConfig(level=logging.INFO, format="%(asctime)s [%(levelname)s] %(message)s", datefmt="%H:%M:%S")
+    return run(args)
+
+
+if __name__ == "__main__":
+    main()

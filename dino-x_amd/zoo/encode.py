@@ -158,18 +158,13 @@ def encode_batch(model: PatchViT, images: Sequence[np.ndarray], spacings: Sequen
     return feats if return_all_tokens else feats[:, 0:1, :]
 
 
-def encode_volume(model: PatchViT, volume: np.ndarray, spacing: Tuple[float, float, float], *,
-                  input_format: Literal["hu_float", "hu16_png", "windowed_float"] = "hu_float", hu_level: float = 40.0,
-                  hu_width: float = 400.0, context: Literal["neighbours", "replicate"] = "neighbours", z_stride: int = 1,
-                  batch_size: int = 64, return_all_tokens: bool = False,
-                  device: Union[str, torch.device, None] = None) -> torch.Tensor:
-    """Features of the slices 0, z_stride, 2 z_stride, ... of a ``(Z, H, W)`` series: ``(Z', 1, D)`` (CLS) or ``(Z', N, D)``.
-
-    Slice z is encoded as the 2.5D stack the model was trained on -- planes z-1, z, z+1, clamped at the ends of the series
-    (``context="neighbours"``) -- or as plane z three times (``"replicate"``, what ``encode`` makes of an (H, W) image).
-    ``spacing = (sx, sy, sz)`` holds for the whole series.  The volume crosses to the device once; chunks of ``batch_size``
-    slices are preprocessed by the kernel (each plane resized once for all the stacks of the chunk it shows in) into one reused
-    input buffer and forwarded.  Honours an ambient ``torch.autocast`` exactly as ``encode`` does."""
+def forward_volume_chunks(model, volume: np.ndarray, spacing: Tuple[float, float, float], *, input_format: str, hu_level: float, hu_width: float,
+                          context: str, z_stride: int, batch_size: int, device: Union[str, torch.device, None]):
+    """The chunk loop of a ``(Z, H, W)`` series, shared by ``encode_volume`` and ``dinox.segment.segment_volume``: checks the arguments,
+    moves the volume to the device once, then yields ``(slices, model(x, spacing=...))`` per chunk of ``batch_size`` of the slices
+    0, z_stride, ... -- ``x`` the chunk's 2.5D stacks, preprocessed by the kernel into one reused input buffer (each plane resized once
+    for all the stacks of the chunk it shows in).  ``model`` is anything with ``img_size``, ``scale_aware`` and that call (a PatchViT, a
+    SegModel).  The forward runs under no_grad in the caller's autocast state.  The checks run at the first ``next()``."""
     from dinox import preprocess as P
     vol = np.asarray(volume)
     if vol.ndim != 3:
@@ -201,7 +196,7 @@ def encode_volume(model: PatchViT, volume: np.ndarray, spacing: Tuple[float, flo
     jobs = torch.from_numpy(np.concatenate(tables, 0)).pin_memory().to(device, non_blocking=True) if device.type == "cuda" else None
     buf = torch.empty((len(chunks[0]), 3, S, S), dtype=torch.float32, device=device)
     sp = torch.tensor([list(spacing)], dtype=torch.float32, device=device) if model.scale_aware else None
-    feats, at = [], 0
+    at = 0
     for tb, ch in zip(tables, chunks):
         n = len(ch)
         x = P.device_preprocess(src, tb if jobs is None else jobs[at:at + len(tb)], n, S, input_format, hu_level, hu_width, out=buf[:n],
@@ -209,5 +204,21 @@ def encode_volume(model: PatchViT, volume: np.ndarray, spacing: Tuple[float, flo
         at += len(tb)
         with torch.no_grad():
             f = model(x, spacing=None if sp is None else sp.expand(n, 3).contiguous())
-        feats.append(f if return_all_tokens else f[:, 0:1, :])
-    return torch.cat(feats, 0)
+        yield ch, f
+
+
+def encode_volume(model: PatchViT, volume: np.ndarray, spacing: Tuple[float, float, float], *,
+                  input_format: Literal["hu_float", "hu16_png", "windowed_float"] = "hu_float", hu_level: float = 40.0,
+                  hu_width: float = 400.0, context: Literal["neighbours", "replicate"] = "neighbours", z_stride: int = 1,
+                  batch_size: int = 64, return_all_tokens: bool = False,
+                  device: Union[str, torch.device, None] = None) -> torch.Tensor:
+    """Features of the slices 0, z_stride, 2 z_stride, ... of a ``(Z, H, W)`` series: ``(Z', 1, D)`` (CLS) or ``(Z', N, D)``.
+
+    Slice z is encoded as the 2.5D stack the model was trained on -- planes z-1, z, z+1, clamped at the ends of the series
+    (``context="neighbours"``) -- or as plane z three times (``"replicate"``, what ``encode`` makes of an (H, W) image).
+    ``spacing = (sx, sy, sz)`` holds for the whole series.  The volume crosses to the device once; chunks of ``batch_size``
+    slices are preprocessed by the kernel (each plane resized once for all the stacks of the chunk it shows in) into one reused
+    input buffer and forwarded (``forward_volume_chunks``).  Honours an ambient ``torch.autocast`` exactly as ``encode`` does."""
+    chunks = forward_volume_chunks(model, volume, spacing, input_format=input_format, hu_level=hu_level, hu_width=hu_width, context=context,
+                                   z_stride=z_stride, batch_size=batch_size, device=device)
+    return torch.cat([f if return_all_tokens else f[:, 0:1, :] for _, f in chunks], 0)

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define DINOX_ABI_VERSION 3   /* 3: + dinox_block_forward / _backward, dinox_gemm_timer_*, dinox_retrieval_* (later also dinox_retrieval_rank_windowed*, dinox_row_dots), dinox_knn_*, dinox_gram_*, dinox_softmax_probe*, dinox_ntxent_* (later also dinox_ntxent_*_rect), dinox_normalize_bwd, dinox_mae_*, dinox_attention_rows*, dinox_attention_rollout_step*, dinox_ibot_*, dinox_gather_rows, dinox_scatter_add_rows, dinox_seg_*, dinox_surface_*, dinox_cc_* (all additive: no entry
+#define DINOX_ABI_VERSION 3   /* 3: + dinox_block_forward / _backward, dinox_gemm_timer_*, dinox_retrieval_* (later also dinox_retrieval_rank_windowed*, dinox_row_dots), dinox_knn_*, dinox_gram_*, dinox_softmax_probe*, dinox_ntxent_* (later also dinox_ntxent_*_rect), dinox_normalize_bwd, dinox_mae_*, dinox_attention_rows*, dinox_attention_rollout_step*, dinox_ibot_*, dinox_gather_rows, dinox_scatter_add_rows, dinox_seg_*, dinox_surface_*, dinox_cc_*, dinox_cc3d_* (all additive: no entry
                                * of an earlier library changed, so the number callers test, dinox_version() == 3, stays; probe the symbol
                                * to learn whether a given build has the later additions) */
 
@@ -891,6 +891,37 @@ int dinox_cc_filter(const uint8_t* labels, const int32_t* comp, const int32_t* a
 int dinox_cc_match(const uint8_t* pred, const int32_t* pred_comp, const int32_t* pred_area, const uint8_t* gt, const int32_t* gt_comp,
                    const int32_t* gt_area, const int32_t* min_px, int64_t* counts, void* ws, int64_t B, int H, int W, int C, int t_num, int t_den,
                    void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Connected components of ONE label volume: the calls above for a series instead of a batch of independent images (kernels:
+ * csrc/cclabel3d.hip on the stages of csrc/cclabel.hip; dinox.ops.cc_label_3d, cc_filter_3d, lesion_counts_3d;
+ * dinox.segment.segment_volume, postprocess_volume).  Everything is as in the section above with these differences:
+ *   labels[Z][H][W]  uint8, dense, 1 <= H, W <= 1024, Z >= 1 and Z H W <= 2^30 (every voxel index and every area fits int32).  mask likewise.
+ *   Neighbours: connectivity 6, the voxels that share a face; 18, a face or an edge; 26, a face, an edge or a corner.
+ *   Canonical form: comp[Z][H][W] int32 = the linear index (z H + y) W + x of the component's first voxel in raster order, -1 where the
+ *               voxel is in no component; area[Z][H][W] int32 = the voxel count at the root, 0 elsewhere; ncomp[C] int64.
+ *   Filter: min_vox is a host scalar >= 0 (one volume, one minimum).  Tie rule: of components with equal volume the one with the SMALLEST
+ *               root index is the largest (one 64-bit maximum over area << 31 | (2^31 - 1 - root)).  counts[3 C + 1] as above.
+ *   Match: min_vox a host scalar >= 0; counts[C][4] int64 = (n_gt, n_gt_hit, n_pred, n_pred_hit), the hit criterion unchanged.
+ * Labelling runs the tile and tile-border launches per slice with the in-plane part of the connectivity (4 for 6, 8 for 18 and 26) on
+ * volume-wide indices, then one launch in which every voxel with z >= 1 unites with its same-class neighbours in slice z - 1 (agent-scope
+ * atomics throughout; one union per run where the voxel directly above matches, the in-plane unions imply the rest), then the flatten
+ * launch over the whole volume.  No loop waits for another wave; integer work only: equal inputs give equal bits.
+ *
+ * dinox_cc3d_ws_bytes: bytes of workspace for any of the three calls, 8 Z H W + 8 C (0 for sizes the calls refuse; contents need not be
+ *   initialised; 8-byte aligned).
+ * dinox_cc3d_label: connectivity 6, 18 or 26; bad[1] int64, zeroed on the stream first.
+ * dinox_cc3d_filter: comp / area as dinox_cc3d_label wrote them for `labels` (same mask, same connectivity).
+ * dinox_cc3d_match: pred_comp / pred_area from dinox_cc3d_label(pred, mask = gt), gt_comp / gt_area from dinox_cc3d_label(gt, mask = NULL).
+ * ------------------------------------------------------------------------------------------ */
+int64_t dinox_cc3d_ws_bytes(int64_t Z, int H, int W, int C);
+int dinox_cc3d_label(const uint8_t* labels, const uint8_t* mask, int32_t* comp, int32_t* area, int64_t* ncomp, int64_t* bad, void* ws, int64_t Z,
+                     int H, int W, int C, int connectivity, void* stream);
+int dinox_cc3d_filter(const uint8_t* labels, const int32_t* comp, const int32_t* area, int min_vox, const uint8_t* y, uint8_t* out,
+                      int64_t* counts, void* ws, int64_t Z, int H, int W, int C, int c0, int keep_largest, void* stream);
+int dinox_cc3d_match(const uint8_t* pred, const int32_t* pred_comp, const int32_t* pred_area, const uint8_t* gt, const int32_t* gt_comp,
+                     const int32_t* gt_area, int min_vox, int64_t* counts, void* ws, int64_t Z, int H, int W, int C, int t_num, int t_den,
+                     void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Per-launch timing of dinox_gemm (diagnostic; bench.py's roofline object).  Between start and stop every dinox_gemm launch -- also
