@@ -27,7 +27,6 @@
 // (K of one head: 175 KB at N = 1370, d = 64, bf16).  N^2 d fma per (image, head) is the cost; with B heads workgroups the launch
 // is far from filling 256 CUs at B = 1, which is accepted for an instrument that runs once per thousand steps.
 #include "common.h"
-#include "kernels.h"
 
 namespace dinox {
 
@@ -196,18 +195,33 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_fold_kernel(const float* _
   w_out[t] = fmaf(coef, a, residual * w_in[t]);
 }
 
-bool attention_rollout_step_ok(int B, int N, int heads, int d) {
+static bool attention_rollout_step_ok(int B, int N, int heads, int d) {
   return B >= 1 && N >= 1 && N <= RO_NMAX && heads >= 1 && d >= 1 && d <= RO_DMAX && (int64_t)B * heads <= 0x7fffffff &&
          ceil_div((int64_t)B * N, RO_THREADS) <= 0x7fffffff;
 }
 
-size_t attention_rollout_step_ws_bytes(int B, int N, int heads) {
+}  // namespace dinox
+
+using namespace dinox;
+
+extern "C" int dinox_attention_rollout_step_ok(int B, int N, int heads, int d) { return attention_rollout_step_ok(B, N, heads, d) ? 1 : 0; }
+
+extern "C" size_t dinox_attention_rollout_step_ws_bytes(int B, int N, int heads) {
   if (B < 1 || N < 1 || heads < 1) return 0;
   return (size_t)B * (size_t)heads * (size_t)N * sizeof(float);
 }
 
-int launch_attention_rollout_step(const void* qkv, const float* w_in, float* w_out, void* ws, int B, int N, int heads, int d, float residual,
-                                  int dtype, hipStream_t st) {
+extern "C" int dinox_attention_rollout_step(const void* qkv, const float* w_in, float* w_out, void* ws, int B, int N, int heads, int d,
+                                            float residual, int dtype, void* stream) {
+  DX_REQUIRE(qkv && w_in && w_out && ws, DINOX_EINVAL, "attention_rollout_step: null pointer");
+  DX_REQUIRE(dtype == DINOX_F32 || dtype == DINOX_BF16, DINOX_EINVAL, "attention_rollout_step: dtype %d", dtype);
+  DX_REQUIRE(attention_rollout_step_ok(B, N, heads, d), DINOX_EINVAL,
+             "attention_rollout_step: B=%d N=%d heads=%d d=%d (B, heads >= 1; 1 <= N <= 4096; 1 <= d <= 256)", B, N, heads, d);
+  DX_REQUIRE(residual >= 0.f && residual <= 1.f, DINOX_EINVAL, "attention_rollout_step: residual %g outside [0, 1]", (double)residual);
+  const float* in_end = w_in + (size_t)B * N;
+  const float* out_end = w_out + (size_t)B * N;
+  DX_REQUIRE(in_end <= w_out || out_end <= w_in, DINOX_EINVAL, "attention_rollout_step: w_out must not alias w_in (the fold reads w_in)");
+  hipStream_t st = as_stream(stream);
   const float sc = 1.0f / sqrtf((float)d);
   const size_t lds = (size_t)RO_ROWS * ((size_t)N + (size_t)d) * sizeof(float);
   const dim3 grid((unsigned)(B * heads)), block(RO_THREADS);
@@ -234,5 +248,3 @@ int launch_attention_rollout_step(const void* qkv, const float* w_in, float* w_o
                      heads, residual, (1.0f - residual) / (float)heads);
   return check_launch("attention_rollout_step (fold)");
 }
-
-}  // namespace dinox

@@ -21,7 +21,6 @@
 // 1374 tokens).  Memory-bound on K; with B heads workgroups (192 at ViT-S, 6..16 for a single image) the launch is far from
 // filling 256 CUs, which is accepted for an instrument that runs once per thousand steps.
 #include "common.h"
-#include "kernels.h"
 
 namespace dinox {
 
@@ -115,12 +114,23 @@ __global__ __launch_bounds__(AR_THREADS) void attention_rows_kernel(const void* 
   }
 }
 
-bool attention_rows_ok(int B, int N, int heads, int d, int Q) {
+static bool attention_rows_ok(int B, int N, int heads, int d, int Q) {
   return B >= 1 && N >= 1 && heads >= 1 && d >= 1 && d <= AR_DMAX && Q >= 1 && Q <= AR_QMAX && (int64_t)B * heads <= 0x7fffffff;
 }
 
-int launch_attention_rows(const void* qkv, const int* query_idx, float* probs, float* lse, int B, int N, int heads, int d, int Q, int dtype,
-                          hipStream_t st) {
+}  // namespace dinox
+
+using namespace dinox;
+
+extern "C" int dinox_attention_rows_ok(int B, int N, int heads, int d, int Q) { return attention_rows_ok(B, N, heads, d, Q) ? 1 : 0; }
+
+extern "C" int dinox_attention_rows(const void* qkv, const int* query_idx, float* probs, float* lse, int B, int N, int heads, int d, int Q,
+                                    int dtype, void* stream) {
+  DX_REQUIRE(qkv && query_idx && probs, DINOX_EINVAL, "attention_rows: null pointer");
+  DX_REQUIRE(dtype == DINOX_F32 || dtype == DINOX_BF16, DINOX_EINVAL, "attention_rows: dtype %d", dtype);
+  DX_REQUIRE(attention_rows_ok(B, N, heads, d, Q), DINOX_EINVAL,
+             "attention_rows: B=%d N=%d heads=%d d=%d Q=%d (B, N, heads >= 1; 1 <= d <= 256; 1 <= Q <= 8)", B, N, heads, d, Q);
+  hipStream_t st = as_stream(stream);
   const float sc = 1.0f / sqrtf((float)d);
   const dim3 grid((unsigned)(B * heads)), block(AR_THREADS);
   // 16-byte key loads: every key row starts at qkv + (token 3 heads + heads + h) d elements, so d % (16 / element size) == 0 and an
@@ -137,5 +147,3 @@ int launch_attention_rows(const void* qkv, const int* query_idx, float* probs, f
 #undef AR_LAUNCH
   return check_launch("attention_rows");
 }
-
-}  // namespace dinox

@@ -1,6 +1,7 @@
 // cc_common.h -- what the two connected-component files share: cclabel.hip (a batch of independent [H][W] images) and cclabel3d.hip (one
 // [Z][H][W] volume).  The union-find primitives on an int32 parent array with parent[i] <= i, the wave-reduced integer add, the class of
-// a pixel, the launch constants, and the stage launchers that cclabel.hip defines and cclabel3d.hip runs again on a volume.
+// a pixel, the launch constants, the size limits both families' entry points check, and the stage launchers that cclabel.hip defines and
+// cclabel3d.hip runs again on a volume.
 //
 // Why every loop here ends is argued at each function; none waits for another wave (cclabel.hip's header has the whole argument).
 #pragma once
@@ -13,6 +14,7 @@ constexpr int CC_TILE = 32;                        // tile side: 1024 local pare
 constexpr int CC_TPX = CC_TILE * CC_TILE;
 constexpr int CC_THREADS = 256;                    // four pixels of a tile, or of a chunk, per thread
 constexpr int CC_CHUNK = 4 * CC_THREADS;           // pixels of one image per work item of the per-pixel kernels
+constexpr int CC_MAX_SIDE = 1024;                  // a root index y W + x and an area both fit 20 bits beside each other in the 64-bit tie key
 constexpr int CC_NONE = 255;                       // class of a pixel in no component
 constexpr int64_t CC_GRID_CAP = 1 << 20;           // workgroups per launch; the kernels stride over what is left
 constexpr int CC_KEY_BITS = 20;                    // images: root < 2^20 and area <= 2^20, area << 20 | (2^20 - 1 - root) orders "larger, then lower root"
@@ -88,6 +90,24 @@ __device__ __forceinline__ int cc_class(const uint8_t* __restrict__ lab, const u
 static inline int cc_zero(void* p, int64_t bytes, hipStream_t st, const char* what) {
   const hipError_t e = hipMemsetAsync(p, 0, (size_t)bytes, st);
   return e == hipSuccess ? 0 : fail((int)e, "%s: hipMemsetAsync: %s", what, hipGetErrorString(e));
+}
+
+// ---------------------------------------------------------------- host: the size limits of `lead` images, or slices, of H x W pixels in C classes
+// Said once: 0 inside all of them, else the number of the first one broken.  max_px bounds lead and lead H W.
+static inline int cc_broken_limit(int64_t lead, int64_t max_px, int H, int W, int C) {
+  if (!(H >= 1 && H <= CC_MAX_SIDE && W >= 1 && W <= CC_MAX_SIDE)) return 1;
+  if (!(C >= 2 && C <= SEG_MAX_CLASSES)) return 2;
+  if (!(lead >= 1 && lead <= max_px && lead * H * W <= max_px)) return 3;
+  return 0;
+}
+// 0, or entry `what`'s refusal of the first broken limit.  `letter` names the leading extent ('B', 'Z') and `tail` says its limit.
+static inline int cc_check_sizes(const char* what, char letter, int64_t lead, int64_t max_px, const char* tail, int H, int W, int C) {
+  switch (cc_broken_limit(lead, max_px, H, W, C)) {
+    case 1: return fail(DINOX_EINVAL, "%s: H=%d W=%d (1 <= H, W <= %d)", what, H, W, CC_MAX_SIDE);
+    case 2: return fail(DINOX_EINVAL, "%s: C=%d (2 <= C <= %d)", what, C, SEG_MAX_CLASSES);
+    case 3: return fail(DINOX_EINVAL, "%s: %c=%lld (%c >= 1 and %s)", what, letter, (long long)lead, letter, tail);
+  }
+  return 0;
 }
 
 // ---------------------------------------------------------------- the stages (cclabel.hip), for B images or, `volume`, the B slices of one volume

@@ -1,5 +1,5 @@
 // cclabel.hip -- connected components of a uint8 label map: labelling in a canonical form, the clean-up filter (minimum area, largest
-// component) and lesion-wise match counts (entry points and argument checks: abi.hip; definitions: include/dinox.h).
+// component) and lesion-wise match counts (definitions: include/dinox.h).
 //
 // Labelling is union-find over the pixels of one image with the invariant parent[i] <= i, so a component's root is its smallest index
 // y W + x, which is the canonical label.  Three launches:
@@ -279,9 +279,6 @@ __global__ __launch_bounds__(CC_THREADS) void cc_count_kernel(const uint8_t* __r
 static_assert(CC_THREADS == 4 * SEG_MAX_CLASSES, "cc_count_kernel zeroes one counter per thread");
 static_assert((int64_t)CC_MAX_SIDE * CC_MAX_SIDE <= (1 << CC_KEY_BITS), "root and area must fit the tie key");
 
-// label: parent [B][H][W] int32.  filter: best [B][C] uint64.  match: ip, ig [B][H][W] int32 each.
-int64_t cc_ws_bytes(int64_t B, int H, int W, int C) { return 8 * B * (int64_t)H * W + 8 * B * C; }
-
 static int cc_check(const char* what, const char* stage) {
   char msg[96];
   snprintf(msg, sizeof msg, "%s (%s)", what, stage);
@@ -356,23 +353,54 @@ int cc_run_match(const uint8_t* pred, const int32_t* pred_comp, const int32_t* p
   return cc_check(what, "counts");
 }
 
-int launch_cc_label(const uint8_t* labels, const uint8_t* mask, int32_t* comp, int32_t* area, int64_t* ncomp, int64_t* bad, void* ws, int64_t B, int H,
-                    int W, int C, int conn, hipStream_t st) {
-  int rc = cc_zero(ncomp, B * C * (int64_t)sizeof(int64_t), st, "cc_label");
+}  // namespace dinox
+
+using namespace dinox;
+
+// ---------------------------------------------------------------- entry points
+// B H W < 2^31: every pixel index of an image fits int32 (and 20 bits: H, W <= 1024), every batch offset int64.
+constexpr int64_t CC_MAX_PIXELS = ((int64_t)1 << 31) - 1;
+static int cc_sizes(const char* what, int64_t B, int H, int W, int C) {
+  return cc_check_sizes(what, 'B', B, CC_MAX_PIXELS, "B H W < 2^31; cut a longer batch in pieces", H, W, C);
+}
+
+// label: parent [B][H][W] int32.  filter: best [B][C] uint64.  match: ip, ig [B][H][W] int32 each.
+extern "C" int64_t dinox_cc_ws_bytes(int64_t B, int H, int W, int C) {
+  return cc_broken_limit(B, CC_MAX_PIXELS, H, W, C) ? 0 : 8 * B * (int64_t)H * W + 8 * B * C;
+}
+
+extern "C" int dinox_cc_label(const uint8_t* labels, const uint8_t* mask, int32_t* comp, int32_t* area, int64_t* ncomp, int64_t* bad, void* ws, int64_t B,
+                              int H, int W, int C, int connectivity, void* stream) {
+  DX_REQUIRE(labels && comp && area && ncomp && bad && ws, DINOX_EINVAL, "cc_label: null pointer");
+  int rc = cc_sizes("cc_label", B, H, W, C);
   if (rc) return rc;
-  rc = cc_run_planes(labels, mask, (int*)ws, area, bad, B, H, W, C, conn, 0, st, "cc_label");
+  DX_REQUIRE(connectivity == 4 || connectivity == 8, DINOX_EINVAL, "cc_label: connectivity=%d (4 or 8)", connectivity);
+  hipStream_t st = as_stream(stream);
+  rc = cc_zero(ncomp, B * C * (int64_t)sizeof(int64_t), st, "cc_label");
+  if (rc) return rc;
+  rc = cc_run_planes(labels, mask, (int*)ws, area, bad, B, H, W, C, connectivity, 0, st, "cc_label");
   return rc ? rc : cc_run_flatten(labels, (int*)ws, comp, area, ncomp, B, (int64_t)H * W, C, st, "cc_label");
 }
 
-int launch_cc_filter(const uint8_t* labels, const int32_t* comp, const int32_t* area, const int32_t* min_px, const uint8_t* y, uint8_t* out,
-                     int64_t* counts, void* ws, int64_t B, int H, int W, int C, int c0, int keep_largest, hipStream_t st) {
-  return cc_run_filter(labels, comp, area, min_px, 1, y, out, counts, ws, B, (int64_t)H * W, C, c0, keep_largest, CC_KEY_BITS, st, "cc_filter");
+extern "C" int dinox_cc_filter(const uint8_t* labels, const int32_t* comp, const int32_t* area, const int32_t* min_px, const uint8_t* y, uint8_t* out,
+                               int64_t* counts, void* ws, int64_t B, int H, int W, int C, int c0, int keep_largest, void* stream) {
+  DX_REQUIRE(labels && comp && area && out && ws, DINOX_EINVAL, "cc_filter: null pointer");
+  DX_REQUIRE((y == nullptr) == (counts == nullptr), DINOX_EINVAL, "cc_filter: y and counts go together (both or neither)");
+  const int rc = cc_sizes("cc_filter", B, H, W, C);
+  if (rc) return rc;
+  DX_REQUIRE(c0 >= 0 && c0 <= C, DINOX_EINVAL, "cc_filter: c0=%d (0 <= c0 <= C = %d)", c0, C);
+  return cc_run_filter(labels, comp, area, min_px, 1, y, out, counts, ws, B, (int64_t)H * W, C, c0, keep_largest ? 1 : 0, CC_KEY_BITS, as_stream(stream),
+                       "cc_filter");
 }
 
-int launch_cc_match(const uint8_t* pred, const int32_t* pred_comp, const int32_t* pred_area, const uint8_t* gt, const int32_t* gt_comp,
-                    const int32_t* gt_area, const int32_t* min_px, int64_t* counts, void* ws, int64_t B, int H, int W, int C, int t_num, int t_den,
-                    hipStream_t st) {
-  return cc_run_match(pred, pred_comp, pred_area, gt, gt_comp, gt_area, min_px, 1, counts, ws, B, (int64_t)H * W, C, t_num, t_den, st, "cc_match");
+extern "C" int dinox_cc_match(const uint8_t* pred, const int32_t* pred_comp, const int32_t* pred_area, const uint8_t* gt, const int32_t* gt_comp,
+                              const int32_t* gt_area, const int32_t* min_px, int64_t* counts, void* ws, int64_t B, int H, int W, int C, int t_num,
+                              int t_den, void* stream) {
+  DX_REQUIRE(pred && pred_comp && pred_area && gt && gt_comp && gt_area && counts && ws, DINOX_EINVAL, "cc_match: null pointer");
+  const int rc = cc_sizes("cc_match", B, H, W, C);
+  if (rc) return rc;
+  DX_REQUIRE(t_den > 0 && t_den < (1 << 20) && t_num >= 0 && t_num <= t_den, DINOX_EINVAL,
+             "cc_match: overlap %d/%d (0 <= t_num <= t_den, 0 < t_den < 2^20)", t_num, t_den);
+  return cc_run_match(pred, pred_comp, pred_area, gt, gt_comp, gt_area, min_px, 1, counts, ws, B, (int64_t)H * W, C, t_num, t_den, as_stream(stream),
+                      "cc_match");
 }
-
-}  // namespace dinox

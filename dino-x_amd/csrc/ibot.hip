@@ -8,11 +8,12 @@
 // fp32 math.  No float atomics: every sum has a fixed order (stated at each kernel), so a step is bit-reproducible.  Every index read from
 // device memory is range-checked before it becomes an address; an entry outside is skipped.
 #include "small_common.h"
-#include "kernels.h"
 
 namespace dinox {
 
 constexpr int IB_THREADS = 256;
+constexpr int IBOT_MASK_CHUNK = 64;        // masked rows per partial sum of put_mask_bwd: ws holds ceil(M / 64) x D floats
+constexpr int IBOT_CE_REG_MAX_K = 8192;    // widest row the register-resident cross-entropy holds: 8 float4 per thread and matrix
 
 // ---------------------------------------------------------------- mask token in / out of the patch rows
 template <int DT>
@@ -212,36 +213,75 @@ __global__ __launch_bounds__(IB_THREADS) void ibot_center_ema_kernel(float* __re
   if (k < K && n >= 1.0f) c[k] = c[k] * mom + (sum_count[k] / n) * (1.0f - mom);
 }
 
-// ---------------------------------------------------------------- launchers (arguments were validated by the entry points in abi.hip)
-int launch_ibot_put_mask(void* patches, const float* mask_token, const int* idx, int M, int64_t rows, int D, int dtype, hipStream_t st) {
-  DX_LAUNCH_DT(ibot_put_mask_kernel, dtype, dim3(grid_1d((int64_t)M * D, IB_THREADS, 4096)), dim3(IB_THREADS), st, patches, mask_token, idx, M, rows, D);
+}  // namespace dinox
+
+using namespace dinox;
+
+// ---------------------------------------------------------------- entry points
+// M masked rows out of `rows` (flat int32 positions), D features.
+static bool ibot_rows_ok(int64_t M, int64_t rows, int D) {
+  return M >= 1 && M <= 0x7fffffff && rows >= 1 && rows <= 0x7fffffff && D >= 1 && D <= (1 << 16);
+}
+
+extern "C" int dinox_ibot_put_mask(void* patches, const float* mask_token, const int* idx, int M, int64_t rows, int D, int dtype, void* stream) {
+  DX_REQUIRE(patches && mask_token && idx, DINOX_EINVAL, "ibot_put_mask: null pointer");
+  DX_REQUIRE(dtype_ok(dtype), DINOX_EINVAL, "ibot_put_mask: dtype %d", dtype);
+  DX_REQUIRE(ibot_rows_ok(M, rows, D), DINOX_EINVAL, "ibot_put_mask: M=%d rows=%lld D=%d (M, rows >= 1; 1 <= D <= 65536)", M, (long long)rows, D);
+  DX_LAUNCH_DT(ibot_put_mask_kernel, dtype, dim3(grid_1d((int64_t)M * D, IB_THREADS, 4096)), dim3(IB_THREADS), as_stream(stream), patches, mask_token, idx,
+               M, rows, D);
   return check_launch("ibot_put_mask");
 }
 
-int launch_ibot_put_mask_bwd(void* dpatches, const int* idx, float* dmask, float* ws, int M, int64_t rows, int D, int dtype, hipStream_t st) {
+extern "C" int dinox_ibot_put_mask_bwd(void* dpatches, const int* idx, float* dmask_token, float* ws, int M, int64_t rows, int D, int dtype,
+                                       void* stream) {
+  DX_REQUIRE(dpatches && idx && dmask_token && ws, DINOX_EINVAL, "ibot_put_mask_bwd: null pointer");
+  DX_REQUIRE(dtype_ok(dtype), DINOX_EINVAL, "ibot_put_mask_bwd: dtype %d", dtype);
+  DX_REQUIRE(ibot_rows_ok(M, rows, D) && M <= 65535 * IBOT_MASK_CHUNK, DINOX_EINVAL,
+             "ibot_put_mask_bwd: M=%d rows=%lld D=%d (1 <= M <= %d; rows >= 1; 1 <= D <= 65536)", M, (long long)rows, D, 65535 * IBOT_MASK_CHUNK);
+  hipStream_t st = as_stream(stream);
   const int chunks = (int)ceil_div(M, IBOT_MASK_CHUNK), col_blocks = (int)ceil_div(D, IB_THREADS);
   DX_LAUNCH_DT(ibot_mask_partial_kernel, dtype, dim3((unsigned)col_blocks, (unsigned)chunks), dim3(IB_THREADS), st, dpatches, idx, ws, M, rows, D);
   int rc = check_launch("ibot_put_mask_bwd");
   if (rc) return rc;
   const dim3 grid((unsigned)col_blocks + grid_1d((int64_t)M * D, IB_THREADS, 4096));
-  DX_LAUNCH_DT(ibot_mask_combine_kernel, dtype, grid, dim3(IB_THREADS), st, dpatches, idx, ws, dmask, M, rows, D, chunks, col_blocks);
+  DX_LAUNCH_DT(ibot_mask_combine_kernel, dtype, grid, dim3(IB_THREADS), st, dpatches, idx, ws, dmask_token, M, rows, D, chunks, col_blocks);
   return check_launch("ibot_put_mask_bwd_combine");
 }
 
-int launch_gather_rows(const float* src, const int* row, void* dst, int64_t M, int64_t src_rows, int D, int64_t dst_row0, int dtype,
-                       hipStream_t st) {
-  DX_LAUNCH_DT(gather_rows_kernel, dtype, dim3(grid_1d(M * D, IB_THREADS, 4096)), dim3(IB_THREADS), st, src, row, dst, M, src_rows, D, dst_row0);
+extern "C" int dinox_gather_rows(const float* src, const int* row, void* dst, int64_t M, int64_t src_rows, int D, int64_t dst_row0, int dst_dtype,
+                                 void* stream) {
+  DX_REQUIRE(src && row && dst, DINOX_EINVAL, "gather_rows: null pointer");
+  DX_REQUIRE(dtype_ok(dst_dtype), DINOX_EINVAL, "gather_rows: dtype %d", dst_dtype);
+  DX_REQUIRE(ibot_rows_ok(M, src_rows, D) && dst_row0 >= 0, DINOX_EINVAL, "gather_rows: M=%lld src_rows=%lld D=%d dst_row0=%lld", (long long)M,
+             (long long)src_rows, D, (long long)dst_row0);
+  DX_LAUNCH_DT(gather_rows_kernel, dst_dtype, dim3(grid_1d(M * D, IB_THREADS, 4096)), dim3(IB_THREADS), as_stream(stream), src, row, dst, M, src_rows, D,
+               dst_row0);
   return check_launch("gather_rows");
 }
 
-int launch_scatter_add_rows(const void* src, const int* row, float* dst, int64_t M, int64_t dst_rows, int D, int64_t src_row0, int dtype,
-                            hipStream_t st) {
-  DX_LAUNCH_DT(scatter_add_rows_kernel, dtype, dim3(grid_1d(M * D, IB_THREADS, 4096)), dim3(IB_THREADS), st, src, row, dst, M, dst_rows, D, src_row0);
+extern "C" int dinox_scatter_add_rows(const void* src, const int* row, float* dst, int64_t M, int64_t dst_rows, int D, int64_t src_row0,
+                                      int src_dtype, void* stream) {
+  DX_REQUIRE(src && row && dst, DINOX_EINVAL, "scatter_add_rows: null pointer");
+  DX_REQUIRE(dtype_ok(src_dtype), DINOX_EINVAL, "scatter_add_rows: dtype %d", src_dtype);
+  DX_REQUIRE(ibot_rows_ok(M, dst_rows, D) && src_row0 >= 0, DINOX_EINVAL, "scatter_add_rows: M=%lld dst_rows=%lld D=%d src_row0=%lld", (long long)M,
+             (long long)dst_rows, D, (long long)src_row0);
+  DX_LAUNCH_DT(scatter_add_rows_kernel, src_dtype, dim3(grid_1d(M * D, IB_THREADS, 4096)), dim3(IB_THREADS), as_stream(stream), src, row, dst, M, dst_rows,
+               D, src_row0);
   return check_launch("scatter_add_rows");
 }
 
-int launch_ibot_ce(const float* s, const float* t, const float* center, const float* w, float inv_ts, float inv_tt, float scale, float gscale,
-                   float* loss, float* ds, float* row_loss, int M, int K, hipStream_t st) {
+extern "C" int dinox_ibot_ce(const float* s, const float* t, const float* center, const float* w, float student_temp, float teacher_temp,
+                             float scale, float grad_scale, float* loss, float* ds, float* row_loss, int M, int K, void* stream) {
+  DX_REQUIRE(s && t && center && w && loss && row_loss, DINOX_EINVAL, "ibot_ce: null pointer");
+  DX_REQUIRE(M >= 1 && K >= 1, DINOX_EINVAL, "ibot_ce: M=%d K=%d", M, K);
+  DX_REQUIRE(student_temp > 0.f && teacher_temp > 0.f, DINOX_EINVAL, "ibot_ce: temperatures must be > 0");
+  if (ds) {
+    const size_t n = (size_t)M * (size_t)K;
+    const float* de = ds + n;
+    DX_REQUIRE((de <= s || s + n <= ds) && (de <= t || t + n <= ds), DINOX_EINVAL, "ibot_ce: ds must not alias s or t");
+  }
+  hipStream_t st = as_stream(stream);
+  const float inv_ts = 1.0f / student_temp, inv_tt = 1.0f / teacher_temp, gscale = grad_scale * scale;
   const bool reg = K % 4 == 0 && K <= IBOT_CE_REG_MAX_K && aligned16(s, t, center, ds);
   const dim3 grid((unsigned)M), block(IB_THREADS);
   if (reg) {
@@ -261,9 +301,8 @@ int launch_ibot_ce(const float* s, const float* t, const float* center, const fl
   return check_launch("ibot_ce_sum");
 }
 
-int launch_ibot_center_ema(float* center, const float* sum_count, float momentum, int K, hipStream_t st) {
-  hipLaunchKernelGGL(ibot_center_ema_kernel, dim3((unsigned)ceil_div(K, IB_THREADS)), dim3(IB_THREADS), 0, st, center, sum_count, momentum, K);
+extern "C" int dinox_ibot_center_ema(float* center, const float* sum_count, float momentum, int K, void* stream) {
+  DX_REQUIRE(center && sum_count && K >= 1, DINOX_EINVAL, "ibot_center_ema: bad arguments");
+  hipLaunchKernelGGL(ibot_center_ema_kernel, dim3((unsigned)ceil_div(K, IB_THREADS)), dim3(IB_THREADS), 0, as_stream(stream), center, sum_count, momentum, K);
   return check_launch("ibot_center_ema");
 }
-
-}  // namespace dinox

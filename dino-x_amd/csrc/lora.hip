@@ -1,4 +1,4 @@
-// lora.hip -- the low-rank side of a LoRA-wrapped linear layer (entry points and argument checks: abi.hip; contract: include/dinox.h).
+// lora.hip -- the low-rank side of a LoRA-wrapped linear layer (contract: include/dinox.h).
 //   y = x W^T + b + s (xl A^T) B^T: the base product is dinox_gemm; these kernels form the fp32 addend it takes as RESIDUAL, the
 //   matching dX addend, and dA / dB.  A, B, u = xl A^T and v = dy B are fp32 and every sum is an fp32 fma chain in a fixed order.
 // The contractions over the long axes (u = xl A^T and v = dy B over K / N columns, dA = v^T xl and dB = dy^T u over the rows) run on the
@@ -6,10 +6,14 @@
 // load, which is exact, so nothing on the adapter path is rounded to bf16 in either mode; per output element the instruction is one
 // fp32 fma chain in the order its operands are fed.  Activation tiles go through LDS: the global reads are row-contiguous, the operand
 // reads bank-contiguous.
+#include <type_traits>
+
 #include "small_common.h"
-#include "kernels.h"
 
 namespace dinox {
+
+constexpr int LORA_MAX_RANK = 64;          // two 32-wide accumulator blocks per wave; u and v of one row chunk (2 x 128 x r floats) sit in LDS beside a 66 KiB tile
+constexpr int LORA_GRAD_CHUNK = 128;       // rows per partial sum of dinox_lora_grad: ws holds ceil(M / 128) x (r K + N r) floats
 
 // The vector forms read 4 elements of an activation row at once: 8 bytes of bf16, 16 of fp32.
 static bool row_aligned(const void* p, int dtype) { return (reinterpret_cast<uintptr_t>(p) & (dtype == DINOX_BF16 ? 7 : 15)) == 0; }
@@ -122,22 +126,6 @@ __global__ __launch_bounds__(256) void lora_down_kernel(const void* __restrict__
   chunk_dot<DT, LAYOUT>(x, row0, rows, Kd, S, r, vec != 0, svec != 0, lora_lds, u + row0 * r, rows, threadIdx.x);
 }
 
-int launch_lora_down(const void* x, const float* S, float* u, int64_t M, int Kd, int r, int layout, int dtype, hipStream_t st) {
-  const int vec = Kd % 4 == 0 && row_aligned(x, dtype), svec = layout == 0 && Kd % 4 == 0 && aligned16(S);
-  const unsigned grid = (unsigned)ceil_div(M, (int64_t)LT_ROWS);
-  const size_t lds = (size_t)LT_FLOATS * sizeof(float);
-  auto go = [&](auto dt, auto lay) -> int {
-    auto kern = lora_down_kernel<decltype(dt)::value, decltype(lay)::value>;
-    const int rc = reserve_lds((const void*)kern, lds, "lora_down");
-    if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, x, S, u, M, Kd, r, vec, svec);
-    return 0;
-  };
-  auto by_lay = [&](auto dt) { return layout ? go(dt, std::integral_constant<int, 1>{}) : go(dt, std::integral_constant<int, 0>{}); };
-  const int rc = dtype == DINOX_BF16 ? by_lay(std::integral_constant<int, DINOX_BF16>{}) : by_lay(std::integral_constant<int, DINOX_F32>{});
-  return rc ? rc : check_launch("lora_down");
-}
-
 // ---------------------------------------------------------------- up: t[M][N] = s u . S (+ res)
 // A thread owns 4 rows x VEC columns; the r-long chains run in ascending j.  LAYOUT 0: S(n, j) = S[n * r + j]; LAYOUT 1: S(n, j) = S[j * N + n].
 template <int LAYOUT, int VEC>
@@ -207,21 +195,6 @@ __global__ __launch_bounds__(256) void lora_up_kernel(const float* __restrict__ 
       t[o] = res ? q + res[o] : q;
     }
   }
-}
-
-bool lora_up_grid_ok(int64_t M, int N) { return ceil_div(ceil_div(M, 4) * (int64_t)N, 256) <= 0x7fffffff; }
-
-int launch_lora_up(const float* u, const float* S, const float* res, float* t, float s, int64_t M, int N, int r, int layout, hipStream_t st) {
-  const bool vec = N % 4 == 0 && aligned16(t, res) && (layout == 0 || aligned16(S));
-  const int64_t items = ceil_div(M, 4) * (int64_t)(vec ? N / 4 : N);
-  const unsigned grid = (unsigned)ceil_div(items, 256);
-  const int r4 = layout == 0 && r % 4 == 0 && aligned16(S, u);
-  auto go = [&](auto lay, auto v) {
-    hipLaunchKernelGGL((lora_up_kernel<decltype(lay)::value, decltype(v)::value>), dim3(grid), dim3(256), 0, st, u, S, res, t, s, M, N, r, r4);
-  };
-  auto by_vec = [&](auto lay) { vec ? go(lay, std::integral_constant<int, 4>{}) : go(lay, std::integral_constant<int, 1>{}); };
-  layout ? by_vec(std::integral_constant<int, 1>{}) : by_vec(std::integral_constant<int, 0>{});
-  return check_launch("lora_up");
 }
 
 // ---------------------------------------------------------------- grad: dA = s v^T xl, dB = s dy^T u
@@ -308,25 +281,6 @@ __global__ __launch_bounds__(256) void lora_grad_reduce_kernel(const float* __re
   else dB[e - nA] = s * acc;
 }
 
-int64_t lora_grad_chunks(int64_t M) { return ceil_div(M, (int64_t)LORA_GRAD_CHUNK); }
-
-int launch_lora_grad(const void* xl, const void* dy, const float* A, const float* B, float s, float* dA, float* dB, float* ws, int64_t M, int K,
-                     int N, int r, int dtype, hipStream_t st) {
-  const int vecK = K % 4 == 0 && row_aligned(xl, dtype), vecN = N % 4 == 0 && row_aligned(dy, dtype), avec = K % 4 == 0 && aligned16(A);
-  const int64_t chunks = lora_grad_chunks(M), nA = (int64_t)r * K, nB = (int64_t)N * r;
-  const size_t lds = ((size_t)LT_FLOATS + (size_t)2 * LT_ROWS * r) * sizeof(float);      // 66 KiB + 1 KiB per rank: 130 KiB at r = 64
-  auto go = [&](auto kern) -> int {
-    const int rc = reserve_lds((const void*)kern, lds, "lora_grad");
-    if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)chunks), dim3(256), lds, st, xl, dy, A, B, ws, M, K, N, r, vecK, vecN, avec);
-    return check_launch("lora_grad (partials)");
-  };
-  const int rc = dtype == DINOX_BF16 ? go(lora_grad_partial_kernel<DINOX_BF16>) : go(lora_grad_partial_kernel<DINOX_F32>);
-  if (rc) return rc;
-  hipLaunchKernelGGL(lora_grad_reduce_kernel, dim3((unsigned)ceil_div(nA + nB, 256)), dim3(256), 0, st, ws, dA, dB, s, (int)chunks, nA, nB);
-  return check_launch("lora_grad (sum)");
-}
-
 // ---------------------------------------------------------------- dropout without a stored mask
 __host__ __device__ static inline uint32_t lora_mix(uint32_t x) {
   x ^= x >> 16;
@@ -355,19 +309,116 @@ __global__ __launch_bounds__(256) void lora_dropout_kernel(const void* in, void*
   }
 }
 
-uint32_t lora_dropout_key(uint64_t seed, uint64_t offset) {
+static uint32_t lora_dropout_key(uint64_t seed, uint64_t offset) {
   const uint32_t ks = lora_mix((uint32_t)seed ^ lora_mix((uint32_t)(seed >> 32) + 0x9e3779b9u));
   return lora_mix((uint32_t)offset ^ lora_mix((uint32_t)(offset >> 32) + ks));
 }
 
-int launch_lora_dropout(const void* in, void* out, int64_t n, float p, uint64_t seed, uint64_t offset, int dtype, hipStream_t st) {
+}  // namespace dinox
+
+using namespace dinox;
+
+// ---------------------------------------------------------------- entry points
+static bool lora_rank_ok(int r) { return r >= 1 && r <= LORA_MAX_RANK; }
+static bool lora_dim_ok(int d) { return d >= 1 && d <= (1 << 20); }
+static bool lora_rows_ok(int64_t M) { return M >= 1 && M <= 0x7fffffff; }
+static bool lora_up_grid_ok(int64_t M, int N) { return ceil_div(ceil_div(M, 4) * (int64_t)N, 256) <= 0x7fffffff; }
+
+extern "C" int dinox_lora_down(const void* x, const float* small, float* u, int64_t M, int K, int r, int small_layout, int dtype, void* stream) {
+  DX_REQUIRE(x && small && u, DINOX_EINVAL, "lora_down: null pointer");
+  DX_REQUIRE(dtype_ok(dtype) && (small_layout == 0 || small_layout == 1), DINOX_EINVAL, "lora_down: dtype %d, small_layout %d", dtype,
+             small_layout);
+  DX_REQUIRE(lora_rank_ok(r), DINOX_EINVAL, "lora_down: r=%d (1 <= r <= %d)", r, LORA_MAX_RANK);
+  DX_REQUIRE(lora_rows_ok(M) && lora_dim_ok(K), DINOX_EINVAL, "lora_down: M=%lld K=%d (1 <= M <= 2^31 - 1; 1 <= K <= 2^20)", (long long)M, K);
+  hipStream_t st = as_stream(stream);
+  const int vec = K % 4 == 0 && row_aligned(x, dtype), svec = small_layout == 0 && K % 4 == 0 && aligned16(small);
+  const unsigned grid = (unsigned)ceil_div(M, (int64_t)LT_ROWS);
+  const size_t lds = (size_t)LT_FLOATS * sizeof(float);
+  auto go = [&](auto dt, auto lay) -> int {
+    auto kern = lora_down_kernel<decltype(dt)::value, decltype(lay)::value>;
+    const int rc = reserve_lds((const void*)kern, lds, "lora_down");
+    if (rc) return rc;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, x, small, u, M, K, r, vec, svec);
+    return 0;
+  };
+  auto by_lay = [&](auto dt) { return small_layout ? go(dt, std::integral_constant<int, 1>{}) : go(dt, std::integral_constant<int, 0>{}); };
+  const int rc = dtype == DINOX_BF16 ? by_lay(std::integral_constant<int, DINOX_BF16>{}) : by_lay(std::integral_constant<int, DINOX_F32>{});
+  return rc ? rc : check_launch("lora_down");
+}
+
+// The up product t = s u . S (+ res), for dinox_lora_up and, with B as the rows and A stored [r][K], dinox_lora_merge.
+static int lora_up(const float* u, const float* S, const float* res, float* t, float s, int64_t M, int N, int r, int layout, hipStream_t st) {
+  const bool vec = N % 4 == 0 && aligned16(t, res) && (layout == 0 || aligned16(S));
+  const int64_t items = ceil_div(M, 4) * (int64_t)(vec ? N / 4 : N);
+  const unsigned grid = (unsigned)ceil_div(items, 256);
+  const int r4 = layout == 0 && r % 4 == 0 && aligned16(S, u);
+  auto go = [&](auto lay, auto v) {
+    hipLaunchKernelGGL((lora_up_kernel<decltype(lay)::value, decltype(v)::value>), dim3(grid), dim3(256), 0, st, u, S, res, t, s, M, N, r, r4);
+  };
+  auto by_vec = [&](auto lay) { vec ? go(lay, std::integral_constant<int, 4>{}) : go(lay, std::integral_constant<int, 1>{}); };
+  layout ? by_vec(std::integral_constant<int, 1>{}) : by_vec(std::integral_constant<int, 0>{});
+  return check_launch("lora_up");
+}
+
+extern "C" int dinox_lora_up(const float* u, const float* small, const float* res, float* t, float s, int64_t M, int N, int r, int small_layout,
+                             void* stream) {
+  DX_REQUIRE(u && small && t, DINOX_EINVAL, "lora_up: null pointer");
+  DX_REQUIRE(small_layout == 0 || small_layout == 1, DINOX_EINVAL, "lora_up: small_layout %d", small_layout);
+  DX_REQUIRE(lora_rank_ok(r), DINOX_EINVAL, "lora_up: r=%d (1 <= r <= %d)", r, LORA_MAX_RANK);
+  DX_REQUIRE(lora_rows_ok(M) && lora_dim_ok(N) && lora_up_grid_ok(M, N), DINOX_EINVAL,
+             "lora_up: M=%lld N=%d (1 <= M <= 2^31 - 1; 1 <= N <= 2^20; M N / 4 <= 2^39)", (long long)M, N);
+  return lora_up(u, small, res, t, s, M, N, r, small_layout, as_stream(stream));
+}
+
+static int64_t lora_grad_chunks(int64_t M) { return ceil_div(M, (int64_t)LORA_GRAD_CHUNK); }
+
+extern "C" int64_t dinox_lora_grad_ws_bytes(int64_t M, int K, int N, int r) {
+  if (!(lora_rows_ok(M) && lora_dim_ok(K) && lora_dim_ok(N) && lora_rank_ok(r))) return 0;
+  return lora_grad_chunks(M) * ((int64_t)r * K + (int64_t)N * r) * (int64_t)sizeof(float);
+}
+
+extern "C" int dinox_lora_grad(const void* xl, const void* dy, const float* A, const float* B, float s, float* dA, float* dB, float* ws, int64_t M,
+                               int K, int N, int r, int dtype, void* stream) {
+  DX_REQUIRE(xl && dy && A && B && dA && dB && ws, DINOX_EINVAL, "lora_grad: null pointer");
+  DX_REQUIRE(dtype_ok(dtype), DINOX_EINVAL, "lora_grad: dtype %d", dtype);
+  DX_REQUIRE(lora_rank_ok(r), DINOX_EINVAL, "lora_grad: r=%d (1 <= r <= %d)", r, LORA_MAX_RANK);
+  DX_REQUIRE(lora_rows_ok(M) && lora_dim_ok(K) && lora_dim_ok(N), DINOX_EINVAL, "lora_grad: M=%lld K=%d N=%d (1 <= M <= 2^31 - 1; 1 <= K, N <= 2^20)",
+             (long long)M, K, N);
+  hipStream_t st = as_stream(stream);
+  const int vecK = K % 4 == 0 && row_aligned(xl, dtype), vecN = N % 4 == 0 && row_aligned(dy, dtype), avec = K % 4 == 0 && aligned16(A);
+  const int64_t chunks = lora_grad_chunks(M), nA = (int64_t)r * K, nB = (int64_t)N * r;
+  const size_t lds = ((size_t)LT_FLOATS + (size_t)2 * LT_ROWS * r) * sizeof(float);      // 66 KiB + 1 KiB per rank: 130 KiB at r = 64
+  auto go = [&](auto kern) -> int {
+    const int rc = reserve_lds((const void*)kern, lds, "lora_grad");
+    if (rc) return rc;
+    hipLaunchKernelGGL(kern, dim3((unsigned)chunks), dim3(256), lds, st, xl, dy, A, B, ws, M, K, N, r, vecK, vecN, avec);
+    return check_launch("lora_grad (partials)");
+  };
+  const int rc = dtype == DINOX_BF16 ? go(lora_grad_partial_kernel<DINOX_BF16>) : go(lora_grad_partial_kernel<DINOX_F32>);
+  if (rc) return rc;
+  hipLaunchKernelGGL(lora_grad_reduce_kernel, dim3((unsigned)ceil_div(nA + nB, 256)), dim3(256), 0, st, ws, dA, dB, s, (int)chunks, nA, nB);
+  return check_launch("lora_grad (sum)");
+}
+
+extern "C" int dinox_lora_dropout(const void* in, void* out, int64_t n, float p, uint64_t seed, uint64_t offset, int dtype, void* stream) {
+  DX_REQUIRE(in && out, DINOX_EINVAL, "lora_dropout: null pointer");
+  DX_REQUIRE(dtype_ok(dtype), DINOX_EINVAL, "lora_dropout: dtype %d", dtype);
+  DX_REQUIRE(p >= 0.f && p < 1.f, DINOX_EINVAL, "lora_dropout: p=%g outside [0, 1)", (double)p);
+  DX_REQUIRE(n >= 1 && n <= ((int64_t)1 << 40), DINOX_EINVAL, "lora_dropout: n=%lld (1 <= n <= 2^40)", (long long)n);
   const int vec = row_aligned(in, dtype) && row_aligned(out, dtype);
   const uint32_t key = lora_dropout_key(seed, offset);
   const uint32_t thr = (uint32_t)ceil((double)p * 16777216.0);          // keep iff the 24-bit draw >= p 2^24
   const float scale = 1.0f / (1.0f - p);
   const unsigned grid = (unsigned)ceil_div(ceil_div(n, 4), 256);
-  DX_LAUNCH_DT(lora_dropout_kernel, dtype, dim3(grid), dim3(256), st, in, out, n, scale, key, thr, vec);
+  DX_LAUNCH_DT(lora_dropout_kernel, dtype, dim3(grid), dim3(256), as_stream(stream), in, out, n, scale, key, thr, vec);
   return check_launch("lora_dropout");
 }
 
-}  // namespace dinox
+extern "C" int dinox_lora_merge(const float* w, const float* A, const float* B, float* w_out, float s, int sign, int N, int K, int r, void* stream) {
+  DX_REQUIRE(w && A && B && w_out, DINOX_EINVAL, "lora_merge: null pointer");
+  DX_REQUIRE(sign == 1 || sign == -1, DINOX_EINVAL, "lora_merge: sign %d (+1 merges, -1 unmerges)", sign);
+  DX_REQUIRE(lora_rank_ok(r), DINOX_EINVAL, "lora_merge: r=%d (1 <= r <= %d)", r, LORA_MAX_RANK);
+  DX_REQUIRE(lora_dim_ok(N) && lora_dim_ok(K) && lora_up_grid_ok(N, K), DINOX_EINVAL, "lora_merge: N=%d K=%d (1 <= N, K <= 2^20)", N, K);
+  // w_out[n][k] = w[n][k] + (sign s) sum_j B[n][j] A[j][k]: the up product with B as its rows and A stored [r][K]
+  return lora_up(B, A, w, w_out, (float)sign * s, N, K, r, 1, as_stream(stream));
+}

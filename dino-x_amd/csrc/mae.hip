@@ -9,11 +9,12 @@
 // All memory-bound.  No float atomics: every sum has a fixed order (the chains are stated at each kernel), so a step is bit-reproducible.
 // Every index read from device memory (ids_keep, ids_restore) is range-checked before it becomes an address.
 #include "small_common.h"
-#include "kernels.h"
 
 namespace dinox {
 
 constexpr int MAE_THREADS = 256;
+constexpr int MAE_MAX_L = 4096;      // patches per sample: the sort keys of one sample sit in LDS
+constexpr int MAE_MAX_PATCH = 32;    // patch edge of the loss kernels: one target patch (3 p^2 floats) sits in LDS
 
 __device__ __forceinline__ int clamp_idx(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
 
@@ -278,70 +279,6 @@ __global__ __launch_bounds__(MAE_THREADS) void mae_loss_bwd_kernel(const void* _
   }
 }
 
-// ---------------------------------------------------------------- launchers (arguments were validated by the entry points in abi.hip)
-int launch_mae_mask_ids(const float* noise, int* ids_restore, int* ids_keep, int V, int L, int Lk, hipStream_t st) {
-  hipLaunchKernelGGL(mae_mask_ids_kernel, dim3((unsigned)V), dim3(MAE_THREADS), 0, st, noise, ids_restore, ids_keep, L, Lk);
-  return check_launch("mae_mask_ids");
-}
-
-int launch_mae_gather_unfold(const float* x, const int* ids_keep, void* u, int V, int H, int W, int patch, int Lk, int ld, int dtype,
-                             hipStream_t st) {
-  const bool vec = patch % 4 == 0 && ld % 4 == 0 && aligned16(x, u);
-  const dim3 grid(grid_1d((int64_t)V * Lk * (ld / (vec ? 4 : 1)), MAE_THREADS, 4096));
-  DX_LAUNCH_DT_VW(mae_gather_unfold_kernel, dtype, vec, grid, dim3(MAE_THREADS), st, x, ids_keep, u, V, H, W, patch, Lk, ld);
-  return check_launch("mae_gather_unfold");
-}
-
-int launch_mae_tokens_fwd(const void* patches, const float* cls, const float* pos, const int* ids_keep, float* tok, int V, int L, int Lk,
-                          int D, int dtype, hipStream_t st) {
-  const bool vec = D % 4 == 0 && aligned16(patches, cls, pos, tok);
-  const dim3 grid(grid_1d((int64_t)V * (1 + Lk) * (D / (vec ? 4 : 1)), MAE_THREADS, 4096));
-  DX_LAUNCH_DT_VW(mae_tokens_fwd_kernel, dtype, vec, grid, dim3(MAE_THREADS), st, patches, cls, pos, ids_keep, tok, V, L, Lk, D);
-  return check_launch("mae_tokens_fwd");
-}
-
-int launch_mae_tokens_bwd(const float* dtok, const int* ids_restore, void* dpatches, float* dcls, float* dpos, int V, int L, int Lk, int D,
-                          int dtype, hipStream_t st) {
-  const bool vec = D % 4 == 0 && aligned16(dtok, dpatches, dcls, dpos);
-  const int DV = D / (vec ? 4 : 1), chunks = (int)ceil_div(DV, MAE_THREADS), param_blocks = (1 + L) * chunks;
-  const dim3 grid((unsigned)param_blocks + grid_1d((int64_t)V * Lk * DV, MAE_THREADS, 4096));
-  DX_LAUNCH_DT_VW(mae_tokens_bwd_kernel, dtype, vec, grid, dim3(MAE_THREADS), st, dtok, ids_restore, dpatches, dcls, dpos, V, L, Lk, D, chunks, param_blocks);
-  return check_launch("mae_tokens_bwd");
-}
-
-int launch_mae_unshuffle_fwd(const void* e, const float* mask_token, const float* dpe, const int* ids_restore, float* xd, int V, int L,
-                             int Lk, int D, int dtype, hipStream_t st) {
-  const bool vec = D % 4 == 0 && aligned16(e, mask_token, dpe, xd);
-  const dim3 grid(grid_1d((int64_t)V * (1 + L) * (D / (vec ? 4 : 1)), MAE_THREADS, 4096));
-  DX_LAUNCH_DT_VW(mae_unshuffle_fwd_kernel, dtype, vec, grid, dim3(MAE_THREADS), st, e, mask_token, dpe, ids_restore, xd, V, L, Lk, D);
-  return check_launch("mae_unshuffle_fwd");
-}
-
-int launch_mae_unshuffle_bwd(const float* g, const int* ids_keep, const int* ids_restore, void* de, float* dmask, float* ws, int V, int L,
-                             int Lk, int D, int dtype, hipStream_t st) {
-  const bool vec = D % 4 == 0 && aligned16(g, de, dmask, ws);
-  const int DV = D / (vec ? 4 : 1), chunks = (int)ceil_div(DV, MAE_THREADS), part_blocks = V * chunks;
-  const dim3 grid((unsigned)part_blocks + grid_1d((int64_t)V * (1 + Lk) * DV, MAE_THREADS, 4096));
-  DX_LAUNCH_DT_VW(mae_unshuffle_bwd_kernel, dtype, vec, grid, dim3(MAE_THREADS), st, g, ids_keep, ids_restore, de, ws, V, L, Lk, D, chunks, part_blocks);
-  int rc = check_launch("mae_unshuffle_bwd");
-  if (rc) return rc;
-  if (vec) hipLaunchKernelGGL(mae_colsum_rows_kernel<4>, dim3((unsigned)chunks), dim3(MAE_THREADS), 0, st, ws, dmask, V, D);
-  else hipLaunchKernelGGL(mae_colsum_rows_kernel<1>, dim3((unsigned)chunks), dim3(MAE_THREADS), 0, st, ws, dmask, V, D);
-  return check_launch("mae_unshuffle_bwd_mask");
-}
-
-int launch_mae_loss_fwd(const void* pred, const float* x, const int* ids_restore, float* loss, float* ws, int V, int H, int W, int patch,
-                        int Lk, int lead, int dtype, hipStream_t st) {
-  const int L = (H / patch) * (W / patch), K = 3 * patch * patch;
-  const bool vec = K % 4 == 0 && aligned16(pred);
-  const dim3 grid((unsigned)((int64_t)V * L));
-  DX_LAUNCH_DT_VW(mae_loss_rows_kernel, dtype, vec, grid, dim3(MAE_THREADS), st, pred, x, ids_restore, ws, H, W, patch, Lk, lead);
-  int rc = check_launch("mae_loss_fwd");
-  if (rc) return rc;
-  hipLaunchKernelGGL(mae_loss_mean_kernel, dim3(1), dim3(MAE_THREADS), 0, st, ws, (int64_t)V * L, (float)V * (float)(L - Lk), loss);
-  return check_launch("mae_loss_fwd_mean");
-}
-
 template <int DT, int DTO>
 static void mae_loss_bwd_vw(bool vec, dim3 grid, hipStream_t st, const void* pred, const float* x, const int* ids_restore, void* dpred, int H,
                             int W, int p, int Lk, int lead, float scale) {
@@ -349,17 +286,128 @@ static void mae_loss_bwd_vw(bool vec, dim3 grid, hipStream_t st, const void* pre
   else hipLaunchKernelGGL((mae_loss_bwd_kernel<DT, DTO, 1>), grid, dim3(MAE_THREADS), 0, st, pred, x, ids_restore, dpred, H, W, p, Lk, lead, scale);
 }
 
-int launch_mae_loss_bwd(const void* pred, const float* x, const int* ids_restore, void* dpred, float gscale, int V, int H, int W, int patch,
-                        int Lk, int lead, int dtype, int out_dtype, hipStream_t st) {
+}  // namespace dinox
+
+using namespace dinox;
+
+// ---------------------------------------------------------------- entry points
+// V samples of L patches of which 1 <= Lk < L are kept; D features.  (V * (1 + L) rows index a 32-bit grid in the loss kernels.)
+static bool mae_shape_ok(int V, int L, int Lk, int D) {
+  return V >= 1 && V <= (1 << 20) && L >= 2 && L <= MAE_MAX_L && Lk >= 1 && Lk < L && D >= 1 && D <= (1 << 16) &&
+         (int64_t)V * (1 + L) <= 0x7fffffff;
+}
+static bool mae_image_ok(int V, int H, int W, int patch, int Lk) {
+  if (!(H > 0 && W > 0 && patch > 0 && H % patch == 0 && W % patch == 0 && H <= (1 << 14) && W <= (1 << 14))) return false;
+  const int64_t L = (int64_t)(H / patch) * (W / patch);
+  return L <= MAE_MAX_L && mae_shape_ok(V, (int)L, Lk, 1);
+}
+
+extern "C" int dinox_mae_mask_ids(const float* noise, int* ids_restore, int* ids_keep, int V, int L, int Lk, void* stream) {
+  DX_REQUIRE(noise && ids_restore && ids_keep, DINOX_EINVAL, "mae_mask_ids: null pointer");
+  DX_REQUIRE(mae_shape_ok(V, L, Lk, 1), DINOX_EINVAL, "mae_mask_ids: V=%d L=%d Lk=%d (V >= 1, 2 <= L <= %d, 1 <= Lk < L)", V, L, Lk, MAE_MAX_L);
+  hipLaunchKernelGGL(mae_mask_ids_kernel, dim3((unsigned)V), dim3(MAE_THREADS), 0, as_stream(stream), noise, ids_restore, ids_keep, L, Lk);
+  return check_launch("mae_mask_ids");
+}
+
+extern "C" int dinox_mae_gather_unfold(const float* x, const int* ids_keep, void* u, int V, int H, int W, int patch, int Lk, int ld,
+                                       int out_dtype, void* stream) {
+  DX_REQUIRE(x && ids_keep && u, DINOX_EINVAL, "mae_gather_unfold: null pointer");
+  DX_REQUIRE(dtype_ok(out_dtype), DINOX_EINVAL, "mae_gather_unfold: dtype %d", out_dtype);
+  DX_REQUIRE(mae_image_ok(V, H, W, patch, Lk) && patch <= 1024 && ld >= 3 * patch * patch && ld <= (1 << 22), DINOX_EINVAL,
+             "mae_gather_unfold: V=%d H=%d W=%d patch=%d Lk=%d ld=%d (H, W multiples of patch; 2 <= L <= %d; 1 <= Lk < L; ld >= 3 patch^2)", V, H,
+             W, patch, Lk, ld, MAE_MAX_L);
+  const bool vec = patch % 4 == 0 && ld % 4 == 0 && aligned16(x, u);
+  const dim3 grid(grid_1d((int64_t)V * Lk * (ld / (vec ? 4 : 1)), MAE_THREADS, 4096));
+  DX_LAUNCH_DT_VW(mae_gather_unfold_kernel, out_dtype, vec, grid, dim3(MAE_THREADS), as_stream(stream), x, ids_keep, u, V, H, W, patch, Lk, ld);
+  return check_launch("mae_gather_unfold");
+}
+
+extern "C" int dinox_mae_tokens_fwd(const void* patches, const float* cls, const float* pos, const int* ids_keep, float* tokens, int V, int L,
+                                    int Lk, int D, int patches_dtype, void* stream) {
+  DX_REQUIRE(patches && cls && pos && ids_keep && tokens, DINOX_EINVAL, "mae_tokens_fwd: null pointer");
+  DX_REQUIRE(dtype_ok(patches_dtype), DINOX_EINVAL, "mae_tokens_fwd: dtype %d", patches_dtype);
+  DX_REQUIRE(mae_shape_ok(V, L, Lk, D), DINOX_EINVAL, "mae_tokens_fwd: V=%d L=%d Lk=%d D=%d (2 <= L <= %d, 1 <= Lk < L)", V, L, Lk, D, MAE_MAX_L);
+  const bool vec = D % 4 == 0 && aligned16(patches, cls, pos, tokens);
+  const dim3 grid(grid_1d((int64_t)V * (1 + Lk) * (D / (vec ? 4 : 1)), MAE_THREADS, 4096));
+  DX_LAUNCH_DT_VW(mae_tokens_fwd_kernel, patches_dtype, vec, grid, dim3(MAE_THREADS), as_stream(stream), patches, cls, pos, ids_keep, tokens, V, L, Lk, D);
+  return check_launch("mae_tokens_fwd");
+}
+
+extern "C" int dinox_mae_tokens_bwd(const float* dtokens, const int* ids_restore, void* dpatches, float* dcls, float* dpos, int V, int L, int Lk,
+                                    int D, int patches_dtype, void* stream) {
+  DX_REQUIRE(dtokens && ids_restore && dpatches && dcls && dpos, DINOX_EINVAL, "mae_tokens_bwd: null pointer");
+  DX_REQUIRE(dtype_ok(patches_dtype), DINOX_EINVAL, "mae_tokens_bwd: dtype %d", patches_dtype);
+  DX_REQUIRE(mae_shape_ok(V, L, Lk, D), DINOX_EINVAL, "mae_tokens_bwd: V=%d L=%d Lk=%d D=%d (2 <= L <= %d, 1 <= Lk < L)", V, L, Lk, D, MAE_MAX_L);
+  const bool vec = D % 4 == 0 && aligned16(dtokens, dpatches, dcls, dpos);
+  const int DV = D / (vec ? 4 : 1), chunks = (int)ceil_div(DV, MAE_THREADS), param_blocks = (1 + L) * chunks;
+  const dim3 grid((unsigned)param_blocks + grid_1d((int64_t)V * Lk * DV, MAE_THREADS, 4096));
+  DX_LAUNCH_DT_VW(mae_tokens_bwd_kernel, patches_dtype, vec, grid, dim3(MAE_THREADS), as_stream(stream), dtokens, ids_restore, dpatches, dcls, dpos, V, L,
+                  Lk, D, chunks, param_blocks);
+  return check_launch("mae_tokens_bwd");
+}
+
+extern "C" int dinox_mae_unshuffle_fwd(const void* e, const float* mask_token, const float* dec_pos, const int* ids_restore, float* xd, int V,
+                                       int L, int Lk, int D, int e_dtype, void* stream) {
+  DX_REQUIRE(e && mask_token && dec_pos && ids_restore && xd, DINOX_EINVAL, "mae_unshuffle_fwd: null pointer");
+  DX_REQUIRE(dtype_ok(e_dtype), DINOX_EINVAL, "mae_unshuffle_fwd: dtype %d", e_dtype);
+  DX_REQUIRE(mae_shape_ok(V, L, Lk, D), DINOX_EINVAL, "mae_unshuffle_fwd: V=%d L=%d Lk=%d D=%d (2 <= L <= %d, 1 <= Lk < L)", V, L, Lk, D, MAE_MAX_L);
+  const bool vec = D % 4 == 0 && aligned16(e, mask_token, dec_pos, xd);
+  const dim3 grid(grid_1d((int64_t)V * (1 + L) * (D / (vec ? 4 : 1)), MAE_THREADS, 4096));
+  DX_LAUNCH_DT_VW(mae_unshuffle_fwd_kernel, e_dtype, vec, grid, dim3(MAE_THREADS), as_stream(stream), e, mask_token, dec_pos, ids_restore, xd, V, L, Lk, D);
+  return check_launch("mae_unshuffle_fwd");
+}
+
+extern "C" int dinox_mae_unshuffle_bwd(const float* g, const int* ids_keep, const int* ids_restore, void* de, float* dmask_token, float* ws,
+                                       int V, int L, int Lk, int D, int de_dtype, void* stream) {
+  DX_REQUIRE(g && ids_keep && ids_restore && de && dmask_token && ws, DINOX_EINVAL, "mae_unshuffle_bwd: null pointer");
+  DX_REQUIRE(dtype_ok(de_dtype), DINOX_EINVAL, "mae_unshuffle_bwd: dtype %d", de_dtype);
+  DX_REQUIRE(mae_shape_ok(V, L, Lk, D), DINOX_EINVAL, "mae_unshuffle_bwd: V=%d L=%d Lk=%d D=%d (2 <= L <= %d, 1 <= Lk < L)", V, L, Lk, D, MAE_MAX_L);
+  hipStream_t st = as_stream(stream);
+  const bool vec = D % 4 == 0 && aligned16(g, de, dmask_token, ws);
+  const int DV = D / (vec ? 4 : 1), chunks = (int)ceil_div(DV, MAE_THREADS), part_blocks = V * chunks;
+  const dim3 grid((unsigned)part_blocks + grid_1d((int64_t)V * (1 + Lk) * DV, MAE_THREADS, 4096));
+  DX_LAUNCH_DT_VW(mae_unshuffle_bwd_kernel, de_dtype, vec, grid, dim3(MAE_THREADS), st, g, ids_keep, ids_restore, de, ws, V, L, Lk, D, chunks, part_blocks);
+  int rc = check_launch("mae_unshuffle_bwd");
+  if (rc) return rc;
+  if (vec) hipLaunchKernelGGL(mae_colsum_rows_kernel<4>, dim3((unsigned)chunks), dim3(MAE_THREADS), 0, st, ws, dmask_token, V, D);
+  else hipLaunchKernelGGL(mae_colsum_rows_kernel<1>, dim3((unsigned)chunks), dim3(MAE_THREADS), 0, st, ws, dmask_token, V, D);
+  return check_launch("mae_unshuffle_bwd_mask");
+}
+
+extern "C" int dinox_mae_loss_fwd(const void* pred, const float* x, const int* ids_restore, float* loss, float* ws, int V, int H, int W, int patch,
+                                  int Lk, int lead, int pred_dtype, void* stream) {
+  DX_REQUIRE(pred && x && ids_restore && loss && ws, DINOX_EINVAL, "mae_loss_fwd: null pointer");
+  DX_REQUIRE(dtype_ok(pred_dtype), DINOX_EINVAL, "mae_loss_fwd: dtype %d", pred_dtype);
+  DX_REQUIRE(mae_image_ok(V, H, W, patch, Lk) && patch <= MAE_MAX_PATCH && (lead == 0 || lead == 1), DINOX_EINVAL,
+             "mae_loss_fwd: V=%d H=%d W=%d patch=%d Lk=%d lead=%d (H, W multiples of patch <= %d; 2 <= L <= %d; 1 <= Lk < L; lead 0 or 1)", V, H, W,
+             patch, Lk, lead, MAE_MAX_PATCH, MAE_MAX_L);
+  hipStream_t st = as_stream(stream);
+  const int L = (H / patch) * (W / patch), K = 3 * patch * patch;
+  const bool vec = K % 4 == 0 && aligned16(pred);
+  const dim3 grid((unsigned)((int64_t)V * L));
+  DX_LAUNCH_DT_VW(mae_loss_rows_kernel, pred_dtype, vec, grid, dim3(MAE_THREADS), st, pred, x, ids_restore, ws, H, W, patch, Lk, lead);
+  int rc = check_launch("mae_loss_fwd");
+  if (rc) return rc;
+  hipLaunchKernelGGL(mae_loss_mean_kernel, dim3(1), dim3(MAE_THREADS), 0, st, ws, (int64_t)V * L, (float)V * (float)(L - Lk), loss);
+  return check_launch("mae_loss_fwd_mean");
+}
+
+extern "C" int dinox_mae_loss_bwd(const void* pred, const float* x, const int* ids_restore, void* dpred, float gscale, int V, int H, int W,
+                                  int patch, int Lk, int lead, int pred_dtype, int dpred_dtype, void* stream) {
+  DX_REQUIRE(pred && x && ids_restore && dpred, DINOX_EINVAL, "mae_loss_bwd: null pointer");
+  DX_REQUIRE(dtype_ok(pred_dtype) && dtype_ok(dpred_dtype), DINOX_EINVAL, "mae_loss_bwd: dtypes %d, %d", pred_dtype, dpred_dtype);
+  DX_REQUIRE(mae_image_ok(V, H, W, patch, Lk) && patch <= MAE_MAX_PATCH && (lead == 0 || lead == 1), DINOX_EINVAL,
+             "mae_loss_bwd: V=%d H=%d W=%d patch=%d Lk=%d lead=%d (H, W multiples of patch <= %d; 2 <= L <= %d; 1 <= Lk < L; lead 0 or 1)", V, H, W,
+             patch, Lk, lead, MAE_MAX_PATCH, MAE_MAX_L);
+  DX_REQUIRE(dpred != pred, DINOX_EINVAL, "mae_loss_bwd: dpred must not alias pred");
+  hipStream_t st = as_stream(stream);
   const int L = (H / patch) * (W / patch), K = 3 * patch * patch;
   const bool vec = K % 4 == 0 && aligned16(pred, dpred);
   const dim3 grid((unsigned)((int64_t)V * (lead + L)));
   const float scale = (float)((double)gscale * 2.0 / ((double)K * (double)V * (double)(L - Lk)));
-  if (dtype == DINOX_F32 && out_dtype == DINOX_F32) mae_loss_bwd_vw<DINOX_F32, DINOX_F32>(vec, grid, st, pred, x, ids_restore, dpred, H, W, patch, Lk, lead, scale);
-  else if (dtype == DINOX_F32) mae_loss_bwd_vw<DINOX_F32, DINOX_BF16>(vec, grid, st, pred, x, ids_restore, dpred, H, W, patch, Lk, lead, scale);
-  else if (out_dtype == DINOX_F32) mae_loss_bwd_vw<DINOX_BF16, DINOX_F32>(vec, grid, st, pred, x, ids_restore, dpred, H, W, patch, Lk, lead, scale);
+  if (pred_dtype == DINOX_F32 && dpred_dtype == DINOX_F32) mae_loss_bwd_vw<DINOX_F32, DINOX_F32>(vec, grid, st, pred, x, ids_restore, dpred, H, W, patch, Lk, lead, scale);
+  else if (pred_dtype == DINOX_F32) mae_loss_bwd_vw<DINOX_F32, DINOX_BF16>(vec, grid, st, pred, x, ids_restore, dpred, H, W, patch, Lk, lead, scale);
+  else if (dpred_dtype == DINOX_F32) mae_loss_bwd_vw<DINOX_BF16, DINOX_F32>(vec, grid, st, pred, x, ids_restore, dpred, H, W, patch, Lk, lead, scale);
   else mae_loss_bwd_vw<DINOX_BF16, DINOX_BF16>(vec, grid, st, pred, x, ids_restore, dpred, H, W, patch, Lk, lead, scale);
   return check_launch("mae_loss_bwd");
 }
-
-}  // namespace dinox

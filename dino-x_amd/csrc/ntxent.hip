@@ -11,7 +11,6 @@
 // similarity matmul in bf16; this engine stays at fp32 there, i.e. closer to the reference's own fp32 step.
 // No float atomics: every sum has a fixed order, so a step is bit-reproducible.
 #include "small_common.h"
-#include "kernels.h"
 
 namespace dinox {
 
@@ -171,7 +170,17 @@ __global__ __launch_bounds__(NX_THREADS) void normalize_bwd_kernel(const float* 
   for (int d = 4 * D4 + threadIdx.x; d < D; d += NX_THREADS) o[d] = (g[d] - u[d] * c) * inv;
 }
 
-int launch_ntxent_rows(const float* S, int64_t lds, int M, float inv_tau, float* lse, float* row_loss, float* loss, hipStream_t st) {
+}  // namespace dinox
+
+using namespace dinox;
+
+static bool ntxent_rows_ok(int M) { return M >= 2 && M % 2 == 0 && M <= 65535 * 32; }
+
+extern "C" int dinox_ntxent_rows(const float* S, int64_t lds, int M, float inv_tau, float* lse, float* row_loss, float* loss, void* stream) {
+  DX_REQUIRE(S && lse && row_loss && loss, DINOX_EINVAL, "ntxent_rows: null pointer");
+  DX_REQUIRE(ntxent_rows_ok(M), DINOX_EINVAL, "ntxent_rows: M=%d (the rows are [z1; z2]: an even count of at least 2)", M);
+  DX_REQUIRE(lds >= M && inv_tau > 0.f, DINOX_EINVAL, "ntxent_rows: lds=%lld M=%d inv_tau=%g", (long long)lds, M, (double)inv_tau);
+  hipStream_t st = as_stream(stream);
   hipLaunchKernelGGL(ntxent_rows_kernel, dim3((unsigned)M), dim3(NX_THREADS), 0, st, S, lds, M, inv_tau, lse, row_loss);
   const int rc = check_launch("ntxent_rows");
   if (rc) return rc;
@@ -179,36 +188,62 @@ int launch_ntxent_rows(const float* S, int64_t lds, int M, float inv_tau, float*
   return check_launch("ntxent_rows_mean");
 }
 
-int launch_ntxent_coeff(const float* S, int64_t lds, const float* lse, int M, float inv_tau, float gscale, float* W, int64_t ldw,
-                        hipStream_t st) {
+extern "C" int dinox_ntxent_coeff(const float* S, int64_t lds, const float* lse, int M, float inv_tau, float gscale, float* W, int64_t ldw,
+                                  void* stream) {
+  DX_REQUIRE(S && lse && W, DINOX_EINVAL, "ntxent_coeff: null pointer");
+  DX_REQUIRE(ntxent_rows_ok(M), DINOX_EINVAL, "ntxent_coeff: M=%d (the rows are [z1; z2]: an even count of at least 2)", M);
+  DX_REQUIRE(lds >= M && ldw >= M && inv_tau > 0.f, DINOX_EINVAL, "ntxent_coeff: lds=%lld ldw=%lld M=%d inv_tau=%g", (long long)lds,
+             (long long)ldw, M, (double)inv_tau);
+  DX_REQUIRE(W != S, DINOX_EINVAL, "ntxent_coeff: W must not alias S (a tile reads its mirror image, which another workgroup writes)");
   const unsigned tiles = (unsigned)ceil_div(M, NX_TILE);
   const float scale = gscale * inv_tau / (float)M;
-  hipLaunchKernelGGL(ntxent_coeff_kernel, dim3(tiles, tiles), dim3(NX_THREADS), 0, st, S, lds, lse, M, inv_tau, scale, W, ldw);
+  hipLaunchKernelGGL(ntxent_coeff_kernel, dim3(tiles, tiles), dim3(NX_THREADS), 0, as_stream(stream), S, lds, lse, M, inv_tau, scale, W, ldw);
   return check_launch("ntxent_coeff");
 }
 
-int launch_ntxent_rows_rect(const float* S, int64_t lds, int Ml, int Mg, int row0, int Bl, float inv_tau, float* lse, float* row_loss,
-                            float* loss_sum, hipStream_t st) {
+// The rectangular forms: Ml = 2 Bl local rows against Mg = world * Ml gathered columns, this rank's block at column row0.
+static int ntxent_rect_ok(const char* what, int64_t lds, int Ml, int Mg, int row0, int Bl, float inv_tau) {
+  DX_REQUIRE(ntxent_rows_ok(Ml), DINOX_EINVAL, "%s: Ml=%d (the local rows are [z1; z2]: an even count of at least 2)", what, Ml);
+  DX_REQUIRE(Bl * 2 == Ml, DINOX_EINVAL, "%s: Bl=%d is not half of Ml=%d", what, Bl, Ml);
+  DX_REQUIRE(Mg >= Ml && Mg % Ml == 0 && Mg <= 65535 * 32, DINOX_EINVAL, "%s: Mg=%d is not a multiple of Ml=%d (every rank holds Ml rows)", what,
+             Mg, Ml);
+  DX_REQUIRE(row0 >= 0 && row0 <= Mg - Ml && row0 % Ml == 0, DINOX_EINVAL, "%s: row0=%d is not the start of a rank's block (Ml=%d, Mg=%d)", what,
+             row0, Ml, Mg);
+  DX_REQUIRE(lds >= Mg && inv_tau > 0.f, DINOX_EINVAL, "%s: lds=%lld Mg=%d inv_tau=%g", what, (long long)lds, Mg, (double)inv_tau);
+  return 0;
+}
+
+extern "C" int dinox_ntxent_rows_rect(const float* S, int64_t lds, int Ml, int Mg, int row0, int Bl, float inv_tau, float* lse, float* row_loss,
+                                      float* loss_sum, void* stream) {
+  DX_REQUIRE(S && lse && row_loss && loss_sum, DINOX_EINVAL, "ntxent_rows_rect: null pointer");
+  int rc = ntxent_rect_ok("ntxent_rows_rect", lds, Ml, Mg, row0, Bl, inv_tau);
+  if (rc) return rc;
+  hipStream_t st = as_stream(stream);
   hipLaunchKernelGGL(ntxent_rows_rect_kernel, dim3((unsigned)Ml), dim3(NX_THREADS), 0, st, S, lds, Mg, row0, Bl, inv_tau, lse, row_loss);
-  const int rc = check_launch("ntxent_rows_rect");
+  rc = check_launch("ntxent_rows_rect");
   if (rc) return rc;
   hipLaunchKernelGGL(ntxent_sum_kernel, dim3(1), dim3(NX_THREADS), 0, st, row_loss, Ml, 1.0f, loss_sum);
   return check_launch("ntxent_rows_rect_sum");
 }
 
-int launch_ntxent_coeff_rect(const float* S, int64_t lds, const float* lse_local, const float* lse_all, int Ml, int Mg, int row0, int Bl,
-                             float inv_tau, float gscale, float* W, int64_t ldw, hipStream_t st) {
+extern "C" int dinox_ntxent_coeff_rect(const float* S, int64_t lds, const float* lse_local, const float* lse_all, int Ml, int Mg, int row0,
+                                       int Bl, float inv_tau, float gscale, float* W, int64_t ldw, void* stream) {
+  DX_REQUIRE(S && lse_local && lse_all && W, DINOX_EINVAL, "ntxent_coeff_rect: null pointer");
+  const int rc = ntxent_rect_ok("ntxent_coeff_rect", lds, Ml, Mg, row0, Bl, inv_tau);
+  if (rc) return rc;
+  DX_REQUIRE(ldw >= Mg, DINOX_EINVAL, "ntxent_coeff_rect: ldw=%lld Mg=%d", (long long)ldw, Mg);
   const float scale = gscale * inv_tau / (float)Ml;
-  hipLaunchKernelGGL(ntxent_coeff_rect_kernel, dim3((unsigned)ceil_div(Mg, NX_TILE), (unsigned)ceil_div(Ml, NX_TILE)), dim3(NX_THREADS), 0, st,
-                     S, lds, lse_local, lse_all, Ml, Mg, row0, Bl, inv_tau, scale, W, ldw);
+  hipLaunchKernelGGL(ntxent_coeff_rect_kernel, dim3((unsigned)ceil_div(Mg, NX_TILE), (unsigned)ceil_div(Ml, NX_TILE)), dim3(NX_THREADS), 0,
+                     as_stream(stream), S, lds, lse_local, lse_all, Ml, Mg, row0, Bl, inv_tau, scale, W, ldw);
   return check_launch("ntxent_coeff_rect");
 }
 
-int launch_normalize_bwd(const float* dxh, const float* xh, const float* norm, float* dx, int64_t V, int D, float eps, hipStream_t st) {
+extern "C" int dinox_normalize_bwd(const float* dxh, const float* xh, const float* norm, float* dx, int64_t V, int D, float eps, void* stream) {
+  DX_REQUIRE(dxh && xh && norm && dx, DINOX_EINVAL, "normalize_bwd: null pointer");
+  DX_REQUIRE(V > 0 && V <= 0x7fffffff && D > 0 && eps > 0.f, DINOX_EINVAL, "normalize_bwd: V=%lld D=%d eps=%g", (long long)V, D, (double)eps);
+  hipStream_t st = as_stream(stream);
   const bool vec = D % 4 == 0 && aligned16(dxh, xh, dx);
   if (vec) hipLaunchKernelGGL(normalize_bwd_kernel<true>, dim3((unsigned)V), dim3(NX_THREADS), 0, st, dxh, xh, norm, dx, D, eps);
   else hipLaunchKernelGGL(normalize_bwd_kernel<false>, dim3((unsigned)V), dim3(NX_THREADS), 0, st, dxh, xh, norm, dx, D, eps);
   return check_launch("normalize_bwd");
 }
-
-}  // namespace dinox

@@ -1,6 +1,6 @@
 // segloss.hip -- dense segmentation loss on patch logits: bilinear upsampling (align_corners = False), softmax, cross-entropy and soft Dice,
-// their gradient, and the arg-max prediction, without a full-resolution logit tensor in memory in either direction (entry points and
-// argument checks: abi.hip; definitions: include/dinox.h).
+// their gradient, and the arg-max prediction, without a full-resolution logit tensor in memory in either direction (definitions:
+// include/dinox.h).
 //
 // Layout.  The S x S pixels of an image fall into g x g CELLS: cell (cy, cx) holds the pixels whose upper-left tap is patch (cy, cx), i.e.
 // rows [lo(cy), lo(cy + 1)) and columns [lo(cx), lo(cx + 1)) with lo(0) = 0, lo(k) = k u + u / 2, lo(g) = S.  Every pixel of a cell
@@ -17,6 +17,8 @@
 namespace dinox {
 
 constexpr int SEG_WAVES = 4;                      // waves (= cells in flight) per workgroup
+constexpr int SEG_MAX_UPSAMPLE = 32;              // a cell (the pixels that share their four taps) is at most 1.5 u = 48 columns: one wave row
+constexpr int SEG_FWD_CELLS = 8;                  // cells per partial sum of dinox_seg_loss_fwd
 
 __device__ __forceinline__ int seg_lo(int k, int g, int u, int S) { return k <= 0 ? 0 : (k >= g ? S : k * u + u / 2); }
 
@@ -347,16 +349,50 @@ static inline void seg_by_width(int C, F&& f) {
 
 static int seg_wide(const void* p, int u) { return u % 8 == 0 && (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 
-int64_t seg_fwd_parts(int64_t B, int g) { return ceil_div(B * g * g, (int64_t)SEG_FWD_CELLS); }
+static int64_t seg_fwd_parts(int64_t B, int g) { return ceil_div(B * g * g, (int64_t)SEG_FWD_CELLS); }
 
-int64_t seg_loss_ws_bytes(int64_t B, int g, int C) {
+}  // namespace dinox
+
+using namespace dinox;
+
+// ---------------------------------------------------------------- entry points
+// The size limits, said once: 0 when (B, g, u, C) is inside all of them, else the number of the first one broken (seg_geometry words it).
+// B g^2 cells and B S^2 pixels stay far inside int64 and the grids inside 2^31 - 1.
+static int seg_broken_limit(int64_t B, int g, int u, int C) {
+  if (!(B >= 1 && B <= (1 << 20) && g >= 1 && g <= 4096)) return 1;
+  if (!(u >= 1 && u <= SEG_MAX_UPSAMPLE)) return 2;
+  if (!(C >= 2)) return 3;
+  if (!(C <= SEG_MAX_CLASSES)) return 4;
+  if (!(B * g * g <= ((int64_t)1 << 32))) return 5;
+  return 0;
+}
+
+// 0, or the error code after the message is set.
+static int seg_geometry(const char* who, int64_t B, int g, int u, int C) {
+  switch (seg_broken_limit(B, g, u, C)) {
+    case 1: return fail(DINOX_EINVAL, "%s: B=%lld g=%d (1 <= B <= 2^20; 1 <= g <= 4096)", who, (long long)B, g);
+    case 2: return fail(DINOX_EINVAL, "%s: u=%d (1 <= u <= %d)", who, u, SEG_MAX_UPSAMPLE);
+    case 3: return fail(DINOX_EINVAL, "%s: C=%d (2 <= C <= %d)", who, C, SEG_MAX_CLASSES);
+    case 4: return fail(DINOX_EUNSUPPORTED, "%s: C=%d classes: at most %d are held in registers", who, C, SEG_MAX_CLASSES);
+    case 5: return fail(DINOX_EINVAL, "%s: B g^2 = %lld cells (at most 2^32)", who, (long long)(B * g * g));
+  }
+  return 0;
+}
+
+extern "C" int64_t dinox_seg_loss_ws_bytes(int64_t B, int g, int u, int C) {
+  if (seg_broken_limit(B, g, u, C)) return 0;
   const int64_t ncell = B * g * g, parts = seg_fwd_parts(B, g);
   const int64_t fwd = parts * (1 + 2 * C) * 4 + parts * (C + 2) * 4, bwd = ncell * 4 * C * 4;
   return fwd > bwd ? fwd : bwd;
 }
 
-int launch_seg_loss_fwd(const float* z, const uint8_t* y, float* loss, float* stats, int64_t* nv, void* ws, int64_t B, int g, int u, int C, int c0,
-                        float w_ce, float w_dice, hipStream_t st) {
+extern "C" int dinox_seg_loss_fwd(const float* z, const uint8_t* y, float* loss, float* stats, int64_t* nv, void* ws, int64_t B, int g, int u, int C,
+                                  int c0, float w_ce, float w_dice, void* stream) {
+  DX_REQUIRE(z && y && loss && stats && nv && ws, DINOX_EINVAL, "seg_loss_fwd: null pointer");
+  int rc = seg_geometry("seg_loss_fwd", B, g, u, C);
+  if (rc) return rc;
+  DX_REQUIRE(c0 == 0 || c0 == 1, DINOX_EINVAL, "seg_loss_fwd: c0=%d (0: every class in the Dice term, 1: without class 0)", c0);
+  hipStream_t st = as_stream(stream);
   const int64_t ncell = B * g * g, parts = seg_fwd_parts(B, g);
   float* wsf = (float*)ws;
   unsigned* wsi = (unsigned*)(wsf + parts * (1 + 2 * C));
@@ -366,14 +402,19 @@ int launch_seg_loss_fwd(const float* z, const uint8_t* y, float* loss, float* st
     hipLaunchKernelGGL((seg_fwd_partial_kernel<decltype(cp)::value>), dim3(grid), dim3(64 * SEG_WAVES), 0, st, z, y, wsf, wsi, g, u, C, inv2u,
                        seg_wide(y, u), ncell, parts);
   });
-  int rc = check_launch("seg_loss_fwd (partials)");
+  rc = check_launch("seg_loss_fwd (partials)");
   if (rc) return rc;
   hipLaunchKernelGGL(seg_fwd_final_kernel, dim3(1), dim3(256), 0, st, wsf, wsi, loss, stats, nv, C, c0, w_ce, w_dice, parts);
   return check_launch("seg_loss_fwd (sum)");
 }
 
-int launch_seg_loss_bwd(const float* z, const uint8_t* y, const float* stats, const int64_t* nv, float* dz, void* ws, int64_t B, int g, int u, int C,
-                        int c0, float w_ce, float w_dice, float gscale, hipStream_t st) {
+extern "C" int dinox_seg_loss_bwd(const float* z, const uint8_t* y, const float* stats, const int64_t* nv, float* dz, void* ws, int64_t B, int g,
+                                  int u, int C, int c0, float w_ce, float w_dice, float grad_scale, void* stream) {
+  DX_REQUIRE(z && y && stats && nv && dz && ws, DINOX_EINVAL, "seg_loss_bwd: null pointer");
+  int rc = seg_geometry("seg_loss_bwd", B, g, u, C);
+  if (rc) return rc;
+  DX_REQUIRE(c0 == 0 || c0 == 1, DINOX_EINVAL, "seg_loss_bwd: c0=%d (0: every class in the Dice term, 1: without class 0)", c0);
+  hipStream_t st = as_stream(stream);
   const int64_t ncell = B * g * g;
   float* wsb = (float*)ws;
   const unsigned grid = (unsigned)ceil_div(ncell, (int64_t)SEG_WAVES);
@@ -382,14 +423,19 @@ int launch_seg_loss_bwd(const float* z, const uint8_t* y, const float* stats, co
     hipLaunchKernelGGL((seg_bwd_cells_kernel<decltype(cp)::value>), dim3(grid), dim3(64 * SEG_WAVES), 0, st, z, y, stats, nv, wsb, g, u, C, c0, w_ce,
                        w_dice, inv2u, seg_wide(y, u), ncell);
   });
-  int rc = check_launch("seg_loss_bwd (cells)");
+  rc = check_launch("seg_loss_bwd (cells)");
   if (rc) return rc;
   const int64_t total = ncell * C;
-  hipLaunchKernelGGL(seg_bwd_gather_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, st, wsb, dz, gscale, g, C, total);
+  hipLaunchKernelGGL(seg_bwd_gather_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, st, wsb, dz, grad_scale, g, C, total);
   return check_launch("seg_loss_bwd (gather)");
 }
 
-int launch_seg_predict(const float* z, const uint8_t* y, uint8_t* pred, int64_t* counts, int64_t B, int g, int u, int C, hipStream_t st) {
+extern "C" int dinox_seg_predict(const float* z, const uint8_t* y, uint8_t* pred, int64_t* counts, int64_t B, int g, int u, int C, void* stream) {
+  DX_REQUIRE(z && pred, DINOX_EINVAL, "seg_predict: null pointer");
+  DX_REQUIRE((y == nullptr) == (counts == nullptr), DINOX_EINVAL, "seg_predict: labels and counts come together (both or neither)");
+  const int rc = seg_geometry("seg_predict", B, g, u, C);
+  if (rc) return rc;
+  hipStream_t st = as_stream(stream);
   const int64_t ncell = B * g * g;
   if (counts) {
     const hipError_t e = hipMemsetAsync(counts, 0, (size_t)(3 * C + 1) * sizeof(int64_t), st);
@@ -403,5 +449,3 @@ int launch_seg_predict(const float* z, const uint8_t* y, uint8_t* pred, int64_t*
   });
   return check_launch("seg_predict");
 }
-
-}  // namespace dinox

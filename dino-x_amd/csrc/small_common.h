@@ -19,6 +19,9 @@ static inline bool aligned16(const P*... p) {
   return ((... | (uintptr_t)p) & 15) == 0;
 }
 
+// The two element types of the small kernels (what DX_LAUNCH_DT below can launch).
+static inline bool dtype_ok(int dt) { return dt == DINOX_F32 || dt == DINOX_BF16; }
+
 // ---------------------------------------------------------------- device: VW = 1 (any size) or 4 (16-byte fp32 / 8-byte bf16) row elements
 template <int VW>
 struct fvec {

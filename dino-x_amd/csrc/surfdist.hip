@@ -1,6 +1,6 @@
 // surfdist.hip -- surface distances between two label maps in mm: per (image, class, direction) the number of border pixels, the sum, the
-// maximum and a nearest-rank quantile of their distances to the other map's border, and the number within each tolerance (entry point
-// and argument checks: abi.hip; definitions: include/dinox.h).  An exact separable Euclidean distance transform, three launches:
+// maximum and a nearest-rank quantile of their distances to the other map's border, and the number within each tolerance (definitions:
+// include/dinox.h).  An exact separable Euclidean distance transform, three launches:
 //
 //   1. surf_columns_kernel: a THREAD per column of one (image, plane in {pred, gt}, class), lanes along x.  It reads the label maps as
 //      they are (no one-hot planes), decides border membership from the four edge neighbours and writes per pixel the vertical distance in
@@ -22,6 +22,8 @@
 
 namespace dinox {
 
+constexpr int SURF_MAX_SIDE = 1024;                // a row of squared column distances (4 KiB) sits in LDS; a column distance fits uint16 beside its sentinel
+constexpr int SURF_MAX_TOL = 8;                    // tolerance counters per lane, in registers
 constexpr unsigned SURF_NONE = 0xffffu;            // column distance: no border pixel in this column (a real one is at most 1023)
 constexpr float SURF_SKIP = -1.0f;                 // distance plane: not a border pixel of the query side (sign bit set)
 constexpr unsigned SURF_INF = 0x7f800000u;         // distance plane: the other side has no border at all
@@ -202,11 +204,33 @@ __global__ __launch_bounds__(256) void surf_reduce_kernel(const float* __restric
   }
 }
 
-// ---------------------------------------------------------------- host
-int64_t surface_ws_bytes(int64_t B, int H, int W, int C) { return B * C * 2 * (int64_t)H * W * (int64_t)(sizeof(uint16_t) + sizeof(float)); }
+}  // namespace dinox
 
-int launch_surface_stats(const uint8_t* pred, const uint8_t* gt, const float* spacing, const float* tol, int64_t* counts, float* values, int64_t* bad,
-                         void* ws, int64_t B, int H, int W, int C, int T, int q_num, int q_den, hipStream_t st) {
+using namespace dinox;
+
+// ---------------------------------------------------------------- entry points
+// B C 2 H workgroups (the row launch) stay inside 2^30 and every plane index inside int64.
+static bool surface_sizes_ok(int64_t B, int H, int W, int C) {
+  return B >= 1 && B <= (1 << 20) && H >= 1 && H <= SURF_MAX_SIDE && W >= 1 && W <= SURF_MAX_SIDE && C >= 2 && C <= SEG_MAX_CLASSES &&
+         B * C * 2 * H <= ((int64_t)1 << 30);
+}
+
+extern "C" int64_t dinox_surface_ws_bytes(int64_t B, int H, int W, int C) {
+  return surface_sizes_ok(B, H, W, C) ? B * C * 2 * (int64_t)H * W * (int64_t)(sizeof(uint16_t) + sizeof(float)) : 0;
+}
+
+extern "C" int dinox_surface_stats(const uint8_t* pred, const uint8_t* gt, const float* spacing, const float* tol, int64_t* counts, float* values,
+                                   int64_t* bad, void* ws, int64_t B, int H, int W, int C, int T, int q_num, int q_den, void* stream) {
+  DX_REQUIRE(pred && gt && spacing && tol && counts && values && bad && ws, DINOX_EINVAL, "surface_stats: null pointer");
+  DX_REQUIRE(H >= 1 && H <= SURF_MAX_SIDE && W >= 1 && W <= SURF_MAX_SIDE, DINOX_EINVAL, "surface_stats: H=%d W=%d (1 <= H, W <= %d)", H, W,
+             SURF_MAX_SIDE);
+  DX_REQUIRE(C >= 2 && C <= SEG_MAX_CLASSES, DINOX_EINVAL, "surface_stats: C=%d (2 <= C <= %d)", C, SEG_MAX_CLASSES);
+  DX_REQUIRE(surface_sizes_ok(B, H, W, C), DINOX_EINVAL, "surface_stats: B=%lld (B >= 1 and B C 2 H <= 2^30; evaluate a longer batch in pieces)",
+             (long long)B);
+  DX_REQUIRE(T >= 1 && T <= SURF_MAX_TOL, DINOX_EINVAL, "surface_stats: T=%d tolerances (1 <= T <= %d)", T, SURF_MAX_TOL);
+  for (int t = 0; t < T; ++t) DX_REQUIRE(tol[t] >= 0.f && tol[t] <= 3.0e38f, DINOX_EINVAL, "surface_stats: tolerance %d is %g (finite and >= 0)", t, (double)tol[t]);
+  DX_REQUIRE(q_num > 0 && q_num <= q_den, DINOX_EINVAL, "surface_stats: quantile %d/%d (0 < q_num <= q_den)", q_num, q_den);
+  hipStream_t st = as_stream(stream);
   const int64_t planes = B * C * 2, hw = (int64_t)H * W;
   uint16_t* col = (uint16_t*)ws;
   float* dist = (float*)(col + planes * hw);        // planes * hw * 2 bytes: a multiple of 4
@@ -224,5 +248,3 @@ int launch_surface_stats(const uint8_t* pred, const uint8_t* gt, const float* sp
   hipLaunchKernelGGL(surf_reduce_kernel, dim3((unsigned)planes), dim3(256), 0, st, dist, counts, values, tv, hw, T, q_num, q_den);
   return check_launch("surface_stats (reduce)");
 }
-
-}  // namespace dinox

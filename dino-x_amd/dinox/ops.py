@@ -2474,7 +2474,7 @@ class MaeLossFn(torch.autograd.Function):
 
 
 # ---------------------------------------------------------------- iBOT masked-patch objective (csrc/ibot.hip)
-IBOT_MASK_CHUNK = 64      # csrc/kernels.h: masked rows per partial sum of dinox_ibot_put_mask_bwd
+IBOT_MASK_CHUNK = 64      # csrc/ibot.hip: masked rows per partial sum of dinox_ibot_put_mask_bwd
 
 
 def _row_index(idx: Tensor, what: str) -> Tensor:

@@ -36,7 +36,7 @@ DEFAULT_TARGET_MODULES = ["qkv", "proj", "fc1", "fc2"]
 
 ADAPTER = "default"                           # the one adapter name, as in peft's parameter paths
 CONFIG_FILE, WEIGHTS_FILE = "adapter_config.json", "adapter_model.safetensors"
-MAX_RANK = 64                                 # csrc/kernels.h LORA_MAX_RANK
+MAX_RANK = 64                                 # csrc/lora.hip LORA_MAX_RANK
 
 # substrings of parameter names that stay frozen whatever the caller asks for
 _PHYSICAL = ("scale_embed.", "patch_embed.", "cls_token", "pos_embed", "registers")

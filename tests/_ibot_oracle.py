@@ -9,7 +9,7 @@ import torch
 import _small_kernels_oracle as SO
 from _small_kernels_oracle import CE_DS_RTOL, CE_LOSS_RTOL, F64, TINY, U, block_adds, dino_inputs, f32  # noqa: F401  (re-exported to the tests)
 
-MASK_CHUNK = 64      # csrc/kernels.h IBOT_MASK_CHUNK
+MASK_CHUNK = 64      # csrc/ibot.hip IBOT_MASK_CHUNK
 
 
 # ------------------------------------------------------------------------------------------ cross-entropy

@@ -13,7 +13,7 @@ import numpy as np
 
 from oracle.gemm_bounds import U32, half_ulp_bf16
 
-CHUNK = 128                                   # csrc/kernels.h LORA_GRAD_CHUNK
+CHUNK = 128                                   # csrc/lora.hip LORA_GRAD_CHUNK
 M32 = 0xFFFFFFFF
 
 

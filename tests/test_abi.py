@@ -141,3 +141,33 @@ def test_gemm_dispatch_by_shape(monkeypatch):
     assert name(T, 1152, 384, epi=EPI_BIAS | EPI_GELU, aux=0x60000) == "gemm_bf16_nt_areg"                                # side tensor = pre-activation: not taken
     monkeypatch.setenv("DINOX_NT_PP", "2")
     assert name(804, 1152, 384, epi=EPI_BIAS) == "gemm_bf16_nt_pp128"                                                     # forced (tests)
+
+
+def test_every_entry_point_is_defined_beside_its_kernels():
+    """The layout of csrc/, read from the sources as text: every entry point has exactly one definition in a .hip file, abi.hip
+    defines the three library-level ones only, and kernels.h declares a launch_* function only if a .hip file other than its
+    definer calls it."""
+    import glob
+    from dinox import _lib
+    csrc = os.path.join(ROOT, "dino-x_amd", "csrc")
+    hips = {os.path.basename(f): open(f).read() for f in sorted(glob.glob(os.path.join(csrc, "*.hip")))}
+    assert len(hips) >= 40 and "abi.hip" in hips
+    definition = re.compile(r'^extern "C"[^\n(;]*?\b(dinox_[a-z0-9_]+)\s*\(', re.M)
+    defined = {f: definition.findall(text) for f, text in hips.items()}
+    names = set(header_prototypes()) | set(_lib.SIZE_T_SIGNATURES)
+    assert len(names) >= 121
+    for name in sorted(names):
+        homes = [f for f, found in defined.items() for n in found if n == name]
+        assert len(homes) == 1, f"{name} is defined in {homes}: exactly one csrc/*.hip must define it"
+    assert {n for found in defined.values() for n in found} == names, "an extern \"C\" dinox_* definition that dinox.h does not declare"
+    assert sorted(defined["abi.hip"]) == ["dinox_device_ok", "dinox_last_error", "dinox_version"]
+
+    kernels_h = open(os.path.join(csrc, "kernels.h")).read()
+    declared = re.findall(r"^\s*[a-z_0-9:]+\s+(launch_[a-z0-9_]+)\s*\(", kernels_h, flags=re.M)
+    assert len(declared) >= 10 and "launch_gemm_bf16" in declared
+    for fn in declared:
+        word = re.compile(r"\b" + fn + r"\b")
+        definers = [f for f, text in hips.items() if re.search(r"^[a-z_0-9:]+\s+" + fn + r"\s*\(", text, flags=re.M)]
+        assert len(definers) == 1, f"{fn}: defined in {definers}"
+        callers = [f for f, text in hips.items() if f != definers[0] and word.search(text)]
+        assert callers, f"kernels.h declares {fn}, which only {definers[0]} mentions: make it static there"

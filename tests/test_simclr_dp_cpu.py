@@ -122,11 +122,11 @@ NAMES = ("dinox_ntxent_rows_rect", "dinox_ntxent_coeff_rect")
 def test_new_entry_points_are_declared_exported_and_bound():
     from dinox import _lib
     header = open(os.path.join(ROOT, "include", "dinox.h")).read()
-    kernels_h = open(os.path.join(ROOT, "dino-x_amd", "csrc", "kernels.h")).read()
+    ntxent_hip = open(os.path.join(ROOT, "dino-x_amd", "csrc", "ntxent.hip")).read()
     exported = C.CDLL(_lib.LIB_PATH)
     for name in NAMES:
         assert f"int {name}(" in header and name in _lib.SIGNATURES and hasattr(exported, name)
-        assert f"int launch_{name[len('dinox_'):]}(" in kernels_h
+        assert f'extern "C" int {name}(' in ntxent_hip
     assert len(_lib.SIGNATURES["dinox_ntxent_rows_rect"][1]) == 11 and len(_lib.SIGNATURES["dinox_ntxent_coeff_rect"][1]) == 13
     assert "#define DINOX_ABI_VERSION 3" in header and _lib.lib.dinox_version() == 3          # additive: no new ABI version
 
