@@ -358,32 +358,48 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_generic(const void* __restr
                                                              const float* __restrict__ rstd, float* dx,
                                                              void* __restrict__ dx_lowp, float* __restrict__ ws,
                                                              int64_t rows, int dim, const float* dx_add) {
-  // Generic fallback: one wave per row for dx; dw/db partials via LDS atomics per block.
+  // Generic fallback: one wave per row for dx; dw/db partials in one LDS row per block.  A lane owns fixed columns and the block's four
+  // waves add their rows in turn (wave 0 first), so a cell's sum has ONE order: LDS atomics from four waves arrive in any order, and
+  // dw / db then differ in the last bit from launch to launch.  The row loop is uniform across the block for the barriers.
   extern __shared__ __attribute__((aligned(16))) float lds[];
   for (int c = threadIdx.x; c < 2 * dim; c += LN_THREADS) lds[c] = 0.f;
   __syncthreads();
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (int64_t)blockIdx.x * (LN_THREADS / 64) + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int64_t nwaves = (int64_t)gridDim.x * (LN_THREADS / 64);
   const float inv = 1.0f / (float)dim;
-  for (int64_t r = wave; r < rows; r += nwaves) {
-    const float mu = mean[r], rs = rstd[r];
-    float s1 = 0.f, s2 = 0.f;
-    for (int c = lane; c < dim; c += 64) {
-      const float d = elem<DY_DT>::ld(dy, r * dim + c), xh = (x[r * dim + c] - mu) * rs, g = d * w[c];
-      s1 += g;
-      s2 += g * xh;
-      atomicAdd(&lds[c], d * xh);
-      atomicAdd(&lds[dim + c], d);
+  for (int64_t rb = (int64_t)blockIdx.x * (LN_THREADS / 64); rb < rows; rb += nwaves) {
+    const int64_t r = rb + wv;
+    const bool live = r < rows;
+    float mu = 0.f, rs = 0.f, m1 = 0.f, m2 = 0.f;
+    if (live) {
+      mu = mean[r];
+      rs = rstd[r];
+      float s1 = 0.f, s2 = 0.f;
+      for (int c = lane; c < dim; c += 64) {
+        const float d = elem<DY_DT>::ld(dy, r * dim + c), xh = (x[r * dim + c] - mu) * rs, g = d * w[c];
+        s1 += g;
+        s2 += g * xh;
+      }
+      m1 = wave_sum(s1) * inv;
+      m2 = wave_sum(s2) * inv;
     }
-    const float m1 = wave_sum(s1) * inv, m2 = wave_sum(s2) * inv;
-    for (int c = lane; c < dim; c += 64) {
-      const float d = elem<DY_DT>::ld(dy, r * dim + c), xh = (x[r * dim + c] - mu) * rs;
-      float o = rs * (d * w[c] - m1 - xh * m2);
-      if (dx_add) o += dx_add[r * dim + c];
-      dx[r * dim + c] = o;
-      if (dx_lowp) ((bf16_t*)dx_lowp)[r * dim + c] = f32_to_bf16(o);
+    for (int turn = 0; turn < LN_THREADS / 64; ++turn) {
+      if (turn == wv && live)
+        for (int c = lane; c < dim; c += 64) {
+          const float d = elem<DY_DT>::ld(dy, r * dim + c), xh = (x[r * dim + c] - mu) * rs;
+          lds[c] += d * xh;
+          lds[dim + c] += d;
+        }
+      __syncthreads();
     }
+    if (live)
+      for (int c = lane; c < dim; c += 64) {
+        const float d = elem<DY_DT>::ld(dy, r * dim + c), xh = (x[r * dim + c] - mu) * rs;
+        float o = rs * (d * w[c] - m1 - xh * m2);
+        if (dx_add) o += dx_add[r * dim + c];
+        dx[r * dim + c] = o;
+        if (dx_lowp) ((bf16_t*)dx_lowp)[r * dim + c] = f32_to_bf16(o);
+      }
   }
   __syncthreads();
   float* out = ws + (size_t)blockIdx.x * 2 * dim;
