@@ -30,10 +30,9 @@
 #include "common.h"
 #include "gemm_common.h"
 #include "gemm_pp_common.h"
+#include "ln_row.h"
 
 namespace dinox {
-
-typedef unsigned pr_u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int PR_BM = 208, PR_BN = 384, PR_BK = 32;
 constexpr int PR_RB = PR_BM / 16;                             // 13 row blocks
@@ -221,18 +220,12 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp384(GemmParams p, PpLnE
         const float mu = ln.mean[r], rs = ln.rstd[r];
         const float4 (&xv)[3] = xr[q % DEPTH];
         const float4 (&a)[3] = ar[q % DEPTH];
-        float4 d[3], xh[3], g[3];
+        float4 xh[3], g[3];
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-          const uint2 pk = *reinterpret_cast<const uint2*>(smem + row * PR_OROW + (hl + 32 * j) * 8);
-          d[j] = make_float4(__uint_as_float(pk.x << 16), __uint_as_float(pk.x & 0xffff0000u), __uint_as_float(pk.y << 16), __uint_as_float(pk.y & 0xffff0000u));
-          xh[j] = make_float4((xv[j].x - mu) * rs, (xv[j].y - mu) * rs, (xv[j].z - mu) * rs, (xv[j].w - mu) * rs);
-          g[j] = make_float4(d[j].x * wreg[j].x, d[j].y * wreg[j].y, d[j].z * wreg[j].z, d[j].w * wreg[j].w);
-          aw[j].x += d[j].x * xh[j].x; aw[j].y += d[j].y * xh[j].y; aw[j].z += d[j].z * xh[j].z; aw[j].w += d[j].w * xh[j].w;
-          ab[j].x += d[j].x; ab[j].y += d[j].y; ab[j].z += d[j].z; ab[j].w += d[j].w;
-          s1 += (g[j].x + g[j].y) + (g[j].z + g[j].w);
-          s2 += (g[j].x * xh[j].x + g[j].y * xh[j].y) + (g[j].z * xh[j].z + g[j].w * xh[j].w);
+          const float4 d = bf16x4_to_f32(*reinterpret_cast<const uint2*>(smem + row * PR_OROW + (hl + 32 * j) * 8));
+          ln_bwd_accum(xv[j], d, wreg[j], mu, rs, xh[j], g[j], aw[j], ab[j], s1, s2);
         }
 #pragma unroll
         for (int o = 16; o > 0; o >>= 1) {
@@ -241,19 +234,8 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp384(GemmParams p, PpLnE
         }
         const float m1 = s1 * (1.0f / PR_BN), m2 = s2 * (1.0f / PR_BN);
 #pragma unroll
-        for (int j = 0; j < 3; ++j) {
-          float4 o;
-          o.x = rs * (g[j].x - m1 - xh[j].x * m2) + a[j].x;
-          o.y = rs * (g[j].y - m1 - xh[j].y * m2) + a[j].y;
-          o.z = rs * (g[j].z - m1 - xh[j].z * m2) + a[j].z;
-          o.w = rs * (g[j].w - m1 - xh[j].w * m2) + a[j].w;
-          store_stream(reinterpret_cast<float4*>((float*)p.C + r * PR_BN) + (hl + 32 * j), o);
-          if (ln.y) {
-            ushort4 pq;
-            pq.x = f32_to_bf16(o.x); pq.y = f32_to_bf16(o.y); pq.z = f32_to_bf16(o.z); pq.w = f32_to_bf16(o.w);
-            store_stream(reinterpret_cast<ushort4*>((bf16_t*)ln.y + r * PR_BN) + (hl + 32 * j), pq);
-          }
-        }
+        for (int j = 0; j < 3; ++j)
+          ln_bwd_store((float*)p.C, ln.y, r * PR_BN + 4 * (hl + 32 * j), ln_bwd_dx(g[j], xh[j], rs, m1, m2, a[j]));
       }
     }
     pp_sync();                                                  // the image is dead: the sixteen half-waves' column sums meet in its place
@@ -362,13 +344,11 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_pp384(GemmParams p, PpLnE
           char* const yp = (char*)ln.y + ((m0 + row) * (int64_t)PR_BN + hl * 4) * 2;
 #pragma unroll
           for (int k = 0; k < 3; ++k) {
-            const pp_f32x4 g4 = *reinterpret_cast<const pp_f32x4*>(gb + hl * 4 + k * 128);
-            const pp_f32x4 b4 = *reinterpret_cast<const pp_f32x4*>(gb + PR_BN + hl * 4 + k * 128);
+            const float4 g4 = *reinterpret_cast<const float4*>(gb + hl * 4 + k * 128);
+            const float4 b4 = *reinterpret_cast<const float4*>(gb + PR_BN + hl * 4 + k * 128);
             __builtin_nontemporal_store(x[k], reinterpret_cast<pp_f32x4*>(xp + k * 512));
-            uint2 pk;
-            pk.x = pp_pack2((x[k][0] - mean) * rstd * g4[0] + b4[0], (x[k][1] - mean) * rstd * g4[1] + b4[1]);
-            pk.y = pp_pack2((x[k][2] - mean) * rstd * g4[2] + b4[2], (x[k][3] - mean) * rstd * g4[3] + b4[3]);
-            __builtin_nontemporal_store(pr_u32x2{pk.x, pk.y}, reinterpret_cast<pr_u32x2*>(yp + k * 256));
+            const float4 o = ln_scale_shift(__builtin_bit_cast(float4, x[k]), mean, rstd, g4, b4);
+            __builtin_nontemporal_store(dx_u32x2{pp_pack2(o.x, o.y), pp_pack2(o.z, o.w)}, reinterpret_cast<dx_u32x2*>(yp + k * 256));
           }
           if (hl == 0) {
             ln.mean[m0 + row] = mean;

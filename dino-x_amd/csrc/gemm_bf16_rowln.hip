@@ -26,6 +26,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "ln_row.h"
 
 namespace dinox {
 
@@ -336,16 +337,15 @@ __global__ __launch_bounds__(512, NS == 2 ? 4 : 2) void gemm_bf16_rowln(RowLnPar
       for (int g = 0; g < 4; ++g) {
         const float4 g4 = *reinterpret_cast<const float4*>(gam_s + j * 32 + 8 * g + 4 * fh);
         const float4 b4 = *reinterpret_cast<const float4*>(bet_s + j * 32 + 8 * g + 4 * fh);
-        const float y0 = (acc[i][j][4 * g] - mean) * rstd * g4.x + b4.x, y1 = (acc[i][j][4 * g + 1] - mean) * rstd * g4.y + b4.y;
-        const float y2 = (acc[i][j][4 * g + 2] - mean) * rstd * g4.z + b4.z, y3 = (acc[i][j][4 * g + 3] - mean) * rstd * g4.w + b4.w;
+        const float4 y4 = ln_scale_shift(make_float4(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]), mean, rstd, g4, b4);
         if (Y_DT == DINOX_BF16) {
           uint2 pk;
-          pk.x = (unsigned)f32_to_bf16(y0) | ((unsigned)f32_to_bf16(y1) << 16);
-          pk.y = (unsigned)f32_to_bf16(y2) | ((unsigned)f32_to_bf16(y3) << 16);
+          pk.x = (unsigned)f32_to_bf16(y4.x) | ((unsigned)f32_to_bf16(y4.y) << 16);
+          pk.y = (unsigned)f32_to_bf16(y4.z) | ((unsigned)f32_to_bf16(y4.w) << 16);
           // bf16 tile: 64-byte rows, four 16-byte chunks; this lane's 8 bytes are half fh of chunk g
           *reinterpret_cast<uint2*>(stg + rowl * 64 + ((g ^ (rowl & 3)) << 4) + 8 * fh) = pk;
         } else {
-          *reinterpret_cast<float4*>(stg + rp_off[g]) = make_float4(y0, y1, y2, y3);
+          *reinterpret_cast<float4*>(stg + rp_off[g]) = y4;
         }
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");

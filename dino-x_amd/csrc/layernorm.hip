@@ -3,8 +3,11 @@
 // row is read once into registers (float4 per lane), statistics by wave shuffles, no LDS on the
 // forward path.  Algorithmic bytes per row: fwd 4D read + (4|2)D write; bwd (4|2)D + 4D read, 4D
 // (+4D when accumulating, +2D for the bf16 copy) written.
+#include <type_traits>
+
 #include "common.h"
 #include "kernels.h"
+#include "ln_row.h"
 
 namespace dinox {
 
@@ -53,21 +56,7 @@ __global__ __launch_bounds__(LN_THREADS) void ln_fwd_kernel(const float* __restr
       if (c < nvec) {
         const float4 ww = reinterpret_cast<const float4*>(w)[c];
         const float4 bb = reinterpret_cast<const float4*>(b)[c];
-        float4 o;
-        o.x = (v[j].x - mu) * rs * ww.x + bb.x;
-        o.y = (v[j].y - mu) * rs * ww.y + bb.y;
-        o.z = (v[j].z - mu) * rs * ww.z + bb.z;
-        o.w = (v[j].w - mu) * rs * ww.w + bb.w;
-        if (OUT_DT == DINOX_F32) {
-          store_stream(reinterpret_cast<float4*>((float*)y + r * dim) + c, o);
-        } else {
-          ushort4 p;
-          p.x = f32_to_bf16(o.x);
-          p.y = f32_to_bf16(o.y);
-          p.z = f32_to_bf16(o.z);
-          p.w = f32_to_bf16(o.w);
-          store_stream(reinterpret_cast<ushort4*>((bf16_t*)y + r * dim) + c, p);
-        }
+        store_row4<OUT_DT>(y, r * dim + 4 * c, ln_scale_shift(v[j], mu, rs, ww, bb));
       }
     }
   }
@@ -107,23 +96,7 @@ __global__ __launch_bounds__(LN_THREADS) void ln_fwd_384(const float* __restrict
       rstd[r] = rs;
     }
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      float4 o;
-      o.x = (v[j].x - mu) * rs * ww[j].x + bb[j].x;
-      o.y = (v[j].y - mu) * rs * ww[j].y + bb[j].y;
-      o.z = (v[j].z - mu) * rs * ww[j].z + bb[j].z;
-      o.w = (v[j].w - mu) * rs * ww[j].w + bb[j].w;
-      if (OUT_DT == DINOX_F32) {
-        store_stream(reinterpret_cast<float4*>((float*)y + r * DIM) + (sl + 32 * j), o);
-      } else {
-        ushort4 p;
-        p.x = f32_to_bf16(o.x);
-        p.y = f32_to_bf16(o.y);
-        p.z = f32_to_bf16(o.z);
-        p.w = f32_to_bf16(o.w);
-        store_stream(reinterpret_cast<ushort4*>((bf16_t*)y + r * DIM) + (sl + 32 * j), p);
-      }
-    }
+    for (int j = 0; j < 3; ++j) store_row4<OUT_DT>(y, r * DIM + 4 * (sl + 32 * j), ln_scale_shift(v[j], mu, rs, ww[j], bb[j]));
   };
   for (int64_t r0 = half; r0 < rows; r0 += 2 * nhalves) {
     const int64_t r1 = r0 + nhalves;
@@ -165,7 +138,7 @@ __global__ __launch_bounds__(LN_THREADS) void ln_fwd_generic(const float* __rest
       mean[r] = mu;
       rstd[r] = rs;
     }
-    for (int c = lane; c < dim; c += 64) elem<OUT_DT>::st(y, r * dim + c, (xr[c] - mu) * rs * w[c] + b[c]);
+    for (int c = lane; c < dim; c += 64) elem<OUT_DT>::st(y, r * dim + c, ln_scale_shift(xr[c], mu, rs, w[c], b[c]));
   }
 }
 
@@ -201,6 +174,7 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(const void* __restri
       const int c = lane + 64 * j;
       add[j] = (dx_add && c < nvec) ? reinterpret_cast<const float4*>(dx_add + r * dim)[c] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
+    // (own text from here to the stores, not ln_row.h's: DESIGN.md "LayerNorm row arithmetic", deliberately left)
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
       const int c = lane + 64 * j;
@@ -284,12 +258,7 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_384(const void* __restrict_
     for (int j = 0; j < 3; ++j) {
       const int c = sl + 32 * j;
       xv[j] = reinterpret_cast<const float4*>(x + r * DIM)[c];
-      if (DY_DT == DINOX_F32) {
-        d[j] = reinterpret_cast<const float4*>((const float*)dy + r * DIM)[c];
-      } else {
-        const ushort4 p = reinterpret_cast<const ushort4*>((const bf16_t*)dy + r * DIM)[c];
-        d[j] = make_float4(bf16_to_f32(p.x), bf16_to_f32(p.y), bf16_to_f32(p.z), bf16_to_f32(p.w));
-      }
+      d[j] = load_row4<DY_DT>(dy, r * DIM + 4 * c);
       a[j] = dx_add ? reinterpret_cast<const float4*>(dx_add + r * DIM)[c] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
   };
@@ -298,30 +267,10 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_384(const void* __restrict_
     float4 xh[3], g[3];
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      xh[j] = make_float4((xv[j].x - mu) * rs, (xv[j].y - mu) * rs, (xv[j].z - mu) * rs, (xv[j].w - mu) * rs);
-      g[j] = make_float4(d[j].x * wreg[j].x, d[j].y * wreg[j].y, d[j].z * wreg[j].z, d[j].w * wreg[j].w);
-      aw[j].x += d[j].x * xh[j].x; aw[j].y += d[j].y * xh[j].y; aw[j].z += d[j].z * xh[j].z; aw[j].w += d[j].w * xh[j].w;
-      ab[j].x += d[j].x; ab[j].y += d[j].y; ab[j].z += d[j].z; ab[j].w += d[j].w;
-      s1 += (g[j].x + g[j].y) + (g[j].z + g[j].w);
-      s2 += (g[j].x * xh[j].x + g[j].y * xh[j].y) + (g[j].z * xh[j].z + g[j].w * xh[j].w);
-    }
+    for (int j = 0; j < 3; ++j) ln_bwd_accum(xv[j], d[j], wreg[j], mu, rs, xh[j], g[j], aw[j], ab[j], s1, s2);
     const float m1 = half_wave_sum(s1) * (1.0f / DIM), m2 = half_wave_sum(s2) * (1.0f / DIM);
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const int c = sl + 32 * j;
-      float4 o;
-      o.x = rs * (g[j].x - m1 - xh[j].x * m2) + a[j].x;
-      o.y = rs * (g[j].y - m1 - xh[j].y * m2) + a[j].y;
-      o.z = rs * (g[j].z - m1 - xh[j].z * m2) + a[j].z;
-      o.w = rs * (g[j].w - m1 - xh[j].w * m2) + a[j].w;
-      store_stream(reinterpret_cast<float4*>(dx + r * DIM) + c, o);
-      if (dx_lowp) {
-        ushort4 p;
-        p.x = f32_to_bf16(o.x); p.y = f32_to_bf16(o.y); p.z = f32_to_bf16(o.z); p.w = f32_to_bf16(o.w);
-        store_stream(reinterpret_cast<ushort4*>((bf16_t*)dx_lowp + r * DIM) + c, p);
-      }
-    }
+    for (int j = 0; j < 3; ++j) ln_bwd_store(dx, dx_lowp, r * DIM + 4 * (sl + 32 * j), ln_bwd_dx(g[j], xh[j], rs, m1, m2, a[j]));
   };
   for (int64_t r0 = half; r0 < rows; r0 += 2 * nhalves) {
     const int64_t r1 = r0 + nhalves;
@@ -438,6 +387,25 @@ static bool ln_use384() {                             // the width-384 kernels u
   return !no384;
 }
 
+// The instantiation of a vector kernel for (dtype, float4 per lane = ceil(dim / 4 / 64)): f(DT, NV) gets both as integral constants.
+template <typename F>
+static void ln_for_dtype_nv(int dtype, int dim, F&& f) {
+  const int nv = (int)ceil_div(dim / 4, 64);
+  auto ladder = [&](auto dt) {
+    if (nv <= 1) f(dt, std::integral_constant<int, 1>{});
+    else if (nv <= 2) f(dt, std::integral_constant<int, 2>{});
+    else if (nv <= 4) f(dt, std::integral_constant<int, 4>{});
+    else f(dt, std::integral_constant<int, LN_MAXV>{});
+  };
+  if (dtype == DINOX_F32) ladder(std::integral_constant<int, DINOX_F32>{});
+  else ladder(std::integral_constant<int, DINOX_BF16>{});
+}
+
+static int launch_ln_bwd_reduce(const float* ws, float* dw, float* db, int parts, int dim, int accumulate, hipStream_t st) {
+  hipLaunchKernelGGL(ln_bwd_reduce, dim3((unsigned)ceil_div(2 * dim, 4)), dim3(256), 0, st, ws, dw, db, parts, dim, accumulate ? 1 : 0);
+  return check_launch("layernorm_bwd_reduce");
+}
+
 }  // namespace dinox
 
 using namespace dinox;
@@ -457,18 +425,13 @@ extern "C" int dinox_layernorm_fwd(const float* x, const float* w, const float* 
     hipLaunchKernelGGL((out_dtype == DINOX_F32 ? ln_fwd_384<DINOX_F32> : ln_fwd_384<DINOX_BF16>), dim3((unsigned)blk), dim3(LN_THREADS), 0, st, x, w, b, y, mean, rstd, rows, eps);
     return check_launch("layernorm_fwd");
   }
-#define LN_FWD(DT, NV) hipLaunchKernelGGL((ln_fwd_kernel<DT, NV>), dim3((unsigned)blocks), dim3(LN_THREADS), 0, st, x, w, b, y, mean, rstd, rows, dim, eps)
   if (fast) {
-    const int nv = (int)ceil_div(dim / 4, 64);
-    if (out_dtype == DINOX_F32) {
-      if (nv <= 1) LN_FWD(DINOX_F32, 1); else if (nv <= 2) LN_FWD(DINOX_F32, 2); else if (nv <= 4) LN_FWD(DINOX_F32, 4); else LN_FWD(DINOX_F32, 8);
-    } else {
-      if (nv <= 1) LN_FWD(DINOX_BF16, 1); else if (nv <= 2) LN_FWD(DINOX_BF16, 2); else if (nv <= 4) LN_FWD(DINOX_BF16, 4); else LN_FWD(DINOX_BF16, 8);
-    }
+    ln_for_dtype_nv(out_dtype, dim, [&](auto dt, auto nv) {
+      hipLaunchKernelGGL((ln_fwd_kernel<decltype(dt)::value, decltype(nv)::value>), dim3((unsigned)blocks), dim3(LN_THREADS), 0, st, x, w, b, y, mean, rstd, rows, dim, eps);
+    });
   } else {
     hipLaunchKernelGGL((out_dtype == DINOX_F32 ? ln_fwd_generic<DINOX_F32> : ln_fwd_generic<DINOX_BF16>), dim3((unsigned)blocks), dim3(LN_THREADS), 0, st, x, w, b, y, mean, rstd, rows, dim, eps);
   }
-#undef LN_FWD
   return check_launch("layernorm_fwd");
 }
 
@@ -495,27 +458,19 @@ extern "C" int dinox_layernorm_bwd(const void* dy, const float* x, const float* 
     const int nblk = (int)(want < parts ? want : (parts < 768 ? parts : 768));
     hipLaunchKernelGGL((dy_dtype == DINOX_F32 ? ln_bwd_384<DINOX_F32> : ln_bwd_384<DINOX_BF16>), dim3(nblk), dim3(LN_THREADS), lds, st, dy, x, w, mean, rstd, dx, dx_lowp, wsf, rows, dx_add);
     if (int rc = check_launch("layernorm_bwd")) return rc;
-    hipLaunchKernelGGL(ln_bwd_reduce, dim3((unsigned)ceil_div(2 * dim, 4)), dim3(256), 0, st, wsf, dw, db, nblk, dim, accumulate ? 1 : 0);
-    return check_launch("layernorm_bwd_reduce");
+    return launch_ln_bwd_reduce(wsf, dw, db, nblk, dim, accumulate, st);
   }
-#define LN_BWD(DT, NV) hipLaunchKernelGGL((ln_bwd_kernel<DT, NV>), dim3(parts), dim3(LN_THREADS), lds, st, dy, x, w, mean, rstd, dx, dx_lowp, wsf, rows, dim, dx_add)
   if (fast) {
-    const int nv = (int)ceil_div(dim / 4, 64);
-    if (dy_dtype == DINOX_F32) {
-      if (nv <= 1) LN_BWD(DINOX_F32, 1); else if (nv <= 2) LN_BWD(DINOX_F32, 2); else if (nv <= 4) LN_BWD(DINOX_F32, 4); else LN_BWD(DINOX_F32, 8);
-    } else {
-      if (nv <= 1) LN_BWD(DINOX_BF16, 1); else if (nv <= 2) LN_BWD(DINOX_BF16, 2); else if (nv <= 4) LN_BWD(DINOX_BF16, 4); else LN_BWD(DINOX_BF16, 8);
-    }
+    ln_for_dtype_nv(dy_dtype, dim, [&](auto dt, auto nv) {
+      hipLaunchKernelGGL((ln_bwd_kernel<decltype(dt)::value, decltype(nv)::value>), dim3(parts), dim3(LN_THREADS), lds, st, dy, x, w, mean, rstd, dx, dx_lowp, wsf, rows, dim, dx_add);
+    });
   } else {
     const size_t l2 = (size_t)2 * dim * sizeof(float);
     DX_REQUIRE(l2 <= 64 * 1024, DINOX_EUNSUPPORTED, "layernorm_bwd: dim %d too large", dim);
     hipLaunchKernelGGL((dy_dtype == DINOX_F32 ? ln_bwd_generic<DINOX_F32> : ln_bwd_generic<DINOX_BF16>), dim3(parts), dim3(LN_THREADS), l2, st, dy, x, w, mean, rstd, dx, dx_lowp, wsf, rows, dim, dx_add);
   }
-#undef LN_BWD
-  int rc = check_launch("layernorm_bwd");
-  if (rc) return rc;
-  hipLaunchKernelGGL(ln_bwd_reduce, dim3((unsigned)ceil_div(2 * dim, 4)), dim3(256), 0, st, wsf, dw, db, parts, dim, accumulate ? 1 : 0);
-  return check_launch("layernorm_bwd_reduce");
+  if (int rc = check_launch("layernorm_bwd")) return rc;
+  return launch_ln_bwd_reduce(wsf, dw, db, parts, dim, accumulate, st);
 }
 
 // dX product + LayerNorm backward in one launch (width 384, bf16 operands):  dy = a w^T rounded to bf16 (what the two launches hand
@@ -534,7 +489,5 @@ extern "C" int dinox_linear_ln_bwd(const void* a, const void* w, const float* x,
              DINOX_EALIGN, "linear_ln_bwd: operands must be 16-byte aligned");
   hipStream_t st = as_stream(stream);
   if (int rc = launch_gemm_bf16_nt_pp384_lnbwd(a, w, x, gamma, mean, rstd, dx, dx_add, dx_lowp, (float*)ws, M, K, st)) return rc;
-  hipLaunchKernelGGL(ln_bwd_reduce, dim3((unsigned)ceil_div(2 * 384, 4)), dim3(256), 0, st, (const float*)ws, dgamma, dbeta, pp384_lnbwd_tiles(M), 384,
-                     accumulate ? 1 : 0);
-  return check_launch("linear_ln_bwd_reduce");
+  return launch_ln_bwd_reduce((const float*)ws, dgamma, dbeta, pp384_lnbwd_tiles(M), 384, accumulate, st);
 }

@@ -43,7 +43,7 @@ __global__ __launch_bounds__(256) void unfold_vec8_kernel(const float* __restric
     const float4 a = *reinterpret_cast<const float4*>(src), b = *reinterpret_cast<const float4*>(src + 4);
     const int64_t o = row * (int64_t)(3 * p * p) + (int64_t)(c * p + py) * p + px8 * 8;
     if (DT == DINOX_BF16) {
-      s16x8 pk;
+      s16x8 pk;                                       // (own text, not ln_row.h's f32x4_to_bf16: that changes this kernel's code, DESIGN.md "LayerNorm row arithmetic")
       pk[0] = (short)f32_to_bf16(a.x); pk[1] = (short)f32_to_bf16(a.y); pk[2] = (short)f32_to_bf16(a.z); pk[3] = (short)f32_to_bf16(a.w);
       pk[4] = (short)f32_to_bf16(b.x); pk[5] = (short)f32_to_bf16(b.y); pk[6] = (short)f32_to_bf16(b.z); pk[7] = (short)f32_to_bf16(b.w);
       *reinterpret_cast<s16x8*>((bf16_t*)u + o) = pk;

@@ -1392,7 +1392,7 @@ def test_linear_residual_ln(dx, M, K, res, bias, ydt, pp, monkeypatch):
     assert rel_l2(y.float(), yg.float()) < (4e-3 if ydt == torch.bfloat16 else 2e-5) and rel_l2(rstd, rg) < 1e-5
 
 
-@pytest.mark.parametrize("M,K,add", [(4096 + 17, 1536, "other"), (208 * 9 + 1, 1152, "alias"), (5000, 384, None), (90, 128, "other"), (208 * 40, 1152, "alias")])
+@pytest.mark.parametrize("M,K,add", [(4096 + 17, 1536, "other"), (208 * 9 + 1, 1152, "alias"), (5000, 384, None), (90, 128, "other"), (208 * 40, 1152, "alias"), (209, 384, "alias")])
 def test_linear_ln_bwd_equals_two_launches(dx, M, K, add, monkeypatch):
     """dinox_linear_ln_bwd (csrc/gemm_bf16_pp384.hip's LayerNorm-backward epilogue: the input-gradient product into width 384 and the
     LayerNorm backward behind it in one launch) against dinox_gemm + dinox_layernorm_bwd: dx equal to the last bit (dy is rounded to
