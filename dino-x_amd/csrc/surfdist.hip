@@ -17,27 +17,14 @@
 // else is in the batch.  A label is compared with class numbers and 255 only; it never becomes an address.
 // A distance is sqrt(fl(fl(fl(s_x k)^2) + fl(fl(s_y m)^2))) with contraction off and a correctly rounded square root: within 3 u of the
 // exact one, relatively (u = 2^-24).
-#include "small_common.h"
-#include "kernels.h"
+#include "surf_common.h"
 
 namespace dinox {
 
-constexpr int SURF_MAX_SIDE = 1024;                // a row of squared column distances (4 KiB) sits in LDS; a column distance fits uint16 beside its sentinel
-constexpr int SURF_MAX_TOL = 8;                    // tolerance counters per lane, in registers
-constexpr unsigned SURF_NONE = 0xffffu;            // column distance: no border pixel in this column (a real one is at most 1023)
-constexpr float SURF_SKIP = -1.0f;                 // distance plane: not a border pixel of the query side (sign bit set)
-constexpr unsigned SURF_INF = 0x7f800000u;         // distance plane: the other side has no border at all
-
-struct SurfTol {
-  float v[SURF_MAX_TOL];
-};
-
-// p is in the set of (plane, c): pred: gt != 255 and pred == c; gt: gt == c.  Outside the image: not in the set.
+// p is in the set of (plane, c) (surf_member).  Outside the image: not in the set.
 __device__ __forceinline__ bool surf_in(const uint8_t* __restrict__ pb, const uint8_t* __restrict__ gb, int plane, int c, int H, int W, int y, int x) {
   if (y < 0 || y >= H || x < 0 || x >= W) return false;
-  const int64_t i = (int64_t)y * W + x;
-  const int g = gb[i];
-  return plane == 0 ? (g != 255 && pb[i] == c) : g == c;
+  return surf_member(pb, gb, (int64_t)y * W + x, plane, c);
 }
 
 // ---------------------------------------------------------------- 1: border membership and the column scan
@@ -62,7 +49,7 @@ __global__ __launch_bounds__(256) void surf_columns_kernel(const uint8_t* __rest
     const bool border = cur && !(up && down && surf_in(pb, gb, plane, c, H, W, y, x - 1) && surf_in(pb, gb, plane, c, H, W, y, x + 1));
     if (c == 0) {
       const int v = plane == 0 ? pb[(int64_t)y * W + x] : gb[(int64_t)y * W + x];
-      nbad += (v >= C && (plane == 0 || v != 255)) ? 1u : 0u;
+      nbad += surf_bad_label(v, plane, C) ? 1u : 0u;
     }
     if (border) last = y;
     cd[(int64_t)y * W] = (uint16_t)(last < 0 ? SURF_NONE : (unsigned)(y - last));
@@ -186,12 +173,12 @@ __global__ __launch_bounds__(256) void surf_reduce_kernel(const float* __restric
     for (int64_t i = tid; i < hw; i += 256) {
       const unsigned bits = d[i];
       if (bits >> 31) continue;
-      if (shift == 24 || (bits >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[(bits >> shift) & 255u], 1u);
+      if (surf_radix_takes_part(bits, prefix, shift)) atomicAdd(&hist[(bits >> shift) & 255u], 1u);
     }
     __syncthreads();
     if (tid == 0) {
-      unsigned k = sel[1], digit = 0;
-      while (digit < 255 && hist[digit] < k) k -= hist[digit++];
+      unsigned k = sel[1];
+      const unsigned digit = surf_radix_pick(hist, k);
       sel[0] = prefix | (digit << shift);
       sel[1] = k;
     }

@@ -150,6 +150,8 @@ SIGNATURES = {
     "dinox_seg_predict": (i32, [vp, vp, vp, vp, i64, i32, i32, i32, vp]),
     "dinox_surface_ws_bytes": (i64, [i64, i32, i32, i32]),
     "dinox_surface_stats": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp]),
+    "dinox_surface3d_ws_bytes": (i64, [i64, i32, i32, i32]),
+    "dinox_surface3d_stats": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp]),
     "dinox_cc_ws_bytes": (i64, [i64, i32, i32, i32]),
     "dinox_cc_label": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp]),
     "dinox_cc_filter": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp]),

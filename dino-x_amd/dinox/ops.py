@@ -3104,6 +3104,23 @@ def _surface_spacing(spacing, B: int, device) -> Tensor:
     return _c(sp)
 
 
+def _surface_params(fn: str, num_classes, tolerances, q):
+    """(C, tolerances as floats) of surface_stats / surface_stats_3d; ValueError for anything the kernels do not take."""
+    C = num_classes
+    if isinstance(C, bool) or not isinstance(C, int) or not 2 <= C <= SEG_MAX_CLASSES:
+        raise ValueError(f"{fn}: num_classes must be an integer in [2, {SEG_MAX_CLASSES}], got {C!r}")
+    try:
+        tol = [float(t) for t in tolerances]
+    except TypeError as e:
+        raise ValueError(f"{fn}: tolerances must be a sequence of numbers, got {tolerances!r}") from e
+    if not 1 <= len(tol) <= SURFACE_MAX_TOLERANCES or not all(math.isfinite(t) and t >= 0 for t in tol):
+        raise ValueError(f"{fn}: 1 to {SURFACE_MAX_TOLERANCES} tolerances in mm, finite and >= 0, got {tolerances!r}")
+    if (not isinstance(q, (tuple, list)) or len(q) != 2 or any(isinstance(v, bool) or not isinstance(v, int) for v in q)
+            or not 0 < q[0] <= q[1] or q[1] >= 1 << 31):
+        raise ValueError(f"{fn}: q must be two integers (q_num, q_den) with 0 < q_num <= q_den, got {q!r}")
+    return C, tol
+
+
 def surface_stats(pred: Tensor, labels: Tensor, spacing, num_classes: int, tolerances=(1.0,), q=(95, 100)):
     """Directed surface-distance statistics of two uint8 label maps [B, H, W] (labels: 255 = ignore) in mm, spacing [B, 2] = (s_y, s_x)
     per image (include/dinox.h has the definitions).  Returns (counts int64 [B, C, 2, 1 + T] = (n, within tolerance t), values fp32
@@ -3112,18 +3129,7 @@ def surface_stats(pred: Tensor, labels: Tensor, spacing, num_classes: int, toler
     so that one call's workspace stays under SURFACE_WS_CAP; the results do not depend on the cut.  A label >= C other than 255 in
     ``labels``, or any value >= C in ``pred``, raises ValueError (one device read of two integers)."""
     B, H, W = _surface_maps(pred, labels)
-    C = num_classes
-    if isinstance(C, bool) or not isinstance(C, int) or not 2 <= C <= SEG_MAX_CLASSES:
-        raise ValueError(f"surface_stats: num_classes must be an integer in [2, {SEG_MAX_CLASSES}], got {C!r}")
-    try:
-        tol = [float(t) for t in tolerances]
-    except TypeError as e:
-        raise ValueError(f"surface_stats: tolerances must be a sequence of numbers, got {tolerances!r}") from e
-    if not 1 <= len(tol) <= SURFACE_MAX_TOLERANCES or not all(math.isfinite(t) and t >= 0 for t in tol):
-        raise ValueError(f"surface_stats: 1 to {SURFACE_MAX_TOLERANCES} tolerances in mm, finite and >= 0, got {tolerances!r}")
-    if (not isinstance(q, (tuple, list)) or len(q) != 2 or any(isinstance(v, bool) or not isinstance(v, int) for v in q)
-            or not 0 < q[0] <= q[1] or q[1] >= 1 << 31):
-        raise ValueError(f"surface_stats: q must be two integers (q_num, q_den) with 0 < q_num <= q_den, got {q!r}")
+    C, tol = _surface_params("surface_stats", num_classes, tolerances, q)
     _need_cuda(pred, labels)
     dev = pred.device
     sp = _surface_spacing(spacing, B, dev)
@@ -3145,6 +3151,52 @@ def surface_stats(pred: Tensor, labels: Tensor, spacing, num_classes: int, toler
     nbad = bad.sum(0).tolist()
     if nbad[0] or nbad[1]:
         raise ValueError(f"surface_stats: {nbad[0]} value(s) of pred are >= C = {C}, {nbad[1]} label(s) are >= C and not {SEG_IGNORE} (ignore)")
+    return counts, values
+
+
+def surface_stats_3d(pred: Tensor, labels: Tensor, spacing, num_classes: int, tolerances=(1.0,), q=(95, 100)):
+    """Directed surface-distance statistics of two uint8 label volumes [Z, H, W] (labels: 255 = ignore) in mm with the voxel
+    spacing = (s_z, s_y, s_x) (include/dinox.h has the definitions: the border is taken with the six face neighbours, so a one-slice volume
+    is all border and does not reproduce ``surface_stats`` of that slice).  Returns (counts int64 [C, 2, 1 + T] = (n, within tolerance t),
+    values fp32 [C, 2, 3] = (sum, max, q[0]/q[1] nearest-rank quantile)), both on the device; direction 0 runs from the border of ``pred``
+    to the border of ``labels``, direction 1 the other way.  dinox.segment.surface_metrics_3d forms HD95 / ASSD / NSD from them.  The
+    workspace is 12 bytes per voxel whatever C is (the classes are walked one at a time).  A label >= C other than 255 in ``labels``, or
+    any value >= C in ``pred``, raises ValueError (one device read of two integers)."""
+    for what, t in (("pred", pred), ("labels", labels)):
+        if not isinstance(t, Tensor) or t.dtype != torch.uint8 or t.dim() != 3:
+            raise ValueError(f"surface_stats_3d: {what} must be uint8 [Z, H, W], got {_describe(t)}")
+    if pred.shape != labels.shape:
+        raise ValueError(f"surface_stats_3d: pred {tuple(pred.shape)} and labels {tuple(labels.shape)} differ in shape")
+    if pred.device != labels.device:
+        raise ValueError(f"surface_stats_3d: pred on {pred.device}, labels on {labels.device}")
+    Z, H, W = pred.shape
+    if not all(1 <= n <= SURFACE_MAX_SIDE for n in (Z, H, W)):
+        raise ValueError(f"surface_stats_3d: volumes must be [Z, H, W] with 1 <= Z, H, W <= {SURFACE_MAX_SIDE}, got {tuple(pred.shape)}")
+    # (so Z H W <= 2^30: every count fits an unsigned 32-bit integer)
+    C, tol = _surface_params("surface_stats_3d", num_classes, tolerances, q)
+    try:
+        sp = [float(v) for v in (spacing.tolist() if isinstance(spacing, Tensor) else spacing)]
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"surface_stats_3d: spacing must be three numbers (s_z, s_y, s_x) in mm per voxel, got {spacing!r}") from e
+    if len(sp) != 3:
+        raise ValueError(f"surface_stats_3d: spacing must be three numbers (s_z, s_y, s_x) in mm per voxel, got {spacing!r}")
+    sp_host = (_lib.f32 * 3)(*sp)                           # host arrays: the entry reads them during the call
+    if not all(math.isfinite(v) and v > 0 for v in sp_host):
+        raise ValueError(f"surface_stats_3d: every spacing must be finite and > 0 (in fp32), got {spacing!r}")
+    _need_cuda(pred, labels)
+    dev = pred.device
+    pred, labels = _c(pred), _c(labels)
+    T = len(tol)
+    tol_host = (_lib.f32 * T)(*tol)
+    counts = torch.empty((C, 2, 1 + T), dtype=torch.int64, device=dev)
+    values = torch.empty((C, 2, 3), dtype=torch.float32, device=dev)
+    ws = torch.empty(int(lib.dinox_surface3d_ws_bytes(Z, H, W, C)) // 4, dtype=torch.float32, device=dev)
+    bad = torch.zeros(2, dtype=torch.int64, device=dev)
+    check(lib.dinox_surface3d_stats(_p(pred), _p(labels), sp_host, tol_host, _p(counts), _p(values), _p(bad), _p(ws), Z, H, W, C, T, int(q[0]), int(q[1]),
+                                    _stream()), "dinox_surface3d_stats")
+    nbad = bad.tolist()
+    if nbad[0] or nbad[1]:
+        raise ValueError(f"surface_stats_3d: {nbad[0]} value(s) of pred are >= C = {C}, {nbad[1]} label(s) are >= C and not {SEG_IGNORE} (ignore)")
     return counts, values
 
 

@@ -7,7 +7,8 @@
 The head's [B, P, C] logits are all that exists in memory; the upsampling to S = g * patch happens inside the loss / predict kernels.
 ``load_segmenter`` puts back what scripts/finetune_segmentation.py wrote.  The metric helpers take the int64 counts [3, C] of
 ``ops.seg_predict`` (true positives, predicted pixels, labelled pixels per class, over the valid pixels); ``surface_metrics`` and
-``SurfaceAccumulator`` turn ``ops.surface_stats`` (csrc/surfdist.hip) into HD95 / ASSD / surface Dice in mm; ``postprocess`` cleans a
+``SurfaceAccumulator`` turn ``ops.surface_stats`` (csrc/surfdist.hip) into HD95 / ASSD / surface Dice in mm, ``surface_metrics_3d`` does
+the same for one volume from ``ops.surface_stats_3d`` (csrc/surfdist3d.hip); ``postprocess`` cleans a
 label map by connected components and ``lesion_metrics`` / ``LesionAccumulator`` turn ``ops.lesion_counts`` (csrc/cclabel.hip) into
 lesion-wise sensitivity, precision, F1 and false positives per image.  For a whole series: ``segment_volume`` (one trip to the device,
 the chunk loop of ``zoo.encode.encode_volume``), ``postprocess_volume`` and ``ops.lesion_counts_3d`` on 3-D components
@@ -189,6 +190,23 @@ def pixel_accuracy(counts) -> float:
 
 
 # ------------------------------------------------------------------------------------------ boundary metrics from ops.surface_stats
+def _surface_metrics(c: torch.Tensor, v: torch.Tensor, diag: torch.Tensor) -> dict:
+    """The metrics of float64 host counts [B, C, 2, 1 + T] and values [B, C, 2, 3]; ``diag`` [B] is what a one-sided class scores."""
+    diag = diag[:, None].expand(-1, c.shape[1])
+    nA, nG = c[:, :, 0, 0], c[:, :, 1, 0]
+    absent, one = (nA == 0) & (nG == 0), (nA == 0) != (nG == 0)
+    den = (nA + nG).clamp(min=1)
+    nan = torch.full_like(den, float("nan"))
+
+    def pick(x):
+        return torch.where(absent, nan, torch.where(one, diag, x))
+
+    nsd = (c[:, :, 0, 1:] + c[:, :, 1, 1:]) / den[..., None]
+    nsd = torch.where(absent[..., None], nan[..., None], torch.where(one[..., None], torch.zeros_like(nsd), nsd))
+    return {"hd95": pick(torch.maximum(v[:, :, 0, 2], v[:, :, 1, 2])), "hd": pick(torch.maximum(v[:, :, 0, 1], v[:, :, 1, 1])),
+            "assd": pick((v[:, :, 0, 0] + v[:, :, 1, 0]) / den), "nsd": nsd}
+
+
 def surface_metrics(counts, values, spacing, shape) -> dict:
     """HD95, HD, ASSD and NSD per image and class from ``ops.surface_stats``'s outputs: counts [B, C, 2, 1 + T], values [B, C, 2, 3],
     spacing [B, 2] = (s_y, s_x) in mm per pixel, shape = (H, W) of the label maps.  Returns float64 tensors on the host:
@@ -202,19 +220,23 @@ def surface_metrics(counts, values, spacing, shape) -> dict:
     if sp.shape != (c.shape[0], 2):
         raise ValueError(f"surface_metrics: spacing must be [{c.shape[0]}, 2] = (s_y, s_x), got {tuple(sp.shape)}")
     H, W = shape
-    diag = torch.sqrt((sp[:, 0] * H) ** 2 + (sp[:, 1] * W) ** 2)[:, None].expand(-1, c.shape[1])
-    nA, nG = c[:, :, 0, 0], c[:, :, 1, 0]
-    absent, one = (nA == 0) & (nG == 0), (nA == 0) != (nG == 0)
-    den = (nA + nG).clamp(min=1)
-    nan = torch.full_like(den, float("nan"))
+    return _surface_metrics(c, v, torch.sqrt((sp[:, 0] * H) ** 2 + (sp[:, 1] * W) ** 2))
 
-    def pick(x):
-        return torch.where(absent, nan, torch.where(one, diag, x))
 
-    nsd = (c[:, :, 0, 1:] + c[:, :, 1, 1:]) / den[..., None]
-    nsd = torch.where(absent[..., None], nan[..., None], torch.where(one[..., None], torch.zeros_like(nsd), nsd))
-    return {"hd95": pick(torch.maximum(v[:, :, 0, 2], v[:, :, 1, 2])), "hd": pick(torch.maximum(v[:, :, 0, 1], v[:, :, 1, 1])),
-            "assd": pick((v[:, :, 0, 0] + v[:, :, 1, 0]) / den), "nsd": nsd}
+def surface_metrics_3d(counts, values, spacing, shape) -> dict:
+    """HD95, HD, ASSD and NSD per class of ONE volume from ``ops.surface_stats_3d``'s outputs: counts [C, 2, 1 + T], values [C, 2, 3],
+    spacing = (s_z, s_y, s_x) in mm per voxel, shape = (Z, H, W) of the label volumes.  Returns float64 tensors on the host in the layout
+    ``SurfaceAccumulator.update`` takes, the volume as one "image": {"hd95", "hd", "assd": [1, C], "nsd": [1, C, T]}.  The rules are
+    ``surface_metrics``': a class absent from both volumes is NaN; a class in exactly one takes the VOLUME diagonal
+    sqrt((s_z Z)^2 + (s_y H)^2 + (s_x W)^2) for the distance metrics and 0 for NSD."""
+    c, v = torch.as_tensor(counts).double().cpu(), torch.as_tensor(values).double().cpu()
+    if c.dim() != 3 or c.shape[1] != 2 or c.shape[2] < 2 or v.shape != c.shape[:2] + (3,):
+        raise ValueError(f"surface_metrics_3d: counts must be [C, 2, 1 + T] and values [C, 2, 3], got {tuple(c.shape)} and {tuple(v.shape)}")
+    sp = torch.as_tensor(spacing, dtype=torch.float64).cpu()     # (a tuple of Python floats stays float64)
+    if sp.shape != (3,) or len(tuple(shape)) != 3:
+        raise ValueError(f"surface_metrics_3d: spacing must be (s_z, s_y, s_x) and shape (Z, H, W), got {tuple(sp.shape)} and {shape!r}")
+    ext = sp * torch.tensor([float(n) for n in shape], dtype=torch.float64)
+    return _surface_metrics(c[None], v[None], torch.sqrt((ext ** 2).sum())[None])
 
 
 class SurfaceAccumulator:

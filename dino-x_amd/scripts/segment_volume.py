@@ -14,6 +14,12 @@
 series is resampled to the grid by dinox.segment.resample_labels_nearest.  ``--report`` then gets, per class, the mean over cases of the
 per-case Dice and the lesion-wise sensitivity, precision, F1 and false positives per case (dinox.segment.CaseAccumulator); a lesion is a
 3-D component of at least ``--min-component-mm3``, hit when at least ``--lesion-overlap`` of it (to 1/1000; 0: any voxel) is matched.
+
+``--tolerance-mm T`` (repeatable, needs ``--labels``) adds the volumetric boundary metrics of every case: the cleaned prediction (what
+``--out`` holds) against the ground truth through ops.surface_stats_3d (csrc/surfdist3d.hip), with the voxel (s_z, s_y, s_x) of the label
+grid, so the slice spacing enters every distance.  The report then also holds, per class, the mean over cases of HD95 and ASSD in mm and
+of the surface Dice (NSD) at every tolerance, with the number of cases behind them; ``--surface-quantile NUM DEN`` replaces the 95/100 of
+HD95 (nearest rank).  A class in only one of the two volumes of a case scores the volume diagonal and NSD 0 there.
 """
 from __future__ import annotations
 
@@ -62,6 +68,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--lesion-overlap", type=float, default=0.0, metavar="F",
                     help="a lesion is hit when at least this fraction of it is matched (taken to 1/1000; 0: any overlap)")
     ap.add_argument("--report", type=Path, default=None, help="JSON of the per-case scores (needs --labels)")
+    ap.add_argument("--tolerance-mm", type=float, action="append", default=None, metavar="T",
+                    help="also score HD95, ASSD and the surface Dice at this tolerance in 3-D, per case; repeatable (needs --labels)")
+    ap.add_argument("--surface-quantile", type=int, nargs=2, default=[95, 100], metavar=("NUM", "DEN"),
+                    help="the nearest-rank quantile reported as hd95_mm")
     return ap
 
 
@@ -75,6 +85,13 @@ def check_args(ap: argparse.ArgumentParser, args: argparse.Namespace) -> None:
         ap.error(f"--labels: one per --volume, got {len(args.labels)} for {len(args.volume)} volume(s)")
     if args.report is not None and args.labels is None:
         ap.error("--report needs --labels")
+    if args.tolerance_mm is not None:
+        if args.labels is None:
+            ap.error("--tolerance-mm needs --labels")
+        if len(args.tolerance_mm) > ops.SURFACE_MAX_TOLERANCES or any(not 0.0 <= t < float("inf") for t in args.tolerance_mm):
+            ap.error(f"--tolerance-mm: 1 to {ops.SURFACE_MAX_TOLERANCES} finite values >= 0, got {args.tolerance_mm}")
+    if not 0 < args.surface_quantile[0] <= args.surface_quantile[1]:
+        ap.error(f"--surface-quantile: two integers with 0 < NUM <= DEN, got {args.surface_quantile}")
     if args.batch_size < 1:
         ap.error(f"--batch-size: an integer >= 1, got {args.batch_size}")
     if any(not 0.0 < s < float("inf") for s in args.spacing):
@@ -107,6 +124,18 @@ def case_report(res: dict, args: argparse.Namespace, overlap) -> dict:
             "min_volume_mm3": float(args.min_component_mm3), "keep_largest": bool(args.keep_largest), "per_class": per_class, "mean": mean}
 
 
+def add_surface_report(report: dict, res: dict, args: argparse.Namespace) -> None:
+    """The volumetric boundary metrics of SurfaceAccumulator.result() (one case = one image) into the report."""
+    tol = list(args.tolerance_mm)
+    report["tolerances_mm"] = tol
+    report["quantile"] = f"{args.surface_quantile[0]}/{args.surface_quantile[1]} (nearest rank)"
+    report["spacing"] = "distances in mm with the label grid's voxel (s_z, s_y, s_x) = (SZ, SY H / S, SX W / S) of every case"
+    report["per_class"].update({"hd95_mm": _floats(res["hd95"]), "assd_mm": _floats(res["assd"]),
+                                "nsd": {f"{t:g}": _floats(res["nsd"][:, i]) for i, t in enumerate(tol)}, "surface_cases": res["images"].tolist()})
+    report["mean"].update({"hd95_mm": _mean_present(res["hd95"][1:]), "assd_mm": _mean_present(res["assd"][1:]),
+                           "nsd": {f"{t:g}": _mean_present(res["nsd"][1:, i]) for i, t in enumerate(tol)}})
+
+
 def run(args: argparse.Namespace):
     ap = build_parser()
     check_args(ap, args)
@@ -122,6 +151,7 @@ def run(args: argparse.Namespace):
     C, S = model.head.num_classes, model.img_size
     overlap = (round(1000 * args.lesion_overlap), 1000)
     acc = SG.CaseAccumulator(C) if args.labels else None
+    surf = SG.SurfaceAccumulator(C, len(args.tolerance_mm)) if args.tolerance_mm else None
     sx, sy, sz = args.spacing
     for i, vpath in enumerate(args.volume):
         vol = np.load(vpath)
@@ -143,9 +173,14 @@ def run(args: argparse.Namespace):
         mv = SG.min_component_vox(args.min_component_mm3, voxel)
         _, cnt = ops.cc_filter_3d(p, C, first_class=C, connectivity=args.connectivity, targets=gt)      # first_class = C: keeps all, counts only
         acc.update(cnt, ops.lesion_counts_3d(p, gt, C, connectivity=args.connectivity, overlap=overlap, min_vox=mv))
+        if surf is not None:
+            sc, sv = ops.surface_stats_3d(p, gt, voxel, C, tolerances=args.tolerance_mm, q=tuple(args.surface_quantile))
+            surf.update(SG.surface_metrics_3d(sc, sv, voxel, tuple(p.shape)))
     if acc is None:
         return None
     report = case_report(acc.result(), args, overlap)
+    if surf is not None:
+        add_surface_report(report, surf.result(), args)
     report["segmenter"], report["backbone"] = str(args.segmenter), str(args.backbone)
     if args.report is not None:
         Path(args.report).parent.mkdir(parents=True, exist_ok=True)

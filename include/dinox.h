@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define DINOX_ABI_VERSION 3   /* 3: + dinox_block_forward / _backward, dinox_gemm_timer_*, dinox_retrieval_* (later also dinox_retrieval_rank_windowed*, dinox_row_dots), dinox_knn_*, dinox_gram_*, dinox_softmax_probe*, dinox_ntxent_* (later also dinox_ntxent_*_rect), dinox_normalize_bwd, dinox_mae_*, dinox_attention_rows*, dinox_attention_rollout_step*, dinox_ibot_*, dinox_gather_rows, dinox_scatter_add_rows, dinox_seg_*, dinox_surface_*, dinox_cc_*, dinox_cc3d_* (all additive: no entry
+#define DINOX_ABI_VERSION 3   /* 3: + dinox_block_forward / _backward, dinox_gemm_timer_*, dinox_retrieval_* (later also dinox_retrieval_rank_windowed*, dinox_row_dots), dinox_knn_*, dinox_gram_*, dinox_softmax_probe*, dinox_ntxent_* (later also dinox_ntxent_*_rect), dinox_normalize_bwd, dinox_mae_*, dinox_attention_rows*, dinox_attention_rollout_step*, dinox_ibot_*, dinox_gather_rows, dinox_scatter_add_rows, dinox_seg_*, dinox_surface_*, dinox_cc_*, dinox_cc3d_*, dinox_surface3d_* (all additive: no entry
                                * of an earlier library changed, so the number callers test, dinox_version() == 3, stays; probe the symbol
                                * to learn whether a given build has the later additions) */
 
@@ -838,6 +838,42 @@ int dinox_seg_predict(const float* z, const uint8_t* y, uint8_t* pred, int64_t* 
 int64_t dinox_surface_ws_bytes(int64_t B, int H, int W, int C);
 int dinox_surface_stats(const uint8_t* pred, const uint8_t* gt, const float* spacing, const float* tol, int64_t* counts, float* values,
                         int64_t* bad, void* ws, int64_t B, int H, int W, int C, int T, int q_num, int q_den, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Surface distances between two label VOLUMES, in mm (kernels: csrc/surfdist3d.hip; dinox.ops.surface_stats_3d,
+ * dinox.segment.surface_metrics_3d).  One volume per call; everything is as in the section above with these differences:
+ *   pred[Z][H][W], gt[Z][H][W]  uint8, dense, 1 <= Z, H, W <= 1024 (an axis distance fits uint16 beside its sentinel, one axis line fits
+ *               LDS), hence Z H W <= 2^30 as the 3-D components have it (every n fits an unsigned 32-bit integer).  Classes 0 .. C - 1, 2 <= C <= 64.  gt == 255 is
+ *               ignore.  Bad values are counted as above: bad[0] pred values >= C, bad[1] gt values >= C other than 255.
+ *   spacing[3]  fp32, a HOST array read during the call: the voxel (s_z, s_y, s_x) in mm, finite and > 0.
+ *   Sets, per class c:  A = {p : gt_p != 255 and pred_p = c},  G = {p : gt_p = c}; an ignored voxel is in neither.
+ *   Border dX of a set X: the voxels of X with at least one of their SIX FACE NEIGHBOURS outside X; a neighbour outside the volume is
+ *               outside X (X and not binary_erosion(X) with the 6-connected cross, the default structuring element of scipy and MedPy in
+ *               3-D).  A volume with Z = 1 therefore has dX = X: both z neighbours of every voxel are outside.  That is intended, and it
+ *               is NOT the 2-D result of the section above for the same slice.
+ *   d(p, Y) = min over q in Y of sqrt((s_z (p_z - q_z))^2 + (s_y (p_y - q_y))^2 + (s_x (p_x - q_x))^2).
+ *   Directed distances, n, sum, maximum, the k-th smallest with k = ceil(n q_num / q_den) in integers, the T tolerance counts and the
+ *               rule for an empty border are those of the section above; HD95, HD, ASSD and NSD are formed by the caller
+ *               (dinox.segment.surface_metrics_3d).
+ * An exact separable distance transform in three axis passes, one class at a time over the same planes: a z scan (distance in voxels to
+ * the nearest border voxel of the z column, uint16), a y minimum over (s_y (y - y'))^2 + (s_z d)^2 at every voxel, an x minimum over
+ * (s_x (x - x'))^2 + that value at the query border voxels only, then a reduction per slice, four digit histograms of a radix select on
+ * the fp32 bit patterns spread over the slices (integer atomics in global memory) and one workgroup that adds the slice sums in ascending
+ * z.  A distance is sqrt(fl(fl(fl(s_x k)^2) + fl(fl(fl(s_y m)^2) + fl(fl(s_z n)^2)))), every operation rounded once: each square is
+ * within (1 + u)^3 of exact, the inner sum (1 + u)^4, the radicand (1 + u)^5, its correctly rounded root within 2.5 u + u = 3.5 u of the
+ * exact distance, relatively (u = 2^-24).  No floating-point atomics; equal inputs give equal bits whatever the workspace held.
+ * The entry checks its arguments on the host (a message before any launch), allocates nothing and does not synchronise.
+ *
+ * dinox_surface3d_ws_bytes: bytes of workspace, 12 Z H W + 8 Z + 8320 -- two uint16 planes of z distances, two fp32 planes that hold the
+ *   squared y-z distances and then the distances, 2 Z slice sums and 8320 bytes of counters and histograms; C does not enter (a pure
+ *   function of the sizes; 0 for sizes the call refuses; contents need not be initialised; 4-byte aligned).
+ * dinox_surface3d_stats: counts[C][2][1 + T] int64 = (n, within tol_0 .. tol_{T-1}); values[C][2][3] fp32 = (sum, max, quantile);
+ *   direction 0 runs from dA to dG, 1 the other way; bad[2] int64, zeroed on the stream first.  spacing and tol are HOST arrays of 3 and
+ *   T floats, read during the call; every other pointer is a device pointer.
+ * ------------------------------------------------------------------------------------------ */
+int64_t dinox_surface3d_ws_bytes(int64_t Z, int H, int W, int C);
+int dinox_surface3d_stats(const uint8_t* pred, const uint8_t* gt, const float* spacing, const float* tol, int64_t* counts, float* values,
+                          int64_t* bad, void* ws, int64_t Z, int H, int W, int C, int T, int q_num, int q_den, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Connected components of a label map: labelling, clean-up and lesion-wise matching (kernels: csrc/cclabel.hip; dinox.ops.cc_label,
