@@ -102,24 +102,42 @@ __device__ __forceinline__ void seg_softmax(float (&l)[CP], int C, float& m, flo
   for (int c = 0; c < CP; ++c) l[c] *= inv;
 }
 
+// What the boundary-term variants of the kernels below take beyond the others (BD = false: nothing, and those instantiations compile to
+// what they were before the term existed).  phi[B][C][S][S]: the signed distance maps of csrc/distmap.hip.
+template <bool BD>
+struct SegBd {};
+template <>
+struct SegBd<true> {
+  const float* phi;
+  int c0;
+  float w_bd;
+  int only_bd;                                    // seg_fwd_final_kernel writes loss[3] alone
+};
+
 // ---------------------------------------------------------------- forward: partial sums of SEG_FWD_CELLS cells per wave
 // wsf[part][1 + 2 C] = (sum of lse - l_y, P[C], I[C]); wsi[part][C + 2] = (Y[C], valid pixels, labels outside [0, C) other than 255).
-template <int CP>
+// BD (the boundary term, dinox_seg_loss_bd_fwd): wsf[part][2 + 2 C], the last float the sum of p_pc phi_c(p) over the valid pixels and c >= c0,
+// phi read at the pixel the lane holds (coalesced along x, the planes below c0 not at all).
+template <int CP, bool BD = false>
 __global__ __launch_bounds__(64 * SEG_WAVES) void seg_fwd_partial_kernel(const float* __restrict__ z, const uint8_t* __restrict__ y, float* __restrict__ wsf,
                                                                          unsigned* __restrict__ wsi, int g, int u, int C, float inv2u, int ywide,
-                                                                         int64_t ncell, int64_t nparts) {
+                                                                         int64_t ncell, int64_t nparts, SegBd<BD> bdp) {
   __shared__ unsigned cnt[SEG_WAVES][CP + 2];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int64_t part = (int64_t)blockIdx.x * SEG_WAVES + wave;
   for (int i = lane; i < CP + 2; i += 64) cnt[wave][i] = 0;
   __syncthreads();
   float P[CP], I[CP], ce = 0.f;
+  [[maybe_unused]] float bd = 0.f;
 #pragma unroll
   for (int c = 0; c < CP; ++c) P[c] = I[c] = 0.f;
   if (part < nparts) {
     const int64_t c_end = (part + 1) * SEG_FWD_CELLS < ncell ? (part + 1) * SEG_FWD_CELLS : ncell;
-    for (int64_t cell = part * SEG_FWD_CELLS; cell < c_end; ++cell)
-      seg_cell_pixels<CP>(z, y, g, u, C, inv2u, ywide, cell, lane, [&](bool ok, int lab, float, float, float(&l)[CP], int, int) {
+    for (int64_t cell = part * SEG_FWD_CELLS; cell < c_end; ++cell) {
+      [[maybe_unused]] const int64_t ss = (int64_t)(g * u) * (g * u);
+      [[maybe_unused]] const float* pb = nullptr;
+      if constexpr (BD) pb = bdp.phi + (cell / ((int64_t)g * g)) * C * ss;
+      seg_cell_pixels<CP>(z, y, g, u, C, inv2u, ywide, cell, lane, [&](bool ok, int lab, float, float, float(&l)[CP], int Y, int X) {
         if (!ok || lab == 255) return;
         if (lab >= C) {
           atomicAdd(&cnt[wave][CP + 1], 1u);
@@ -136,11 +154,19 @@ __global__ __launch_bounds__(64 * SEG_WAVES) void seg_fwd_partial_kernel(const f
           P[c] += l[c];
           I[c] += lab == c ? l[c] : 0.f;
         }
+        if constexpr (BD) {
+          const float* pp = pb + (int64_t)Y * (g * u) + X;
+#pragma unroll
+          for (int c = 0; c < CP; ++c)
+            if (c >= bdp.c0 && c < C) bd += l[c] * pp[c * ss];
+        }
         atomicAdd(&cnt[wave][lab], 1u);
         atomicAdd(&cnt[wave][CP], 1u);
       });
+    }
   }
   ce = wave_sum(ce);
+  if constexpr (BD) bd = wave_sum(bd);
   float outP = 0.f, outI = 0.f;                   // lane c keeps class c's sums: one coalesced store each
 #pragma unroll
   for (int c = 0; c < CP; ++c) {
@@ -149,7 +175,7 @@ __global__ __launch_bounds__(64 * SEG_WAVES) void seg_fwd_partial_kernel(const f
   }
   __syncthreads();                                // the LDS counters of every wave are complete
   if (part < nparts) {
-    float* wf = wsf + part * (1 + 2 * C);
+    float* wf = wsf + part * (1 + 2 * C + (BD ? 1 : 0));
     unsigned* wi = wsi + part * (C + 2);
     if (lane == 0) wf[0] = ce;
     if (lane < C) {
@@ -158,17 +184,22 @@ __global__ __launch_bounds__(64 * SEG_WAVES) void seg_fwd_partial_kernel(const f
       wi[lane] = cnt[wave][lane];
     }
     if (lane == 0) wi[C] = cnt[wave][CP], wi[C + 1] = cnt[wave][CP + 1];
+    if constexpr (BD)
+      if (lane == 0) wf[1 + 2 * C] = bd;
   }
 }
 
 // One workgroup: the partial sums in a fixed order (lane i takes parts i, i + 64, ..., then the butterfly), then the losses.
+// BD: one float more per part (above); loss[3] = its sum / (Nv (C - c0)), and w_bd times that joins L.  only_bd: nothing but loss[3] is
+// written (the other outputs are then those of the kernels without the term, dinox_seg_loss_bd_fwd with w_bd = 0).
+template <bool BD = false>
 __global__ __launch_bounds__(256) void seg_fwd_final_kernel(const float* __restrict__ wsf, const unsigned* __restrict__ wsi, float* __restrict__ loss,
                                                             float* __restrict__ stats, int64_t* __restrict__ nv, int C, int c0, float w_ce,
-                                                            float w_dice, int64_t nparts) {
-  __shared__ float sf[1 + 2 * 64];
+                                                            float w_dice, int64_t nparts, SegBd<BD> bdp) {
+  __shared__ float sf[1 + 2 * 64 + (BD ? 1 : 0)];
   __shared__ double si[64 + 2];
   __shared__ float dc[64];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nf = 1 + 2 * C, ni = C + 2;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nf = 1 + 2 * C + (BD ? 1 : 0), ni = C + 2;
   for (int q = wave; q < nf + ni; q += 4) {
     if (q < nf) {
       float a = 0.f;
@@ -186,6 +217,12 @@ __global__ __launch_bounds__(256) void seg_fwd_final_kernel(const float* __restr
   __syncthreads();
   const double nvd = si[C];
   const int c = threadIdx.x;
+  if constexpr (BD) {
+    if (bdp.only_bd) {                            // uniform
+      if (threadIdx.x == 0) loss[3] = nvd > 0 ? sf[1 + 2 * C] / ((float)nvd * (float)(C - c0)) : 0.f;
+      return;
+    }
+  }
   if (c < C) {
     const float Pc = sf[1 + c], Ic = sf[1 + C + c], Yc = (float)si[c];
     stats[c] = nvd > 0 ? Ic : 0.f;
@@ -204,7 +241,13 @@ __global__ __launch_bounds__(256) void seg_fwd_final_kernel(const float* __restr
       for (int k = c0; k < C; ++k) d += dc[k];
       dice = 1.f - d / (float)(C - c0);
     }
-    loss[0] = w_ce * ce + w_dice * dice;
+    float L = w_ce * ce + w_dice * dice;
+    if constexpr (BD) {
+      const float bd = nvd > 0 ? sf[1 + 2 * C] / ((float)nvd * (float)(C - c0)) : 0.f;
+      L += bdp.w_bd * bd;
+      loss[3] = bd;
+    }
+    loss[0] = L;
     loss[1] = ce;
     loss[2] = dice;
   }
@@ -212,11 +255,13 @@ __global__ __launch_bounds__(256) void seg_fwd_final_kernel(const float* __restr
 
 // ---------------------------------------------------------------- backward: per cell, the four taps' sums of W(p, tap) G_p
 // wsb[cell][4][C]: tap (ty, tx) at index 2 ty + tx; a clamped second tap carries weight 0 (its weight went to the first).
-template <int CP>
+// BD: the boundary term's G_pc += kbd p_pc (phi_pc - sum_k p_pk phi_pk), kbd = w_bd / (Nv (C - c0)), has the Dice term's shape and is added
+// in the same pixel pass, after the same softmax, as a term of its own beside the other two.
+template <int CP, bool BD = false>
 __global__ __launch_bounds__(64 * SEG_WAVES) void seg_bwd_cells_kernel(const float* __restrict__ z, const uint8_t* __restrict__ y,
                                                                        const float* __restrict__ stats, const int64_t* __restrict__ nv,
                                                                        float* __restrict__ wsb, int g, int u, int C, int c0, float w_ce, float w_dice,
-                                                                       float inv2u, int ywide, int64_t ncell) {
+                                                                       float inv2u, int ywide, int64_t ncell, SegBd<BD> bdp) {
   __shared__ float al[CP], be[CP];                // w_dice a_pc = be[c] + [y_p = c] al[c]
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   if (threadIdx.x < CP) {
@@ -236,20 +281,37 @@ __global__ __launch_bounds__(64 * SEG_WAVES) void seg_bwd_cells_kernel(const flo
   if (cell >= ncell) return;                      // no barrier below
   const int64_t nvv = nv[0];
   const float kce = nvv > 0 ? w_ce / (float)nvv : 0.f;
+  [[maybe_unused]] float kbd = 0.f;
+  [[maybe_unused]] const int64_t ss = (int64_t)(g * u) * (g * u);
+  [[maybe_unused]] const float* pb = nullptr;
+  if constexpr (BD) {
+    kbd = nvv > 0 ? bdp.w_bd / ((float)nvv * (float)(C - c0)) : 0.f;
+    pb = bdp.phi + (cell / ((int64_t)g * g)) * C * ss;
+  }
   float T0[CP], T1[CP];
 #pragma unroll
   for (int c = 0; c < CP; ++c) T0[c] = T1[c] = 0.f;
-  seg_cell_pixels<CP>(z, y, g, u, C, inv2u, ywide, cell, lane, [&](bool ok, int lab, float wy0, float wy1, float(&l)[CP], int, int) {
+  seg_cell_pixels<CP>(z, y, g, u, C, inv2u, ywide, cell, lane, [&](bool ok, int lab, float wy0, float wy1, float(&l)[CP], int Y, int X) {
     if (!ok || lab >= C) return;
     float m, sum;
     seg_softmax<CP>(l, C, m, sum);
     float dot = 0.f;
 #pragma unroll
     for (int c = 0; c < CP; ++c) dot += l[c] * (be[c] + (lab == c ? al[c] : 0.f));
+    [[maybe_unused]] float t[CP], dotb = 0.f;     // BD: t = kbd phi_pc and sum_k p_pk t_k
+    if constexpr (BD) {
+      const float* pp = pb + (int64_t)Y * (g * u) + X;
+#pragma unroll
+      for (int c = 0; c < CP; ++c) {
+        t[c] = c >= c0 && c < C ? kbd * pp[c * ss] : 0.f;
+        dotb += l[c] * t[c];
+      }
+    }
 #pragma unroll
     for (int c = 0; c < CP; ++c) {
       const bool hit = lab == c;
-      const float G = kce * (l[c] - (hit ? 1.f : 0.f)) + l[c] * ((be[c] + (hit ? al[c] : 0.f)) - dot);
+      float G = kce * (l[c] - (hit ? 1.f : 0.f)) + l[c] * ((be[c] + (hit ? al[c] : 0.f)) - dot);
+      if constexpr (BD) G += l[c] * (t[c] - dotb);
       T0[c] += wy0 * G;
       T1[c] += wy1 * G;
     }
@@ -400,11 +462,11 @@ extern "C" int dinox_seg_loss_fwd(const float* z, const uint8_t* y, float* loss,
   const float inv2u = 1.0f / (float)(2 * u);
   seg_by_width(C, [&](auto cp) {
     hipLaunchKernelGGL((seg_fwd_partial_kernel<decltype(cp)::value>), dim3(grid), dim3(64 * SEG_WAVES), 0, st, z, y, wsf, wsi, g, u, C, inv2u,
-                       seg_wide(y, u), ncell, parts);
+                       seg_wide(y, u), ncell, parts, SegBd<false>{});
   });
   rc = check_launch("seg_loss_fwd (partials)");
   if (rc) return rc;
-  hipLaunchKernelGGL(seg_fwd_final_kernel, dim3(1), dim3(256), 0, st, wsf, wsi, loss, stats, nv, C, c0, w_ce, w_dice, parts);
+  hipLaunchKernelGGL(seg_fwd_final_kernel<false>, dim3(1), dim3(256), 0, st, wsf, wsi, loss, stats, nv, C, c0, w_ce, w_dice, parts, SegBd<false>{});
   return check_launch("seg_loss_fwd (sum)");
 }
 
@@ -421,13 +483,77 @@ extern "C" int dinox_seg_loss_bwd(const float* z, const uint8_t* y, const float*
   const float inv2u = 1.0f / (float)(2 * u);
   seg_by_width(C, [&](auto cp) {
     hipLaunchKernelGGL((seg_bwd_cells_kernel<decltype(cp)::value>), dim3(grid), dim3(64 * SEG_WAVES), 0, st, z, y, stats, nv, wsb, g, u, C, c0, w_ce,
-                       w_dice, inv2u, seg_wide(y, u), ncell);
+                       w_dice, inv2u, seg_wide(y, u), ncell, SegBd<false>{});
   });
   rc = check_launch("seg_loss_bwd (cells)");
   if (rc) return rc;
   const int64_t total = ncell * C;
   hipLaunchKernelGGL(seg_bwd_gather_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, st, wsb, dz, grad_scale, g, C, total);
   return check_launch("seg_loss_bwd (gather)");
+}
+
+// ---------------------------------------------------------------- the same with the boundary term (phi: csrc/distmap.hip)
+extern "C" size_t dinox_seg_loss_bd_ws_bytes(int64_t B, int g, int u, int C) {
+  if (seg_broken_limit(B, g, u, C)) return 0;
+  const int64_t ncell = B * g * g, parts = seg_fwd_parts(B, g);
+  const int64_t fwd = parts * (2 + 2 * C) * 4 + parts * (C + 2) * 4, bwd = ncell * 4 * C * 4;
+  return (size_t)(fwd > bwd ? fwd : bwd);
+}
+
+extern "C" int dinox_seg_loss_bd_fwd(const float* z, const uint8_t* y, const float* phi, float* loss, float* stats, int64_t* nv, void* ws, int64_t B,
+                                     int g, int u, int C, int c0, float w_ce, float w_dice, float w_bd, void* stream) {
+  DX_REQUIRE(z && y && phi && loss && stats && nv && ws, DINOX_EINVAL, "seg_loss_bd_fwd: null pointer");
+  int rc = seg_geometry("seg_loss_bd_fwd", B, g, u, C);
+  if (rc) return rc;
+  DX_REQUIRE(c0 == 0 || c0 == 1, DINOX_EINVAL, "seg_loss_bd_fwd: c0=%d (0: every class in the Dice and boundary terms, 1: without class 0)", c0);
+  // w_bd = 0 promises the bits of dinox_seg_loss_fwd.  How the compiler fuses the shared sums differs between the two instantiations (seen
+  // at C > 32: P_c accumulated by a fused multiply-add in one, a multiply and an add in the other), so that promise is kept by running
+  // those very kernels; the boundary kernels then report BD alone, in the one case where nothing trains on it.
+  const bool only_bd = w_bd == 0.f;
+  if (only_bd) {
+    rc = dinox_seg_loss_fwd(z, y, loss, stats, nv, ws, B, g, u, C, c0, w_ce, w_dice, stream);
+    if (rc) return rc;
+  }
+  hipStream_t st = as_stream(stream);
+  const int64_t ncell = B * g * g, parts = seg_fwd_parts(B, g);
+  float* wsf = (float*)ws;
+  unsigned* wsi = (unsigned*)(wsf + parts * (2 + 2 * C));
+  const unsigned grid = (unsigned)ceil_div(parts, (int64_t)SEG_WAVES);
+  const float inv2u = 1.0f / (float)(2 * u);
+  const SegBd<true> bdp{phi, c0, w_bd, only_bd ? 1 : 0};
+  seg_by_width(C, [&](auto cp) {
+    hipLaunchKernelGGL((seg_fwd_partial_kernel<decltype(cp)::value, true>), dim3(grid), dim3(64 * SEG_WAVES), 0, st, z, y, wsf, wsi, g, u, C, inv2u,
+                       seg_wide(y, u), ncell, parts, bdp);
+  });
+  rc = check_launch("seg_loss_bd_fwd (partials)");
+  if (rc) return rc;
+  hipLaunchKernelGGL(seg_fwd_final_kernel<true>, dim3(1), dim3(256), 0, st, wsf, wsi, loss, stats, nv, C, c0, w_ce, w_dice, parts, bdp);
+  return check_launch("seg_loss_bd_fwd (sum)");
+}
+
+extern "C" int dinox_seg_loss_bd_bwd(const float* z, const uint8_t* y, const float* phi, const float* stats, const int64_t* nv, float* dz, void* ws,
+                                     int64_t B, int g, int u, int C, int c0, float w_ce, float w_dice, float w_bd, float grad_scale, void* stream) {
+  DX_REQUIRE(z && y && phi && stats && nv && dz && ws, DINOX_EINVAL, "seg_loss_bd_bwd: null pointer");
+  int rc = seg_geometry("seg_loss_bd_bwd", B, g, u, C);
+  if (rc) return rc;
+  DX_REQUIRE(c0 == 0 || c0 == 1, DINOX_EINVAL, "seg_loss_bd_bwd: c0=%d (0: every class in the Dice and boundary terms, 1: without class 0)", c0);
+  if (w_bd == 0.f)                                // the gradient has no boundary term: the kernels without it, and their bits (see the forward)
+    return dinox_seg_loss_bwd(z, y, stats, nv, dz, ws, B, g, u, C, c0, w_ce, w_dice, grad_scale, stream);
+  hipStream_t st = as_stream(stream);
+  const int64_t ncell = B * g * g;
+  float* wsb = (float*)ws;
+  const unsigned grid = (unsigned)ceil_div(ncell, (int64_t)SEG_WAVES);
+  const float inv2u = 1.0f / (float)(2 * u);
+  const SegBd<true> bdp{phi, c0, w_bd, 0};
+  seg_by_width(C, [&](auto cp) {
+    hipLaunchKernelGGL((seg_bwd_cells_kernel<decltype(cp)::value, true>), dim3(grid), dim3(64 * SEG_WAVES), 0, st, z, y, stats, nv, wsb, g, u, C, c0,
+                       w_ce, w_dice, inv2u, seg_wide(y, u), ncell, bdp);
+  });
+  rc = check_launch("seg_loss_bd_bwd (cells)");
+  if (rc) return rc;
+  const int64_t total = ncell * C;
+  hipLaunchKernelGGL(seg_bwd_gather_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, st, wsb, dz, grad_scale, g, C, total);
+  return check_launch("seg_loss_bd_bwd (gather)");
 }
 
 extern "C" int dinox_seg_predict(const float* z, const uint8_t* y, uint8_t* pred, int64_t* counts, int64_t B, int g, int u, int C, void* stream) {

@@ -148,6 +148,9 @@ SIGNATURES = {
     "dinox_seg_loss_fwd": (i32, [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, f32, vp]),
     "dinox_seg_loss_bwd": (i32, [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, f32, f32, vp]),
     "dinox_seg_predict": (i32, [vp, vp, vp, vp, i64, i32, i32, i32, vp]),
+    "dinox_signed_distance": (i32, [vp, vp, vp, vp, vp, i64, i32, i32, i32, vp]),
+    "dinox_seg_loss_bd_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, f32, f32, vp]),
+    "dinox_seg_loss_bd_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, f32, f32, f32, vp]),
     "dinox_surface_ws_bytes": (i64, [i64, i32, i32, i32]),
     "dinox_surface_stats": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp]),
     "dinox_surface3d_ws_bytes": (i64, [i64, i32, i32, i32]),
@@ -200,6 +203,8 @@ SIGNATURES = {
 # against the header one to one).
 SIZE_T_SIGNATURES = {
     "dinox_attention_rollout_step_ws_bytes": (C.c_size_t, [i32, i32, i32]),
+    "dinox_signed_distance_ws_bytes": (C.c_size_t, [i64, i32, i32, i32]),
+    "dinox_seg_loss_bd_ws_bytes": (C.c_size_t, [i64, i32, i32, i32]),
 }
 
 class DinoxLibraryError(ImportError):

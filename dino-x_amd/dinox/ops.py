@@ -3154,6 +3154,97 @@ def surface_stats(pred: Tensor, labels: Tensor, spacing, num_classes: int, toler
     return counts, values
 
 
+# ------------------------------------------------------------------------------------------
+# boundary loss: signed distance maps (csrc/distmap.hip) and the boundary term of the segmentation loss (csrc/segloss.hip)
+# ------------------------------------------------------------------------------------------
+def signed_distance_map(labels: Tensor, spacing, num_classes: int) -> Tensor:
+    """Signed Euclidean distance maps phi fp32 [B, C, H, W] of a uint8 label map [B, H, W] (255 = ignore), spacing [B, 2] = (s_y, s_x) per
+    image (include/dinox.h has the definitions): +distance to the class outside it, -distance to the other valid pixels inside it, 0 at
+    ignored pixels and where the class is absent from the image or covers all of it.  The batch is cut so that one call's workspace stays
+    under SURFACE_WS_CAP; the result does not depend on the cut.  A label >= C other than 255 raises ValueError (one device read)."""
+    if not isinstance(labels, Tensor) or labels.dtype != torch.uint8 or labels.dim() != 3:
+        raise ValueError(f"signed_distance_map: labels must be uint8 [B, H, W], got {_describe(labels)}")
+    B, H, W = labels.shape
+    if B < 1 or not (1 <= H <= SURFACE_MAX_SIDE and 1 <= W <= SURFACE_MAX_SIDE):
+        raise ValueError(f"signed_distance_map: maps must be [B >= 1, H, W] with 1 <= H, W <= {SURFACE_MAX_SIDE}, got {tuple(labels.shape)}")
+    C = num_classes
+    if isinstance(C, bool) or not isinstance(C, int) or not 2 <= C <= SEG_MAX_CLASSES:
+        raise ValueError(f"signed_distance_map: num_classes must be an integer in [2, {SEG_MAX_CLASSES}], got {C!r}")
+    _need_cuda(labels)
+    dev = labels.device
+    try:
+        sp = _surface_spacing(spacing, B, dev)
+    except ValueError as e:
+        raise ValueError(str(e).replace("surface_stats", "signed_distance_map")) from None
+    labels = _c(labels)
+    phi = torch.empty((B, C, H, W), dtype=torch.float32, device=dev)
+    per_image = int(lib.dinox_signed_distance_ws_bytes(1, H, W, C))
+    step = max(1, min(B, SURFACE_WS_CAP // per_image))
+    while step > 1 and not lib.dinox_signed_distance_ws_bytes(step, H, W, C):      # the launch grids bound the images per call as well
+        step //= 2
+    ws = torch.empty(per_image * step // 4, dtype=torch.float32, device=dev)
+    bad = torch.zeros(-(-B // step), dtype=torch.int64, device=dev)
+    for i, b0 in enumerate(range(0, B, step)):
+        n = min(step, B - b0)
+        check(lib.dinox_signed_distance(_p(labels[b0:]), _p(sp[b0:]), _p(phi[b0:]), _p(bad[i:]), _p(ws), n, H, W, C, _stream()),
+              "dinox_signed_distance")
+    _seg_refuse_bad_labels("signed_distance_map", int(bad.sum()), C)
+    return phi
+
+
+def seg_loss_bd_fwd(z: Tensor, y: Tensor, phi: Tensor, w_ce: float = 1.0, w_dice: float = 1.0, w_bd: float = 1.0, c0: int = 0):
+    """seg_loss_fwd with the boundary term: phi fp32 [B, C, S, S] from signed_distance_map(y, ...).  Returns (loss[4] = (L, CE, Dice, BD),
+    L = w_ce CE + w_dice Dice + w_bd BD, stats [3, C], saved); seg_loss_bd_bwd(saved, gscale) gives d(gscale L)/dz.  phi is data: it
+    gets no gradient."""
+    B, g, C = _seg_geometry("seg_loss_bd", z, 1)
+    u = _seg_labels("seg_loss_bd", y, B, g, z)
+    S = g * u
+    if not isinstance(phi, Tensor) or phi.dtype != torch.float32 or tuple(phi.shape) != (B, C, S, S):
+        raise ValueError(f"seg_loss_bd: phi must be fp32 [{B}, {C}, {S}, {S}] (ops.signed_distance_map of the labels), got {_describe(phi)}")
+    if phi.device != z.device:
+        raise ValueError(f"seg_loss_bd: logits on {z.device}, phi on {phi.device}")
+    if c0 not in (0, 1):
+        raise ValueError(f"seg_loss_bd: c0 must be 0 or 1, got {c0!r}")
+    _need_cuda(z, y, phi)
+    z, y, phi = _c(z.float()), _c(y), _c(phi)
+    dev = z.device
+    loss = torch.empty(4, dtype=torch.float32, device=dev)
+    stats = torch.empty((3, C), dtype=torch.float32, device=dev)
+    nv = torch.empty(2, dtype=torch.int64, device=dev)
+    ws = torch.empty(int(lib.dinox_seg_loss_bd_ws_bytes(B, g, u, C)) // 4, dtype=torch.float32, device=dev)
+    check(lib.dinox_seg_loss_bd_fwd(_p(z), _p(y), _p(phi), _p(loss), _p(stats), _p(nv), _p(ws), B, g, u, C, int(c0), float(w_ce), float(w_dice),
+                                    float(w_bd), _stream()), "dinox_seg_loss_bd_fwd")
+    _seg_refuse_bad_labels("seg_loss_bd", int(nv[1]), C)
+    return loss, stats, (z, y, phi, stats, nv, ws, (B, g, u, C, int(c0), float(w_ce), float(w_dice), float(w_bd)))
+
+
+def seg_loss_bd_bwd(saved, gscale: float = 1.0) -> Tensor:
+    """dz [B, g^2, C] fp32 = d(gscale L)/dz of seg_loss_bd_fwd, the boundary term in the same pixel pass as the other two."""
+    z, y, phi, stats, nv, ws, (B, g, u, C, c0, w_ce, w_dice, w_bd) = saved
+    dz = torch.empty_like(z)
+    check(lib.dinox_seg_loss_bd_bwd(_p(z), _p(y), _p(phi), _p(stats), _p(nv), _p(dz), _p(ws), B, g, u, C, c0, w_ce, w_dice, w_bd, float(gscale),
+                                    _stream()), "dinox_seg_loss_bd_bwd")
+    return dz
+
+
+class SegBoundaryLossFn(torch.autograd.Function):
+    """(z, y, phi, w_ce, w_dice, w_bd, c0) -> (L, CE, Dice, BD) as 0-d tensors; the backward takes the upstream gradient of L only (the
+    other three are reported values) and gives one to z only.  z of any floating dtype is cast to fp32."""
+
+    @staticmethod
+    def forward(ctx, z, y, phi, w_ce=1.0, w_dice=1.0, w_bd=1.0, c0=0):
+        loss, _, saved = seg_loss_bd_fwd(z, y, phi, w_ce, w_dice, w_bd, c0)
+        ctx.saved, ctx.zdt = saved, z.dtype
+        total, ce, dice, bd = (loss[i].clone() for i in range(4))
+        ctx.mark_non_differentiable(ce, dice, bd)
+        return total, ce, dice, bd
+
+    @staticmethod
+    def backward(ctx, g, *_reported):
+        d = seg_loss_bd_bwd(ctx.saved, 1.0) * g             # (a device scalar: no host sync, as in SegLossFn)
+        return (d if d.dtype == ctx.zdt else d.to(ctx.zdt)), None, None, None, None, None, None
+
+
 def surface_stats_3d(pred: Tensor, labels: Tensor, spacing, num_classes: int, tolerances=(1.0,), q=(95, 100)):
     """Directed surface-distance statistics of two uint8 label volumes [Z, H, W] (labels: 255 = ignore) in mm with the voxel
     spacing = (s_z, s_y, s_x) (include/dinox.h has the definitions: the border is taken with the six face neighbours, so a one-slice volume

@@ -9,6 +9,9 @@ CSV columns: image_path,mask_path[,spacing_x,spacing_y,spacing_z].  The mask is 
 Image and mask get the same random-resized crop window and the same flip (image bicubic, mask nearest); validation takes the centre crop
 of both.  The loss and the validation metrics run at full resolution inside csrc/segloss.hip (ops.SegLossFn, ops.seg_predict): the
 [B, P, C] patch logits are the only logits in memory.  Optimiser, schedule, pixel reading and the adapter come from finetune_lora.py.
+--boundary-weight W adds Kervadec's boundary loss (the softmax probabilities weighted by the signed distance to each class's region,
+ops.signed_distance_map + ops.SegBoundaryLossFn) with --boundary-ramp-epochs and --boundary-units px|mm; 0, the default, is the run
+without it.
 Written to --output whenever the early-stopping metric improves: the adapter files (rank > 0), seg_head.pth, finetune_config.json and,
 with --unfreeze-blocks, unfrozen_blocks.pth; dinox.segment.load_segmenter puts them back together.
 """
@@ -96,24 +99,38 @@ def _center_pair(x: torch.Tensor, m: torch.Tensor, size: int):
     return x[:, t:t + size, l:l + size], m[t:t + size, l:l + size]
 
 
+def _center_factors(h: int, w: int, size: int) -> Tuple[float, float]:
+    """(h / nh, w / nw) of _center_pair: source pixels per pixel of the centre crop (evaluate_segmentation.py's convention)."""
+    k = size / min(h, w)
+    return h / max(size, round(h * k)), w / max(size, round(w * k))
+
+
+def paired_transform_grid(x: torch.Tensor, m: torch.Tensor, size: int, gen: torch.Generator, augment: bool):
+    """paired_transform (below) and the grid it lands on: (image, mask, (f_y, f_x)), f = source pixels per output pixel along each axis --
+    ch / size and cw / size for a crop window ch x cw, the centre crop's resize factors otherwise.  The same draws in the same order."""
+    if x.shape[-2:] != m.shape[-2:]:
+        raise ValueError(f"image {tuple(x.shape[-2:])} and mask {tuple(m.shape[-2:])} differ in size")
+    h, w = x.shape[-2:]
+    if augment:
+        win = _crop_window(h, w, gen)
+        if win is None:
+            x, m, f = *_center_pair(x, m, size), _center_factors(h, w, size)
+        else:
+            t, l, ch, cw = win
+            x, m = fl._resize(x[:, t:t + ch, l:l + cw], size, size), _resize_mask(m[t:t + ch, l:l + cw], size, size)
+            f = (ch / size, cw / size)
+        if float(torch.rand(1, generator=gen)) < 0.5:
+            x, m = x.flip(-1), m.flip(-1)
+    else:
+        x, m, f = *_center_pair(x, m, size), _center_factors(h, w, size)
+    return fl.normalize(x).contiguous(), m.contiguous(), f
+
+
 def paired_transform(x: torch.Tensor, m: torch.Tensor, size: int, gen: torch.Generator, augment: bool):
     """image [3, H, W] in [0, 1] and mask uint8 [H, W] -> (normalised image [3, size, size], mask uint8 [size, size]).  ``augment``: one
     random-resized crop window and one horizontal flip for both; otherwise the centre crop of both.  The image is resized bicubic, the
     mask nearest, so the mask holds only values of the source mask."""
-    if x.shape[-2:] != m.shape[-2:]:
-        raise ValueError(f"image {tuple(x.shape[-2:])} and mask {tuple(m.shape[-2:])} differ in size")
-    if augment:
-        win = _crop_window(x.shape[-2], x.shape[-1], gen)
-        if win is None:
-            x, m = _center_pair(x, m, size)
-        else:
-            t, l, ch, cw = win
-            x, m = fl._resize(x[:, t:t + ch, l:l + cw], size, size), _resize_mask(m[t:t + ch, l:l + cw], size, size)
-        if float(torch.rand(1, generator=gen)) < 0.5:
-            x, m = x.flip(-1), m.flip(-1)
-    else:
-        x, m = _center_pair(x, m, size)
-    return fl.normalize(x).contiguous(), m.contiguous()
+    return paired_transform_grid(x, m, size, gen, augment)[:2]
 
 
 class MaskedImages(fl.LabeledImages):
@@ -163,6 +180,26 @@ class SyntheticMasks(fl.LabeledImages):
         return x, self.spacings[i], m
 
 
+class GridMaskedImages(MaskedImages):
+    """MaskedImages that also returns the spacing of the grid the sample landed on, (s_y, s_x) in mm per label-map pixel (--boundary-units
+    mm): the CSV's (spacing_y f_y, spacing_x f_x) with paired_transform_grid's factors."""
+
+    def __getitem__(self, i: int):
+        row = self.rows[i]
+        x, m, (fy, fx) = paired_transform_grid(self.pixels(row)[None].expand(3, -1, -1), self.read_mask(row), self.img_size, self.gen,
+                                               self.augment)
+        return (x, torch.tensor(row.spacing, dtype=torch.float32), m,
+                torch.tensor([row.spacing[1] * fy, row.spacing[0] * fx], dtype=torch.float32))
+
+
+class GridSyntheticMasks(SyntheticMasks):
+    """SyntheticMasks with the (s_y, s_x) of its own spacings as the grid spacing: the maps keep their own, cropped or not."""
+
+    def __getitem__(self, i: int):
+        x, sp, m = super().__getitem__(i)
+        return x, sp, m, torch.stack([sp[1], sp[0]])
+
+
 # ------------------------------------------------------------------------------------------ epochs, saving
 @dataclass
 class SegConfig(fl.FinetuneConfig):
@@ -171,6 +208,22 @@ class SegConfig(fl.FinetuneConfig):
     dice_c0: int = 0
     ignore_index: int = IGNORE
     best_dice_per_class: Optional[List[float]] = None
+    boundary_weight: float = 0.0
+    boundary_ramp_epochs: int = 0
+    boundary_units: str = "px"
+
+
+def boundary_weight(w: float, ramp_epochs: int, epoch: int) -> float:
+    """The training weight of the boundary term in 0-based ``epoch``: w min(1, (epoch + 1) / ramp_epochs); ramp_epochs = 0: constant."""
+    return w if ramp_epochs <= 0 else w * min(1.0, (epoch + 1) / ramp_epochs)
+
+
+def _batches_grid(loader, device, scale_aware):
+    """_batches with the spacing of each sample's label grid [B, 2] = (s_y, s_x): the loader's fourth element, or 1 (pixels) without one."""
+    for batch in loader:
+        x, sp, m = batch[:3]
+        grid = batch[3].to(device) if len(batch) > 3 else torch.ones((x.shape[0], 2), dtype=torch.float32, device=device)
+        yield x.to(device), (sp.to(device) if scale_aware else None), m.to(device), grid
 
 
 def _batches(loader, device, scale_aware):
@@ -178,9 +231,21 @@ def _batches(loader, device, scale_aware):
         yield x.to(device), (sp.to(device) if scale_aware else None), m.to(device)
 
 
-def train_epoch(model, loader, opt: fl.ArenaAdamW, sched, device, scale_aware, amp, w_ce, w_dice, c0) -> float:
+def train_epoch(model, loader, opt: fl.ArenaAdamW, sched, device, scale_aware, amp, w_ce, w_dice, c0, w_bd: float = 0.0) -> float:
+    """w_bd > 0: the boundary term joins the loss, phi computed on the device once per batch from the batch's masks."""
     model.train()
     tot, n = 0.0, 0
+    if w_bd > 0:
+        for x, sp, m, grid in _batches_grid(loader, device, scale_aware):
+            opt.zero_grad()
+            with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+                logits = model(x, spacing=sp)
+            phi = ops.signed_distance_map(m, grid, logits.shape[-1])
+            loss = ops.SegBoundaryLossFn.apply(logits, m, phi, w_ce, w_dice, w_bd, c0)[0]
+            loss.backward()
+            opt.step(sched(opt.t))
+            tot, n = tot + float(loss.detach()), n + 1
+        return tot / max(n, 1)
     for x, sp, m in _batches(loader, device, scale_aware):
         opt.zero_grad()
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
@@ -193,14 +258,19 @@ def train_epoch(model, loader, opt: fl.ArenaAdamW, sched, device, scale_aware, a
 
 
 @torch.no_grad()
-def validate(model, loader, device, scale_aware, amp, w_ce, w_dice, c0):
-    """-> (mean loss, metrics, counts int64 [3, C] on the host, label maps uint8 [n, S, S] on the host)."""
+def validate(model, loader, device, scale_aware, amp, w_ce, w_dice, c0, w_bd: float = 0.0):
+    """-> (mean loss, metrics, counts int64 [3, C] on the host, label maps uint8 [n, S, S] on the host).  w_bd > 0: the loss carries the
+    boundary term at that weight."""
     model.eval()
     tot, n, counts, preds = 0.0, 0, None, []
-    for x, sp, m in _batches(loader, device, scale_aware):
+    for x, sp, m, grid in (_batches_grid(loader, device, scale_aware) if w_bd > 0 else ((*b, None) for b in _batches(loader, device, scale_aware))):
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
             logits = model(x, spacing=sp)
-        tot, n = tot + float(ops.seg_loss_fwd(logits, m, w_ce, w_dice, c0)[0][0]), n + 1
+        if w_bd > 0:
+            phi = ops.signed_distance_map(m, grid, logits.shape[-1])
+            tot, n = tot + float(ops.seg_loss_bd_fwd(logits, m, phi, w_ce, w_dice, w_bd, c0)[0][0]), n + 1
+        else:
+            tot, n = tot + float(ops.seg_loss_fwd(logits, m, w_ce, w_dice, c0)[0][0]), n + 1
         pred, cnt = ops.seg_predict(logits, model.patch, m)
         counts = cnt.clone() if counts is None else counts + cnt
         preds.append(pred.cpu())
@@ -244,10 +314,52 @@ def build_parser() -> argparse.ArgumentParser:
     return ap
 
 
+def build_boundary_parser() -> argparse.ArgumentParser:
+    """The options of the boundary loss.  They are a parser of their own (build_parser() keeps its flag set); parse_cli reads them out of
+    the command line first."""
+    ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    ap.add_argument("--boundary-weight", type=float, default=0.0, metavar="W",
+                    help="weight of the boundary term (signed distance to each class's region times its softmax probability); 0: off")
+    ap.add_argument("--boundary-ramp-epochs", type=int, default=0, metavar="E",
+                    help="the training weight in epoch e (from 0) is W min(1, (e + 1) / E); 0: constant.  Validation always uses W")
+    ap.add_argument("--boundary-units", choices=["px", "mm"], default="px",
+                    help="distances in label-map pixels, or in mm on the spacing of the augmented grid (synthetic maps keep their own)")
+    return ap
+
+
+def parse_cli(argv=None) -> argparse.Namespace:
+    """The boundary options (build_boundary_parser) first, everything else through build_parser; one namespace."""
+    bd, rest = build_boundary_parser().parse_known_args(argv)
+    ap = build_parser()
+    ap.epilog = "Boundary loss: " + " ".join(build_boundary_parser().format_help().split()[1:])
+    args = ap.parse_args(rest)
+    for k, v in vars(bd).items():
+        setattr(args, k, v)
+    return args
+
+
+def warn_mm_without_spacing(rows: List[MaskedRow], units: str) -> bool:
+    """--boundary-units mm on a CSV without spacing columns: warn and take 1 mm per source pixel, as evaluate_segmentation.py does."""
+    if units == "mm" and rows and not rows[0].has_spacing:
+        log.warning("--boundary-units mm, but the CSV has no spacing_x/y/z columns: 1 mm per source pixel is assumed, so the boundary "
+                    "term measures in source pixels")
+        return True
+    return False
+
+
 def run(args: argparse.Namespace) -> dict:
     """One run -> {"config": SegConfig, "val_pred": the best epoch's validation label maps uint8 [n, S, S] (host), "val_dataset": the
-    validation set}."""
+    validation set}.  A namespace without the boundary attributes (build_parser() alone) runs without the boundary term."""
     ap = build_parser()
+    w_bd, ramp = float(getattr(args, "boundary_weight", 0.0)), int(getattr(args, "boundary_ramp_epochs", 0))
+    units = getattr(args, "boundary_units", "px")
+    if not (w_bd >= 0 and math.isfinite(w_bd)):
+        ap.error(f"--boundary-weight {w_bd}: the weight must be finite and >= 0 (0: no boundary term)")
+    if ramp < 0:
+        ap.error(f"--boundary-ramp-epochs {ramp}: the number of ramp epochs must be >= 0 (0: constant weight)")
+    if units not in ("px", "mm"):
+        ap.error(f"--boundary-units {units!r}: px or mm")
+    mm = w_bd > 0 and units == "mm"                          # only then does a sample carry its grid spacing
     if args.ignore_index != IGNORE:
         ap.error(f"--ignore-index {args.ignore_index}: only {IGNORE} is supported (the kernels compare labels with that value)")
     if not 2 <= args.num_classes <= ops.SEG_MAX_CLASSES:
@@ -270,16 +382,20 @@ def run(args: argparse.Namespace) -> dict:
     if args.synthetic:
         n_val = max(args.synthetic // 4, 1)
         n_train = args.synthetic - n_val
-        train_ds = SyntheticMasks(n_train, img, args.num_classes, seed, first=0, augment=True)
-        val_ds = SyntheticMasks(n_val, img, args.num_classes, seed, first=n_train, augment=False)
+        synth = GridSyntheticMasks if mm else SyntheticMasks
+        train_ds = synth(n_train, img, args.num_classes, seed, first=0, augment=True)
+        val_ds = synth(n_val, img, args.num_classes, seed, first=n_train, augment=False)
         workers = 0
     else:
         rows_t, rows_v = read_csv(args.train_csv), read_csv(args.val_csv)
         if scale_aware and not rows_t[0].has_spacing:
             log.warning("scale-aware backbone, but the CSV has no spacing_x/y/z columns: 1 mm is assumed everywhere")
         kw = dict(input_format=args.input_format, window_level=args.window_level, window_width=args.window_width, data_root=args.data_root)
-        train_ds = MaskedImages(rows_t, img, augment=True, seed=seed + 1, **kw)
-        val_ds = MaskedImages(rows_v, img, augment=False, **kw)
+        if w_bd > 0:
+            warn_mm_without_spacing(rows_t, units)
+        masked = GridMaskedImages if mm else MaskedImages
+        train_ds = masked(rows_t, img, augment=True, seed=seed + 1, **kw)
+        val_ds = masked(rows_v, img, augment=False, **kw)
         workers = args.num_workers
     gen = torch.Generator().manual_seed(seed)
     train_loader = torch.utils.data.DataLoader(train_ds, batch_size=args.batch_size, shuffle=True, drop_last=True, num_workers=workers,
@@ -314,13 +430,15 @@ def run(args: argparse.Namespace) -> dict:
                     epochs=args.epochs, batch_size=args.batch_size, input_format=args.input_format, scale_aware=scale_aware,
                     train_samples=len(train_ds), val_samples=len(val_ds), seed=args.seed, unfreeze_blocks=args.unfreeze_blocks,
                     backbone_lr=args.backbone_lr if args.unfreeze_blocks > 0 else None, ce_weight=args.ce_weight, dice_weight=args.dice_weight,
-                    dice_c0=c0, ignore_index=args.ignore_index)
+                    dice_c0=c0, ignore_index=args.ignore_index, boundary_weight=w_bd, boundary_ramp_epochs=ramp, boundary_units=units)
     higher = args.es_metric != "loss"
     best, stale, t0, best_pred = (-math.inf if higher else math.inf), 0, time.time(), None
     for epoch in range(1, args.epochs + 1):
+        bd = (boundary_weight(w_bd, ramp, epoch - 1), w_bd) if w_bd > 0 else None     # (this epoch's training weight, validation's)
         tr = train_epoch(model, train_loader, opt, lambda s: fl.lr_factor(s, warm, steps), device, scale_aware, amp, args.ce_weight,
-                         args.dice_weight, c0)
-        vl, metrics, counts, preds = validate(model, val_loader, device, scale_aware, amp, args.ce_weight, args.dice_weight, c0)
+                         args.dice_weight, c0, *(bd[:1] if bd else ()))
+        vl, metrics, counts, preds = validate(model, val_loader, device, scale_aware, amp, args.ce_weight, args.dice_weight, c0,
+                                              *(bd[1:] if bd else ()))
         cfg.train_loss_history.append(tr)
         log.info("epoch %d/%d  train %.4f  %s", epoch, args.epochs, tr, "  ".join(f"{k} {v:.4f}" for k, v in metrics.items()))
         cur = metrics[args.es_metric] if higher else vl
@@ -339,7 +457,7 @@ def run(args: argparse.Namespace) -> dict:
 
 
 def main(argv=None) -> SegConfig:
-    args = build_parser().parse_args(argv)
+    args = parse_cli(argv)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s [%(levelname)s] %(message)s", datefmt="%H:%M:%S")
     return run(args)["config"]
 

@@ -876,6 +876,57 @@ int dinox_surface3d_stats(const uint8_t* pred, const uint8_t* gt, const float* s
                           int64_t* bad, void* ws, int64_t Z, int H, int W, int C, int T, int q_num, int q_den, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Boundary loss: the signed distance map of a label map and the boundary term of the dense segmentation loss (Kervadec et al., MIDL
+ * 2019; kernels: csrc/distmap.hip and the *_bd_* kernels of csrc/segloss.hip; dinox.ops.signed_distance_map, dinox.ops.SegBoundaryLossFn).
+ *
+ * Signed distance map.
+ *   y[B][H][W]  uint8, dense, 1 <= H, W <= 1024 (rectangular maps are fine), B >= 1 and B C H <= 2^30.  Classes 0 .. C - 1, 2 <= C <= 64
+ *               (C > 64: DINOX_EUNSUPPORTED; C < 2: DINOX_EINVAL).  255 is ignore.  A value >= C other than 255 is an argument error: it
+ *               belongs to no set (a label is only ever compared, never an address) and the call COUNTS them -- bad[0] -- for the caller
+ *               to refuse.
+ *   spacing[B][2]  fp32 on the device, (s_y, s_x) per pixel of each image (mm, or 1 for distances in pixels), finite and > 0.
+ *   Sets, per image b and class c:  G = {p : y_p = c},  R = {p : y_p != c, y_p != 255, y_p < C}; an ignored pixel is in neither and is
+ *               never a source.
+ *   d(p, X) = min over q in X of sqrt((s_y (p_y - q_y))^2 + (s_x (p_x - q_x))^2), between pixel centres.
+ *   phi_c(p) = +d(p, G) for p in R,  -d(p, R) for p in G,  0 at ignored pixels, and 0 wherever the set the pixel needs is empty (the class
+ *               is absent from the image, or covers every valid pixel of it).
+ *   Nothing outside the image counts as outside the class (unlike the border of the surface metrics above): an organ cut by the crop has
+ *               no boundary at the image edge.  Without ignored pixels phi_c is
+ *               distance_transform_edt(~G, sampling) * ~G - distance_transform_edt(G, sampling) * G of scipy.ndimage.
+ * The exact separable transform of the surface kernels, dense: a column scan (per pixel the vertical distance in pixels to the nearest G
+ * and to the nearest R pixel of its column, two uint16 planes), then per row the minimum over x' of (s_x (x - x'))^2 + (s_y d)^2 against
+ * the plane the pixel's own membership selects, the square root and the sign.  A distance is sqrt(fl(fl(s_x k)^2 + fl(s_y m)^2)), every
+ * operation rounded once: within 3 * 2^-24 of the exact one, relatively.  There are no sums and no floating-point atomics: equal inputs
+ * give equal bits, an image's planes do not depend on the rest of the batch, nor a class's plane on C beyond which pixels are valid.
+ *
+ * Boundary term.  z, y, the bilinear upsampling, p = softmax, Nv and c0 are those of the dense segmentation loss above; phi[B][C][S][S] fp32
+ * as produced here (the planes below c0 are not read).
+ *   BD = (1 / (Nv (C - c0))) sum_valid sum_{c >= c0} p_pc phi_c(p);   L = w_ce CE + w_dice Dice + w_bd BD.
+ *   G_pc gains (w_bd / (Nv (C - c0))) p_pc (phi_pc - sum_{k >= c0} p_pk phi_pk), phi_pk = 0 for k < c0: the Dice term's p (a - sum p a)
+ *   with a per-pixel a, so it rides the same pixel pass -- one softmax per pixel per direction, no further launch over the pixels.
+ *   BD can be negative (a good prediction sits inside its region).  Nv = 0: BD = 0 and the gradient is exactly 0.  With w_bd = 0 the
+ *   calls return L, CE, Dice, stats and dz bit-equal to dinox_seg_loss_fwd / _bwd -- they run those very kernels, and the forward reports
+ *   BD from a launch of the boundary kernels of its own (the one case with a second launch over the pixels; nothing trains on it).
+ * Every entry checks its arguments on the host (a message before any launch), allocates nothing and does not synchronise; sums keep the
+ * fixed order of the section above.
+ *
+ * dinox_signed_distance_ws_bytes: bytes of workspace, 4 B C H W -- the two uint16 planes (a pure function of the sizes; 0 for sizes the call
+ *   refuses; contents need not be initialised; 4-byte aligned).
+ * dinox_signed_distance: phi[B][C][H][W] fp32, dense; bad[1] int64, zeroed on the stream first.  Every pointer is a device pointer.
+ * dinox_seg_loss_bd_ws_bytes: as dinox_seg_loss_ws_bytes, one float more per partial sum of the forward.
+ * dinox_seg_loss_bd_fwd: loss[4] = (L, CE, Dice, BD) fp32; stats and nv as dinox_seg_loss_fwd.
+ * dinox_seg_loss_bd_bwd: dz[B][P][C] fp32 from z, y, phi and the forward's stats and nv.
+ * ------------------------------------------------------------------------------------------ */
+size_t dinox_signed_distance_ws_bytes(int64_t B, int H, int W, int C);
+int dinox_signed_distance(const uint8_t* y, const float* spacing, float* phi, int64_t* bad, void* ws, int64_t B, int H, int W, int C,
+                          void* stream);
+size_t dinox_seg_loss_bd_ws_bytes(int64_t B, int g, int u, int C);
+int dinox_seg_loss_bd_fwd(const float* z, const uint8_t* y, const float* phi, float* loss, float* stats, int64_t* nv, void* ws, int64_t B,
+                          int g, int u, int C, int c0, float w_ce, float w_dice, float w_bd, void* stream);
+int dinox_seg_loss_bd_bwd(const float* z, const uint8_t* y, const float* phi, const float* stats, const int64_t* nv, float* dz, void* ws,
+                          int64_t B, int g, int u, int C, int c0, float w_ce, float w_dice, float w_bd, float grad_scale, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Connected components of a label map: labelling, clean-up and lesion-wise matching (kernels: csrc/cclabel.hip; dinox.ops.cc_label,
  * cc_filter, lesion_counts; dinox.segment.postprocess, lesion_metrics).
  *   labels[B][H][W]  uint8, dense, 1 <= H, W <= 1024 (rectangular is fine), B >= 1 and B H W < 2^31.  Classes 0 .. C - 1, 2 <= C <= 64.
