@@ -4,7 +4,8 @@ error paths; two ranks over gloo against one process at the whole batch; the RCC
 simclr_negatives="global" on one rank.
 
 The bar is the project's NT-Xent bar (tests/test_simclr_gpu.py): loss within 1e-3 relative, every gradient row within 1e-3 of that row's
-max-abs, rows whose oracle gradient is zero exactly zero, everything finite."""
+max-abs, rows whose oracle gradient is zero exactly zero, everything finite.  The element-wise judge of the kernels themselves
+(a-priori fp32 bounds per kernel, hostile S) is tests/test_ntxent_bounds_gpu.py."""
 import os
 import socket
 import subprocess
