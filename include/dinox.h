@@ -406,7 +406,10 @@ int dinox_ntxent_coeff_rect(const float* S, int64_t lds, const float* lse_local,
  * the Lk of lowest noise are kept.  ids_restore [V][L] int32 = rank of every patch; ids_keep [V][Lk] int32 = patch of every kept rank.
  * A patch is "removed" when its rank is outside [0, Lk).  Limits: 1 <= V <= 2^20, 2 <= L <= 4096, 1 <= Lk < L, 1 <= D <= 65536,
  * patch <= 32 for the loss entries; anything else, a null pointer or a dtype other than DINOX_F32 / DINOX_BF16 returns DINOX_EINVAL
- * before any launch.  Indices read from ids_* are range-checked on the device before use.  No float atomics; every sum has a fixed order.
+ * before any launch.  Indices read from ids_* are range-checked on the device before use: an ids_restore entry outside [0, Lk) (negative
+ * or too large) counts as removed and is never used as a row; an ids_keep entry is clamped into [0, L) (below 0 -> patch 0, L and above
+ * -> patch L - 1).  Nothing outside the operands is read or written for any index value; the loss divisor stays V (L - Lk).
+ * No float atomics; every sum has a fixed order.
  *   mask_ids:      ids_restore[v][p] = #{q : noise[v][q] < noise[v][p], or equal and q < p} (torch.argsort(stable=True) twice; -0 == +0,
  *                  NaN above everything); ids_keep[v][r] = p where the rank r < Lk.  One workgroup per sample.
  *   gather_unfold: u[(v Lk + r)][c p p + py p + px] = x[v][c][gy p + py][gx p + px] for patch ids_keep[v][r] = gy (W/p) + gx, rows of

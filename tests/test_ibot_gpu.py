@@ -186,6 +186,63 @@ def test_out_of_range_indices_touch_nothing(dx):
     assert bool((out == 5.0).all()) and bool((buf == 3.0).all())
 
 
+# The four row kernels launch grid_1d(M * D, 256, 4096): with M * D just above 4096 * 256 (and no multiple of it) every workgroup's
+# grid-stride loop takes a second, partial trip, which the cases above (M * D <= 30 000) never do.
+CAP_M, CAP_D, CAP_ROWS = 4034, 260, 4100
+
+
+def _cap_case(seed):
+    assert 4096 * 256 < CAP_M * CAP_D < 2 * 4096 * 256 and (CAP_M * CAP_D) % (4096 * 256) != 0
+    r = np.random.default_rng(seed)
+    return r, np.sort(r.choice(CAP_ROWS, CAP_M, replace=False)).astype(np.int32)
+
+
+def test_gather_rows_past_the_grid_cap(dx):
+    ops, _ = dx
+    r, row = _cap_case(1)
+    src = r.standard_normal((CAP_ROWS, CAP_D)).astype(np.float32)
+    out = torch.full((CAP_M + 2, CAP_D), 7.0, device=DEV)
+    ops.gather_rows(torch.from_numpy(src).to(DEV), torch.from_numpy(row).to(DEV), torch.float32, out=out, out_row0=1)
+    got = out.cpu().numpy()
+    assert np.array_equal(got[1:1 + CAP_M], src[row]) and np.all(got[0] == 7.0) and np.all(got[1 + CAP_M] == 7.0)
+
+
+def test_scatter_add_rows_past_the_grid_cap(dx):
+    ops, _ = dx
+    r, row = _cap_case(2)
+    dst = r.standard_normal((CAP_ROWS, CAP_D)).astype(np.float32)
+    add = r.standard_normal((CAP_M, CAP_D)).astype(np.float32)
+    dst_d = torch.from_numpy(dst).to(DEV)
+    ops.scatter_add_rows_(dst_d, torch.from_numpy(row).to(DEV), torch.from_numpy(add).to(DEV))
+    want, mag = dst.astype(np.float64), np.abs(dst.astype(np.float64))
+    want[row] += add
+    mag[row] += np.abs(add)
+    within("scatter_add_rows[cap]", dst_d.cpu().numpy(), want, IO.U * mag + IO.TINY)            # one rounded add per element
+    untouched = np.setdiff1d(np.arange(CAP_ROWS), row)
+    assert np.array_equal(dst_d.cpu().numpy()[untouched], dst[untouched])
+
+
+def test_put_mask_past_the_grid_cap(dx):
+    ops, _ = dx
+    r, idx = _cap_case(3)
+    patches = r.standard_normal((CAP_ROWS, CAP_D)).astype(np.float32)
+    token = r.standard_normal(CAP_D).astype(np.float32)
+    pd = torch.from_numpy(patches).to(DEV)
+    ops.ibot_put_mask_(pd, torch.from_numpy(token).to(DEV), torch.from_numpy(idx).to(DEV))
+    assert np.array_equal(pd.cpu().numpy(), IO.put_mask(patches, token, idx, False))
+
+
+def test_put_mask_bwd_past_the_grid_cap(dx):
+    ops, _ = dx
+    r, idx = _cap_case(4)
+    g = r.standard_normal((CAP_ROWS, CAP_D)).astype(np.float32)
+    gd = torch.from_numpy(g).to(DEV)
+    dmask = ops.ibot_put_mask_bwd_(gd, torch.from_numpy(idx).to(DEV))
+    want, mag, zeroed = IO.put_mask_bwd(g, idx)
+    within("put_mask_bwd[cap]", dmask.reshape(-1).cpu().numpy(), want, (len(idx) + 2) * IO.U * mag + IO.TINY)
+    assert np.array_equal(gd.cpu().numpy(), zeroed)                                              # exactly 0 on the masked rows, untouched elsewhere
+
+
 def test_entries_reject_bad_arguments_on_the_device(dx):
     """With live device pointers: every invalid argument is DINOX_EINVAL and the outputs keep their fill (nothing was launched)."""
     from dinox import _lib
