@@ -311,6 +311,10 @@ int dinox_gram_normalize_bwd(const float* dxh, const void* shat, const float* sn
  * The random draws stay on the host:  view_i[v] = {element offset of the (3,H,W) u16 stack in raw, H, W, top,
  * left, h, w, flip};  view_f[v] = {level - width/2, max(width, 1)}   (both tables in device memory).
  * max_crop = the largest h or w in the table (sizes the LDS footprint; a view that exceeds it is written as NaN).
+ * Tested as stated (tests/test_resample_bounds_gpu.py): the tables sized from the true max_crop always suffice; when max_crop is
+ * understated, a 16 x 16 output tile whose tap table or source footprint does not fit is written as NaN, whole -- nothing is read or
+ * written out of range -- and every other tile is computed as usual.  More than 150 KiB of LDS
+ * (dinox_slice_views_lds_bytes): DINOX_EUNSUPPORTED before any launch, out untouched.
  * ------------------------------------------------------------------------------------------ */
 int64_t dinox_slice_views_lds_bytes(int S, int max_crop);
 int dinox_slice_views(const void* raw_u16, const int64_t* view_i, const float* view_f, float* out, int V, int S, int max_crop,
@@ -338,6 +342,10 @@ int dinox_slice_views_patches(const void* raw_u16, const int64_t* view_i, const 
  * inside src; a destination outside [0, 3 n_images) is skipped.  src_dtype: DINOX_U16 | DINOX_I16 | DINOX_F32, one per launch.
  * max_side = the largest H or W in the table (sizes the LDS footprint; a plane that exceeds it is written as NaN).  More than
  * 150 KiB of LDS (dinox_encode_preprocess_lds_bytes): DINOX_EUNSUPPORTED before any launch.  n_jobs <= 65535.
+ * Tested as stated (tests/test_resample_bounds_gpu.py): a 16 x 16 output tile whose tap table or footprint does not fit the tables
+ * sized from max_side is written as NaN, whole, to every destination of its job; a destination index outside [0, 3 n_images) is
+ * skipped and the job's other destinations are written; a job whose number of destinations is outside 1..3 is poisoned: NaN goes
+ * to each of its three slots that names a destination inside the range, and to nothing else.
  * ------------------------------------------------------------------------------------------ */
 #define DINOX_FMT_HU_FLOAT 0
 #define DINOX_FMT_HU16_PNG 1

@@ -119,19 +119,7 @@ def test_volume_jobs_errors_and_check_jobs():
 
 
 # ---------------------------------------------------------------- 3. the filter rule
-def axis_weights(n, S):
-    """PIL's bilinear coefficients along one axis (the rule of csrc/encode_prep.hip): [(first tap, weights)] per output index."""
-    scale = n / S
-    fs = max(scale, 1.0)
-    support = fs
-    out = []
-    for i in range(S):
-        centre = (i + 0.5) * scale
-        x0 = max(int(centre - support + 0.5), 0)
-        x1 = min(int(centre + support + 0.5), n)
-        w = np.array([max(0.0, 1.0 - abs((x - centre + 0.5) / fs)) for x in range(x0, x1)], dtype=np.float64)
-        out.append((x0, w / w.sum()))
-    return out
+from oracle.resample_bounds import pil_bilinear_weights as axis_weights  # noqa: E402  (PIL's rule; shared with the bounds of oracle/resample_bounds.py)
 
 
 def resize_rule(plane, S):
