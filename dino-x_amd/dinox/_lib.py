@@ -190,6 +190,8 @@ SIGNATURES = {
     "dinox_row_dots": (i32, [vp, i64, vp, i64, i64, i64, vp, vp]),
     "dinox_knn_ws_bytes": (i64, [i64, i64, i64, i32]),
     "dinox_knn_topk": (i32, [vp, i64, vp, i64, vp, i64, i64, i64, i32, vp, vp, vp, vp]),
+    "dinox_labelprop_ws_bytes": (i64, [i32, i32, i32, i32, i32]),
+    "dinox_labelprop": (i32, [vp, i64, vp, i64, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp]),
     "dinox_gram_ws_bytes": (i64, [i64, i64]),
     "dinox_gram_f32": (i32, [vp, i64, i64, i64, vp, vp, vp, vp, vp]),
     "dinox_softmax_probe_ws_bytes": (i64, [i64, i64, i32]),

@@ -2877,6 +2877,70 @@ def knn_topk(q: Tensor, k: Tensor, K: int, exclude=None):
     return idx, val
 
 
+LABELPROP_MIN_C, LABELPROP_MAX_C = 2, 64
+
+
+def _lp_int(name: str, what: str, v, lo: int, hi: Optional[int] = None) -> int:
+    try:
+        n = None if isinstance(v, bool) else operator.index(v)                 # Python and NumPy integers; not bool, not float
+    except TypeError:
+        n = None
+    if n is None or n < lo or (hi is not None and n > hi):
+        rng = f"in [{lo}, {hi}]" if hi is not None else f">= {lo}"
+        raise ValueError(f"{name}: {what} must be an integer {rng}, got {v!r}")
+    return n
+
+
+def label_propagate(q: Tensor, k: Tensor, seg: Tensor, g: int, K: int = 5, radius: int = 12, temperature: float = 0.1):
+    """One step of dense label propagation (csrc/labelprop.hip; definitions in include/dinox.h): for each of the N = g g fp32 patch rows of
+    q [N, D], the K best-matching rows of k [F N, D] -- the patches of F context slots, key j = f N + y' g + x' -- among those within
+    ``radius`` patches in y and in x (radius < 0 or >= g - 1: the whole grid), then the softmax-weighted vote
+    out[p] = sum_i w_i seg[j_i] / sum_i w_i with w_i = exp((s_i - s_1) / temperature) over their soft labels seg [F N, C].  Returns
+    (out fp32 [N, C], idx int32 [N, K], val fp32 [N, K]); idx / val are ordered by (score descending, index ascending) and are bitwise
+    ``knn_topk(q, k, K)`` for a whole-grid radius; slots past the candidates hold (-1, -inf), and a row without candidates votes zero.
+    out is not renormalised over the classes.  Rows are used as given (normalise them first: normalize_rows).  Row-major views with a
+    leading dimension are accepted for q and k.  Arguments are checked before the device is: a wrong call raises ValueError anywhere."""
+    name = "label_propagate"
+    if not all(isinstance(t, Tensor) for t in (q, k, seg)) or any(t.dtype != torch.float32 or t.dim() != 2 for t in (q, k, seg)) \
+            or q.shape[1] != k.shape[1] or k.shape[0] != seg.shape[0]:
+        raise ValueError(f"{name}: fp32 q [N, D], k [F N, D] and seg [F N, C] expected, got {_describe(q, k, seg)}")
+    g = _lp_int(name, "g", g, 1)
+    K = _lp_int(name, "K", K, 1, KNN_MAX_K)
+    radius = _lp_int(name, "radius", radius, -(1 << 31), (1 << 31) - 1)
+    (N, D), Nk, C = q.shape, k.shape[0], seg.shape[1]
+    if N != g * g:
+        raise ValueError(f"{name}: q has {N} rows, the grid g = {g} has g g = {g * g} patches")
+    if D < 1:
+        raise ValueError(f"{name}: empty feature rows (D = {D})")
+    if Nk < N or Nk % N != 0:
+        raise ValueError(f"{name}: k has {Nk} rows, which is not F >= 1 times the N = {N} patches of a slice")
+    if not LABELPROP_MIN_C <= C <= LABELPROP_MAX_C:
+        raise ValueError(f"{name}: seg has C = {C} classes, outside [{LABELPROP_MIN_C}, {LABELPROP_MAX_C}]")
+    if Nk > 0x7fffffff - 128:
+        raise ValueError(f"{name}: F N = {Nk} keys exceed 2^31 - 129")
+    if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not math.isfinite(temperature) or temperature <= 0:
+        raise ValueError(f"{name}: temperature must be a finite number > 0, got {temperature!r}")
+    inv_t = float(torch.tensor(1.0 / float(temperature), dtype=torch.float32))
+    if not (math.isfinite(inv_t) and inv_t > 0):
+        raise ValueError(f"{name}: 1 / temperature = {inv_t} is not a finite positive fp32 number (temperature {temperature!r})")
+    if not (q.device == k.device == seg.device):
+        raise ValueError(f"{name}: q on {q.device}, k on {k.device}, seg on {seg.device}")
+    _need_cuda(q, k, seg)
+    if q.stride(1) != 1 or q.stride(0) < D:
+        q = q.contiguous()
+    if k.stride(1) != 1 or k.stride(0) < D:
+        k = k.contiguous()
+    seg = _c(seg)
+    F, dev = Nk // N, q.device
+    out = torch.empty((N, C), dtype=torch.float32, device=dev)
+    idx = torch.empty((N, K), dtype=torch.int32, device=dev)
+    val = torch.empty((N, K), dtype=torch.float32, device=dev)
+    ws = torch.empty(int(lib.dinox_labelprop_ws_bytes(g, F, D, C, K)), dtype=torch.uint8, device=dev)
+    check(lib.dinox_labelprop(_p(q), q.stride(0), _p(k), k.stride(0), _p(seg), g, F, D, C, K, radius, inv_t, _p(out), _p(idx), _p(val),
+                              _p(ws), _stream()), "dinox_labelprop")
+    return out, idx, val
+
+
 # ------------------------------------------------------------------------------------------
 # probes (csrc/gram.hip, csrc/probe.hip)
 # ------------------------------------------------------------------------------------------

@@ -715,6 +715,36 @@ int dinox_knn_topk(const float* q, int64_t ldq, const float* k, int64_t ldk, con
                    int32_t* out_idx, float* out_val, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * One step of dense label propagation (Caron et al. 2021, the video-segmentation protocol of DINO; here the sequence is the z axis of a
+ * series): for every patch of the target slice the K best-matching patches of F context slots inside a spatial window, then a
+ * softmax-weighted vote over their soft labels.  No [N][F N] affinity matrix is ever held.
+ *   q   fp32 [N][D], row stride ldq: the patch features of the target slice, N = g g, patch p = y g + x
+ *   k   fp32 [F N][D], row stride ldk: the patch features of the F context slots, key j = f N + y' g + x'
+ *   seg fp32 [F N][C], contiguous: the soft labels of the context patches (a row may be all zero)
+ * Candidates of p = (y, x): the keys (f, y', x') with |y' - y| <= radius and |x' - x| <= radius, the window clipped at the grid border;
+ * radius < 0 or radius >= g - 1: the whole grid.
+ * Score: s(p, j) = sum_d q[p][d] k[j][d], the tile loop of dinox_knn_topk (exact-fp32 MFMA, one d-ordered fma chain): BITWISE its score.
+ * Selection: row p of out_idx / out_val [N][K] = the first K candidates in the order (score descending, key index ascending), the total
+ * order of dinox_knn_topk: with a whole-grid radius the two rows equal dinox_knn_topk(q, k, exclude = NULL) bitwise.  Fewer than K
+ * candidates: the remaining slots hold (-1, -inf).  A NaN score never enters: a NaN query row returns K times (-1, -inf), a NaN key is
+ * never chosen; rows that meet NaNs neither fault nor hang (no address depends on a score, no loop on a comparison).
+ * Vote over the filled slots i = 1..n of row p (a prefix):  w_i = exp((s_i - s_1) inv_temperature),
+ *   out[p][c] = sum_i w_i seg[j_i][c] / sum_i w_i,   fp32 [N][C], NOT renormalised over c; a row with no filled slot is all zero.
+ * The exponent argument is rounded to fp32 once, exp is within 1 ulp, the numerator is one fp32 fma chain over i ascending, the
+ * denominator is summed over i ascending in fp32 with compensation (one rounding), then one division.
+ * Tile skipping: a tile of 128 consecutive keys is neither loaded nor multiplied when none of its keys lies in a grid row within radius
+ * of a grid row of the 128 consecutive patches of the query strip; the window proper is tested per (patch, key) at selection.
+ * 1 <= K <= 32, 2 <= C <= 64, g, F, D >= 1, F g g <= 2^31 - 129, ldq, ldk >= D, inv_temperature finite and > 0; anything else, or a null
+ * pointer, returns DINOX_EINVAL before any launch.
+ * ws: dinox_labelprop_ws_bytes(g, F, D, C, K) bytes (8 K bytes per patch and key split; a pure function of g and F; 0 for every argument
+ * set the call refuses; contents need not be initialised).  Two launches on the stream, plain stores, a fixed merge order of the key
+ * splits, no atomics: results are bit-reproducible.
+ * ------------------------------------------------------------------------------------------ */
+int64_t dinox_labelprop_ws_bytes(int g, int F, int D, int C, int K);
+int dinox_labelprop(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* seg, int g, int F, int D, int C, int K, int radius,
+                    float inv_temperature, float* out, int32_t* out_idx, float* out_val, void* ws, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Second moments of the columns of x [N][D] fp32 (ldx >= D) -- replaces the host NumPy / scikit-learn passes of the reference's ridge and
  * embedding-statistics metrics (scripts/evaluate_panorgan.py:569-697).  With z_i = x_i - shift (ONE fp32 subtraction per element; shift
  * NULL: z = x):   gram[a][b] = sum_i z_ia z_ib  (double [D][D], symmetric to the bit),   colsum[a] = sum_i z_ia  (double [D]).
