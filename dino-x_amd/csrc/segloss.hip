@@ -13,6 +13,7 @@
 // A label is compared with class numbers and 255 only; it never becomes an address beyond a [0, C) slot of an LDS counter.
 #include "small_common.h"
 #include "kernels.h"
+#include "seg_common.h"
 
 namespace dinox {
 
@@ -395,19 +396,7 @@ __global__ __launch_bounds__(64 * SEG_WAVES) void seg_predict_kernel(const float
 }
 
 // ---------------------------------------------------------------- host
-static int seg_cp(int C) { return C <= 4 ? 4 : C <= 8 ? 8 : C <= 16 ? 16 : C <= 32 ? 32 : 64; }
-
-// f(std::integral_constant<int, CP>) for the register width that holds C classes
-template <typename F>
-static inline void seg_by_width(int C, F&& f) {
-  switch (seg_cp(C)) {
-    case 4: f(std::integral_constant<int, 4>{}); break;
-    case 8: f(std::integral_constant<int, 8>{}); break;
-    case 16: f(std::integral_constant<int, 16>{}); break;
-    case 32: f(std::integral_constant<int, 32>{}); break;
-    default: f(std::integral_constant<int, 64>{}); break;
-  }
-}
+// seg_cp / seg_by_width (the register width that holds C classes): seg_common.h
 
 static int seg_wide(const void* p, int u) { return u % 8 == 0 && (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 

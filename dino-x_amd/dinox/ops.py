@@ -19,6 +19,7 @@ import os
 import weakref
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -3132,6 +3133,102 @@ def seg_predict(z: Tensor, u: int, labels: Optional[Tensor] = None):
         return pred
     _seg_refuse_bad_labels("seg_predict", int(counts[3 * C]), C)
     return pred, counts[:3 * C].view(3, C)
+
+
+# ------------------------------------------------------------------------------------------
+# sliding-window prediction: the blend of overlapping tiles' patch logits (csrc/segblend.hip)
+# ------------------------------------------------------------------------------------------
+SEG_BLEND_MAX_FLIPS = 4
+
+
+def _host_table(name: str, what: str, v, dtype) -> np.ndarray:
+    """A 1-D host copy of a small table given as a sequence, an ndarray or a tensor (a device tensor costs one read)."""
+    a = v.detach().cpu().numpy() if isinstance(v, Tensor) else np.asarray(v)
+    if a.ndim != 1 or a.size < 1 or a.dtype == np.bool_ or not (np.issubdtype(a.dtype, np.integer) if dtype == np.int32
+                                                                 else np.issubdtype(a.dtype, np.floating)):
+        raise ValueError(f"{name}: {what} must be a 1-D, non-empty {'integer' if dtype == np.int32 else 'floating-point'} table, got "
+                         f"{a.dtype} {a.shape}")
+    if dtype == np.int32 and (np.abs(a.astype(np.int64)) >= 1 << 31).any():
+        raise ValueError(f"{name}: {what} holds a value outside int32")
+    return np.ascontiguousarray(a, dtype=dtype)
+
+
+def _seg_blend_origins(name: str, what: str, o: np.ndarray, L: int, t: int) -> None:
+    """Tile origins along one axis of length L: strictly ascending, from 0 to L - t, no step above t (so every pixel is covered)."""
+    if int(o[0]) != 0 or int(o[-1]) != L - t:
+        raise ValueError(f"{name}: {what} must start at 0 and end at {L} - {t} = {L - t} to cover the image, got {o[0]} .. {o[-1]}")
+    d = np.diff(o.astype(np.int64))
+    if (d <= 0).any():
+        raise ValueError(f"{name}: {what} must be strictly ascending")
+    if (d > t).any():
+        raise ValueError(f"{name}: {what} leave a gap: consecutive origins {int(d.max())} apart with tiles of side {t}")
+
+
+def seg_blend_predict(z: Tensor, ys, xs, flips, win, H: int, W: int, t: int, labels: Optional[Tensor] = None, want_conf: bool = False):
+    """Label map of B images of size H x W from the patch logits of their overlapping tiles, z [B, F, ny, nx, g^2, C]: tile (iy, ix) is
+    the t x t crop at (ys[iy], xs[ix]), variant f saw it mirrored along x (``flips[f] & 1``) and / or y (``& 2``).  Every pixel blends
+    the bilinearly upsampled logits (align_corners=False, any t) of the tiles that cover it with weights ``win[ly] win[lx]`` -- ``win``
+    fp32 [t], e.g. ``dinox.tiled.blend_window`` -- and takes the arg-max (lowest index on a tie); include/dinox.h has the definitions.
+    ``ys``, ``xs``, ``flips`` and ``win`` are small host tables (sequences, ndarrays or tensors); they are checked here -- ascending
+    origins from 0 to L - t without a gap, flip codes in [0, 4), weights finite and > 0 -- because the kernel trusts them.
+    Returns pred uint8 [B, H, W]; with ``labels`` (uint8 [B, H, W], 255 = ignore) (pred, counts int64 [3, C]) as ``seg_predict``; with
+    ``want_conf`` the fp32 [B, H, W] confidence 1 / sum_c exp(L_c - L_max) is appended."""
+    name = "seg_blend_predict"
+    if not isinstance(z, Tensor) or z.dim() != 6 or not z.is_floating_point():
+        raise ValueError(f"{name}: tile logits must be a floating-point [B, F, ny, nx, P, C] tensor, got {_describe(z)}")
+    B, F, ny, nx, P, C = z.shape
+    g = math.isqrt(P)
+    if min(B, ny, nx) < 1:
+        raise ValueError(f"{name}: T = B F ny nx must be >= 1 (z is {tuple(z.shape)})")
+    if not 1 <= F <= SEG_BLEND_MAX_FLIPS:
+        raise ValueError(f"{name}: F = {F} flip variants, must lie in [1, {SEG_BLEND_MAX_FLIPS}]")
+    if P < 1 or g * g != P:
+        raise ValueError(f"{name}: P = {P} patches are not a square grid (z is {tuple(z.shape)})")
+    if not 2 <= C <= SEG_MAX_CLASSES:
+        raise ValueError(f"{name}: C must lie in [2, {SEG_MAX_CLASSES}], got {C}")
+    for what, v in (("H", H), ("W", W), ("t", t)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= 1 << 20:
+            raise ValueError(f"{name}: {what} must be an integer in [1, 2^20], got {v!r}")
+    H, W, t = int(H), int(W), int(t)
+    if t > min(H, W):
+        raise ValueError(f"{name}: tile side t = {t} exceeds min(H, W) = {min(H, W)}")
+    if t * g > 1 << 28 or g > 4096:
+        raise ValueError(f"{name}: g = {g}, t = {t}: g <= 4096 and t g <= 2^28")
+    ys_h, xs_h = _host_table(name, "ys", ys, np.int32), _host_table(name, "xs", xs, np.int32)
+    fl_h, win_h = _host_table(name, "flips", flips, np.int32), _host_table(name, "win", win, np.float32)
+    if ys_h.size != ny or xs_h.size != nx or fl_h.size != F:
+        raise ValueError(f"{name}: ys, xs, flips have {ys_h.size}, {xs_h.size}, {fl_h.size} entries; z {tuple(z.shape)} wants {ny}, {nx}, {F}")
+    _seg_blend_origins(name, "ys", ys_h, H, t)
+    _seg_blend_origins(name, "xs", xs_h, W, t)
+    if ((fl_h < 0) | (fl_h > 3)).any():
+        raise ValueError(f"{name}: flip codes must lie in [0, 4) (bit 0: mirrored along x, bit 1: along y), got {fl_h.tolist()}")
+    if win_h.size != t or not bool((np.isfinite(win_h) & (win_h > 0)).all()):
+        raise ValueError(f"{name}: win must hold t = {t} finite weights > 0 (got {win_h.size}, min {float(np.min(win_h))!r})")
+    if labels is not None:
+        if not isinstance(labels, Tensor) or labels.dtype != torch.uint8 or tuple(labels.shape) != (B, H, W):
+            raise ValueError(f"{name}: labels must be uint8 [{B}, {H}, {W}] (255 = ignore), got {_describe(labels)}")
+        if labels.device != z.device:
+            raise ValueError(f"{name}: logits on {z.device}, labels on {labels.device}")
+    _need_cuda(z, labels)
+    z = _c(z.float())
+    dev = z.device
+    tab = torch.from_numpy(np.concatenate([ys_h, xs_h, fl_h])).to(dev)
+    wn = torch.from_numpy(win_h).to(dev)
+    pred = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+    conf = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_conf else None
+    counts = None
+    if labels is not None:
+        labels = _c(labels)
+        counts = torch.empty(3 * C + 1, dtype=torch.int64, device=dev)
+    check(lib.dinox_seg_blend_predict(_p(z), tab.data_ptr(), tab.data_ptr() + 4 * ny, tab.data_ptr() + 4 * (ny + nx), _p(wn), _p(labels), _p(pred),
+                                      _p(conf), _p(counts), B, F, ny, nx, g, t, C, H, W, _stream()), "dinox_seg_blend_predict")
+    out = [pred]
+    if counts is not None:
+        _seg_refuse_bad_labels(name, int(counts[3 * C]), C)
+        out.append(counts[:3 * C].view(3, C))
+    if want_conf:
+        out.append(conf)
+    return out[0] if len(out) == 1 else tuple(out)
 
 
 # ------------------------------------------------------------------------------------------

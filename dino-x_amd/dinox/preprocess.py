@@ -109,6 +109,33 @@ def volume_jobs(Z: int, H: int, W: int, z_indices: Sequence[int], context: str =
     return np.asarray(rows, dtype=np.int64).reshape(-1, JOB_FIELDS)
 
 
+def volume_tile_jobs(Z: int, H: int, W: int, items: Sequence[Tuple[int, int, int]], t: int, context: str = "neighbours") -> np.ndarray:
+    """``volume_jobs`` for t x t tiles: image k of the batch is the crop at rows [y0, y0 + t), columns [x0, x0 + t) of the 2.5D stack of
+    slice z, ``items[k] = (z, y0, x0)``.  A crop is a job like any other -- offset plane H W + y0 W + x0, size t x t, row stride W -- and
+    every plane crop any requested stack shows is ONE job with all its destinations (further jobs where more than three want it)."""
+    if context not in CONTEXTS:
+        raise ValueError(f"Unknown context: '{context}'. Supported: 'neighbours', 'replicate'")
+    if int(t) != t or not 1 <= t <= min(H, W):
+        raise ValueError(f"tile side {t!r} outside [1, min(H, W) = {min(H, W)}]")
+    t = int(t)
+    wanted: Dict[Tuple[int, int, int], List[int]] = {}
+    for k, (z, y0, x0) in enumerate(items):
+        z, y0, x0 = int(z), int(y0), int(x0)
+        if not 0 <= z < Z:
+            raise ValueError(f"slice index {z} outside a volume of {Z} slices")
+        if not (0 <= y0 <= H - t and 0 <= x0 <= W - t):
+            raise ValueError(f"tile at ({y0}, {x0}) of side {t} reaches past a {H} x {W} plane")
+        for c, plane in enumerate(stack_planes(Z, z, context)):
+            wanted.setdefault((plane, y0, x0), []).append(3 * k + c)
+    rows = []
+    for plane, y0, x0 in sorted(wanted):
+        dests = wanted[(plane, y0, x0)]
+        for at in range(0, len(dests), 3):
+            part = dests[at:at + 3]
+            rows.append((plane * H * W + y0 * W + x0, t, t, W, 1, len(part), *(part + [-1] * (3 - len(part)))))
+    return np.asarray(rows, dtype=np.int64).reshape(-1, JOB_FIELDS)
+
+
 def check_jobs(jobs: np.ndarray, src_numel: int, n_images: int) -> int:
     """Host-side bounds check of a job table against its source buffer (the kernel trusts the table); returns max_side."""
     jobs = np.asarray(jobs)

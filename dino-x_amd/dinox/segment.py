@@ -12,7 +12,9 @@ the same for one volume from ``ops.surface_stats_3d`` (csrc/surfdist3d.hip); ``p
 label map by connected components and ``lesion_metrics`` / ``LesionAccumulator`` turn ``ops.lesion_counts`` (csrc/cclabel.hip) into
 lesion-wise sensitivity, precision, F1 and false positives per image.  For a whole series: ``segment_volume`` (one trip to the device,
 the chunk loop of ``zoo.encode.encode_volume``), ``postprocess_volume`` and ``ops.lesion_counts_3d`` on 3-D components
-(csrc/cclabel3d.hip), ``resample_labels_nearest`` for the ground truth and ``CaseAccumulator`` for per-case scores.
+(csrc/cclabel3d.hip), ``resample_labels_nearest`` for the ground truth and ``CaseAccumulator`` for per-case scores.  All of the above
+label the model's S x S grid; ``segment_tiled`` / ``segment_volume_tiled`` (dinox/tiled.py, csrc/segblend.hip) label the image's own
+grid by sliding window.
 """
 from __future__ import annotations
 
@@ -443,3 +445,7 @@ def load_segmenter(backbone_path, output_dir, device: Union[str, torch.device] =
     for p in model.parameters():
         p.requires_grad = False
     return model.eval()
+
+
+# ------------------------------------------------------------------------------------------ sliding-window inference at native resolution
+from dinox.tiled import blend_window, segment_tiled, segment_volume_tiled, tile_plan, tile_starts  # noqa: E402,F401

@@ -20,6 +20,13 @@ per-case Dice and the lesion-wise sensitivity, precision, F1 and false positives
 grid, so the slice spacing enters every distance.  The report then also holds, per class, the mean over cases of HD95 and ASSD in mm and
 of the surface Dice (NSD) at every tolerance, with the number of cases behind them; ``--surface-quantile NUM DEN`` replaces the 95/100 of
 HD95 (nearest rank).  A class in only one of the two volumes of a case scores the volume diagonal and NSD 0 there.
+
+``--tiled`` predicts by sliding window at the series' own resolution instead (dinox.segment.segment_volume_tiled, csrc/segblend.hip):
+tiles of side ``--tile N`` (default: the model's input size, clamped to the plane) overlapping by ``--overlap F``, their logits blended
+under ``--blend-window`` (gaussian or constant), with ``--tta-flips`` averaged over the four mirror variants.  ``--out`` then holds
+uint8 (Z, H, W), ``--labels`` must be (Z, H, W) and is compared as it is (nothing is resampled), and ``--min-component-mm3`` and
+``--tolerance-mm`` use the scanner's voxel (SZ, SY, SX).  The report records the tile geometry and the grid of the scores; a metric whose
+kernel declines the native size is reported with the kernel's message instead of a value.
 """
 from __future__ import annotations
 
@@ -54,7 +61,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--volume", required=True, type=Path, action="append", help=".npy file holding a (Z, H, W) series; repeatable")
     ap.add_argument("--spacing", type=float, nargs=3, required=True, metavar=("SX", "SY", "SZ"),
                     help="mm per source pixel in x and y and the slice spacing, for every --volume")
-    ap.add_argument("--out", required=True, type=Path, help="output .npy: uint8 (Z, S, S)")
+    ap.add_argument("--out", required=True, type=Path, help="output .npy: uint8 (Z, S, S); with --tiled (Z, H, W)")
     for dest in ("input_format", "window_level", "window_width"):
         ap._add_action(base[dest])
     ap.add_argument("--context", default="neighbours", choices=("neighbours", "replicate"), help="the 2.5D stack of a slice")
@@ -72,11 +79,31 @@ def build_parser() -> argparse.ArgumentParser:
                     help="also score HD95, ASSD and the surface Dice at this tolerance in 3-D, per case; repeatable (needs --labels)")
     ap.add_argument("--surface-quantile", type=int, nargs=2, default=[95, 100], metavar=("NUM", "DEN"),
                     help="the nearest-rank quantile reported as hd95_mm")
+    ap.add_argument("--tiled", action="store_true", help="sliding-window prediction on the series' own (Z, H, W) grid")
+    ap.add_argument("--tile", type=int, default=argparse.SUPPRESS, metavar="N",
+                    help="tile side in source pixels (needs --tiled; default: the model's input size, clamped to the plane)")
+    ap.add_argument("--overlap", type=float, default=argparse.SUPPRESS, metavar="F", help="overlap of neighbouring tiles, 0 <= F < 1 (needs --tiled; default: 0.5)")
+    ap.add_argument("--blend-window", choices=("gaussian", "constant"), default=argparse.SUPPRESS,
+                    help="weights of a tile's pixels in the blend (needs --tiled; default: gaussian)")
+    ap.add_argument("--tta-flips", action="store_true", help="average the four mirror variants of every tile (needs --tiled)")
     return ap
 
 
+TILED_DEFAULTS = {"tile": None, "overlap": 0.5, "blend_window": "gaussian"}
+
+
 def check_args(ap: argparse.ArgumentParser, args: argparse.Namespace) -> None:
-    """The argument errors that need no file and no device."""
+    """The argument errors that need no file and no device; fills in the defaults of the --tiled options."""
+    given = [f"--{k.replace('_', '-')}" for k in TILED_DEFAULTS if hasattr(args, k)] + (["--tta-flips"] if args.tta_flips else [])
+    if given and not args.tiled:
+        ap.error(f"{', '.join(given)}: only with --tiled")
+    for k, v in TILED_DEFAULTS.items():
+        if not hasattr(args, k):
+            setattr(args, k, v)
+    if args.tile is not None and args.tile < 1:
+        ap.error(f"--tile: an integer >= 1, got {args.tile}")
+    if not 0.0 <= args.overlap < 1.0:
+        ap.error(f"--overlap: a fraction in [0, 1), got {args.overlap}")
     if not 0.0 <= args.min_component_mm3 < float("inf"):
         ap.error(f"--min-component-mm3: a finite volume >= 0, got {args.min_component_mm3}")
     if not 0.0 <= args.lesion_overlap <= 1.0:
@@ -111,6 +138,14 @@ def grid_labels(ap: argparse.ArgumentParser, path: Path, vol_shape, S: int) -> n
     ap.error(f"--labels {path}: shape {gt.shape} is neither the series' {tuple(vol_shape)} nor the label grid's {(Z, S, S)}")
 
 
+def native_labels(ap: argparse.ArgumentParser, path: Path, vol_shape) -> np.ndarray:
+    """The ground truth of one case under --tiled: on the series' own grid, taken as it is."""
+    gt = np.load(path)
+    if gt.dtype != np.uint8 or gt.shape != tuple(vol_shape):
+        ap.error(f"--labels {path}: with --tiled uint8 {tuple(vol_shape)} (the series' own grid) is expected, got {gt.dtype} {gt.shape}")
+    return gt
+
+
 def case_report(res: dict, args: argparse.Namespace, overlap) -> dict:
     """The report of CaseAccumulator.result(); the means run over the foreground classes (>= 1) that have a value."""
     les = res["lesions"]
@@ -136,6 +171,27 @@ def add_surface_report(report: dict, res: dict, args: argparse.Namespace) -> Non
                            "nsd": {f"{t:g}": _mean_present(res["nsd"][1:, i]) for i, t in enumerate(tol)}})
 
 
+def score_tiled_case(ap, args, i: int, vol_shape, pred: np.ndarray, C: int, overlap, acc, surf, declined: dict, device) -> None:
+    """One case under --tiled: prediction and ground truth on the series' own grid, the real voxel.  A metric kernel that declines the
+    native size leaves its message in ``declined`` for the report; nothing is resampled to make it fit."""
+    sx, sy, sz = args.spacing
+    gt = torch.from_numpy(native_labels(ap, args.labels[i], vol_shape)).to(device)
+    p = torch.from_numpy(pred).to(device)
+    voxel = (sz, sy, sx)
+    try:
+        mv = SG.min_component_vox(args.min_component_mm3, voxel)
+        _, cnt = ops.cc_filter_3d(p, C, first_class=C, connectivity=args.connectivity, targets=gt)      # first_class = C: keeps all, counts only
+        acc.update(cnt, ops.lesion_counts_3d(p, gt, C, connectivity=args.connectivity, overlap=overlap, min_vox=mv))
+    except (ValueError, RuntimeError) as e:
+        declined.setdefault("dice_and_lesions", {})[str(i)] = str(e)
+    if surf is not None:
+        try:
+            sc, sv = ops.surface_stats_3d(p, gt, voxel, C, tolerances=args.tolerance_mm, q=tuple(args.surface_quantile))
+            surf.update(SG.surface_metrics_3d(sc, sv, voxel, tuple(p.shape)))
+        except (ValueError, RuntimeError) as e:
+            declined.setdefault("surface", {})[str(i)] = str(e)
+
+
 def run(args: argparse.Namespace):
     ap = build_parser()
     check_args(ap, args)
@@ -153,19 +209,33 @@ def run(args: argparse.Namespace):
     acc = SG.CaseAccumulator(C) if args.labels else None
     surf = SG.SurfaceAccumulator(C, len(args.tolerance_mm)) if args.tolerance_mm else None
     sx, sy, sz = args.spacing
+    declined, grids = {}, []                        # --tiled: metric -> {case: the kernel's message}; the tile grid of every case
     for i, vpath in enumerate(args.volume):
         vol = np.load(vpath)
         if vol.ndim != 3:
             ap.error(f"--volume {vpath}: a (Z, H, W) array expected, got {vol.shape}")
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=not args.no_amp):
-            pred = SG.segment_volume(model, vol, (sx, sy, sz), input_format=args.input_format, hu_level=args.window_level,
-                                     hu_width=args.window_width, context=args.context, batch_size=args.batch_size, device=device,
-                                     keep_largest=args.keep_largest, min_volume_mm3=args.min_component_mm3, connectivity=args.connectivity)
+            if args.tiled:
+                plan = SG.tile_plan(model, vol.shape[1], vol.shape[2], args.tile, args.overlap, args.blend_window, args.tta_flips)
+                grids.append({"shape": list(vol.shape), "tile": plan["tile"], "ys": plan["ys"], "xs": plan["xs"]})
+                pred = SG.segment_volume_tiled(model, vol, (sx, sy, sz), tile=args.tile, overlap=args.overlap, window=args.blend_window,
+                                               tta_flips=args.tta_flips, input_format=args.input_format, hu_level=args.window_level,
+                                               hu_width=args.window_width, context=args.context, batch_size=args.batch_size, device=device,
+                                               keep_largest=args.keep_largest, min_volume_mm3=args.min_component_mm3,
+                                               connectivity=args.connectivity)
+            else:
+                pred = SG.segment_volume(model, vol, (sx, sy, sz), input_format=args.input_format, hu_level=args.window_level,
+                                         hu_width=args.window_width, context=args.context, batch_size=args.batch_size, device=device,
+                                         keep_largest=args.keep_largest, min_volume_mm3=args.min_component_mm3,
+                                         connectivity=args.connectivity)
         out = args.out if len(args.volume) == 1 else args.out.with_name(f"{args.out.stem}_{i}{args.out.suffix}")
         Path(out).parent.mkdir(parents=True, exist_ok=True)
         np.save(out, pred)
         log.info("%s: %s -> %s", vpath, tuple(vol.shape), out)
         if acc is None:
+            continue
+        if args.tiled:
+            score_tiled_case(ap, args, i, vol.shape, pred, C, overlap, acc, surf, declined, device)
             continue
         gt = torch.from_numpy(grid_labels(ap, args.labels[i], vol.shape, S)).to(device)
         p = torch.from_numpy(pred).to(device)
@@ -181,6 +251,13 @@ def run(args: argparse.Namespace):
     report = case_report(acc.result(), args, overlap)
     if surf is not None:
         add_surface_report(report, surf.result(), args)
+    if args.tiled:
+        report["tiled"] = {"tile": grids[0]["tile"] if len({g["tile"] for g in grids}) == 1 else [g["tile"] for g in grids],
+                           "overlap": args.overlap, "window": args.blend_window, "flips": [0, 1, 2, 3] if args.tta_flips else [0],
+                           "tile_grid": grids, "score_grid": "native: the (Z, H, W) grid of every series, voxel (s_z, s_y, s_x) = (SZ, SY, SX) mm",
+                           "declined": declined}
+        if surf is not None:
+            report["spacing"] = "distances in mm with the series' own voxel (s_z, s_y, s_x) = (SZ, SY, SX)"
     report["segmenter"], report["backbone"] = str(args.segmenter), str(args.backbone)
     if args.report is not None:
         Path(args.report).parent.mkdir(parents=True, exist_ok=True)

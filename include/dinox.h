@@ -846,6 +846,32 @@ int dinox_seg_loss_bwd(const float* z, const uint8_t* y, const float* stats, con
 int dinox_seg_predict(const float* z, const uint8_t* y, uint8_t* pred, int64_t* counts, int64_t B, int g, int u, int C, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Sliding-window prediction at native resolution (kernel: csrc/segblend.hip; dinox.ops.seg_blend_predict, dinox.tiled).  B images of one
+ * size H x W were cut into t x t tiles on a separable grid of origins ys[ny] x xs[nx]; every tile went through the model F times (mirror
+ * variants) and left g x g patch logit rows.  Each output pixel gathers the tiles that cover it: no [C][H][W] map is written, nothing is
+ * scattered, and there is no floating-point atomic.
+ *   z[B][F][ny][nx][g g][C]  fp32, dense.  2 <= C <= 64 (C > 64: DINOX_EUNSUPPORTED).  1 <= F <= 4.
+ *   ys[ny], xs[nx]  device int32, ascending tile origins, 0 <= ys[i] <= H - t, 0 <= xs[i] <= W - t.  The kernel TRUSTS both tables (the
+ *               caller checks its host copies); a pixel that no tile covers gets label 0 and a NaN confidence.
+ *   flips[F]    device int32: bit 0 = the model saw the tile mirrored along x, bit 1 = along y.
+ *   win[t]      device fp32, the 1-D window: tile pixel (ly, lx) weighs w = win[ly] win[lx] (one fp32 product; the kernel evaluates no
+ *               window function, the host rounds it once).
+ *   Per pixel (y, x), variant f and covering tile (iy, ix):  ly = y - ys[iy], mirrored to t - 1 - ly if flips[f] & 2;  lx alike with
+ *               bit 0.  Along each axis the patch coordinate is s = max((l + 0.5) g / t - 0.5, 0), taps k = floor(s) and min(k + 1, g - 1),
+ *               the weight of the second tap is the integer (2 l + 1) g - t - 2 t k over 2 t (0 where s was clamped or the second tap is
+ *               clamped onto the first): bilinear, align_corners = False, for any t >= 1.  l_c = the 4-tap interpolation, x first.
+ *   L_c = (sum w l_c) / (sum w), both sums over f, then iy, then ix, all ascending, in fp32;  one division per class.
+ *   pred[B][H][W] uint8 = argmax_c L_c, the lowest index on an exact tie; always < C, whatever the bits of z.
+ *   conf[B][H][W] fp32 (or NULL) = 1 / sum_c exp(L_c - max_c L_c).
+ *   y[B][H][W] uint8 or NULL (then counts NULL too: both or neither): counts[3 C + 1] int64 exactly as dinox_seg_predict's.
+ * Equal inputs give equal bits.  T = B F ny nx >= 1, 1 <= g <= 4096, 1 <= t <= min(H, W), H, W <= 2^20, B <= 2^20 and B H ceil(W / 64)
+ * <= 2^32; anything else, or a null pointer, is DINOX_EINVAL with a message before any launch.
+ * ------------------------------------------------------------------------------------------ */
+int dinox_seg_blend_predict(const float* z, const int32_t* ys, const int32_t* xs, const int32_t* flips, const float* win, const uint8_t* y,
+                            uint8_t* pred, float* conf, int64_t* counts, int64_t B, int F, int ny, int nx, int g, int t, int C, int H, int W,
+                            void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Surface distances between two label maps, in mm (kernels: csrc/surfdist.hip; dinox.ops.surface_stats, dinox.segment.surface_metrics).
  *   pred[B][H][W], gt[B][H][W]  uint8, dense, 1 <= H, W <= 1024 (rectangular maps are fine: nothing here knows a patch grid), B >= 1 and
  *               B C 2 H <= 2^30.  Classes 0 .. C - 1, 2 <= C <= 64.  gt == 255 is ignore.  A pred value >= C, or a gt value >= C other
