@@ -3232,6 +3232,85 @@ def seg_blend_predict(z: Tensor, ys, xs, flips, win, H: int, W: int, t: int, lab
 
 
 # ------------------------------------------------------------------------------------------
+# patch sampling for training at native resolution (csrc/segpatch.hip)
+# ------------------------------------------------------------------------------------------
+SEG_PATCH_MAX_SIDE = 1 << 14        # S
+SEG_PATCH_MAX_PLANE = 1 << 20       # H, W of a source plane
+SEG_PATCH_MAX_RUNS = 1 << 31        # B S ceil(S / 64): the grid
+
+
+def _host_matrix(name: str, what: str, v, cols: int, dtype) -> np.ndarray:
+    """A [B, cols] host copy of a job table given as a nested sequence, an ndarray or a tensor (a device tensor costs one read)."""
+    a = v.detach().cpu().numpy() if isinstance(v, Tensor) else np.asarray(v)
+    integer = dtype == np.int64
+    if a.ndim != 2 or a.shape[1] != cols or a.dtype == np.bool_ or not (np.issubdtype(a.dtype, np.integer) if integer
+                                                                         else np.issubdtype(a.dtype, np.number)):
+        raise ValueError(f"{name}: {what} must be a [B, {cols}] {'integer' if integer else 'numeric'} table, got {a.dtype} {a.shape}")
+    return np.ascontiguousarray(a, dtype=dtype)
+
+
+def seg_patch_sample(img_pool: Tensor, msk_pool: Tensor, jobs, par, S: int, mean, std, pad: float = 0.0, *, out=None):
+    """B training patches in one launch: (x fp32 [B, 3, S, S], m uint8 [B, S, S]) sampled from the device-resident pools ``img_pool``
+    (fp32, 1-D, planes already windowed to [0, 1]) and ``msk_pool`` (uint8, 1-D) under each job's inverse affine map -- the image
+    bilinear with ``pad`` outside the plane, then gain * v^gamma and (v - mean_c) / std_c; the label nearest with 255 (ignore) outside;
+    include/dinox.h has the definitions.  ``jobs`` int64 [B, 4] = (image offset, mask offset, H, W) and ``par`` fp32 [B, 8] =
+    (a00, a01, a02, a10, a11, a12, gamma, gain) are host tables (nested sequences, ndarrays or tensors).  They are checked here, before
+    the library is touched, because the kernel trusts ``jobs``: every plane inside its pool, 1 <= H, W <= 2^20, ``par`` finite,
+    gamma > 0, 1 <= S <= 2^14, B S ceil(S / 64) <= 2^31.  ``out = (x, m)``: contiguous tensors of those shapes to write into instead of fresh ones -- views into larger buffers included,
+    which is how the tests put guard elements around both outputs and reach the label store path of an unaligned ``m``."""
+    name = "seg_patch_sample"
+    if not isinstance(img_pool, Tensor) or img_pool.dtype != torch.float32 or img_pool.dim() != 1 or not img_pool.is_contiguous():
+        raise ValueError(f"{name}: img_pool must be a contiguous 1-D float32 tensor, got {_describe(img_pool)}")
+    if not isinstance(msk_pool, Tensor) or msk_pool.dtype != torch.uint8 or msk_pool.dim() != 1 or not msk_pool.is_contiguous():
+        raise ValueError(f"{name}: msk_pool must be a contiguous 1-D uint8 tensor, got {_describe(msk_pool)}")
+    if img_pool.device != msk_pool.device:
+        raise ValueError(f"{name}: img_pool on {img_pool.device}, msk_pool on {msk_pool.device}")
+    if isinstance(S, bool) or not isinstance(S, (int, np.integer)) or not 1 <= S <= SEG_PATCH_MAX_SIDE:
+        raise ValueError(f"{name}: S must be an integer in [1, 2^14], got {S!r}")
+    S = int(S)
+    jb, pr = _host_matrix(name, "jobs", jobs, 4, np.int64), _host_matrix(name, "par", par, 8, np.float32)
+    B = jb.shape[0]
+    if pr.shape[0] != B:
+        raise ValueError(f"{name}: {B} jobs but {pr.shape[0]} rows of par")
+    if B < 1 or B > 1 << 20 or B * S * (-(-S // 64)) > SEG_PATCH_MAX_RUNS:
+        raise ValueError(f"{name}: B = {B} patches of side {S}: 1 <= B <= 2^20 and B S ceil(S / 64) <= 2^31 (what one grid takes)")
+    hw = jb[:, 2:]
+    if ((hw < 1) | (hw > SEG_PATCH_MAX_PLANE)).any():
+        k = int(np.argmax(((hw < 1) | (hw > SEG_PATCH_MAX_PLANE)).any(1)))
+        raise ValueError(f"{name}: job {k}: plane of H x W = {int(hw[k, 0])} x {int(hw[k, 1])}; both must lie in [1, 2^20]")
+    area = hw[:, 0] * hw[:, 1]
+    for col, pool, what in ((0, img_pool, "img_pool"), (1, msk_pool, "msk_pool")):
+        bad = (jb[:, col] < 0) | (jb[:, col] > pool.numel() - area)
+        if bad.any():
+            k = int(np.argmax(bad))
+            raise ValueError(f"{name}: job {k}: plane [{int(jb[k, col])}, {int(jb[k, col] + area[k])}) leaves {what} of {pool.numel()} elements")
+    if not np.isfinite(pr).all():
+        raise ValueError(f"{name}: par holds a non-finite value (job {int(np.argmax(~np.isfinite(pr).all(1)))})")
+    if (pr[:, 6] <= 0).any():
+        k = int(np.argmax(pr[:, 6] <= 0))
+        raise ValueError(f"{name}: job {k}: gamma = {float(pr[k, 6])!r} must be > 0")
+    mean_h, std_h = np.asarray(mean, dtype=np.float32).reshape(-1), np.asarray(std, dtype=np.float32).reshape(-1)
+    if mean_h.size != 3 or std_h.size != 3 or not (np.isfinite(mean_h).all() and np.isfinite(std_h).all() and (std_h > 0).all()):
+        raise ValueError(f"{name}: mean and std must be 3 finite values each, std > 0, got {mean_h.tolist()} and {std_h.tolist()}")
+    if not math.isfinite(float(pad)):
+        raise ValueError(f"{name}: pad = {pad!r} is not finite")
+    dev = img_pool.device
+    if out is not None:
+        x, m = out
+        if not (isinstance(x, Tensor) and x.dtype == torch.float32 and tuple(x.shape) == (B, 3, S, S) and x.is_contiguous() and x.device == dev
+                and isinstance(m, Tensor) and m.dtype == torch.uint8 and tuple(m.shape) == (B, S, S) and m.is_contiguous() and m.device == dev):
+            raise ValueError(f"{name}: out must be contiguous (float32 [{B}, 3, {S}, {S}], uint8 [{B}, {S}, {S}]) on {dev}, got {_describe(*out)}")
+    _need_cuda(img_pool, msk_pool)
+    if out is None:
+        x = torch.empty((B, 3, S, S), dtype=torch.float32, device=dev)
+        m = torch.empty((B, S, S), dtype=torch.uint8, device=dev)
+    jd, pd = torch.from_numpy(jb).to(dev), torch.from_numpy(pr).to(dev)
+    check(lib.dinox_seg_patch_sample(_p(img_pool), _p(msk_pool), _p(jd), _p(pd), _p(x), _p(m), B, S, mean_h.ctypes.data, std_h.ctypes.data,
+                                     float(pad), _stream()), "dinox_seg_patch_sample")
+    return x, m
+
+
+# ------------------------------------------------------------------------------------------
 # surface distances between two label maps (csrc/surfdist.hip)
 # ------------------------------------------------------------------------------------------
 SURFACE_MAX_SIDE = 1024

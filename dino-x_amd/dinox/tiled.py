@@ -80,10 +80,12 @@ def _flipped(x: torch.Tensor, code: int) -> torch.Tensor:
 
 
 def _tiled_labels(model, vol: np.ndarray, spacing, plan: dict, input_format: str, hu_level: float, hu_width: float, context: str,
-                  batch_size: int, device) -> torch.Tensor:
+                  batch_size: int, device, labels: Optional[torch.Tensor] = None):
     """uint8 [Z, H, W] on the device: the tiles of every slice in the order (z, iy, ix), ``batch_size`` at a time through the
     preprocessing kernel and the model (every mirror variant a device-side flip of the same preprocessed batch); their logits wait
-    in a buffer of a few slices, and each time whole slices are complete one ``ops.seg_blend_predict`` launch labels them."""
+    in a buffer of a few slices, and each time whole slices are complete one ``ops.seg_blend_predict`` launch labels them.
+    ``labels`` (uint8 [Z, H, W] on the device, 255 = ignore): returns (label volume, counts int64 [3, C]), the blend launches' own
+    counts added up."""
     from dinox import preprocess as P
     Z, H, W = vol.shape
     S, g = model.img_size, model.img_size // model.patch
@@ -106,6 +108,7 @@ def _tiled_labels(model, vol: np.ndarray, spacing, plan: dict, input_format: str
     zbuf = torch.empty((G, F, n_t, g * g, C), dtype=torch.float32, device=device)
     out = torch.empty((Z, H, W), dtype=torch.uint8, device=device)
     done, at = 0, 0                                 # slices labelled so far (= the slice in zbuf[0]); rows of `jobs` consumed
+    counts = None if labels is None else torch.zeros((3, C), dtype=torch.int64, device=device)
     for tb, a, b in zip(tables, bounds[:-1], bounds[1:]):
         n = b - a
         x = P.device_preprocess(src, jobs[at:at + len(tb)], n, S, input_format, hu_level, hu_width, out=xbuf[:n], src_dtype=src_dtype,
@@ -122,12 +125,33 @@ def _tiled_labels(model, vol: np.ndarray, spacing, plan: dict, input_format: str
                 k += m
         full = b // n_t - done                      # whole slices now complete
         if full > 0:
-            out[done:done + full] = ops.seg_blend_predict(zbuf[:full].view(full, F, ny, nx, g * g, C), ys, xs, flips, plan["win"], H, W, t)
+            zfull = zbuf[:full].view(full, F, ny, nx, g * g, C)
+            if labels is None:
+                out[done:done + full] = ops.seg_blend_predict(zfull, ys, xs, flips, plan["win"], H, W, t)
+            else:
+                out[done:done + full], cnt = ops.seg_blend_predict(zfull, ys, xs, flips, plan["win"], H, W, t, labels=labels[done:done + full])
+                counts += cnt
             if b % n_t:                             # the slice under way moves to the front
                 zbuf[0, :, :b % n_t] = zbuf[full, :, :b % n_t].clone()
             done += full
     assert done == Z
-    return out
+    return out if labels is None else (out, counts)
+
+
+def tiled_label_counts(model, planes: np.ndarray, labels: np.ndarray, spacing: Tuple[float, float, float] = (1.0, 1.0, 1.0), *,
+                       tile: Optional[int] = None, overlap: float = 0.5, window: str = "gaussian", batch_size: int = 64,
+                       device: Union[str, torch.device, None] = None):
+    """Tiled validation of images of ONE size: ``planes`` fp32 (n, H, W), already windowed to [0, 1] ("windowed_float"), each labelled on
+    its own grid as ``segment_tiled`` labels it, against ``labels`` uint8 (n, H, W) (255 = ignore).  Returns (label maps uint8 (n, H, W)
+    on the host, counts int64 [3, C] on the device: the blend kernel's true positives, predicted and labelled pixels per class)."""
+    vol, lab = np.asarray(planes, dtype=np.float32), np.asarray(labels)
+    if vol.ndim != 3 or lab.shape != vol.shape or lab.dtype != np.uint8:
+        raise ValueError(f"tiled_label_counts: planes {vol.shape} and uint8 labels {lab.dtype} {lab.shape} must be equal (n, H, W) stacks")
+    device = _check_common(model, vol, "windowed_float", "replicate", batch_size, device)
+    plan = tile_plan(model, vol.shape[1], vol.shape[2], tile, overlap, window, False)
+    out, counts = _tiled_labels(model, vol, spacing, plan, "windowed_float", 0.0, 1.0, "replicate", int(batch_size), device,
+                                labels=torch.from_numpy(lab).to(device))
+    return out.cpu().numpy(), counts
 
 
 def _check_common(model, vol: np.ndarray, input_format: str, context: str, batch_size: int, device):

@@ -12,6 +12,10 @@ of both.  The loss and the validation metrics run at full resolution inside csrc
 --boundary-weight W adds Kervadec's boundary loss (the softmax probabilities weighted by the signed distance to each class's region,
 ops.signed_distance_map + ops.SegBoundaryLossFn) with --boundary-ramp-epochs and --boundary-units px|mm; 0, the default, is the run
 without it.
+--patch-train trains on patches at native resolution instead (dinox.patches, csrc/segpatch.hip): the training set lives on the device,
+every batch is drawn as affine jobs (foreground-oversampled centres, rotation, scaling, mirrors, gamma, gain) and sampled by one kernel
+launch -- no DataLoader, no host transform -- which is what scripts/segment_volume.py --tiled shows the model afterwards.  --patch-val
+tiled validates each image on its own grid through the sliding-window path.
 Written to --output whenever the early-stopping metric improves: the adapter files (rank > 0), seg_head.pth, finetune_config.json and,
 with --unfreeze-blocks, unfrozen_blocks.pth; dinox.segment.load_segmenter puts them back together.
 """
@@ -40,7 +44,7 @@ for _p in (_HERE.parent, _HERE):
         sys.path.insert(0, str(_p))
 
 import finetune_lora as fl  # noqa: E402
-from dinox import ops, segment as SG  # noqa: E402
+from dinox import ops, patches as PT, segment as SG, tiled as TL  # noqa: E402
 from zoo.hub import load_model  # noqa: E402
 from zoo.peft import apply_lora, save_adapter  # noqa: E402
 
@@ -211,6 +215,13 @@ class SegConfig(fl.FinetuneConfig):
     boundary_weight: float = 0.0
     boundary_ramp_epochs: int = 0
     boundary_units: str = "px"
+    patch_train: bool = False                                # the patch settings: off, and then every other one is at its "unset" value
+    patch_size: int = 0
+    patch_fg_prob: float = 0.0
+    patch_rotate_deg: float = 0.0
+    patch_scale: Optional[List[float]] = None
+    patches_per_epoch: int = 0
+    patch_val: str = "center"
 
 
 def boundary_weight(w: float, ramp_epochs: int, epoch: int) -> float:
@@ -280,6 +291,65 @@ def validate(model, loader, device, scale_aware, amp, w_ce, w_dice, c0, w_bd: fl
     return metrics["loss"], metrics, counts, torch.cat(preds)
 
 
+# nnU-Net's intensity augmentation: gamma on 30 % of the patches, a multiplicative brightness on 15 %
+PATCH_GAMMA = dict(gamma_range=(0.7, 1.5), gamma_prob=0.3, gain_range=(0.75, 1.25), gain_prob=0.15)
+
+
+def dataset_planes(ds) -> List[Tuple[np.ndarray, np.ndarray, Tuple[float, float, float]]]:
+    """(image fp32 (H, W) in [0, 1], mask uint8 (H, W), (sx, sy, sz)) of every sample of a MaskedImages / SyntheticMasks, untransformed."""
+    if hasattr(ds, "images"):
+        return [(ds.images[i, 0].numpy(), ds.masks[i].numpy(), tuple(float(v) for v in ds.spacings[i])) for i in range(len(ds))]
+    return [(ds.pixels(r).numpy(), ds.read_mask(r).numpy(), tuple(float(v) for v in r.spacing)) for r in ds.rows]
+
+
+def train_epoch_patches(model, pool: PT.PatchPool, gen: torch.Generator, steps: int, batch_size: int, draw: dict, opt: fl.ArenaAdamW, sched,
+                        device, scale_aware, amp, w_ce, w_dice, c0, w_bd: float = 0.0, mm: bool = False) -> float:
+    """train_epoch on ``steps`` batches of patches: jobs drawn on the host (dinox.patches.draw_patch_jobs, ``draw`` its keywords), both
+    tensors of a batch from one ops.seg_patch_sample launch.  ``mm``: the boundary term measures on the jobs' own grid spacing."""
+    model.train()
+    tot, S = 0.0, draw["S"]
+    for _ in range(steps):
+        d = PT.draw_patch_jobs(pool, batch_size, gen, **draw)
+        x, m = ops.seg_patch_sample(pool.img, pool.msk, d["jobs"], d["par"], S, fl.MEAN, fl.STD)
+        sp = torch.from_numpy(d["model_spacing"]).to(device) if scale_aware else None
+        opt.zero_grad()
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+            logits = model(x, spacing=sp)
+        if w_bd > 0:
+            grid = torch.from_numpy(d["grid_spacing"]).to(device) if mm else torch.ones((batch_size, 2), dtype=torch.float32, device=device)
+            phi = ops.signed_distance_map(m, grid, logits.shape[-1])
+            loss = ops.SegBoundaryLossFn.apply(logits, m, phi, w_ce, w_dice, w_bd, c0)[0]
+        else:
+            loss = ops.SegLossFn.apply(logits, m, w_ce, w_dice, c0)[0]
+        loss.backward()
+        opt.step(sched(opt.t))
+        tot += float(loss.detach())
+    return tot / max(steps, 1)
+
+
+@torch.no_grad()
+def validate_tiled(model, planes, tile: int, batch_size: int, device, amp, c0):
+    """Every validation image on its own grid (dinox.tiled: overlap 0.5, Gaussian window, tile side ``tile``), grouped by size and spacing
+    since a blend launch takes one size.  -> (1 - mean Dice, metrics, counts int64 [3, C] on the host, the label maps as a list of uint8
+    (H, W) arrays).  No soft loss exists on this path: "loss" is 1 - mean Dice of the label maps, from the blend kernel's counts."""
+    model.eval()
+    groups = {}
+    for k, (im, _, sp) in enumerate(planes):
+        groups.setdefault((im.shape, sp), []).append(k)
+    counts, preds = None, [None] * len(planes)
+    for (_, sp), ks in groups.items():
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+            out, cnt = TL.tiled_label_counts(model, np.stack([planes[k][0] for k in ks]), np.stack([planes[k][1] for k in ks]), sp, tile=tile,
+                                             overlap=0.5, window="gaussian", batch_size=batch_size, device=device)
+        counts = cnt.clone() if counts is None else counts + cnt
+        for k, o in zip(ks, out):
+            preds[k] = o
+    counts = counts.cpu()
+    dice = SG.mean_dice(counts, skip_background=bool(c0))
+    metrics = {"loss": 1.0 - dice, "mean_dice": dice, "miou": SG.miou(counts), "pixel_accuracy": SG.pixel_accuracy(counts)}
+    return metrics["loss"], metrics, counts, preds
+
+
 def save_segmenter(model: SG.SegModel, vit: nn.Module, output_dir: Path, config: SegConfig) -> None:
     output_dir = Path(output_dir)
     output_dir.mkdir(parents=True, exist_ok=True)
@@ -327,13 +397,32 @@ def build_boundary_parser() -> argparse.ArgumentParser:
     return ap
 
 
+def build_patch_parser() -> argparse.ArgumentParser:
+    """The options of patch training.  A parser of their own, as the boundary options are; parse_cli reads them out of the command line."""
+    ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    ap.add_argument("--patch-train", action="store_true", help="train on patches at native resolution, sampled on the device")
+    ap.add_argument("--patch-size", type=int, default=None, metavar="T", help="side of a patch in source pixels at scale 1 (default: the model's S)")
+    ap.add_argument("--patch-fg-prob", type=float, default=0.33, help="share of patches centred on a pixel of a class present in the sample")
+    ap.add_argument("--patch-rotate-deg", type=float, default=15.0, help="rotation drawn uniformly in [-D, D] degrees")
+    ap.add_argument("--patch-scale", type=float, nargs=2, default=[0.7, 1.4], metavar=("LO", "HI"),
+                    help="source pixels per output pixel, relative to T / S, drawn uniformly in [LO, HI]")
+    ap.add_argument("--patches-per-epoch", type=int, default=None, metavar="N", help="patches per epoch (default: the number of training samples)")
+    ap.add_argument("--patch-pool-gib", type=float, default=16.0, help="refuse a training set that needs more device memory than this")
+    ap.add_argument("--patch-val", choices=["center", "tiled"], default="center",
+                    help="validation: the centre crop at S x S, or every image on its own grid by sliding window (tile side T, overlap 0.5)")
+    return ap
+
+
 def parse_cli(argv=None) -> argparse.Namespace:
-    """The boundary options (build_boundary_parser) first, everything else through build_parser; one namespace."""
+    """The boundary options (build_boundary_parser) and the patch options (build_patch_parser) first, everything else through
+    build_parser; one namespace."""
     bd, rest = build_boundary_parser().parse_known_args(argv)
+    pt, rest = build_patch_parser().parse_known_args(rest)
     ap = build_parser()
-    ap.epilog = "Boundary loss: " + " ".join(build_boundary_parser().format_help().split()[1:])
+    ap.epilog = ("Boundary loss: " + " ".join(build_boundary_parser().format_help().split()[1:]) + "  Patch training: "
+                 + " ".join(build_patch_parser().format_help().split()[1:]))
     args = ap.parse_args(rest)
-    for k, v in vars(bd).items():
+    for k, v in (*vars(bd).items(), *vars(pt).items()):
         setattr(args, k, v)
     return args
 
@@ -348,8 +437,8 @@ def warn_mm_without_spacing(rows: List[MaskedRow], units: str) -> bool:
 
 
 def run(args: argparse.Namespace) -> dict:
-    """One run -> {"config": SegConfig, "val_pred": the best epoch's validation label maps uint8 [n, S, S] (host), "val_dataset": the
-    validation set}.  A namespace without the boundary attributes (build_parser() alone) runs without the boundary term."""
+    """One run -> {"config": SegConfig, "val_pred": the best epoch's validation label maps uint8 [n, S, S] (host; under --patch-val tiled
+    a list of (H, W) arrays, each image's own grid), "val_dataset": the validation set}.  A namespace without the boundary attributes (build_parser() alone) runs without the boundary term."""
     ap = build_parser()
     w_bd, ramp = float(getattr(args, "boundary_weight", 0.0)), int(getattr(args, "boundary_ramp_epochs", 0))
     units = getattr(args, "boundary_units", "px")
@@ -360,6 +449,25 @@ def run(args: argparse.Namespace) -> dict:
     if units not in ("px", "mm"):
         ap.error(f"--boundary-units {units!r}: px or mm")
     mm = w_bd > 0 and units == "mm"                          # only then does a sample carry its grid spacing
+    pdef = build_patch_parser().parse_args([])               # a namespace without the patch attributes runs without patch training
+    patch = {k: getattr(args, k, v) for k, v in vars(pdef).items()}
+    if patch["patch_size"] is not None and patch["patch_size"] < 1:
+        ap.error(f"--patch-size {patch['patch_size']}: the patch side must be >= 1")
+    if not 0.0 <= patch["patch_fg_prob"] <= 1.0:
+        ap.error(f"--patch-fg-prob {patch['patch_fg_prob']}: a probability in [0, 1]")
+    if not 0.0 <= patch["patch_rotate_deg"] <= 180.0:
+        ap.error(f"--patch-rotate-deg {patch['patch_rotate_deg']}: degrees in [0, 180]")
+    lo, hi = patch["patch_scale"]
+    if not (math.isfinite(lo) and math.isfinite(hi) and 0 < lo <= hi):
+        ap.error(f"--patch-scale {lo} {hi}: finite, 0 < LO <= HI")
+    if patch["patches_per_epoch"] is not None and patch["patches_per_epoch"] < args.batch_size:
+        ap.error(f"--patches-per-epoch {patch['patches_per_epoch']} does not fill one batch of {args.batch_size}")
+    if not patch["patch_pool_gib"] > 0:
+        ap.error(f"--patch-pool-gib {patch['patch_pool_gib']}: must be > 0")
+    if patch["patch_val"] not in ("center", "tiled"):
+        ap.error(f"--patch-val {patch['patch_val']!r}: center or tiled")
+    if patch["patch_val"] == "tiled" and not patch["patch_train"]:
+        ap.error("--patch-val tiled belongs to --patch-train")
     if args.ignore_index != IGNORE:
         ap.error(f"--ignore-index {args.ignore_index}: only {IGNORE} is supported (the kernels compare labels with that value)")
     if not 2 <= args.num_classes <= ops.SEG_MAX_CLASSES:
@@ -398,10 +506,16 @@ def run(args: argparse.Namespace) -> dict:
         val_ds = masked(rows_v, img, augment=False, **kw)
         workers = args.num_workers
     gen = torch.Generator().manual_seed(seed)
-    train_loader = torch.utils.data.DataLoader(train_ds, batch_size=args.batch_size, shuffle=True, drop_last=True, num_workers=workers,
-                                               generator=gen)
-    val_loader = torch.utils.data.DataLoader(val_ds, batch_size=args.batch_size, shuffle=False, num_workers=workers)
-    if len(train_loader) == 0:
+    if patch["patch_train"]:                                 # no loader: the datasets only hand their untransformed planes to the pool
+        train_loader = None
+        per_epoch = (patch["patches_per_epoch"] or len(train_ds)) // args.batch_size
+    else:
+        train_loader = torch.utils.data.DataLoader(train_ds, batch_size=args.batch_size, shuffle=True, drop_last=True, num_workers=workers,
+                                                   generator=gen)
+        per_epoch = len(train_loader)
+    val_loader = (torch.utils.data.DataLoader(val_ds, batch_size=args.batch_size, shuffle=False, num_workers=workers)
+                  if patch["patch_val"] == "center" else None)
+    if per_epoch == 0:
         ap.error(f"{len(train_ds)} training samples do not fill one batch of {args.batch_size}")
 
     if args.rank > 0:
@@ -424,21 +538,42 @@ def run(args: argparse.Namespace) -> dict:
     log.info("%d adapter + %d unfrozen + %d head parameters train%s", sum(p.numel() for p in fast) - sum(p.numel() for p in model.head.parameters()),
              sum(p.numel() for p in base_params), sum(p.numel() for p in model.head.parameters()), " (backbone under no_grad)" if frozen else "")
     opt = fl.ArenaAdamW([(fast, args.lr), (base_params, args.backbone_lr)], args.weight_decay)
-    steps, warm = args.epochs * len(train_loader), args.warmup_epochs * len(train_loader)
+    if patch["patch_train"]:
+        tile = patch["patch_size"] or img
+        train_planes = dataset_planes(train_ds)
+        try:
+            pool = PT.PatchPool([p[0] for p in train_planes], [p[1] for p in train_planes], [p[2] for p in train_planes], device=device,
+                                max_gib=patch["patch_pool_gib"], seed=seed)
+        except ValueError as e:
+            ap.error(str(e))
+        draw = dict(S=img, t=tile, fg_prob=patch["patch_fg_prob"], rotate_deg=patch["patch_rotate_deg"], scale_range=(lo, hi), **PATCH_GAMMA)
+        patch_gen = torch.Generator().manual_seed(seed + 2)
+        val_planes = dataset_planes(val_ds) if patch["patch_val"] == "tiled" else None
+    steps, warm = args.epochs * per_epoch, args.warmup_epochs * per_epoch
 
     cfg = SegConfig(backbone=str(args.backbone), task="segmentation", num_classes=args.num_classes, rank=args.rank, alpha=args.alpha, lr=args.lr,
                     epochs=args.epochs, batch_size=args.batch_size, input_format=args.input_format, scale_aware=scale_aware,
                     train_samples=len(train_ds), val_samples=len(val_ds), seed=args.seed, unfreeze_blocks=args.unfreeze_blocks,
                     backbone_lr=args.backbone_lr if args.unfreeze_blocks > 0 else None, ce_weight=args.ce_weight, dice_weight=args.dice_weight,
                     dice_c0=c0, ignore_index=args.ignore_index, boundary_weight=w_bd, boundary_ramp_epochs=ramp, boundary_units=units)
+    if patch["patch_train"]:
+        cfg.patch_train, cfg.patch_size, cfg.patch_fg_prob, cfg.patch_rotate_deg = True, tile, patch["patch_fg_prob"], patch["patch_rotate_deg"]
+        cfg.patch_scale, cfg.patches_per_epoch, cfg.patch_val = [lo, hi], per_epoch * args.batch_size, patch["patch_val"]
     higher = args.es_metric != "loss"
     best, stale, t0, best_pred = (-math.inf if higher else math.inf), 0, time.time(), None
     for epoch in range(1, args.epochs + 1):
         bd = (boundary_weight(w_bd, ramp, epoch - 1), w_bd) if w_bd > 0 else None     # (this epoch's training weight, validation's)
-        tr = train_epoch(model, train_loader, opt, lambda s: fl.lr_factor(s, warm, steps), device, scale_aware, amp, args.ce_weight,
-                         args.dice_weight, c0, *(bd[:1] if bd else ()))
-        vl, metrics, counts, preds = validate(model, val_loader, device, scale_aware, amp, args.ce_weight, args.dice_weight, c0,
-                                              *(bd[1:] if bd else ()))
+        if patch["patch_train"]:
+            tr = train_epoch_patches(model, pool, patch_gen, per_epoch, args.batch_size, draw, opt, lambda s: fl.lr_factor(s, warm, steps), device,
+                                     scale_aware, amp, args.ce_weight, args.dice_weight, c0, bd[0] if bd else 0.0, mm)
+        else:
+            tr = train_epoch(model, train_loader, opt, lambda s: fl.lr_factor(s, warm, steps), device, scale_aware, amp, args.ce_weight,
+                             args.dice_weight, c0, *(bd[:1] if bd else ()))
+        if patch["patch_val"] == "tiled":
+            vl, metrics, counts, preds = validate_tiled(model, val_planes, tile, args.batch_size, device, amp, c0)
+        else:
+            vl, metrics, counts, preds = validate(model, val_loader, device, scale_aware, amp, args.ce_weight, args.dice_weight, c0,
+                                                  *(bd[1:] if bd else ()))
         cfg.train_loss_history.append(tr)
         log.info("epoch %d/%d  train %.4f  %s", epoch, args.epochs, tr, "  ".join(f"{k} {v:.4f}" for k, v in metrics.items()))
         cur = metrics[args.es_metric] if higher else vl

@@ -872,6 +872,34 @@ int dinox_seg_blend_predict(const float* z, const int32_t* ys, const int32_t* xs
                             void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Patch sampling for segmentation training at native resolution (kernel: csrc/segpatch.hip; dinox.ops.seg_patch_sample, dinox.patches).
+ * One launch turns B jobs into the image batch x[B][3][S][S] fp32 and the label batch m[B][S][S] uint8.  Both are sampled from a
+ * device-resident pool under the job's inverse affine map; the source point is computed once per output pixel and serves both.
+ *   img         fp32 planes, already windowed to [0, 1];  msk  uint8 planes.  A plane is H x W, contiguous.
+ *   jobs[B][4]  device int64 = {element offset of the image plane in img, element offset of the mask plane in msk, H, W}, 1 <= H, W <= 2^20.
+ *               Planes of different sizes may meet in one launch; offsets carry no alignment promise.  The kernel TRUSTS jobs (the caller
+ *               checks its host copy against the sizes of the pools).
+ *   par[B][8]   device fp32 = {a00, a01, a02, a10, a11, a12, gamma, gain}, finite, gamma > 0 (the caller's check; see Safety).
+ *   Coordinates.  Output pixel (oy, ox) has dx = ox + 0.5 - S / 2 and dy = oy + 0.5 - S / 2 (exact in fp32), and
+ *               sx = fmaf(a00, dx, fmaf(a01, dy, a02)),   sy = fmaf(a10, dx, fmaf(a11, dy, a12))
+ *               in fp32, in exactly this order: a CPU fp32 emulation reproduces sx and sy to the bit.  Source pixel i covers [i, i + 1).
+ *   Label.      m = msk[floor(sy)][floor(sx)] if 0 <= sx < W and 0 <= sy < H, else 255 (the ignore value of the loss kernels: padding
+ *               never trains).
+ *   Image.      Bilinear at u = sx - 0.5, v = sy - 0.5 (one fp32 subtraction each): taps floor(u), floor(u) + 1 with weights 1 - wx, wx,
+ *               wx = u - floor(u) (exact); rows alike; x first.  A tap outside the plane takes `pad`; a point with u <= -1, u >= W,
+ *               v <= -1 or v >= H (every tap outside) gives exactly `pad`.  Then v' = gain max(v, 0)^gamma, the power (powf) and its
+ *               clamp skipped when gamma == 1, so that the identity job is exact; then x_c = (v' - mean_c) / std_c for c = 0, 1, 2 (the one
+ *               plane replicated), an IEEE subtraction and division.  mean, std: HOST arrays of 3 floats read during the call, std > 0.
+ *   Safety.     No content of par moves an access: a coordinate is compared with the plane's bounds in fp32 BEFORE any conversion to an
+ *               integer (a NaN or a huge value is outside), and every tap index is used only after 0 <= i < W (or H) was tested.
+ * Plain stores, no atomics, no LDS: equal inputs give equal bytes.  1 <= S <= 2^14, 1 <= B <= 2^20 and B S ceil(S / 64) <= 2^31; anything
+ * else, a null pointer, a non-finite mean, std or pad, or std <= 0 is DINOX_EINVAL with a message before any launch.  The entry allocates
+ * nothing and does not synchronise.  No antialiasing when a job shrinks the source.
+ * ------------------------------------------------------------------------------------------ */
+int dinox_seg_patch_sample(const float* img, const uint8_t* msk, const int64_t* jobs, const float* par, float* x, uint8_t* m, int64_t B, int S,
+                           const float* mean, const float* stdev, float pad, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Surface distances between two label maps, in mm (kernels: csrc/surfdist.hip; dinox.ops.surface_stats, dinox.segment.surface_metrics).
  *   pred[B][H][W], gt[B][H][W]  uint8, dense, 1 <= H, W <= 1024 (rectangular maps are fine: nothing here knows a patch grid), B >= 1 and
  *               B C 2 H <= 2^30.  Classes 0 .. C - 1, 2 <= C <= 64.  gt == 255 is ignore.  A pred value >= C, or a gt value >= C other
