@@ -17,7 +17,7 @@ import math
 import operator
 import os
 import weakref
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -3133,6 +3133,64 @@ def seg_predict(z: Tensor, u: int, labels: Optional[Tensor] = None):
         return pred
     _seg_refuse_bad_labels("seg_predict", int(counts[3 * C]), C)
     return pred, counts[:3 * C].view(3, C)
+
+
+# ------------------------------------------------------------------------------------------
+# calibration of the upsampled softmax: confidence, entropy, reliability histogram, NLL / Brier / Newton sums (csrc/segcalib.hip)
+# ------------------------------------------------------------------------------------------
+SEG_CALIB_MAX_BINS = 64
+
+
+class SegCalib(NamedTuple):
+    """What ``seg_calib`` returns.  ``pred`` uint8, ``conf`` and ``entropy`` fp32 [B, S, S] (None where not asked for); with labels
+    ``hist`` int64 [NB, 3] = per bin (count, correct, Q: the confidences in 2^-24 fixed point), ``tail`` int64 [3] = (valid pixels, labels
+    >= C other than 255 -- always 0 here, such labels raise --, valid pixels whose confidence is not finite) and ``sums`` fp32 [5] = (NLL,
+    Brier, G = dNLL/ds, H = d2NLL/ds2, entropy) totals over the valid pixels with finite confidence; None without labels."""
+    pred: Optional[Tensor]
+    conf: Optional[Tensor]
+    entropy: Optional[Tensor]
+    hist: Optional[Tensor]
+    tail: Optional[Tensor]
+    sums: Optional[Tensor]
+
+
+def seg_calib(z: Tensor, u: int, labels: Optional[Tensor] = None, *, inv_temperature: float = 1.0, bins: int = 15, want_pred: bool = True,
+              want_conf: bool = False, want_entropy: bool = False) -> SegCalib:
+    """One launch over the patch logits z [B, g^2, C] at S = g u (include/dinox.h has the definitions): the arg-max map of ``seg_predict``
+    (bit for bit, whatever the temperature), the confidence p[pred] and the normalised entropy of softmax(inv_temperature * l), and with
+    ``labels`` (uint8 [B, S, S], 255 = ignore) the reliability histogram over ``bins`` equal-width confidence bins and the five sums.
+    Nothing of full resolution is allocated but the maps asked for.  A label >= C other than 255 raises the ValueError of ``seg_predict``
+    (one device read)."""
+    B, g, C = _seg_geometry("seg_calib", z, u)
+    if labels is not None and _seg_labels("seg_calib", labels, B, g, z) != u:
+        raise ValueError(f"seg_calib: labels {tuple(labels.shape)} do not have side g u = {g * u}")
+    if isinstance(bins, bool) or not isinstance(bins, int) or not 1 <= bins <= SEG_CALIB_MAX_BINS:
+        raise ValueError(f"seg_calib: bins must be an integer in [1, {SEG_CALIB_MAX_BINS}], got {bins!r}")
+    s = float(inv_temperature)
+    if not (s > 0 and math.isfinite(s) and math.isfinite(float(np.float32(s))) and float(np.float32(s)) > 0):
+        raise ValueError(f"seg_calib: inv_temperature must be finite and > 0 (in fp32), got {inv_temperature!r}")
+    if labels is None and not (want_pred or want_conf or want_entropy):
+        raise ValueError("seg_calib: nothing to compute (no labels and no map asked for)")
+    _need_cuda(z, labels)
+    z = _c(z.float())
+    dev = z.device
+    S = g * u
+    pred = torch.empty((B, S, S), dtype=torch.uint8, device=dev) if want_pred else None
+    conf = torch.empty((B, S, S), dtype=torch.float32, device=dev) if want_conf else None
+    ent = torch.empty((B, S, S), dtype=torch.float32, device=dev) if want_entropy else None
+    hist = sums = ws = None
+    if labels is not None:
+        labels = _c(labels)
+        hist = torch.empty(3 * bins + 3, dtype=torch.int64, device=dev)
+        sums = torch.empty(5, dtype=torch.float32, device=dev)
+        ws = torch.empty(int(lib.dinox_seg_calib_ws_bytes(B, g, u, C, bins)) // 4, dtype=torch.float32, device=dev)
+    check(lib.dinox_seg_calib(_p(z), _p(labels), s, _p(pred), _p(conf), _p(ent), _p(hist), _p(sums), _p(ws), B, g, u, C, bins, _stream()),
+          "dinox_seg_calib")
+    if hist is None:
+        return SegCalib(pred, conf, ent, None, None, None)
+    tail = hist[3 * bins:]
+    _seg_refuse_bad_labels("seg_calib", int(tail[1]), C)
+    return SegCalib(pred, conf, ent, hist[:3 * bins].view(bins, 3), tail, sums)
 
 
 # ------------------------------------------------------------------------------------------

@@ -14,7 +14,9 @@ lesion-wise sensitivity, precision, F1 and false positives per image.  For a who
 the chunk loop of ``zoo.encode.encode_volume``), ``postprocess_volume`` and ``ops.lesion_counts_3d`` on 3-D components
 (csrc/cclabel3d.hip), ``resample_labels_nearest`` for the ground truth and ``CaseAccumulator`` for per-case scores.  All of the above
 label the model's S x S grid; ``segment_tiled`` / ``segment_volume_tiled`` (dinox/tiled.py, csrc/segblend.hip) label the image's own
-grid by sliding window.
+grid by sliding window.  How far the probabilities can be trusted: ``ops.seg_calib`` (csrc/segcalib.hip) gives confidence and entropy
+maps (``segment(..., return_confidence=True)``), ``calibration_report`` / ``CalibrationAccumulator`` turn its integer histogram into
+ECE, NLL and Brier score, and ``fit_temperature`` fits ``SegModel.temperature``.
 """
 from __future__ import annotations
 
@@ -57,6 +59,8 @@ class SegModel(nn.Module):
     def __init__(self, backbone: nn.Module, head: SegHead, frozen_backbone: bool = False) -> None:
         super().__init__()
         self.backbone, self.head, self.frozen_backbone = backbone, head, frozen_backbone
+        # softmax temperature of the confidence / entropy maps (fit_temperature); never applied in forward: the logits stay as they are
+        self.temperature = 1.0
 
     @property
     def img_size(self) -> int:
@@ -89,14 +93,19 @@ class SegModel(nn.Module):
 def segment(model: SegModel, image: np.ndarray, pixel_spacing: Tuple[float, float] = (1.0, 1.0), slice_thickness: float = 1.0, *,
             input_format: Literal["hu_float", "hu16_png", "windowed_float"] = "hu_float", hu_level: float = 40.0, hu_width: float = 400.0,
             device: Union[str, torch.device, None] = None, preprocess: Literal["host", "device", "auto"] = "host",
-            keep_largest: bool = False, min_area_mm2: float = 0.0, connectivity: int = 8) -> np.ndarray:
+            keep_largest: bool = False, min_area_mm2: float = 0.0, connectivity: int = 8, return_confidence: bool = False,
+            return_entropy: bool = False):
     """Label map of one image: uint8 (S, S) with S = model.img_size, the arg-max of the upsampled patch logits.  Preprocessing, argument
     checking and the spacing convention are those of ``zoo.encode`` (its ``_batch``), so a stored head sees what ``encode()`` sees.
     Honours an ambient ``torch.autocast`` as ``encode`` does.
 
     ``keep_largest`` / ``min_area_mm2`` > 0 clean the map with ``postprocess`` before it leaves the device (with the defaults nothing
     changes).  The area is measured on the model's grid: ``pixel_spacing`` is (mm per source pixel along x, along y), as for ``encode``,
-    and the h x w image is resized to S x S, so a pixel of the label map is (s_y, s_x) = (pixel_spacing[1] h / S, pixel_spacing[0] w / S) mm."""
+    and the h x w image is resized to S x S, so a pixel of the label map is (s_y, s_x) = (pixel_spacing[1] h / S, pixel_spacing[0] w / S) mm.
+
+    ``return_confidence`` / ``return_entropy``: the return becomes ``(labels, conf[, entropy])`` with fp32 (S, S) maps of the winning
+    class's softmax probability and of the entropy / log C, both at ``model.temperature`` and of the raw arg-max (clean-up touches the
+    labels only).  One ``ops.seg_calib`` launch then gives labels and maps; the labels are the same bits either way."""
     from zoo.encode import _batch
     if device is None:
         device = next(model.parameters()).device
@@ -106,21 +115,37 @@ def segment(model: SegModel, image: np.ndarray, pixel_spacing: Tuple[float, floa
         spacing = torch.tensor([[pixel_spacing[0], pixel_spacing[1], slice_thickness]], dtype=torch.float32, device=device)
     with torch.no_grad():
         logits = model(x, spacing=spacing)
-    pred = ops.seg_predict(logits, model.patch)
+    maps = ()
+    if return_confidence or return_entropy:
+        res = ops.seg_calib(logits, model.patch, inv_temperature=1.0 / _temperature(model), want_conf=return_confidence,
+                            want_entropy=return_entropy)
+        pred, maps = res.pred, tuple(m for m in (res.conf, res.entropy) if m is not None)
+    else:
+        pred = ops.seg_predict(logits, model.patch)
     if keep_largest or min_area_mm2 > 0:
         arr = np.asarray(image)
         h, w = arr.shape[1:] if arr.ndim == 3 and arr.shape[2] != 3 else arr.shape[:2]
         S = model.img_size
         pred = postprocess(pred, model.head.num_classes, [[pixel_spacing[1] * h / S, pixel_spacing[0] * w / S]], keep_largest=keep_largest,
                            min_area_mm2=min_area_mm2, connectivity=connectivity)
+    if maps:
+        return (pred[0].cpu().numpy(),) + tuple(m[0].cpu().numpy() for m in maps)
     return pred[0].cpu().numpy()
+
+
+def _temperature(model) -> float:
+    """model.temperature as a finite float > 0 (1.0 for a model that carries none)."""
+    t = float(getattr(model, "temperature", 1.0))
+    if not (t > 0 and math.isfinite(t)):
+        raise ValueError(f"the segmenter's temperature must be finite and > 0, got {t!r}")
+    return t
 
 
 def segment_volume(model: SegModel, volume: np.ndarray, spacing: Tuple[float, float, float] = (1.0, 1.0, 1.0), *,
                    input_format: Literal["hu_float", "hu16_png", "windowed_float"] = "hu_float", hu_level: float = 40.0, hu_width: float = 400.0,
                    context: Literal["neighbours", "replicate"] = "neighbours", batch_size: int = 64,
                    device: Union[str, torch.device, None] = None, keep_largest: bool = False, min_volume_mm3: float = 0.0,
-                   connectivity: int = 26) -> np.ndarray:
+                   connectivity: int = 26, return_confidence: bool = False, return_entropy: bool = False):
     """Label volume of a ``(Z, H, W)`` series: uint8 (Z, S, S) with S = model.img_size.  The volume crosses to the device once and is
     preprocessed and forwarded in chunks of ``batch_size`` slices exactly as ``zoo.encode.encode_volume`` does it (``context``: the 2.5D
     stack of a slice); every chunk's patch logits go through ``ops.seg_predict`` into one device buffer, which is copied back once.
@@ -128,21 +153,40 @@ def segment_volume(model: SegModel, volume: np.ndarray, spacing: Tuple[float, fl
 
     ``keep_largest`` / ``min_volume_mm3`` > 0 clean the volume with ``postprocess_volume`` (3-D components, ``connectivity`` 6, 18 or 26)
     before it leaves the device.  The voxel of the label grid follows ``segment``'s convention: the h x w planes are resized to S x S, so
-    it measures (s_z, s_y, s_x) = (spacing[2], spacing[1] h / S, spacing[0] w / S) mm."""
+    it measures (s_z, s_y, s_x) = (spacing[2], spacing[1] h / S, spacing[0] w / S) mm.
+
+    ``return_confidence`` / ``return_entropy``: as for ``segment`` -- the return becomes ``(labels, conf[, entropy])`` with fp32 (Z, S, S)
+    maps at ``model.temperature``, from one ``ops.seg_calib`` launch per chunk in place of ``ops.seg_predict`` (the same label bits)."""
     from zoo.encode import forward_volume_chunks
     min_component_vox(min_volume_mm3)               # refuses a negative or non-finite volume before any work is done
     if connectivity not in (6, 18, 26):
         raise ValueError(f"segment_volume: connectivity must be 6, 18 or 26, got {connectivity!r}")
-    S, out = model.img_size, None
+    want_maps = return_confidence or return_entropy
+    inv_t = 1.0 / _temperature(model) if want_maps else 1.0
+    S, out, conf, ent = model.img_size, None, None, None
     for ch, logits in forward_volume_chunks(model, volume, spacing, input_format=input_format, hu_level=hu_level, hu_width=hu_width,
                                             context=context, z_stride=1, batch_size=batch_size, device=device):
         if out is None:
-            out = torch.empty((np.asarray(volume).shape[0], S, S), dtype=torch.uint8, device=logits.device)
-        out[ch[0]:ch[0] + len(ch)] = ops.seg_predict(logits, model.patch)
+            Z = np.asarray(volume).shape[0]
+            out = torch.empty((Z, S, S), dtype=torch.uint8, device=logits.device)
+            conf = torch.empty((Z, S, S), dtype=torch.float32, device=logits.device) if return_confidence else None
+            ent = torch.empty((Z, S, S), dtype=torch.float32, device=logits.device) if return_entropy else None
+        sl = slice(ch[0], ch[0] + len(ch))
+        if want_maps:
+            res = ops.seg_calib(logits, model.patch, inv_temperature=inv_t, want_conf=return_confidence, want_entropy=return_entropy)
+            out[sl] = res.pred
+            if conf is not None:
+                conf[sl] = res.conf
+            if ent is not None:
+                ent[sl] = res.entropy
+        else:
+            out[sl] = ops.seg_predict(logits, model.patch)
     if keep_largest or min_volume_mm3 > 0:
         _, h, w = np.asarray(volume).shape
         out = postprocess_volume(out, model.head.num_classes, (spacing[2], spacing[1] * h / S, spacing[0] * w / S), keep_largest=keep_largest,
                                  min_volume_mm3=min_volume_mm3, connectivity=connectivity)
+    if want_maps:
+        return (out.cpu().numpy(),) + tuple(m.cpu().numpy() for m in (conf, ent) if m is not None)
     return out.cpu().numpy()
 
 
@@ -419,6 +463,114 @@ class CaseAccumulator:
         return {"dice": dice, "cases": self.cases.clone(), "lesions": lesion_metrics(self.lesions, images=self.n)}
 
 
+# ------------------------------------------------------------------------------------------ calibration (ops.seg_calib, csrc/segcalib.hip)
+Q_ONE = 1 << 24                                     # the histogram's confidences are integers in units of 2^-24
+
+
+def calibration_report(hist, tail, sums) -> dict:
+    """Scores from ``ops.seg_calib``'s integers and sums (CPU or device tensors, arrays or lists; no GPU needed): ``hist`` [NB, 3] = per
+    bin (count, correct, Q), ``tail`` [3] = (valid pixels, bad labels, non-finite), ``sums`` [5] = (NLL, Brier, G, H, entropy) totals.
+    Every quotient is one float64 division of exact integers (the sums: of float64 values), so e.g. a table whose bins have
+    correct 2^24 = Q scores ece == 0 exactly.
+
+    {"bins": [{"count", "accuracy" = correct / count, "mean_confidence" = Q / (2^24 count)} or None for an empty bin],
+     "ece" = sum_k (count_k / N) |acc_k - conf_k|, "mce" = the largest gap over the non-empty bins, "nll", "brier", "mean_entropy" (sums / N),
+     "accuracy", "mean_confidence", "pixels" = N = valid - non-finite, "nonfinite"}; with N = 0 every score is None."""
+    rows = [[int(v) for v in r] for r in (hist.tolist() if hasattr(hist, "tolist") else hist)]
+    nv, _, nonfinite = (int(v) for v in (tail.tolist() if hasattr(tail, "tolist") else tail))
+    sm = [float(v) for v in (sums.tolist() if hasattr(sums, "tolist") else sums)]
+    if any(len(r) != 3 for r in rows) or len(sm) != 5:
+        raise ValueError("calibration_report: hist must be [NB, 3] and sums [5]")
+    N = nv - nonfinite
+    if N != sum(r[0] for r in rows):
+        raise ValueError(f"calibration_report: the bins hold {sum(r[0] for r in rows)} pixels, the tail says {nv} - {nonfinite}")
+    bins = [None if n == 0 else {"count": n, "accuracy": k / n, "mean_confidence": q / (Q_ONE * n)} for n, k, q in rows]
+    out = {"bins": bins, "pixels": N, "nonfinite": nonfinite}
+    if N == 0:
+        out.update(dict.fromkeys(("ece", "mce", "nll", "brier", "mean_entropy", "accuracy", "mean_confidence")))
+        return out
+    gaps = [abs(k * Q_ONE - q) for n, k, q in rows]                              # |acc_k - conf_k| count_k 2^24, an integer
+    out.update(ece=sum(gaps) / (Q_ONE * N), mce=max(gp / (Q_ONE * n) for gp, (n, _, _) in zip(gaps, rows) if n),
+               nll=sm[0] / N, brier=sm[1] / N, mean_entropy=sm[4] / N, accuracy=sum(r[1] for r in rows) / N,
+               mean_confidence=sum(r[2] for r in rows) / (Q_ONE * N))
+    return out
+
+
+class CalibrationAccumulator:
+    """Dataset totals of ``ops.seg_calib`` results over a stream of batches: the histogram in int64, the sums in float64."""
+
+    def __init__(self, bins: int = 15) -> None:
+        self.bins = bins
+        self.hist = torch.zeros((bins, 3), dtype=torch.int64)
+        self.tail = torch.zeros(3, dtype=torch.int64)
+        self.sums = torch.zeros(5, dtype=torch.float64)
+
+    def update(self, result) -> None:
+        if result.hist is None or tuple(result.hist.shape) != (self.bins, 3):
+            raise ValueError(f"CalibrationAccumulator: expected a seg_calib result with labels and {self.bins} bins")
+        self.hist += result.hist.cpu()
+        self.tail += result.tail.cpu()
+        self.sums += result.sums.double().cpu()
+
+    def result(self) -> dict:
+        return calibration_report(self.hist, self.tail, self.sums)
+
+
+def fit_temperature(batches, u: int, *, lo: float = 0.05, hi: float = 20.0, tol: float = 1e-4, max_iter: int = 30, calib=None) -> dict:
+    """The temperature T in [lo, hi] that minimises the total NLL of softmax(l / T) over ``batches``, a list of (z, labels) pairs of device
+    tensors (patch logits [B, g^2, C] and uint8 labels [B, S, S] of a validation set), by safeguarded Newton on theta = log s, s = 1 / T.
+
+    One pass = one ``ops.seg_calib`` launch per batch (``want_pred=False``: nothing of full resolution is written) and one read of its
+    five sums; G = dNLL/ds and H = d2NLL/ds2 are added over the batches in float64.  d/dtheta = s G and d2/dtheta2 = s G + s^2 H, so the
+    step is -(s G) / (s G + s^2 H); the sign of G keeps a bracket (NLL is convex in s) and its midpoint replaces a step that leaves the
+    bracket or has a denominator <= 0.  Stops once |step| < tol (the step is still taken).
+
+    -> {"temperature", "iterations", "nll_before" (mean NLL at T = 1), "nll_after", "converged"}; without a valid pixel
+    {"temperature": 1.0, "converged": False, ...}.  ``calib``: what to call instead of ``ops.seg_calib`` (tests)."""
+    calib = calib or ops.seg_calib
+    if not (0 < lo < hi and math.isfinite(hi)):
+        raise ValueError(f"fit_temperature: need 0 < lo < hi < inf, got {lo!r}, {hi!r}")
+    if not (tol > 0 and max_iter >= 1):
+        raise ValueError(f"fit_temperature: need tol > 0 and max_iter >= 1, got {tol!r}, {max_iter!r}")
+    batches = list(batches)
+
+    def totals(s: float, want_n: bool = False):
+        t, n = np.zeros(5), 0
+        for z, y in batches:
+            r = calib(z, u, y, inv_temperature=s, want_pred=False)
+            t += r.sums.double().cpu().numpy()
+            if want_n:
+                tl = r.tail.cpu()
+                n += int(tl[0]) - int(tl[2])
+        return t, n
+
+    first, N = totals(1.0, True)
+    if N == 0:
+        return {"temperature": 1.0, "iterations": 0, "nll_before": None, "nll_after": None, "converged": False}
+    a, b = -math.log(hi), math.log(1.0 / lo)        # the bracket of theta = log s
+    theta, t, converged, it = min(max(0.0, a), b), first, False, 0
+    if theta != 0.0:
+        t, _ = totals(math.exp(theta))
+    while it < max_iter:
+        it += 1
+        s = math.exp(theta)
+        grad, den = s * t[2], s * t[2] + s * s * t[3]
+        if grad > 0:
+            b = theta
+        else:
+            a = theta
+        new = theta - grad / den if den > 0 else None
+        if new is None or not a < new < b:
+            new = 0.5 * (a + b)
+        step, theta = new - theta, new
+        t, _ = totals(math.exp(theta))
+        if abs(step) < tol:
+            converged = True
+            break
+    return {"temperature": math.exp(-theta), "iterations": it, "nll_before": float(first[0]) / N, "nll_after": float(t[0]) / N,
+            "converged": converged}
+
+
 # ------------------------------------------------------------------------------------------ what finetune_segmentation.py wrote
 def load_segmenter(backbone_path, output_dir, device: Union[str, torch.device] = "cuda") -> SegModel:
     """Backbone from ``backbone_path`` (whatever ``zoo.hub.load_model`` takes), then from ``output_dir``: the unfrozen blocks' weights if
@@ -444,6 +596,9 @@ def load_segmenter(backbone_path, output_dir, device: Union[str, torch.device] =
     model = SegModel(backbone, head, frozen_backbone=cfg["rank"] == 0 and cfg.get("unfreeze_blocks", 0) == 0).to(device)
     for p in model.parameters():
         p.requires_grad = False
+    if "temperature" in cfg:                        # --fit-temperature's result: used by the confidence / entropy maps only
+        model.temperature = float(cfg["temperature"])
+        _temperature(model)
     return model.eval()
 
 

@@ -80,13 +80,18 @@ def _flipped(x: torch.Tensor, code: int) -> torch.Tensor:
 
 
 def _tiled_labels(model, vol: np.ndarray, spacing, plan: dict, input_format: str, hu_level: float, hu_width: float, context: str,
-                  batch_size: int, device, labels: Optional[torch.Tensor] = None):
+                  batch_size: int, device, labels: Optional[torch.Tensor] = None, want_conf: bool = False, inv_temperature: float = 1.0):
     """uint8 [Z, H, W] on the device: the tiles of every slice in the order (z, iy, ix), ``batch_size`` at a time through the
     preprocessing kernel and the model (every mirror variant a device-side flip of the same preprocessed batch); their logits wait
     in a buffer of a few slices, and each time whole slices are complete one ``ops.seg_blend_predict`` launch labels them.
     ``labels`` (uint8 [Z, H, W] on the device, 255 = ignore): returns (label volume, counts int64 [3, C]), the blend launches' own
-    counts added up."""
+    counts added up.  ``want_conf`` (without ``labels``): returns (label volume, fp32 [Z, H, W] confidence of the blend kernel, the
+    max-softmax of the blended logits); ``inv_temperature`` != 1 scales the tile logits by it before each blend launch -- the blend is
+    linear in them, so this is the blended logit over T -- and the labels are then that launch's (they can differ from an unscaled run's
+    at exact fp32 near-ties).  With 1 nothing is scaled."""
     from dinox import preprocess as P
+    if want_conf and labels is not None:
+        raise ValueError("_tiled_labels: want_conf goes without labels")
     Z, H, W = vol.shape
     S, g = model.img_size, model.img_size // model.patch
     C = model.head.num_classes
@@ -109,6 +114,7 @@ def _tiled_labels(model, vol: np.ndarray, spacing, plan: dict, input_format: str
     out = torch.empty((Z, H, W), dtype=torch.uint8, device=device)
     done, at = 0, 0                                 # slices labelled so far (= the slice in zbuf[0]); rows of `jobs` consumed
     counts = None if labels is None else torch.zeros((3, C), dtype=torch.int64, device=device)
+    conf = None
     for tb, a, b in zip(tables, bounds[:-1], bounds[1:]):
         n = b - a
         x = P.device_preprocess(src, jobs[at:at + len(tb)], n, S, input_format, hu_level, hu_width, out=xbuf[:n], src_dtype=src_dtype,
@@ -126,7 +132,12 @@ def _tiled_labels(model, vol: np.ndarray, spacing, plan: dict, input_format: str
         full = b // n_t - done                      # whole slices now complete
         if full > 0:
             zfull = zbuf[:full].view(full, F, ny, nx, g * g, C)
-            if labels is None:
+            if want_conf:
+                if conf is None:
+                    conf = torch.empty((Z, H, W), dtype=torch.float32, device=device)
+                out[done:done + full], conf[done:done + full] = ops.seg_blend_predict(
+                    zfull if inv_temperature == 1.0 else zfull * inv_temperature, ys, xs, flips, plan["win"], H, W, t, want_conf=True)
+            elif labels is None:
                 out[done:done + full] = ops.seg_blend_predict(zfull, ys, xs, flips, plan["win"], H, W, t)
             else:
                 out[done:done + full], cnt = ops.seg_blend_predict(zfull, ys, xs, flips, plan["win"], H, W, t, labels=labels[done:done + full])
@@ -135,6 +146,8 @@ def _tiled_labels(model, vol: np.ndarray, spacing, plan: dict, input_format: str
                 zbuf[0, :, :b % n_t] = zbuf[full, :, :b % n_t].clone()
             done += full
     assert done == Z
+    if want_conf:
+        return out, conf
     return out if labels is None else (out, counts)
 
 
@@ -177,7 +190,7 @@ def segment_volume_tiled(model, volume: np.ndarray, spacing: Tuple[float, float,
                          sigma_scale: float = 0.125, input_format: Literal["hu_float", "hu16_png", "windowed_float"] = "hu_float",
                          hu_level: float = 40.0, hu_width: float = 400.0, context: Literal["neighbours", "replicate"] = "neighbours",
                          batch_size: int = 64, device: Union[str, torch.device, None] = None, keep_largest: bool = False,
-                         min_volume_mm3: float = 0.0, connectivity: int = 26) -> np.ndarray:
+                         min_volume_mm3: float = 0.0, connectivity: int = 26, return_confidence: bool = False):
     """Label volume of a ``(Z, H, W)`` series on ITS OWN grid: uint8 (Z, H, W).  Every slice is cut into tiles of side t (``tile``; None:
     min(model.img_size, H, W); clamped to min(H, W)) at ``tile_starts`` along both axes, each tile's 2.5D stack (``context``) goes
     through the preprocessing kernel -- which resizes a tile of side t != S to S x S as it does any image -- and the model,
@@ -187,19 +200,28 @@ def segment_volume_tiled(model, volume: np.ndarray, spacing: Tuple[float, float,
     ambient ``torch.autocast``.
 
     ``keep_largest`` / ``min_volume_mm3`` > 0 clean the volume with ``postprocess_volume``; nothing was resized, so the voxel is the
-    scanner's: (s_z, s_y, s_x) = (spacing[2], spacing[1], spacing[0])."""
-    from dinox.segment import min_component_vox, postprocess_volume
+    scanner's: (s_z, s_y, s_x) = (spacing[2], spacing[1], spacing[0]).
+
+    ``return_confidence``: returns (labels, fp32 (Z, H, W) max-softmax of the blended logits at ``model.temperature``).  With a stored
+    temperature T != 1 the tile logits are divided by T before the blend launch and the labels are that launch's: they can differ from a
+    run without the flag at exact fp32 near-ties.  With T = 1 the labels are the same bits."""
+    from dinox.segment import _temperature, min_component_vox, postprocess_volume
     min_component_vox(min_volume_mm3)
     if connectivity not in (6, 18, 26):
         raise ValueError(f"segment_volume_tiled: connectivity must be 6, 18 or 26, got {connectivity!r}")
     vol = np.asarray(volume)
     device = _check_common(model, vol, input_format, context, batch_size, device)
     plan = tile_plan(model, vol.shape[1], vol.shape[2], tile, overlap, window, tta_flips, sigma_scale)
-    out = _tiled_labels(model, vol, spacing, plan, input_format, hu_level, hu_width, context, int(batch_size), device)
+    conf = None
+    if return_confidence:
+        out, conf = _tiled_labels(model, vol, spacing, plan, input_format, hu_level, hu_width, context, int(batch_size), device, want_conf=True,
+                                  inv_temperature=1.0 / _temperature(model))
+    else:
+        out = _tiled_labels(model, vol, spacing, plan, input_format, hu_level, hu_width, context, int(batch_size), device)
     if keep_largest or min_volume_mm3 > 0:
         out = postprocess_volume(out, model.head.num_classes, (spacing[2], spacing[1], spacing[0]), keep_largest=keep_largest,
                                  min_volume_mm3=min_volume_mm3, connectivity=connectivity)
-    return out.cpu().numpy()
+    return (out.cpu().numpy(), conf.cpu().numpy()) if return_confidence else out.cpu().numpy()
 
 
 def segment_tiled(model, image: np.ndarray, pixel_spacing: Tuple[float, float] = (1.0, 1.0), slice_thickness: float = 1.0, *,

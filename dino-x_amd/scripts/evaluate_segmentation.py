@@ -95,7 +95,37 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--min-component-mm2", type=float, default=0.0, metavar="A",
                     help="score the map with the components of the classes >= 1 under A mm^2 removed; with --lesion-metrics also the "
                          "smallest ground-truth component that counts as a lesion")
+    ap.add_argument("--calibration", action="store_true",
+                    help="add a \"calibration\" object: reliability bins, ECE, MCE, NLL, Brier score and mean entropy of the upsampled softmax "
+                         "(csrc/segcalib.hip).  It describes the RAW arg-max: --keep-largest and --min-component-mm2 do not affect it")
+    ap.add_argument("--calibration-bins", type=int, default=15, metavar="NB", help="equal-width confidence bins of the reliability diagram")
+    ap.add_argument("--temperature", type=float, default=None, metavar="T",
+                    help="softmax temperature of the calibration scores (default: the one stored with the segmenter, else 1)")
+    ap.add_argument("--fit-temperature", action="store_true",
+                    help="fit the temperature that minimises the NLL of this set (its patch logits and labels are kept on the device) and "
+                         "report the calibration before and after; implies --calibration")
+    ap.add_argument("--write-temperature", action="store_true",
+                    help="with --fit-temperature: store the fitted temperature in the segmenter's finetune_config.json")
+    ap.add_argument("--calibration-cache-gib", type=float, default=4.0, metavar="G",
+                    help="--fit-temperature is refused when the cached logits and labels would exceed this many GiB of device memory")
     return ap
+
+
+def check_args(ap: argparse.ArgumentParser, args: argparse.Namespace) -> None:
+    """What can be refused from the arguments alone (ap.error: exit status 2)."""
+    if args.write_temperature and not args.fit_temperature:
+        ap.error("--write-temperature needs --fit-temperature")
+    if not 1 <= args.calibration_bins <= ops.SEG_CALIB_MAX_BINS:
+        ap.error(f"--calibration-bins: an integer in [1, {ops.SEG_CALIB_MAX_BINS}], got {args.calibration_bins}")
+    if args.temperature is not None and not 0.0 < args.temperature < float("inf"):
+        ap.error(f"--temperature: a finite value > 0, got {args.temperature}")
+    if not 0.0 < args.calibration_cache_gib < float("inf"):
+        ap.error(f"--calibration-cache-gib: a finite value > 0, got {args.calibration_cache_gib}")
+
+
+def calibration_object(rep: dict, temperature: float, bins: int) -> dict:
+    """The "calibration" object of the report: calibration_report's fields, the temperature used and the bin count."""
+    return dict(rep, temperature=temperature, num_bins=bins)
 
 
 def _floats(t: torch.Tensor):
@@ -121,10 +151,14 @@ def lesion_report(res: dict, connectivity: int, overlap, min_area_mm2: float) ->
 
 
 @torch.no_grad()
-def evaluate(model: SG.SegModel, loader, device, amp: bool, tolerances, num_classes: int, *, lesion=None, post=None) -> dict:
+def evaluate(model: SG.SegModel, loader, device, amp: bool, tolerances, num_classes: int, *, lesion=None, post=None, calibration=None,
+             cache=None) -> dict:
     """One pass: the [3, C] overlap counts of the whole set and the per-class surface means.  -> the report dict (no file is written).
     ``post``: None or {"keep_largest", "min_area_mm2", "connectivity"} -- every score is then taken on the cleaned map (ops.cc_filter; the
-    area on the evaluated grid's spacing).  ``lesion``: None or {"connectivity", "overlap": (num, den), "min_area_mm2"} -- adds "lesion"."""
+    area on the evaluated grid's spacing).  ``lesion``: None or {"connectivity", "overlap": (num, den), "min_area_mm2"} -- adds "lesion".
+    ``calibration``: None or {"bins", "temperature"} -- adds "calibration", from one ops.seg_calib launch per batch beside the prediction
+    (always of the raw arg-max, whatever ``post`` says).  ``cache``: a list that receives every batch's (patch logits, labels)."""
+    cal = SG.CalibrationAccumulator(calibration["bins"]) if calibration else None
     acc = SG.SurfaceAccumulator(num_classes, len(tolerances))
     les = SG.LesionAccumulator(num_classes) if lesion else None
     counts, n = None, 0
@@ -133,6 +167,11 @@ def evaluate(model: SG.SegModel, loader, device, amp: bool, tolerances, num_clas
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
             logits = model(x, spacing=sp.to(device) if model.scale_aware else None)
         pred, cnt = ops.seg_predict(logits, model.patch, m)
+        if cal:
+            cal.update(ops.seg_calib(logits, model.patch, m, inv_temperature=1.0 / calibration["temperature"], bins=calibration["bins"],
+                                     want_pred=False))
+        if cache is not None:
+            cache.append((logits.float(), m))
         if post:
             pred, cnt = ops.cc_filter(pred, num_classes, min_px=SG.min_component_px(post["min_area_mm2"], grid_sp, pred.shape[0]),
                                       keep_largest=post["keep_largest"], connectivity=post["connectivity"], targets=m)
@@ -156,6 +195,8 @@ def evaluate(model: SG.SegModel, loader, device, amp: bool, tolerances, num_clas
               "spacing": SPACING_CONVENTION, "pixel_accuracy": SG.pixel_accuracy(counts), "per_class": per_class, "mean": mean}
     if post:
         report["postprocess"] = dict(post)
+    if cal:
+        report["calibration"] = calibration_object(cal.result(), calibration["temperature"], calibration["bins"])
     if lesion:
         report["lesion"] = lesion_report(les.result(), lesion["connectivity"], lesion["overlap"], lesion["min_area_mm2"])
     return report
@@ -163,6 +204,7 @@ def evaluate(model: SG.SegModel, loader, device, amp: bool, tolerances, num_clas
 
 def run(args: argparse.Namespace) -> dict:
     ap = build_parser()
+    check_args(ap, args)
     device = torch.device(args.device)
     if device.type != "cuda":
         raise SystemExit(f"this engine computes on MI355X only: --device {args.device} requested (no CPU compute path)")
@@ -206,7 +248,28 @@ def run(args: argparse.Namespace) -> dict:
                         augment=False, data_root=args.data_root)
         workers = args.num_workers
     loader = torch.utils.data.DataLoader(ds, batch_size=args.batch_size, shuffle=False, num_workers=workers)
-    report = evaluate(model, loader, device, not args.no_amp, tolerances, C, lesion=lesion, post=post)
+    calibration = cache = None
+    if args.calibration or args.fit_temperature:
+        calibration = {"bins": args.calibration_bins, "temperature": float(args.temperature if args.temperature is not None else model.temperature)}
+    if args.fit_temperature:
+        need = len(ds) * ((img // model.patch) ** 2 * C * 4 + img * img)
+        if need > args.calibration_cache_gib * 2 ** 30:
+            raise SystemExit(f"--fit-temperature: the patch logits and labels of {len(ds)} images take {need / 2 ** 30:.2f} GiB of device memory, "
+                             f"above --calibration-cache-gib {args.calibration_cache_gib:g}; raise it or fit on a subset")
+        cache = []
+    report = evaluate(model, loader, device, not args.no_amp, tolerances, C, lesion=lesion, post=post, calibration=calibration, cache=cache)
+    if args.fit_temperature:
+        fit = SG.fit_temperature(cache, model.patch)
+        after = SG.CalibrationAccumulator(args.calibration_bins)
+        for z, m in cache:
+            after.update(ops.seg_calib(z, model.patch, m, inv_temperature=1.0 / fit["temperature"], bins=args.calibration_bins, want_pred=False))
+        report["temperature_fit"] = fit
+        report["calibration_fitted"] = calibration_object(after.result(), fit["temperature"], args.calibration_bins)
+        log.info("fitted temperature %.4f: NLL %s -> %s, ECE %s -> %s", fit["temperature"], fit["nll_before"], fit["nll_after"],
+                 report["calibration"]["ece"], report["calibration_fitted"]["ece"])
+        if args.write_temperature:
+            cfg["temperature"] = fit["temperature"]
+            cfg_file.write_text(json.dumps(cfg, indent=2))
     report["segmenter"], report["backbone"] = str(args.segmenter), str(args.backbone)
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     Path(args.out).write_text(json.dumps(report, indent=2))

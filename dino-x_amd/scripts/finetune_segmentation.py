@@ -413,18 +413,48 @@ def build_patch_parser() -> argparse.ArgumentParser:
     return ap
 
 
+def build_calibration_parser() -> argparse.ArgumentParser:
+    """The option of temperature fitting.  A parser of its own, as the boundary options are; parse_cli reads it out of the command line."""
+    ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    ap.add_argument("--fit-temperature", action="store_true",
+                    help="after training, reload the best checkpoint, fit the softmax temperature that minimises the NLL of the validation set "
+                         "(dinox.segment.fit_temperature) and store it as \"temperature\" in finetune_config.json")
+    return ap
+
+
 def parse_cli(argv=None) -> argparse.Namespace:
-    """The boundary options (build_boundary_parser) and the patch options (build_patch_parser) first, everything else through
-    build_parser; one namespace."""
+    """The boundary options (build_boundary_parser), the patch options (build_patch_parser) and the calibration option
+    (build_calibration_parser) first, everything else through build_parser; one namespace."""
     bd, rest = build_boundary_parser().parse_known_args(argv)
     pt, rest = build_patch_parser().parse_known_args(rest)
+    cb, rest = build_calibration_parser().parse_known_args(rest)
     ap = build_parser()
     ap.epilog = ("Boundary loss: " + " ".join(build_boundary_parser().format_help().split()[1:]) + "  Patch training: "
-                 + " ".join(build_patch_parser().format_help().split()[1:]))
+                 + " ".join(build_patch_parser().format_help().split()[1:]) + "  Calibration: "
+                 + " ".join(build_calibration_parser().format_help().split()[1:]))
     args = ap.parse_args(rest)
-    for k, v in (*vars(bd).items(), *vars(pt).items()):
+    for k, v in (*vars(bd).items(), *vars(pt).items(), *vars(cb).items()):
         setattr(args, k, v)
     return args
+
+
+@torch.no_grad()
+def fit_and_store_temperature(backbone_path, output_dir: Path, loader, device, scale_aware: bool, amp: bool) -> dict:
+    """Reloads the best checkpoint from ``output_dir``, caches the validation set's patch logits and labels on the device, fits the
+    temperature and adds "temperature" to the written finetune_config.json (every other byte of it stays).  -> fit_temperature's dict."""
+    model = SG.load_segmenter(backbone_path, output_dir, device)
+    cache = []
+    for x, sp, m in _batches(loader, device, scale_aware):
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+            cache.append((model(x, spacing=sp).float(), m))
+    fit = SG.fit_temperature(cache, model.patch)
+    cfg_file = Path(output_dir) / SG.CONFIG_FILE
+    cfg = json.loads(cfg_file.read_text())
+    cfg["temperature"] = fit["temperature"]
+    cfg_file.write_text(json.dumps(cfg, indent=2))
+    log.info("temperature %.4f (%d passes%s): validation NLL %s -> %s", fit["temperature"], fit["iterations"],
+             "" if fit["converged"] else ", not converged", fit["nll_before"], fit["nll_after"])
+    return fit
 
 
 def warn_mm_without_spacing(rows: List[MaskedRow], units: str) -> bool:
@@ -468,6 +498,9 @@ def run(args: argparse.Namespace) -> dict:
         ap.error(f"--patch-val {patch['patch_val']!r}: center or tiled")
     if patch["patch_val"] == "tiled" and not patch["patch_train"]:
         ap.error("--patch-val tiled belongs to --patch-train")
+    fit_t = bool(getattr(args, "fit_temperature", False))
+    if fit_t and patch["patch_val"] == "tiled":
+        ap.error("--fit-temperature fits on the S x S validation crops: not with --patch-val tiled")
     if args.ignore_index != IGNORE:
         ap.error(f"--ignore-index {args.ignore_index}: only {IGNORE} is supported (the kernels compare labels with that value)")
     if not 2 <= args.num_classes <= ops.SEG_MAX_CLASSES:
@@ -588,6 +621,9 @@ def run(args: argparse.Namespace) -> dict:
                 log.info("no improvement for %d epochs: stopping at epoch %d", stale, epoch)
                 break
     log.info("done in %.1f s: best epoch %d, val loss %.4f", time.time() - t0, cfg.best_epoch, cfg.best_val_loss)
+    if fit_t and best_pred is not None:             # (no checkpoint was written if no epoch ever improved, e.g. a NaN loss)
+        fit = fit_and_store_temperature(args.backbone, Path(args.output), val_loader, device, scale_aware, amp)
+        return {"config": cfg, "val_pred": best_pred, "val_dataset": val_ds, "temperature_fit": fit}
     return {"config": cfg, "val_pred": best_pred, "val_dataset": val_ds}
 
 

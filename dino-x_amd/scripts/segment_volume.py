@@ -86,6 +86,14 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--blend-window", choices=("gaussian", "constant"), default=argparse.SUPPRESS,
                     help="weights of a tile's pixels in the blend (needs --tiled; default: gaussian)")
     ap.add_argument("--tta-flips", action="store_true", help="average the four mirror variants of every tile (needs --tiled)")
+    ap.add_argument("--confidence-out", type=Path, default=None, metavar="NPY",
+                    help="also write the fp32 confidence volume (the winning class's softmax probability at the segmenter's stored "
+                         "temperature), on the grid of --out.  With --tiled it is the blend kernel's max-softmax; a stored temperature "
+                         "T != 1 then divides the tile logits by T before the blend, and the labels are that launch's: they may differ "
+                         "from a run without this flag at exact fp32 near-ties (with T = 1 nothing changes)")
+    ap.add_argument("--entropy-out", type=Path, default=None, metavar="NPY",
+                    help="also write the fp32 volume of the softmax entropy / log C at the stored temperature (not with --tiled: the blend "
+                         "kernel has no entropy output)")
     return ap
 
 
@@ -97,6 +105,8 @@ def check_args(ap: argparse.ArgumentParser, args: argparse.Namespace) -> None:
     given = [f"--{k.replace('_', '-')}" for k in TILED_DEFAULTS if hasattr(args, k)] + (["--tta-flips"] if args.tta_flips else [])
     if given and not args.tiled:
         ap.error(f"{', '.join(given)}: only with --tiled")
+    if args.entropy_out is not None and args.tiled:
+        ap.error("--entropy-out: not with --tiled (the blend kernel has no entropy output)")
     for k, v in TILED_DEFAULTS.items():
         if not hasattr(args, k):
             setattr(args, k, v)
@@ -209,6 +219,7 @@ def run(args: argparse.Namespace):
     acc = SG.CaseAccumulator(C) if args.labels else None
     surf = SG.SurfaceAccumulator(C, len(args.tolerance_mm)) if args.tolerance_mm else None
     sx, sy, sz = args.spacing
+    want_conf, want_ent = args.confidence_out is not None, args.entropy_out is not None
     declined, grids = {}, []                        # --tiled: metric -> {case: the kernel's message}; the tile grid of every case
     for i, vpath in enumerate(args.volume):
         vol = np.load(vpath)
@@ -222,12 +233,18 @@ def run(args: argparse.Namespace):
                                                tta_flips=args.tta_flips, input_format=args.input_format, hu_level=args.window_level,
                                                hu_width=args.window_width, context=args.context, batch_size=args.batch_size, device=device,
                                                keep_largest=args.keep_largest, min_volume_mm3=args.min_component_mm3,
-                                               connectivity=args.connectivity)
+                                               connectivity=args.connectivity, return_confidence=want_conf)
             else:
                 pred = SG.segment_volume(model, vol, (sx, sy, sz), input_format=args.input_format, hu_level=args.window_level,
                                          hu_width=args.window_width, context=args.context, batch_size=args.batch_size, device=device,
                                          keep_largest=args.keep_largest, min_volume_mm3=args.min_component_mm3,
-                                         connectivity=args.connectivity)
+                                         connectivity=args.connectivity, return_confidence=want_conf, return_entropy=want_ent)
+        if want_conf or want_ent:                   # (labels, conf[, entropy])
+            pred, maps = pred[0], dict(zip([p for p, w in ((args.confidence_out, want_conf), (args.entropy_out, want_ent)) if w], pred[1:]))
+            for mpath, arr in maps.items():
+                mout = mpath if len(args.volume) == 1 else mpath.with_name(f"{mpath.stem}_{i}{mpath.suffix}")
+                Path(mout).parent.mkdir(parents=True, exist_ok=True)
+                np.save(mout, arr)
         out = args.out if len(args.volume) == 1 else args.out.with_name(f"{args.out.stem}_{i}{args.out.suffix}")
         Path(out).parent.mkdir(parents=True, exist_ok=True)
         np.save(out, pred)

@@ -846,6 +846,38 @@ int dinox_seg_loss_bwd(const float* z, const uint8_t* y, const float* stats, con
 int dinox_seg_predict(const float* z, const uint8_t* y, uint8_t* pred, int64_t* counts, int64_t B, int g, int u, int C, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Calibration of a dense segmenter (kernel: csrc/segcalib.hip; dinox.ops.seg_calib, dinox.segment.calibration_report / fit_temperature).
+ * z, y, the geometry, the limits and the interpolated logits l_p[c] are those of the section above (same weights, same order of
+ * operations).  s = inv_temperature, finite and > 0.  Per pixel p, one launch over the patch logits, nothing of full resolution but the
+ * requested maps:
+ *   pred    = argmax_c l_p[c], lowest index on an exact tie, taken on the UNSCALED logits: dinox_seg_predict's map bit for bit, whatever s;
+ *   t_c     = s l_p[c] (one fp32 multiply);  p = softmax(t) (max subtracted);  lse = log sum_c exp(t_c);
+ *   conf    = p[pred];
+ *   entropy = (lse - sum_c p_c t_c) fl(1 / log C), clamped to [0, 1] by comparisons (a NaN stays NaN).  A class of probability 0 adds 0 to
+ *             this and every other p-weighted sum (also where its logit is -inf).
+ * pred[B][S][S] uint8, conf and entropy [B][S][S] fp32: each may be NULL; written for every pixel, ignored ones included.
+ * y != NULL (then hist, sums and ws are non-NULL, and NULL with y == NULL: all four or none): statistics over the VALID pixels, y_p != 255
+ * and y_p < C.
+ *   hist[3 NB + 3] int64, zeroed on the stream first, 1 <= NB <= 64.  A valid pixel with finite conf falls into bin
+ *     k = min((int)(conf * (float)NB), NB - 1) (one fp32 multiply; the index is clamped by comparisons before it addresses anything) and
+ *     hist[3 k + (0, 1, 2)] += (1, [pred = y_p], q) with q = (int64)rintf(conf * 16777216.f), the confidence in 2^-24 fixed point.
+ *     hist[3 NB + (0, 1, 2)] = Nv, the number of labels >= C other than 255, the number of valid pixels whose conf is not finite (these
+ *     enter no bin and no sum).  All integers, integer atomics: exact and independent of the order.
+ *   sums[5] fp32 over the valid pixels with finite conf:
+ *     NLL = sum (lse - t_y);  Brier = sum sum_c (p_c - [y_p = c])^2;  G = sum (mu - l_y) with mu = sum_c p_c l_c (= d NLL / d s);
+ *     H = sum sum_c p_c (l_c - mu)^2 (= d^2 NLL / d s^2 >= 0);  sum entropy.
+ *     Fixed order (per lane in row order, wave butterfly, partial sums in ws by plain stores, a second launch adds them ascending): equal
+ *     inputs give equal bits.  No floating-point atomic.
+ * Argument checks on the host with a message before any launch (DINOX_EINVAL: NB outside [1, 64], s not finite or <= 0, pointers that
+ * break the all-or-none rule, nothing to compute); no allocation, no synchronisation.
+ * dinox_seg_calib_ws_bytes: bytes of workspace (a pure function of the sizes; 0 for sizes the call refuses; contents need not be
+ *   initialised; 4-byte aligned).
+ * ------------------------------------------------------------------------------------------ */
+int64_t dinox_seg_calib_ws_bytes(int64_t B, int g, int u, int C, int NB);
+int dinox_seg_calib(const float* z, const uint8_t* y, float inv_temperature, uint8_t* pred, float* conf, float* entropy, int64_t* hist,
+                    float* sums, void* ws, int64_t B, int g, int u, int C, int NB, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Sliding-window prediction at native resolution (kernel: csrc/segblend.hip; dinox.ops.seg_blend_predict, dinox.tiled).  B images of one
  * size H x W were cut into t x t tiles on a separable grid of origins ys[ny] x xs[nx]; every tile went through the model F times (mirror
  * variants) and left g x g patch logit rows.  Each output pixel gathers the tiles that cover it: no [C][H][W] map is written, nothing is
