@@ -1,5 +1,5 @@
-// seg_common.h -- what segloss.hip, segcalib.hip and segblend.hip share: the register width that holds the C logits of a pixel, and (the
-// first two) the walk over the pixels of a cell with its interpolation, the softmax of a pixel's logits and the size limits.
+// seg_common.h -- what segloss.hip, segcalib.hip, segrefine.hip and segblend.hip share: the register width that holds the C logits of a
+// pixel, and (the first three) the walk over the pixels of a cell with its interpolation, the softmax of a pixel's logits and the size limits.
 #pragma once
 #include <type_traits>
 
@@ -88,6 +88,35 @@ __device__ __forceinline__ void seg_cell_pixels(const float* __restrict__ z, con
     for (int c = 0; c < CP; ++c) l[c] = wy0 * zx0[c] + wy1 * zx1[c];
     f(ok, lab, wy0, wy1, l, Y, X);
   }
+}
+
+// l[c] of the one pixel (X, Y) of image b: the taps, the weights and the order of operations of seg_cell_pixels, for a kernel whose threads
+// do not walk cells (csrc/segrefine.hip).  Pixel x lies in the cell of index max(x - u / 2, 0) / u (seg_lo).  The same expressions, not
+// necessarily the same bits: the compiler fuses multiply-adds per kernel (and per class), so a value may differ in the last place.
+template <int CP>
+__device__ __forceinline__ void seg_pixel_logits(const float* __restrict__ z, int64_t b, int g, int u, int C, float inv2u, int X, int Y, float (&l)[CP]) {
+  const int h = u / 2;
+  const int cx = X > h ? (X - h) / u : 0, cy = Y > h ? (Y - h) / u : 0;
+  const float wx1 = seg_w1(X, cx, g, u, inv2u), wx0 = 1.f - wx1;
+  const float wy1 = seg_w1(Y, cy, g, u, inv2u), wy0 = 1.f - wy1;
+  const int cx1 = cx + 1 < g ? cx + 1 : cx, cy1 = cy + 1 < g ? cy + 1 : cy;
+  const float* z00 = z + ((b * g + cy) * g + cx) * C;
+  const float* z01 = z + ((b * g + cy) * g + cx1) * C;
+  const float* z10 = z + ((b * g + cy1) * g + cx) * C;
+  const float* z11 = z + ((b * g + cy1) * g + cx1) * C;
+#pragma unroll
+  for (int c = 0; c < CP; ++c) {
+    const bool in = c < C;
+    const float zx0 = in ? wx0 * z00[c] + wx1 * z01[c] : 0.f;
+    const float zx1 = in ? wx0 * z10[c] + wx1 * z11[c] : 0.f;
+    l[c] = wy0 * zx0 + wy1 * zx1;
+  }
+}
+
+// s l as one rounded multiply: never contracted into a neighbouring addition, so every place that forms it gets the same bits.
+__device__ __forceinline__ float seg_scaled(float s, float l) {
+#pragma clang fp contract(off)
+  return s * l;
 }
 
 // l -> p = softmax(l) in place over c < C; returns max and the sum of exp(l - max).

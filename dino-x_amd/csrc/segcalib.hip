@@ -24,11 +24,7 @@ constexpr int SEG_CALIB_MAX_BINS = 64;
 constexpr int SEG_CALIB_SUMS = 5;                 // NLL, Brier, G, H, entropy
 constexpr int SEG_CALIB_SLOTS = 3 * SEG_CALIB_MAX_BINS + 3;
 
-// s l as one rounded multiply: never contracted into a neighbouring addition, so every place that forms it gets the same bits.
-__device__ __forceinline__ float seg_scaled(float s, float l) {
-#pragma clang fp contract(off)
-  return s * l;
-}
+// seg_scaled (s l as one rounded multiply): seg_common.h -- csrc/segrefine.hip forms the same bits
 
 // cnt[wave][3 k + (0, 1, 2)] = bin k's (count, correct, Q); cnt[wave][3 * 64 + (0, 1, 2)] = (valid pixels, labels >= C other than 255, valid
 // pixels whose confidence is not finite).  wsf[part][5]: the five sums of the part's cells.  y == nullptr: hist and wsf are nullptr too and

@@ -150,6 +150,8 @@ SIGNATURES = {
     "dinox_seg_predict": (i32, [vp, vp, vp, vp, i64, i32, i32, i32, vp]),
     "dinox_seg_calib_ws_bytes": (i64, [i64, i32, i32, i32, i32]),
     "dinox_seg_calib": (i32, [vp, vp, f32, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp]),
+    "dinox_seg_refine_ws_bytes": (i64, [i64, i32, i32, i32]),
+    "dinox_seg_refine": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp, f32, f32, f32, f32, vp]),
     "dinox_seg_blend_predict": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "dinox_seg_patch_sample": (i32, [vp, vp, vp, vp, vp, vp, i64, i32, vp, vp, f32, vp]),
     "dinox_signed_distance": (i32, [vp, vp, vp, vp, vp, i64, i32, i32, i32, vp]),

@@ -3194,6 +3194,89 @@ def seg_calib(z: Tensor, u: int, labels: Optional[Tensor] = None, *, inv_tempera
 
 
 # ------------------------------------------------------------------------------------------
+# edge-aware refinement of the upsampled softmax: mean-field iterations of a local CRF on a guide image (csrc/segrefine.hip)
+# ------------------------------------------------------------------------------------------
+SEG_REFINE_MAX_ITERS = 32
+SEG_REFINE_MAX_RADIUS = 3
+SEG_REFINE_MAX_DILATION = 8
+
+
+def seg_refine_table(radius: int, dilation: int, sigma_xy: float) -> np.ndarray:
+    """The spatial weights g_(dy,dx) = exp(-(dy^2 + dx^2) d^2 / (2 sigma_xy^2)) of the (2r+1)^2 window, row-major, computed in float64
+    and rounded to fp32 (the centre entry is never read)."""
+    o = np.arange(-radius, radius + 1, dtype=np.float64)
+    return np.exp(-(o[:, None] ** 2 + o[None, :] ** 2) * float(dilation) ** 2 / (2.0 * float(sigma_xy) ** 2)).astype(np.float32).reshape(-1)
+
+
+def _seg_refine_number(what: str, v, lo_open: bool) -> float:
+    """v as a float that is finite in fp32 and > 0 (lo_open) or >= 0."""
+    ok = isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v) and math.isfinite(float(np.float32(v)))
+    if not ok or (float(np.float32(v)) <= 0 if lo_open else v < 0):
+        raise ValueError(f"seg_refine: {what} must be finite and {'> 0 (in fp32)' if lo_open else '>= 0'}, got {v!r}")
+    return float(v)
+
+
+def seg_refine(z: Tensor, guide: Tensor, u: int, labels: Optional[Tensor] = None, *, iters: int = 5, radius: int = 2, dilation: int = 2,
+               sigma_xy: float = 3.0, sigma_i: float = 0.5, mix: float = 0.8, weight: float = 4.0, inv_temperature: float = 1.0,
+               want_conf: bool = False):
+    """Edge-aware refinement of the label map of the patch logits z [B, g^2, C] at S = g u (include/dinox.h has the definition): ``iters``
+    mean-field iterations of a local CRF whose unary term is ``inv_temperature`` times the upsampled logits and whose messages come from
+    the (2 radius + 1)^2 window at ``dilation``, weighted by exp(-dist^2 / (2 sigma_xy^2)) in pixels and by (1 - mix) + mix
+    exp(-(I_p - I_j)^2 / (2 sigma_i^2)) on the fp32 ``guide`` [B, S, S]; ``weight`` scales the message.  Returns (pred uint8 [B, S, S],
+    conf fp32 [B, S, S] or None, counts int64 [3, C] or None): the arg-max after the last iteration, its probability (``want_conf``) and,
+    with ``labels`` (uint8 [B, S, S], 255 = ignore), ``seg_predict``'s counts of the refined map.  ``iters = 0`` gives ``seg_predict``'s
+    map and counts and ``seg_calib``'s confidence bit for bit.  The workspace (two fp32 planes [B, C, S, S]) lives for the call only."""
+    B, g, C = _seg_geometry("seg_refine", z, u)
+    S = g * u
+    if labels is not None and _seg_labels("seg_refine", labels, B, g, z) != u:
+        raise ValueError(f"seg_refine: labels {tuple(labels.shape)} do not have side g u = {S}")
+    if not isinstance(guide, Tensor) or guide.dtype != torch.float32 or tuple(guide.shape) != (B, S, S):
+        raise ValueError(f"seg_refine: the guide must be fp32 [{B}, {S}, {S}], got {_describe(guide)}")
+    if guide.device != z.device:
+        raise ValueError(f"seg_refine: logits on {z.device}, guide on {guide.device}")
+    for name, v, top in (("iters", iters, SEG_REFINE_MAX_ITERS), ("radius", radius, SEG_REFINE_MAX_RADIUS), ("dilation", dilation, SEG_REFINE_MAX_DILATION)):
+        lo = 0 if name == "iters" else 1
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= top:
+            raise ValueError(f"seg_refine: {name} must be an integer in [{lo}, {top}], got {v!r}")
+    if radius * dilation >= S:
+        raise ValueError(f"seg_refine: radius * dilation = {radius * dilation} reaches across the image side {S}: no neighbour is left")
+    if 2 * dilation > S:
+        raise ValueError(f"seg_refine: dilation = {dilation} leaves the pixels in the middle of an image of side {S} no neighbour "
+                         f"(2 * dilation <= side)")
+    sigma_xy = _seg_refine_number("sigma_xy", sigma_xy, True)
+    sigma_i = _seg_refine_number("sigma_i", sigma_i, True)
+    weight = _seg_refine_number("weight", weight, False)
+    s = _seg_refine_number("inv_temperature", inv_temperature, True)
+    if isinstance(mix, bool) or not isinstance(mix, (int, float)) or not 0.0 <= mix <= 1.0:
+        raise ValueError(f"seg_refine: mix must lie in [0, 1], got {mix!r}")
+    gtab = seg_refine_table(radius, dilation, sigma_xy)
+    if not (gtab[2 * radius * (radius + 1) + 1] > 0):                         # the neighbour at (0, +1): the largest entry off the centre
+        raise ValueError(f"seg_refine: sigma_xy = {sigma_xy!r} is so small against dilation = {dilation} that every spatial weight is 0 in fp32")
+    inv2 = 1.0 / (2.0 * sigma_i * sigma_i)
+    if not inv2 <= float(np.finfo(np.float32).max):
+        raise ValueError(f"seg_refine: sigma_i = {sigma_i!r}: 1 / (2 sigma_i^2) is not finite in fp32")
+    _need_cuda(z, guide, labels)
+    z, guide = _c(z.float()), _c(guide)
+    dev = z.device
+    pred = torch.empty((B, S, S), dtype=torch.uint8, device=dev)
+    conf = torch.empty((B, S, S), dtype=torch.float32, device=dev) if want_conf else None
+    counts = None
+    if labels is not None:
+        labels = _c(labels)
+        counts = torch.empty(3 * C + 1, dtype=torch.int64, device=dev)
+    nbytes = int(lib.dinox_seg_refine_ws_bytes(B, g, u, C))
+    if nbytes <= 0:
+        raise ValueError(f"seg_refine: B = {B}, S = {S}, C = {C} is beyond the sizes the kernel takes")
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev) if iters > 0 else None
+    check(lib.dinox_seg_refine(_p(z), _p(guide), _p(labels), _p(pred), _p(conf), _p(counts), _p(ws), B, g, u, C, iters, radius, dilation,
+                               gtab.ctypes.data, inv2, float(mix), weight, s, _stream()), "dinox_seg_refine")
+    if counts is None:
+        return pred, conf, None
+    _seg_refuse_bad_labels("seg_refine", int(counts[3 * C]), C)
+    return pred, conf, counts[:3 * C].view(3, C)
+
+
+# ------------------------------------------------------------------------------------------
 # sliding-window prediction: the blend of overlapping tiles' patch logits (csrc/segblend.hip)
 # ------------------------------------------------------------------------------------------
 SEG_BLEND_MAX_FLIPS = 4

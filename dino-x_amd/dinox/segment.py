@@ -16,10 +16,14 @@ the chunk loop of ``zoo.encode.encode_volume``), ``postprocess_volume`` and ``op
 label the model's S x S grid; ``segment_tiled`` / ``segment_volume_tiled`` (dinox/tiled.py, csrc/segblend.hip) label the image's own
 grid by sliding window.  How far the probabilities can be trusted: ``ops.seg_calib`` (csrc/segcalib.hip) gives confidence and entropy
 maps (``segment(..., return_confidence=True)``), ``calibration_report`` / ``CalibrationAccumulator`` turn its integer histogram into
-ECE, NLL and Brier score, and ``fit_temperature`` fits ``SegModel.temperature``.
+ECE, NLL and Brier score, and ``fit_temperature`` fits ``SegModel.temperature``.  Contours that follow the image below the patch scale:
+``segment(..., refine=RefineConfig())`` / ``segment_volume(..., refine=...)`` run ``ops.seg_refine`` (csrc/segrefine.hip), a few mean-field
+iterations of a local CRF guided by the slice's own normalised plane, on the calibrated probabilities and before any clean-up.  The
+defaults of ``RefineConfig`` are untuned on real data.
 """
 from __future__ import annotations
 
+import dataclasses
 import json
 import math
 from pathlib import Path
@@ -35,6 +39,59 @@ from zoo.arch import Linear
 HEAD_FILE = "seg_head.pth"
 CONFIG_FILE = "finetune_config.json"
 BLOCKS_FILE = "unfrozen_blocks.pth"
+
+
+@dataclasses.dataclass(frozen=True)
+class RefineConfig:
+    """The seven parameters of ``ops.seg_refine`` (include/dinox.h has the definition): mean-field iterations, window radius and
+    dilation, the spatial sigma in pixels of the label grid, the appearance sigma in units of the guide (the backbone's normalised input),
+    the share of the appearance term in a pairwise weight and the weight of the message against the logits.  The defaults are those of
+    the op; none has been tuned on real data."""
+    iters: int = 5
+    radius: int = 2
+    dilation: int = 2
+    sigma_xy: float = 3.0
+    sigma_i: float = 0.5
+    mix: float = 0.8
+    weight: float = 4.0
+
+    def __post_init__(self) -> None:
+        for name, lo, hi in (("iters", 0, ops.SEG_REFINE_MAX_ITERS), ("radius", 1, ops.SEG_REFINE_MAX_RADIUS), ("dilation", 1, ops.SEG_REFINE_MAX_DILATION)):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+                raise ValueError(f"RefineConfig: {name} must be an integer in [{lo}, {hi}], got {v!r}")
+        for name, ok, say in (("sigma_xy", lambda v: 0 < v < math.inf, "finite and > 0"), ("sigma_i", lambda v: 0 < v < math.inf, "finite and > 0"),
+                              ("mix", lambda v: 0 <= v <= 1, "in [0, 1]"), ("weight", lambda v: 0 <= v < math.inf, "finite and >= 0")):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not ok(v):
+                raise ValueError(f"RefineConfig: {name} must be {say}, got {v!r}")
+            object.__setattr__(self, name, float(v))
+
+    def to_dict(self) -> dict:
+        return dataclasses.asdict(self)
+
+    @classmethod
+    def from_dict(cls, d: dict) -> "RefineConfig":
+        unknown = sorted(set(d) - {f.name for f in dataclasses.fields(cls)})
+        if unknown:
+            raise ValueError(f"RefineConfig: unknown field(s) {unknown}")
+        return cls(**d)
+
+
+def _check_refine(who: str, refine, return_entropy: bool) -> None:
+    if refine is None:
+        return
+    if not isinstance(refine, RefineConfig):
+        raise ValueError(f"{who}: refine must be None or a RefineConfig, got {type(refine).__name__}")
+    if return_entropy:
+        raise ValueError(f"{who}: return_entropy is not available with refine (the refinement kernel has no entropy output)")
+
+
+def _refine_chunk(model, logits: torch.Tensor, x: torch.Tensor, refine: RefineConfig, want_conf: bool):
+    """(pred, conf or None) of ``ops.seg_refine`` on a batch's patch logits; the guide is channel 1 of the normalised input x [n, 3, S, S]."""
+    pred, conf, _ = ops.seg_refine(logits, x[:, 1].float().contiguous(), model.patch, inv_temperature=1.0 / _temperature(model),
+                                   want_conf=want_conf, **refine.to_dict())
+    return pred, conf
 
 
 class SegHead(nn.Module):
@@ -61,6 +118,8 @@ class SegModel(nn.Module):
         self.backbone, self.head, self.frozen_backbone = backbone, head, frozen_backbone
         # softmax temperature of the confidence / entropy maps (fit_temperature); never applied in forward: the logits stay as they are
         self.temperature = 1.0
+        # the stored RefineConfig of finetune_config.json, or None; never applied implicitly: pass it as segment(..., refine=model.refine)
+        self.refine = None
 
     @property
     def img_size(self) -> int:
@@ -94,7 +153,7 @@ def segment(model: SegModel, image: np.ndarray, pixel_spacing: Tuple[float, floa
             input_format: Literal["hu_float", "hu16_png", "windowed_float"] = "hu_float", hu_level: float = 40.0, hu_width: float = 400.0,
             device: Union[str, torch.device, None] = None, preprocess: Literal["host", "device", "auto"] = "host",
             keep_largest: bool = False, min_area_mm2: float = 0.0, connectivity: int = 8, return_confidence: bool = False,
-            return_entropy: bool = False):
+            return_entropy: bool = False, refine: Optional[RefineConfig] = None):
     """Label map of one image: uint8 (S, S) with S = model.img_size, the arg-max of the upsampled patch logits.  Preprocessing, argument
     checking and the spacing convention are those of ``zoo.encode`` (its ``_batch``), so a stored head sees what ``encode()`` sees.
     Honours an ambient ``torch.autocast`` as ``encode`` does.
@@ -105,7 +164,14 @@ def segment(model: SegModel, image: np.ndarray, pixel_spacing: Tuple[float, floa
 
     ``return_confidence`` / ``return_entropy``: the return becomes ``(labels, conf[, entropy])`` with fp32 (S, S) maps of the winning
     class's softmax probability and of the entropy / log C, both at ``model.temperature`` and of the raw arg-max (clean-up touches the
-    labels only).  One ``ops.seg_calib`` launch then gives labels and maps; the labels are the same bits either way."""
+    labels only).  One ``ops.seg_calib`` launch then gives labels and maps; the labels are the same bits either way.
+
+    ``refine``: a ``RefineConfig`` -- the labels are ``ops.seg_refine``'s (csrc/segrefine.hip) at ``inv_temperature = 1 /
+    model.temperature``, taken BEFORE the clean-up.  The guide is channel 1 of the normalised stack ``zoo.encode._batch`` hands the
+    backbone: the centre plane of a 3-plane input, the image itself otherwise (the three channels of a 2-D image differ only by the
+    ImageNet constants), so ``sigma_i`` is in units of that channel, (windowed value - 0.456) / 0.224.  ``return_confidence`` then returns
+    the refined confidence; ``return_entropy`` is refused.  With ``refine=None`` nothing changes."""
+    _check_refine("segment", refine, return_entropy)
     from zoo.encode import _batch
     if device is None:
         device = next(model.parameters()).device
@@ -116,7 +182,10 @@ def segment(model: SegModel, image: np.ndarray, pixel_spacing: Tuple[float, floa
     with torch.no_grad():
         logits = model(x, spacing=spacing)
     maps = ()
-    if return_confidence or return_entropy:
+    if refine is not None:
+        pred, conf = _refine_chunk(model, logits, x, refine, return_confidence)
+        maps = (conf,) if return_confidence else ()
+    elif return_confidence or return_entropy:
         res = ops.seg_calib(logits, model.patch, inv_temperature=1.0 / _temperature(model), want_conf=return_confidence,
                             want_entropy=return_entropy)
         pred, maps = res.pred, tuple(m for m in (res.conf, res.entropy) if m is not None)
@@ -145,7 +214,8 @@ def segment_volume(model: SegModel, volume: np.ndarray, spacing: Tuple[float, fl
                    input_format: Literal["hu_float", "hu16_png", "windowed_float"] = "hu_float", hu_level: float = 40.0, hu_width: float = 400.0,
                    context: Literal["neighbours", "replicate"] = "neighbours", batch_size: int = 64,
                    device: Union[str, torch.device, None] = None, keep_largest: bool = False, min_volume_mm3: float = 0.0,
-                   connectivity: int = 26, return_confidence: bool = False, return_entropy: bool = False):
+                   connectivity: int = 26, return_confidence: bool = False, return_entropy: bool = False,
+                   refine: Optional[RefineConfig] = None):
     """Label volume of a ``(Z, H, W)`` series: uint8 (Z, S, S) with S = model.img_size.  The volume crosses to the device once and is
     preprocessed and forwarded in chunks of ``batch_size`` slices exactly as ``zoo.encode.encode_volume`` does it (``context``: the 2.5D
     stack of a slice); every chunk's patch logits go through ``ops.seg_predict`` into one device buffer, which is copied back once.
@@ -156,7 +226,12 @@ def segment_volume(model: SegModel, volume: np.ndarray, spacing: Tuple[float, fl
     it measures (s_z, s_y, s_x) = (spacing[2], spacing[1] h / S, spacing[0] w / S) mm.
 
     ``return_confidence`` / ``return_entropy``: as for ``segment`` -- the return becomes ``(labels, conf[, entropy])`` with fp32 (Z, S, S)
-    maps at ``model.temperature``, from one ``ops.seg_calib`` launch per chunk in place of ``ops.seg_predict`` (the same label bits)."""
+    maps at ``model.temperature``, from one ``ops.seg_calib`` launch per chunk in place of ``ops.seg_predict`` (the same label bits).
+
+    ``refine``: as for ``segment`` -- every chunk goes through ``ops.seg_refine`` before ``postprocess_volume``, each slice guided by its own
+    plane: channel 1 of the chunk's 2.5D stacks, which is plane z in both contexts (``dinox.preprocess.stack_planes``).  Slices do not
+    exchange messages, so the result does not depend on ``batch_size``, and the workspace is that of one chunk."""
+    _check_refine("segment_volume", refine, return_entropy)
     from zoo.encode import forward_volume_chunks
     min_component_vox(min_volume_mm3)               # refuses a negative or non-finite volume before any work is done
     if connectivity not in (6, 18, 26):
@@ -164,15 +239,19 @@ def segment_volume(model: SegModel, volume: np.ndarray, spacing: Tuple[float, fl
     want_maps = return_confidence or return_entropy
     inv_t = 1.0 / _temperature(model) if want_maps else 1.0
     S, out, conf, ent = model.img_size, None, None, None
-    for ch, logits in forward_volume_chunks(model, volume, spacing, input_format=input_format, hu_level=hu_level, hu_width=hu_width,
-                                            context=context, z_stride=1, batch_size=batch_size, device=device):
+    for ch, logits, x in forward_volume_chunks(model, volume, spacing, input_format=input_format, hu_level=hu_level, hu_width=hu_width,
+                                               context=context, z_stride=1, batch_size=batch_size, device=device, with_input=True):
         if out is None:
             Z = np.asarray(volume).shape[0]
             out = torch.empty((Z, S, S), dtype=torch.uint8, device=logits.device)
             conf = torch.empty((Z, S, S), dtype=torch.float32, device=logits.device) if return_confidence else None
             ent = torch.empty((Z, S, S), dtype=torch.float32, device=logits.device) if return_entropy else None
         sl = slice(ch[0], ch[0] + len(ch))
-        if want_maps:
+        if refine is not None:
+            out[sl], c = _refine_chunk(model, logits, x, refine, return_confidence)
+            if conf is not None:
+                conf[sl] = c
+        elif want_maps:
             res = ops.seg_calib(logits, model.patch, inv_temperature=inv_t, want_conf=return_confidence, want_entropy=return_entropy)
             out[sl] = res.pred
             if conf is not None:
@@ -599,6 +678,8 @@ def load_segmenter(backbone_path, output_dir, device: Union[str, torch.device] =
     if "temperature" in cfg:                        # --fit-temperature's result: used by the confidence / entropy maps only
         model.temperature = float(cfg["temperature"])
         _temperature(model)
+    if "refine" in cfg:                             # stored, never applied implicitly
+        model.refine = RefineConfig.from_dict(cfg["refine"])
     return model.eval()
 
 

@@ -20,6 +20,15 @@ then taken on the cleaned map and a "postprocess" object records the settings.  
 as means over the foreground classes that have a value, lesion-wise sensitivity, precision, F1 and false positives per image, with the
 summed counts; a lesion is a connected component (``--connectivity``) of at least ``--min-component-mm2``, hit when at least
 ``--lesion-overlap`` of it (to 1/1000; 0: any pixel) is matched by the other map.
+
+``--refine`` (csrc/segrefine.hip, dinox.segment.RefineConfig; opt-in) refines the arg-max by mean-field iterations of a local CRF guided
+by the slice the backbone sees (channel 1 of its normalised input), at the stored temperature and before any clean-up.  Every score of
+the report is then taken on the refined map, and a "refine" object holds the parameters and the Dice and surface scores of the unrefined
+map next to the refined ones, so one run shows the effect (both sides of the pair are taken before ``--keep-largest`` /
+``--min-component-mm2``, so that it isolates the refinement; the report's own scores include the clean-up).  ``--refine-iters``, ``--refine-radius``, ``--refine-dilation``,
+``--refine-sigma-xy``, ``--refine-sigma-i``, ``--refine-mix`` and ``--refine-weight`` replace single parameters (default: what the segmenter
+stores, else RefineConfig's defaults, which are untuned on real data); ``--write-refine`` stores the parameters used in the segmenter's
+finetune_config.json, as ``--write-temperature`` does for the temperature.
 """
 from __future__ import annotations
 
@@ -71,6 +80,43 @@ class EvalSynthetic(fs.SyntheticMasks):
         return x, sp, m, torch.stack([sp[1], sp[0]])
 
 
+REFINE_FIELDS = (("iters", int), ("radius", int), ("dilation", int), ("sigma_xy", float), ("sigma_i", float), ("mix", float), ("weight", float))
+
+
+def add_refine_flags(ap: argparse.ArgumentParser) -> None:
+    """--refine and one flag per field of dinox.segment.RefineConfig (shared with scripts/segment_volume.py)."""
+    ap.add_argument("--refine", action="store_true",
+                    help="refine the label map by mean-field iterations of a local CRF guided by the image (csrc/segrefine.hip), before any clean-up")
+    for name, kind in REFINE_FIELDS:
+        ap.add_argument(f"--refine-{name.replace('_', '-')}", type=kind, default=argparse.SUPPRESS, metavar="V",
+                        help=f"RefineConfig.{name} (needs --refine; default: the segmenter's stored value, else {getattr(SG.RefineConfig(), name)})")
+
+
+def check_refine_flags(ap: argparse.ArgumentParser, args: argparse.Namespace) -> None:
+    given = {name: getattr(args, f"refine_{name}") for name, _ in REFINE_FIELDS if hasattr(args, f"refine_{name}")}
+    if given and not args.refine:
+        ap.error(f"{', '.join('--refine-' + k.replace('_', '-') for k in given)}: only with --refine")
+    try:
+        SG.RefineConfig(**given)
+    except ValueError as e:
+        ap.error(str(e))
+
+
+def refine_config(args: argparse.Namespace, stored, ap: argparse.ArgumentParser = None):
+    """None without --refine; else the stored parameters (a RefineConfig, a dict as finetune_config.json holds it, or None for the
+    defaults) with the given --refine-* flags in place.  A value that RefineConfig refuses is an argument error where ``ap`` is given."""
+    if not args.refine:
+        return None
+    try:
+        base = SG.RefineConfig.from_dict(stored).to_dict() if isinstance(stored, dict) else (stored or SG.RefineConfig()).to_dict()
+        base.update({name: getattr(args, f"refine_{name}") for name, _ in REFINE_FIELDS if hasattr(args, f"refine_{name}")})
+        return SG.RefineConfig(**base)
+    except ValueError as e:
+        if ap is None:
+            raise
+        ap.error(f"--refine: {e}")
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="Dice / IoU and HD95 / ASSD / surface Dice in mm of a fine-tuned segmenter",
                                  formatter_class=argparse.ArgumentDefaultsHelpFormatter)
@@ -108,6 +154,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="with --fit-temperature: store the fitted temperature in the segmenter's finetune_config.json")
     ap.add_argument("--calibration-cache-gib", type=float, default=4.0, metavar="G",
                     help="--fit-temperature is refused when the cached logits and labels would exceed this many GiB of device memory")
+    add_refine_flags(ap)
+    ap.add_argument("--write-refine", action="store_true",
+                    help="with --refine: store the parameters used in the segmenter's finetune_config.json")
     return ap
 
 
@@ -121,6 +170,9 @@ def check_args(ap: argparse.ArgumentParser, args: argparse.Namespace) -> None:
         ap.error(f"--temperature: a finite value > 0, got {args.temperature}")
     if not 0.0 < args.calibration_cache_gib < float("inf"):
         ap.error(f"--calibration-cache-gib: a finite value > 0, got {args.calibration_cache_gib}")
+    if args.write_refine and not args.refine:
+        ap.error("--write-refine needs --refine")
+    check_refine_flags(ap, args)
 
 
 def calibration_object(rep: dict, temperature: float, bins: int) -> dict:
@@ -152,21 +204,35 @@ def lesion_report(res: dict, connectivity: int, overlap, min_area_mm2: float) ->
 
 @torch.no_grad()
 def evaluate(model: SG.SegModel, loader, device, amp: bool, tolerances, num_classes: int, *, lesion=None, post=None, calibration=None,
-             cache=None) -> dict:
+             cache=None, refine=None) -> dict:
     """One pass: the [3, C] overlap counts of the whole set and the per-class surface means.  -> the report dict (no file is written).
     ``post``: None or {"keep_largest", "min_area_mm2", "connectivity"} -- every score is then taken on the cleaned map (ops.cc_filter; the
     area on the evaluated grid's spacing).  ``lesion``: None or {"connectivity", "overlap": (num, den), "min_area_mm2"} -- adds "lesion".
     ``calibration``: None or {"bins", "temperature"} -- adds "calibration", from one ops.seg_calib launch per batch beside the prediction
-    (always of the raw arg-max, whatever ``post`` says).  ``cache``: a list that receives every batch's (patch logits, labels)."""
+    (always of the raw arg-max, whatever ``post`` says).  ``cache``: a list that receives every batch's (patch logits, labels).
+    ``refine``: None or a RefineConfig -- the map is ops.seg_refine's (guide: channel 1 of x, at 1 / model.temperature) before ``post``;
+    adds "refine" with the Dice and surface scores of the unrefined arg-max beside the refined ones, both before any clean-up."""
     cal = SG.CalibrationAccumulator(calibration["bins"]) if calibration else None
     acc = SG.SurfaceAccumulator(num_classes, len(tolerances))
     les = SG.LesionAccumulator(num_classes) if lesion else None
     counts, n = None, 0
+    raw_acc, raw_counts = (SG.SurfaceAccumulator(num_classes, len(tolerances)), None) if refine else (None, None)
+    ref_acc, ref_counts = (SG.SurfaceAccumulator(num_classes, len(tolerances)), None) if refine and post else (None, None)
     for x, sp, m, grid_sp in loader:
         x, m = x.to(device), m.to(device)
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
             logits = model(x, spacing=sp.to(device) if model.scale_aware else None)
         pred, cnt = ops.seg_predict(logits, model.patch, m)
+        if refine:
+            raw_counts = cnt.clone() if raw_counts is None else raw_counts + cnt
+            sc, sv = ops.surface_stats(pred, m, grid_sp, num_classes, tolerances=tolerances)
+            raw_acc.update(SG.surface_metrics(sc, sv, grid_sp, tuple(m.shape[-2:])))
+            pred, _, cnt = ops.seg_refine(logits, x[:, 1].float().contiguous(), model.patch, m, inv_temperature=1.0 / model.temperature,
+                                          **refine.to_dict())
+            if post:                                # the refined map before the clean-up, for the "refine" block
+                ref_counts = cnt.clone() if ref_counts is None else ref_counts + cnt
+                sc, sv = ops.surface_stats(pred, m, grid_sp, num_classes, tolerances=tolerances)
+                ref_acc.update(SG.surface_metrics(sc, sv, grid_sp, tuple(m.shape[-2:])))
         if cal:
             cal.update(ops.seg_calib(logits, model.patch, m, inv_temperature=1.0 / calibration["temperature"], bins=calibration["bins"],
                                      want_pred=False))
@@ -193,6 +259,19 @@ def evaluate(model: SG.SegModel, loader, device, amp: bool, tolerances, num_clas
             "classes": int((res["images"] > 0).sum())}
     report = {"images": n, "num_classes": num_classes, "tolerances_mm": list(tolerances), "quantile": "95/100 (nearest rank)",
               "spacing": SPACING_CONVENTION, "pixel_accuracy": SG.pixel_accuracy(counts), "per_class": per_class, "mean": mean}
+    if refine:
+        raw = raw_acc.result()
+
+        def side(cn, rs):
+            return {"dice": _floats(SG.dice_per_class(cn)), "mean_dice": SG.mean_dice(cn), "hd95_mm": _mean_present(rs["hd95"]),
+                    "assd_mm": _mean_present(rs["assd"]), "nsd": {f"{t:g}": _mean_present(rs["nsd"][:, i]) for i, t in enumerate(tolerances)}}
+
+        # both sides WITHOUT clean-up, so the pair isolates the refinement; with ``post`` the report's own scores are of the refined map
+        # after the clean-up and "refined" is not a copy of them
+        report["refine"] = {"parameters": refine.to_dict(), "temperature": float(model.temperature), "unrefined": side(raw_counts.cpu(), raw),
+                            "refined": side(ref_counts.cpu(), ref_acc.result()) if post else side(counts, res),
+                            "clean_up": "none: \"refined\" equals the report's own scores" if not post else
+                                        "\"unrefined\" and \"refined\" are both taken before the clean-up; the report's own scores after it"}
     if post:
         report["postprocess"] = dict(post)
     if cal:
@@ -234,6 +313,7 @@ def run(args: argparse.Namespace) -> dict:
         ap.error(f"--segmenter {args.segmenter}: task {cfg.get('task')!r} is not 'segmentation'")
     if not torch.cuda.is_available():
         raise SystemExit("this engine computes on MI355X only: no CUDA/HIP device available")
+    refine = refine_config(args, cfg.get("refine"), ap)      # a bad stored "refine" is refused here, before the model is loaded
     model = SG.load_segmenter(args.backbone, args.segmenter, device)
     C, img = cfg["num_classes"], model.img_size
     if args.synthetic:
@@ -257,7 +337,11 @@ def run(args: argparse.Namespace) -> dict:
             raise SystemExit(f"--fit-temperature: the patch logits and labels of {len(ds)} images take {need / 2 ** 30:.2f} GiB of device memory, "
                              f"above --calibration-cache-gib {args.calibration_cache_gib:g}; raise it or fit on a subset")
         cache = []
-    report = evaluate(model, loader, device, not args.no_amp, tolerances, C, lesion=lesion, post=post, calibration=calibration, cache=cache)
+    report = evaluate(model, loader, device, not args.no_amp, tolerances, C, lesion=lesion, post=post, calibration=calibration, cache=cache,
+                      refine=refine)
+    if refine and args.write_refine:
+        cfg["refine"] = refine.to_dict()
+        cfg_file.write_text(json.dumps(cfg, indent=2))
     if args.fit_temperature:
         fit = SG.fit_temperature(cache, model.patch)
         after = SG.CalibrationAccumulator(args.calibration_bins)

@@ -27,6 +27,12 @@ under ``--blend-window`` (gaussian or constant), with ``--tta-flips`` averaged o
 uint8 (Z, H, W), ``--labels`` must be (Z, H, W) and is compared as it is (nothing is resampled), and ``--min-component-mm3`` and
 ``--tolerance-mm`` use the scanner's voxel (SZ, SY, SX).  The report records the tile geometry and the grid of the scores; a metric whose
 kernel declines the native size is reported with the kernel's message instead of a value.
+
+``--refine`` refines every slice's label map before the clean-up (dinox.segment.segment_volume(refine=...), csrc/segrefine.hip): mean-field
+iterations of a local CRF guided by the slice's own normalised plane, at the stored temperature.  ``--refine-iters``, ``--refine-radius``,
+``--refine-dilation``, ``--refine-sigma-xy``, ``--refine-sigma-i``, ``--refine-mix`` and ``--refine-weight`` replace single parameters
+(default: what the segmenter stores, else RefineConfig's defaults, untuned on real data).  ``--confidence-out`` then holds the refined
+confidence.  Not with ``--tiled`` (the blend kernel never materialises the blended logits) and not with ``--entropy-out``.
 """
 from __future__ import annotations
 
@@ -45,7 +51,7 @@ for _p in (_HERE.parent, _HERE):
         sys.path.insert(0, str(_p))
 
 import finetune_lora as fl  # noqa: E402
-from evaluate_segmentation import _floats, _mean_present  # noqa: E402
+from evaluate_segmentation import _floats, _mean_present, add_refine_flags, check_refine_flags, refine_config  # noqa: E402,F401
 from dinox import ops, segment as SG  # noqa: E402
 
 log = logging.getLogger("segment_volume")
@@ -94,6 +100,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--entropy-out", type=Path, default=None, metavar="NPY",
                     help="also write the fp32 volume of the softmax entropy / log C at the stored temperature (not with --tiled: the blend "
                          "kernel has no entropy output)")
+    add_refine_flags(ap)
     return ap
 
 
@@ -107,6 +114,11 @@ def check_args(ap: argparse.ArgumentParser, args: argparse.Namespace) -> None:
         ap.error(f"{', '.join(given)}: only with --tiled")
     if args.entropy_out is not None and args.tiled:
         ap.error("--entropy-out: not with --tiled (the blend kernel has no entropy output)")
+    if args.refine and args.tiled:
+        ap.error("--refine: not with --tiled (the sliding-window path never materialises the blended logits the refinement starts from)")
+    if args.refine and args.entropy_out is not None:
+        ap.error("--entropy-out: not with --refine (the refinement kernel has no entropy output)")
+    check_refine_flags(ap, args)
     for k, v in TILED_DEFAULTS.items():
         if not hasattr(args, k):
             setattr(args, k, v)
@@ -213,6 +225,10 @@ def run(args: argparse.Namespace):
             ap.error(f"{f}: no such file")
     if not torch.cuda.is_available():
         raise SystemExit("this engine computes on MI355X only: no CUDA/HIP device available")
+    refine = None
+    if args.refine:                                 # the stored parameters with the flags in place; a bad value is an argument error
+        cfg_file = Path(args.segmenter) / SG.CONFIG_FILE
+        refine = refine_config(args, json.loads(cfg_file.read_text()).get("refine") if cfg_file.is_file() else None, ap)
     model = SG.load_segmenter(args.backbone, args.segmenter, device)
     C, S = model.head.num_classes, model.img_size
     overlap = (round(1000 * args.lesion_overlap), 1000)
@@ -238,7 +254,8 @@ def run(args: argparse.Namespace):
                 pred = SG.segment_volume(model, vol, (sx, sy, sz), input_format=args.input_format, hu_level=args.window_level,
                                          hu_width=args.window_width, context=args.context, batch_size=args.batch_size, device=device,
                                          keep_largest=args.keep_largest, min_volume_mm3=args.min_component_mm3,
-                                         connectivity=args.connectivity, return_confidence=want_conf, return_entropy=want_ent)
+                                         connectivity=args.connectivity, return_confidence=want_conf, return_entropy=want_ent,
+                                         refine=refine)
         if want_conf or want_ent:                   # (labels, conf[, entropy])
             pred, maps = pred[0], dict(zip([p for p, w in ((args.confidence_out, want_conf), (args.entropy_out, want_ent)) if w], pred[1:]))
             for mpath, arr in maps.items():

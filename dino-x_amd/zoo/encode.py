@@ -159,12 +159,14 @@ def encode_batch(model: PatchViT, images: Sequence[np.ndarray], spacings: Sequen
 
 
 def forward_volume_chunks(model, volume: np.ndarray, spacing: Tuple[float, float, float], *, input_format: str, hu_level: float, hu_width: float,
-                          context: str, z_stride: int, batch_size: int, device: Union[str, torch.device, None]):
+                          context: str, z_stride: int, batch_size: int, device: Union[str, torch.device, None], with_input: bool = False):
     """The chunk loop of a ``(Z, H, W)`` series, shared by ``encode_volume`` and ``dinox.segment.segment_volume``: checks the arguments,
     moves the volume to the device once, then yields ``(slices, model(x, spacing=...))`` per chunk of ``batch_size`` of the slices
     0, z_stride, ... -- ``x`` the chunk's 2.5D stacks, preprocessed by the kernel into one reused input buffer (each plane resized once
     for all the stacks of the chunk it shows in).  ``model`` is anything with ``img_size``, ``scale_aware`` and that call (a PatchViT, a
-    SegModel).  The forward runs under no_grad in the caller's autocast state.  The checks run at the first ``next()``."""
+    SegModel).  The forward runs under no_grad in the caller's autocast state.  The checks run at the first ``next()``.
+    ``with_input``: yields ``(slices, features, x)`` -- ``x`` [n, 3, S, S] fp32 is a view of the reused buffer (channel 1 = the slice's own
+    plane in both contexts, see ``dinox.preprocess.stack_planes``), valid until the next ``next()``."""
     from dinox import preprocess as P
     vol = np.asarray(volume)
     if vol.ndim != 3:
@@ -204,7 +206,7 @@ def forward_volume_chunks(model, volume: np.ndarray, spacing: Tuple[float, float
         at += len(tb)
         with torch.no_grad():
             f = model(x, spacing=None if sp is None else sp.expand(n, 3).contiguous())
-        yield ch, f
+        yield (ch, f, x) if with_input else (ch, f)
 
 
 def encode_volume(model: PatchViT, volume: np.ndarray, spacing: Tuple[float, float, float], *,

@@ -878,6 +878,42 @@ int dinox_seg_calib(const float* z, const uint8_t* y, float inv_temperature, uin
                     float* sums, void* ws, int64_t B, int g, int u, int C, int NB, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Edge-aware label refinement: mean-field iterations of a local CRF on a guide image (kernel: csrc/segrefine.hip; dinox.ops.seg_refine,
+ * dinox.segment.RefineConfig).  Inputs: patch logits z[B][g g][C] fp32, with geometry (B, g, u, C) and limits exactly those of
+ * dinox_seg_predict; a guide image I[B][S][S] fp32, with S = g u; the scalars s (inverse temperature, finite and > 0), T (iterations,
+ * 0...32), r (window radius, 1...3), d (dilation, 1...8), sigma_xy > 0 in pixels of the S-grid, sigma_I > 0 in units of I, lambda in
+ * [0, 1], w >= 0, finite.  With l_p[c] the interpolated logit of seg_common.h (same taps, same order of operations):
+ *   U_p[c]    = s l_p[c]                                   (one fp32 multiply)
+ *   Q^0_p     = softmax_c(U_p)                             (max subtracted)
+ *   N(p)      = { p + d (dy, dx) : |dy|, |dx| <= r, (dy, dx) != (0, 0), inside the image }
+ *   g_(dy,dx) = exp(-(dy^2 + dx^2) d^2 / (2 sigma_xy^2))   (host-computed fp32 table of (2r+1)^2 entries, passed to the kernel)
+ *   a_pj      = (1 - lambda) + lambda exp(-(I_p - I_j)^2 / (2 sigma_I^2))
+ *   m_p[c]    = sum_{j in N(p)} g_pj a_pj Q^(t-1)_j[c]  /  sum_{j in N(p)} g_pj
+ *   Q^t_p     = softmax_c(U_p[c] + w m_p[c])               t = 1...T
+ * The normaliser is the spatial sum over the neighbours inside the image: the appearance term can only weaken a message, never strengthen
+ * it.  The neighbour sum runs in a fixed order: dy outer, dx inner, ascending; equal inputs give equal bits.  Out-of-image neighbours
+ * contribute to neither sum.  r d >= S in an axis, which leaves no neighbour, is refused; so is 2 d > S, which leaves the pixels with
+ * S - d <= x < d and S - d <= y < d no neighbour at any radius (with 2 d <= S every pixel keeps p + (0, d) or p - (0, d): N(p) is never
+ * empty and no normaliser is 0).
+ * Outputs: pred[B][S][S] uint8 = arg-max of Q^T, taken on the pre-softmax values U + w m, lowest index on an exact tie; optional
+ * conf[B][S][S] fp32 = Q^T[pred]; optional y / counts[3 C + 1], exactly as dinox_seg_predict does it (of the refined map; both or neither).
+ * With T = 0, pred and counts are dinox_seg_predict's bit for bit (the arg-max is then taken on the unscaled l_p, as dinox_seg_calib takes
+ * it) and conf is dinox_seg_calib's at the same s.
+ * The kernel receives gtab (a HOST pointer to the (2r+1)^2 values g_(dy,dx), row-major, dy outer; the centre is not read; copied into the
+ * launch arguments) and inv2sI2 = 1 / (2 sigma_I^2).  ws: two ping-pong planes Q[B][C][S][S] fp32 (class-major), needed when T >= 1.
+ * One launch writes Q^0, one launch runs each iteration; the last iteration writes no plane and produces pred, conf and counts itself.
+ * A non-finite logit or guide pixel does not fault: it makes non-finite every value whose windows it enters, and nothing else.
+ * Host checks before any launch (DINOX_EINVAL with a message): the geometry, T, r, d, r d >= S, 2 d > S, s / w / inv2sI2 / lambda / gtab not finite or
+ * out of range (gtab >= 0, and > 0 at the four nearest neighbours so that no normaliser is 0), null z, I, pred or gtab, y without counts
+ * or counts without y, T >= 1 without ws.  No allocation, no synchronisation.
+ * dinox_seg_refine_ws_bytes: bytes of the two planes (a pure function of the sizes; 0 for sizes the call refuses, among them more than
+ *   2^31 - 1 tiles of 32 x 8 pixels or more than 2^40 elements per plane; contents need not be initialised; 4-byte aligned).
+ * ------------------------------------------------------------------------------------------ */
+int64_t dinox_seg_refine_ws_bytes(int64_t B, int g, int u, int C);
+int dinox_seg_refine(const float* z, const float* I, const uint8_t* y, uint8_t* pred, float* conf, int64_t* counts, void* ws, int64_t B, int g,
+                     int u, int C, int T, int r, int d, const float* gtab, float inv2sI2, float lambda, float w, float s, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Sliding-window prediction at native resolution (kernel: csrc/segblend.hip; dinox.ops.seg_blend_predict, dinox.tiled).  B images of one
  * size H x W were cut into t x t tiles on a separable grid of origins ys[ny] x xs[nx]; every tile went through the model F times (mirror
  * variants) and left g x g patch logit rows.  Each output pixel gathers the tiles that cover it: no [C][H][W] map is written, nothing is
