@@ -129,6 +129,122 @@ def test_ops_argument_errors_without_a_device():
             call()
 
 
+# ------------------------------------------------------------------------------------------ the launch plans, mirrored
+# Which template instantiation a call runs cannot be seen from Python, but the plans are pure functions of the sizes.  These are
+# csrc/gram.hip (gram_plan, the VEC predicate) and csrc/probe.hip (pb_groups, pb_lds_bytes, the nb -> NB dispatch, the VEC predicate) again;
+# the shape lists below are the ones tests/test_probes_gpu.py runs, each with the plan facts it is in the list for.
+def cdiv(a, b):
+    return -(-a // b)
+
+
+def rows_are_vec(ld, D, off):
+    """16-byte row loads: the base 16-byte aligned (the buffer is, so the column offset decides) and a pitch of whole quads."""
+    return off % 4 == 0 and (ld or D) % 4 == 0
+
+
+def gram_plan(N, D, ld=0, off=0):
+    T = cdiv(D, 128)
+    tiles = T * (T + 1) // 2
+    slabs = cdiv(N, 16)
+    per = cdiv(slabs, min(cdiv(512, tiles), slabs))
+    splits = cdiv(slabs, per)
+    return dict(T=T, tiles=tiles, splits=splits, slabs=per, last_split_slabs=slabs - (splits - 1) * per, last_slab_rows=N - (slabs - 1) * 16,
+                vec=rows_are_vec(ld, D, off), ws_bytes=splits * (tiles * 128 * 128 + T * 128) * 4)
+
+
+def probe_plan(N, D, C, ld=0, off=0):
+    blocks = cdiv(N, 32)
+    groups = min(blocks, 512)
+    nb = cdiv(D, 128)
+    colsz = cdiv(D, 4) * 4
+    pitch = (colsz - 4 + 63) // 64 * 64 + 4
+    return dict(blocks=blocks, groups=groups, last_block_rows=N - (blocks - 1) * 32, nb=nb, NB=nb if nb <= 4 else 8,
+                lds_bytes=(32 * pitch + 4 * 32 * 33 + 32 * 36 + 32) * 4, vec=rows_are_vec(ld, D, off), ws_bytes=groups * (8 + C * (D + 1) * 4))
+
+
+# ((N, D, ld, column offset), the facts the case exists for).  ld = 0: contiguous rows.
+GRAM_PATHS = [
+    ((300, 1024, 0, 0), dict(T=8, tiles=36, vec=True, splits=10, slabs=2)),                        # ViT-L: the whole 8 x 8 triangle
+    ((700, 768, 0, 0), dict(T=6, tiles=21, vec=True, splits=22, slabs=2)),                         # ViT-B
+    ((300, 1023, 0, 0), dict(T=8, tiles=36, vec=False, splits=10, slabs=2)),                       # odd pitch; the last panel 127 wide
+    ((2000, 384, 0, 0), dict(T=3, tiles=6, vec=True, splits=63, slabs=2, last_split_slabs=1)),     # the statistics shape; a short last split
+    ((8300, 64, 0, 0), dict(T=1, tiles=1, vec=True, splits=260, slabs=2, last_slab_rows=12)),      # one tile; a ragged last slab
+    ((1030, 130, 132, 0), dict(T=2, tiles=3, vec=True, last_slab_rows=6)),                         # a quad across D; a panel 2 columns wide
+    ((513, 64, 80, 1), dict(T=1, vec=False)),                                                      # whole-quad pitch, base one float off
+]
+GRAM_PATH_SHAPES = [s for s, _ in GRAM_PATHS]
+GRAM_PATTERN_SHAPE = (300, 1024)                                # x[i, j] = (j % 7) - 3 on every row: plan of GRAM_PATHS[0]
+
+# ((N, D, C, span), facts) for the contiguous cases, ((N, D, C, ld, column offset), facts) for rows of a wider buffer
+PROBE_PATHS = [
+    ((70, 385, 3, 8.0), dict(NB=4, nb=4, vec=False)),                                              # the lowest NB = 4, odd pitch
+    ((70, 512, 32, 8.0), dict(NB=4, nb=4, vec=True)),                                              # NB = 4 full, all 32 classes
+    ((70, 513, 5, 8.0), dict(NB=8, nb=5, vec=False)),                                              # three idle 128-column blocks
+    ((45, 768, 7, 8.0), dict(NB=8, nb=6, vec=True)),                                               # ViT-B
+    ((45, 1024, 32, 8.0), dict(NB=8, nb=8, vec=True, lds_bytes=153216)),                           # ViT-L: the largest footprint
+    ((45, 1024, 32, 60.0), dict(NB=8, nb=8, vec=True, lds_bytes=153216)),
+    ((16384, 7, 3, 8.0), dict(blocks=512, groups=512)),                                            # the last size with one trip
+    ((16385, 7, 3, 8.0), dict(blocks=513, groups=512, last_block_rows=1)),                         # one workgroup takes a second block
+    ((16421, 7, 3, 8.0), dict(blocks=514, groups=512, last_block_rows=5)),                         # two do; the last block has 5 rows
+    ((16421, 520, 4, 8.0), dict(blocks=514, groups=512, NB=8, nb=5, vec=True)),                    # the walk on NB = 8
+]
+PROBE_PATH_SHAPES = [s for s, _ in PROBE_PATHS]
+PROBE_PITCH_PATHS = [
+    ((70, 66, 5, 68, 0), dict(NB=1, vec=True)),                                                    # VEC, the last quad straddles D
+    ((70, 64, 5, 68, 1), dict(NB=1, vec=False)),                                                   # whole-quad pitch, base one float off
+]
+PROBE_PITCH_SHAPES = [s for s, _ in PROBE_PITCH_PATHS]
+LDS_LIMIT = 160 * 1024                                          # per workgroup on gfx950
+
+
+def holds(plan, facts):
+    return {k: plan[k] for k in facts} == facts
+
+
+def test_gram_shapes_reach_the_paths_they_are_named_for():
+    from dinox import _lib
+    for (N, D, ld, off), facts in GRAM_PATHS:
+        plan = gram_plan(N, D, ld, off)
+        assert _lib.lib.dinox_gram_ws_bytes(N, D) == plan["ws_bytes"], (N, D)
+        assert holds(plan, facts), ((N, D, ld, off), plan)
+        assert 25 * N < 2 ** 24                                                          # the integer test's exactness condition
+    plans = {s: gram_plan(*s) for s in GRAM_PATH_SHAPES}
+    assert sum(p["T"] == 8 for p in plans.values()) >= 2 and any(p["T"] == 6 for p in plans.values())
+    multi = [s for s, p in plans.items() if p["splits"] >= 2 and p["slabs"] >= 2]          # the prefetch-under-products loop
+    assert any(plans[s]["vec"] and plans[s]["tiles"] > 1 for s in multi) and any(not plans[s]["vec"] for s in multi)
+    assert any(p["vec"] and s[1] % 4 for s, p in plans.items())                            # VEC with D % 4 != 0: the ragged quad
+    assert any(not p["vec"] and (s[2] or s[1]) % 4 == 0 for s, p in plans.items())         # non-VEC through the base pointer alone
+    assert holds(gram_plan(*GRAM_PATTERN_SHAPE), GRAM_PATHS[0][1])
+    # the mirror is the library's plan elsewhere too: the shapes of the older tests and the limits
+    for N, D in ((1, 1), (33, 7), (257, 65), (1000, 129), (4099, 385), (513, 64), (65536, 385), (65536, 1024), (15, 1024), (16, 128), (17, 129)):
+        assert _lib.lib.dinox_gram_ws_bytes(N, D) == gram_plan(N, D)["ws_bytes"], (N, D)
+
+
+def test_probe_shapes_reach_the_paths_they_are_named_for():
+    from dinox import _lib
+    P = _lib.lib.dinox_softmax_probe_ws_bytes
+    plans = {}
+    for (N, D, C, _), facts in PROBE_PATHS:
+        plans[(N, D, C, 0, 0)] = plan = probe_plan(N, D, C)
+        assert holds(plan, facts), ((N, D, C), plan)
+    for (N, D, C, ld, off), facts in PROBE_PITCH_PATHS:
+        plans[(N, D, C, ld, off)] = plan = probe_plan(N, D, C, ld, off)
+        assert holds(plan, facts), ((N, D, C, ld, off), plan)
+    for (N, D, C, _, _), plan in plans.items():
+        assert P(N, D, C) == plan["ws_bytes"], (N, D, C)
+        assert plan["lds_bytes"] <= LDS_LIMIT and D <= 128 * plan["NB"]
+    assert {p["NB"] for p in plans.values()} == {1, 4, 8}                                  # NB = 1, 2, 3: PROBE_SHAPES of the GPU file
+    assert {p["nb"] for p in plans.values() if p["NB"] == 8} >= {5, 6, 8}
+    assert max(p["lds_bytes"] for p in plans.values()) == probe_plan(1, 1024, 2)["lds_bytes"]          # the largest any call can ask for
+    walk = [s for s, p in plans.items() if p["blocks"] > p["groups"]]
+    assert any(plans[s]["NB"] == 8 for s in walk) and any(plans[s]["NB"] == 1 for s in walk)
+    assert any(p["blocks"] == p["groups"] == 512 for p in plans.values())
+    assert any(p["vec"] and s[1] % 4 for s, p in plans.items())                            # VEC with D % 4 != 0
+    assert any(not p["vec"] and (s[3] or s[1]) % 4 == 0 for s, p in plans.items())         # non-VEC through the base pointer alone
+    for N, D, C in ((1, 1, 2), (67, 7, 3), (300, 65, 10), (1031, 384, 32), (2050, 129, 5), (65536, 384, 8), (16384, 1024, 32), (16385, 1024, 32)):
+        assert P(N, D, C) == probe_plan(N, D, C)["ws_bytes"], (N, D, C)
+
+
 # ------------------------------------------------------------------------------------------ series split
 def test_series_split_matches_the_reference_and_hand_cases():
     from dinox.probes import series_split

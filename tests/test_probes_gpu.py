@@ -1,6 +1,20 @@
 """GPU checks of the probe block: ``ops.gram`` (csrc/gram.hip) and ``ops.softmax_probe`` (csrc/probe.hip) against float64 NumPy with
 bounds derived from the fp32 format, ``dinox.probes`` end to end on the fixture the real reference recorded
-(tests/golden/panorgan_probes.npz), and scripts/evaluate_panorgan.py with ``--probes``.  Run with ``-m gpu`` on an MI355X."""
+(tests/golden/panorgan_probes.npz), and scripts/evaluate_panorgan.py with ``--probes``.  Run with ``-m gpu`` on an MI355X.
+
+Shapes, gram (N, D, ld, column offset): GRAM_SHAPES are the one-tile and small-triangle cases (T = 1 .. 4, element loads but for (513, 64, ld 80)).
+GRAM_PATH_SHAPES (tests/test_probes_cpu.py, where a mirror of gram_plan pins each to its path): (300, 1024) T = 8, all 36 tiles and
+their inverse map in gram_finish, 16-byte loads, two slabs per split (the prefetch under the products) with a ragged last one;
+(700, 768) T = 6; (300, 1023) the same triangle on element loads with a last panel 127 wide; (2000, 384) the statistics shape, off-diagonal
+tiles on 16-byte loads, a short last split; (8300, 64) one tile, 260 splits, ragged last slab; (1030, 130, ld 132) 16-byte loads with a quad
+across D and a panel two columns wide; (513, 64, ld 80, offset 1) element loads because of the base pointer alone.  The repeated-row
+pattern at D = 1024 makes every tile's content a function of its position.
+Shapes, softmax_probe (N, D, C, span): PROBE_SHAPES run NB = 1, 2, 3 (D = 384 the only 16-byte-load case) in one trip of the row walk.
+PROBE_PATH_SHAPES: D = 385 and 512 run NB = 4 (element / 16-byte loads, 3 / all 32 classes); 513, 768, 1024 run NB = 8 with 3, 2 and 0 idle
+column blocks (1024 x 32 classes: the largest LDS and register footprint, also at span 60); N = 16384 is the last size with one row block
+per workgroup, 16385 and 16421 send one and two workgroups on a second trip (the last block 1 and 5 rows), (16421, 520) does so on NB = 8.
+PROBE_PITCH_SHAPES: D = 66 at pitch 68 is the 16-byte path with a quad across D; D = 64 from column 1 of a pitch-68 buffer is the element
+path through the base pointer alone.  (67, 7, 3) carries the non-finite values, in a row that counts and in one that does not."""
 import functools
 import json
 import math
@@ -14,6 +28,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN, ROOT
+from test_probes_cpu import GRAM_PATH_SHAPES, GRAM_PATTERN_SHAPE, PROBE_PATH_SHAPES, PROBE_PITCH_SHAPES
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -26,15 +41,18 @@ def dev(a):
 
 # ------------------------------------------------------------------------------------------ gram
 GRAM_SHAPES = [(1, 1, 0), (33, 7, 0), (257, 65, 0), (1000, 129, 0), (4099, 385, 0), (513, 64, 80)]      # (N, D, ldx; 0 = D)
+GRAM_CASES = ([pytest.param(*s, 0, id="-".join(map(str, s))) for s in GRAM_SHAPES]
+              + [pytest.param(*s, id="-".join(map(str, s))) for s in GRAM_PATH_SHAPES])                 # (N, D, ldx, column offset)
 
 
-def gram_operand(x, ld):
-    """x on the device as rows of a wider buffer when ld > D (the padding holds NaN: it must never be read into a sum)."""
+def gram_operand(x, ld, off=0):
+    """x on the device as columns off .. off + D of the rows of a wider buffer when ld > D (the rest holds NaN: it must never be read
+    into a sum).  The buffer is 16-byte aligned, so off = 1 puts the base pointer one float off."""
     if not ld:
         return dev(x)
     buf = torch.full((x.shape[0], ld), float("nan"), device=DEV)
-    buf[:, :x.shape[1]] = dev(x)
-    return buf[:, :x.shape[1]]
+    buf[:, off:off + x.shape[1]] = dev(x)
+    return buf[:, off:off + x.shape[1]]
 
 
 def z64(x, shift):
@@ -42,39 +60,51 @@ def z64(x, shift):
     return z.astype(np.float64)
 
 
-def run_gram(x, shift, ld):
+def run_gram(x, shift, ld, off=0):
     from dinox import ops
-    g, cs = ops.gram(gram_operand(x, ld), None if shift is None else dev(shift))
+    g, cs = ops.gram(gram_operand(x, ld, off), None if shift is None else dev(shift))
     return g.cpu().numpy(), cs.cpu().numpy()
 
 
-@pytest.mark.parametrize("N,D,ld", GRAM_SHAPES)
-def test_gram_integer_rows_are_exact(N, D, ld):
+@pytest.mark.parametrize("N,D,ld,off", GRAM_CASES)
+def test_gram_integer_rows_are_exact(N, D, ld, off):
     g = np.random.default_rng(N + D)
     x = g.integers(-3, 4, size=(N, D)).astype(np.float32)
     shift = g.integers(-2, 3, size=D).astype(np.float32)
     for s in (None, shift):
         z = z64(x, s)
-        G, cs = run_gram(x, s, ld)
+        G, cs = run_gram(x, s, ld, off)
         assert G.dtype == np.float64 and G.shape == (D, D) and cs.shape == (D,)
-        assert np.array_equal(G, z.T @ z) and np.array_equal(cs, z.sum(0))       # |z| <= 5, N <= 4099: every partial sum is an integer below 2^24
+        assert np.array_equal(G, z.T @ z) and np.array_equal(cs, z.sum(0))       # |z| <= 5, 25 N < 2^24: every partial sum is an integer below 2^24
 
 
-@pytest.mark.parametrize("N,D,ld", GRAM_SHAPES)
-def test_gram_random_rows_within_the_chain_bound(N, D, ld):
+def test_gram_repeated_row_pattern_pins_the_tile_maps():
+    """x[i, j] = (j % 7) - 3 on every row: gram[a, b] = N z_a z_b, so the content of a 128 x 128 tile is a function of where it lies
+    (128 = 2 mod 7) and a tile stored or read at another place shows as a wrong exact integer."""
+    N, D = GRAM_PATTERN_SHAPE
+    x = np.tile((np.arange(D) % 7 - 3).astype(np.float32), (N, 1))
+    shift = (np.arange(D) % 5 - 2).astype(np.float32)
+    for s in (None, shift):
+        z = z64(x, s)
+        G, cs = run_gram(x, s, 0)
+        assert np.array_equal(G, N * np.outer(z[0], z[0])) and np.array_equal(cs, N * z[0])        # |z| <= 5, 25 N < 2^24
+
+
+@pytest.mark.parametrize("N,D,ld,off", GRAM_CASES)
+def test_gram_random_rows_within_the_chain_bound(N, D, ld, off):
     g = np.random.default_rng(7 * N + D)
     x = (g.standard_normal((N, D)) + 0.5).astype(np.float32)
     mean = x.astype(np.float64).mean(0).astype(np.float32)
     for s in (None, mean):
         z = z64(x, s)
-        G, cs = run_gram(x, s, ld)
+        G, cs = run_gram(x, s, ld, off)
         err, bound = np.abs(G - z.T @ z), N * U * (np.abs(z).T @ np.abs(z))
         cerr, cbound = np.abs(cs - z.sum(0)), N * U * np.abs(z).sum(0)
-        print(f"gram N={N} D={D} shift={'mean' if s is not None else 'none'}: max err / bound {float((err / np.maximum(bound, 1e-300)).max()):.3f}, "
+        print(f"gram N={N} D={D} ld={ld} off={off} shift={'mean' if s is not None else 'none'}: max err / bound {float((err / np.maximum(bound, 1e-300)).max()):.3f}, "
               f"colsum {float((cerr / np.maximum(cbound, 1e-300)).max()):.3f}")
         assert (err <= bound).all() and (cerr <= cbound).all()
         assert np.array_equal(G, G.T)                                            # symmetric to the bit
-        G2, cs2 = run_gram(x, s, ld)
+        G2, cs2 = run_gram(x, s, ld, off)
         assert np.array_equal(G, G2) and np.array_equal(cs, cs2)                 # two launches: the same bits
 
 
@@ -121,20 +151,21 @@ def probe_reference(x, label, theta):
     return p, loss, grad, t, np.abs(X).sum(0)
 
 
-def run_probe(x, label, theta, **kw):
+def run_probe(x, label, theta, ld=0, off=0, **kw):
     from dinox import ops
-    loss, grad, prob = ops.softmax_probe(dev(x), dev(label), dev(theta), **kw)
+    loss, grad, prob = ops.softmax_probe(gram_operand(x, ld, off), dev(label), dev(theta), **kw)
     return (None if loss is None else float(loss), None if grad is None else grad.cpu().numpy(), None if prob is None else prob.cpu().numpy())
 
 
-def check_probe(x, label, theta, what):
+def check_probe(x, label, theta, what, ld=0, off=0):
     p64, loss64, grad64, t, colabs = probe_reference(x, label, theta)
-    loss, grad, prob = run_probe(x, label, theta, want_grad=True, want_prob=True)
+    loss, grad, prob = run_probe(x, label, theta, ld, off, want_grad=True, want_prob=True)
     N = x.shape[0]
     perr, lerr, gerr = np.abs(prob - p64).max(), abs(loss - loss64), np.abs(grad - grad64)
     gb = (4 * t + 1e-6) * colabs[None, :]
     print(f"softmax_probe {what}: t = {t:.2e}; |p - p64| {perr:.2e} (bound {4 * t + 1e-6:.2e}); |loss - loss64| {lerr:.2e} (bound "
-          f"{N * (2 * t + 1e-6):.2e}); grad err / bound {float((gerr / gb).max()):.3f}")
+          f"{N * (2 * t + 1e-6):.2e}); err / bound: p {perr / (4 * t + 1e-6):.3f}, loss {lerr / (N * (2 * t + 1e-6)):.3f}, "
+          f"grad {float((gerr / gb).max()):.3f}")
     assert np.isfinite(prob).all() and math.isfinite(loss) and np.isfinite(grad).all()
     assert perr <= 4 * t + 1e-6
     assert lerr <= N * (2 * t + 1e-6)
@@ -142,16 +173,65 @@ def check_probe(x, label, theta, what):
     return loss, grad, prob
 
 
-@pytest.mark.parametrize("N,D,C,span", PROBE_SHAPES)
+def check_probe_three_forms(x, label, theta, what, ld=0, off=0):
+    """Full form against float64, then the predict form, a second launch and the gradient-only form: the same bits."""
+    loss, grad, prob = check_probe(x, label, theta, what, ld, off)
+    _, _, only = run_probe(x, label, theta, ld, off, want_grad=False, want_prob=True)
+    assert np.array_equal(only, prob)                                            # predict form: the same bits
+    loss2, grad2, prob2 = run_probe(x, label, theta, ld, off, want_grad=True, want_prob=True)
+    assert loss2 == loss and np.array_equal(grad2, grad) and np.array_equal(prob2, prob)       # two launches: the same bits
+    g_only = run_probe(x, label, theta, ld, off, want_grad=True, want_prob=False)
+    assert g_only[2] is None and g_only[0] == loss and np.array_equal(g_only[1], grad)
+    return loss, grad, prob
+
+
+@pytest.mark.parametrize("N,D,C,span", PROBE_SHAPES + PROBE_PATH_SHAPES)
 def test_softmax_probe_against_float64(N, D, C, span):
     x, label, theta = probe_case(N, D, C, span)
-    loss, grad, prob = check_probe(x, label, theta, f"N={N} D={D} C={C} span={span}")
+    check_probe_three_forms(x, label, theta, f"N={N} D={D} C={C} span={span}")
+
+
+@pytest.mark.parametrize("N,D,C,ld,off", PROBE_PITCH_SHAPES)
+def test_softmax_probe_row_loads_at_a_whole_quad_pitch(N, D, C, ld, off):
+    """Rows of a NaN-filled buffer whose pitch is a multiple of four floats: 16-byte loads with the last quad across D when the base is
+    aligned, element loads when only the base pointer is off.  A load past D would bring a NaN into the image."""
+    x, label, theta = probe_case(N, D, C, 8.0)
+    loss, grad, prob = check_probe_three_forms(x, label, theta, f"N={N} D={D} C={C} ld={ld} off={off}", ld, off)
+    plain = run_probe(x, label, theta, want_grad=True, want_prob=True)           # the same rows, contiguous: the same arithmetic
+    assert plain[0] == loss and np.array_equal(plain[1], grad) and np.array_equal(plain[2], prob)
+
+
+@pytest.mark.parametrize("N,D,C,span", [(16421, 7, 3, 8.0), (16421, 520, 4, 8.0)])
+def test_softmax_probe_second_trip_of_rows_that_do_not_count(N, D, C, span):
+    """Every row of the second trip (rows 16384 .. 16420, two workgroups) has a label out of range.  Loss and gradient are those of the
+    float64 reference without these rows; their probabilities are still written; and, since such a row adds exact zeros to what a
+    workgroup carries, the sums have the bits of a call on the first 16384 rows alone.  (At D = 520 the a-priori bound of the intercept
+    gradient, (4 t + 1e-6) N, is wider than what one lost block of 32 rows can change: there the equality of bits is the check of the
+    carried sums, on NB = 8.)"""
+    assert (N, D, C, span) in PROBE_PATH_SHAPES                                  # pinned to blocks = 514 > groups = 512 by the CPU test
+    x, label, theta = probe_case(N, D, C, span)
+    label = label.copy()
+    label[16384:] = np.resize(np.array([-1, C, 2 ** 30, -7, -2 ** 31], np.int64), N - 16384).astype(np.int32)
+    loss, grad, prob = check_probe(x, label, theta, f"N={N} D={D} C={C}, second trip dropped")       # the reference leaves those rows out
+    head = run_probe(x[:16384], label[:16384], theta, want_grad=True, want_prob=True)
+    assert head[0] == loss and np.array_equal(head[1], grad) and np.array_equal(head[2], prob[:16384])
+
+
+@pytest.mark.parametrize("value", [float("nan"), float("inf"), float("-inf")], ids=["nan", "inf", "-inf"])
+def test_softmax_probe_non_finite_value_in_a_row_that_counts(value):
+    """A NaN or infinite logit in a counting row: the row's probabilities and the loss are non-finite (the row does not vanish), every
+    other row's probabilities keep their bits (rows are independent columns of the logit product), and the call returns."""
+    x, label, theta = probe_case(67, 7, 3, 8.0)
+    assert (theta[:, 2] != 0).all()
+    _, _, clean = run_probe(x, label, theta, want_grad=True, want_prob=True)
+    x = x.copy()
+    x[40, 2] = value
+    loss, grad, prob = run_probe(x, label, theta, want_grad=True, want_prob=True)
+    keep = np.arange(67) != 40
+    assert not np.isfinite(prob[40]).all() and not math.isfinite(loss)
+    assert np.isfinite(clean).all() and np.array_equal(prob[keep], clean[keep])
     _, _, only = run_probe(x, label, theta, want_grad=False, want_prob=True)
-    assert np.array_equal(only, prob)                                            # predict form: the same bits
-    loss2, grad2, prob2 = run_probe(x, label, theta, want_grad=True, want_prob=True)
-    assert loss2 == loss and np.array_equal(grad2, grad) and np.array_equal(prob2, prob)       # two launches: the same bits
-    g_only = run_probe(x, label, theta, want_grad=True, want_prob=False)
-    assert g_only[2] is None and g_only[0] == loss and np.array_equal(g_only[1], grad)
+    assert np.array_equal(only, prob, equal_nan=True)                            # predict form: the same bits
 
 
 def test_softmax_probe_rows_of_a_wider_buffer():
