@@ -207,7 +207,7 @@ using namespace dinox;
 extern "C" int dinox_attention_rollout_step_ok(int B, int N, int heads, int d) { return attention_rollout_step_ok(B, N, heads, d) ? 1 : 0; }
 
 extern "C" size_t dinox_attention_rollout_step_ws_bytes(int B, int N, int heads) {
-  if (B < 1 || N < 1 || heads < 1) return 0;
+  if (B < 1 || N < 1 || heads < 1 || !attention_rollout_step_ok(B, N, heads, 1)) return 0;   // what dinox_attention_rollout_step refuses (N > 4096)
   return (size_t)B * (size_t)heads * (size_t)N * sizeof(float);
 }
 

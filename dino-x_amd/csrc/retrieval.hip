@@ -336,7 +336,7 @@ static int64_t rrw_splits(int64_t Nq, int64_t Nk) {
 }
 
 extern "C" int64_t dinox_retrieval_ws_bytes(int64_t Nq, int64_t Nk, int64_t D) {
-  if (Nq <= 0 || Nk <= 0 || D <= 0) return 0;
+  if (Nq <= 0 || Nk <= 0 || D <= 0 || Nq > 0x7fffffff - RR_TQ || Nk > 0x7fffffff - RR_TK) return 0;   // what the call refuses
   return rr_split(Nq, Nk).splits * Nq * 12;      // (count, maximum, its index) per query and key split
 }
 
@@ -371,7 +371,7 @@ extern "C" int dinox_retrieval_rank(const float* q, int64_t ldq, const float* k,
 }
 
 extern "C" int64_t dinox_retrieval_rank_windowed_ws_bytes(int64_t Nq, int64_t Nk, int64_t D) {
-  if (Nq <= 0 || Nk <= 0 || D <= 0) return 0;
+  if (Nq <= 0 || Nk <= 0 || D <= 0 || Nq > 0x7fffffff - RR_TQ || Nk > 0x7fffffff - RR_TK) return 0;   // what the call refuses
   return rrw_splits(Nq, Nk) * Nq * 12;           // (count, maximum, its index) per query and key split
 }
 

@@ -157,7 +157,7 @@ extern "C" int dinox_scale_embed_fwd(const float* spacing, const float* w0, cons
 }
 
 extern "C" int64_t dinox_scale_embed_bwd_ws_bytes(int V, int h, int D) {
-  if (V <= 0 || h <= 0 || D <= 0) return 0;
+  if (V <= 0 || h <= 0 || D <= 0 || ((int64_t)D + h + 16) * 4 > 64 * 1024) return 0;   // what dinox_scale_embed_bwd refuses
   return (int64_t)V * (D + 2 * h) * (int64_t)sizeof(float);       // de [V][D] | dhpre [V][h] | gelu(hpre) [V][h]
 }
 

@@ -236,7 +236,7 @@ int dinox_tokens_bwd(const float* dtokens, void* dpatches, float* dcls, float* d
 int dinox_scale_embed_fwd(const float* spacing, const float* w0, const float* b0, const float* w2,
                           const float* b2, const float* lnw, const float* lnb, float* out, float* hpre,
                           float* e, float* mean, float* rstd, int V, int h, int D, float eps, void* stream);
-int64_t dinox_scale_embed_bwd_ws_bytes(int V, int h, int D);
+int64_t dinox_scale_embed_bwd_ws_bytes(int V, int h, int D);   /* 0 for every size dinox_scale_embed_bwd refuses */
 int dinox_scale_embed_bwd(const float* dout, const float* spacing, const float* w0, const float* w2,
                           const float* lnw, const float* hpre, const float* e, const float* mean,
                           const float* rstd, float* dw0, float* db0, float* dw2, float* db2, float* dlnw,
@@ -513,7 +513,7 @@ int dinox_attention_rows(const void* qkv, const int* query_idx, float* probs, fl
  * Two launches: one workgroup per (image, head), then one thread per (image, key).
  * Limits (dinox_attention_rollout_step_ok: host only, 1 inside): B, heads >= 1, 1 <= N <= 4096 (the 8 x N score rows of a chunk
  * sit in LDS), 1 <= d <= 256; anything else, a residual outside [0, 1], a null pointer or overlapping w returns DINOX_EINVAL before
- * any launch.  dinox_attention_rollout_step_ws_bytes returns 0 for a non-positive size.
+ * any launch.  dinox_attention_rollout_step_ws_bytes returns 0 for every B, N, heads the call refuses.
  * ------------------------------------------------------------------------------------------ */
 int dinox_attention_rollout_step_ok(int B, int N, int heads, int d);
 size_t dinox_attention_rollout_step_ws_bytes(int B, int N, int heads);
@@ -652,7 +652,7 @@ int dinox_block_backward(const dinox_block_bwd_args* args, void* stream);
  *   rank[i]     = #{j : s(i,j) > pos_val[i]} + #{j < target[i] : s(i,j) == pos_val[i]}  -- the positive's place in a stable descending
  *                 sort; rank == 0 is exactly np.argmax(S[i]) == target[i], rank < k is "among the k nearest";
  *   best_val[i] = max_j s(i,j), best_idx[i] = its lowest index.
- * ws: dinox_retrieval_ws_bytes(Nq, Nk, D) bytes (12 bytes per query and key split, a pure function of the three sizes; contents need not be
+ * ws: dinox_retrieval_ws_bytes(Nq, Nk, D) bytes (12 bytes per query and key split, a pure function of the three sizes, 0 for sizes the call refuses; contents need not be
  * initialised).  Any Nq, Nk, D >= 1 (Nq, Nk <= 2^31 - 129).
  * Caller's contract: 0 <= target[i] < Nk.  An index outside that range is CLAMPED into it (it never becomes an address), so the outputs
  * of that query then describe key 0 or key Nk - 1; dinox.ops.retrieval_rank checks the range before the call.
@@ -676,7 +676,7 @@ int dinox_retrieval_rank(const float* q, int64_t ldq, const float* k, int64_t ld
  * for bit, and a window equal to a row range reproduces the call on that range (best_idx shifted by the range's start).
  * Work: a strip of 128 queries sweeps only the key tiles one of its windows touches, so with rows sorted by group the cost is
  * sum n_g^2 scores, not Nq Nk.  Windows may be arbitrary and unsorted (the cost is then the tiles each strip's windows touch).
- * ws: dinox_retrieval_rank_windowed_ws_bytes(Nq, Nk, D) bytes (12 bytes per query and key split, a pure function of the sizes; contents
+ * ws: dinox_retrieval_rank_windowed_ws_bytes(Nq, Nk, D) bytes (12 bytes per query and key split, a pure function of the sizes, 0 for sizes the call refuses; contents
  * need not be initialised).  Any Nq, Nk, D >= 1 (Nq, Nk <= 2^31 - 129), ldq, ldk >= D.
  * Bad input never becomes an address or a loop bound: key_lo[i] and key_hi[i] are CLAMPED into [0, Nk] and target[i] into [0, Nk) as
  * in dinox_retrieval_rank.  An empty window (lo >= hi after clamping) gives rank 0, best_idx = 0x7fffffff, best_val = -inf; pos_val is
