@@ -41,6 +41,7 @@ weight decay to them.  The reference loop always passes spacing for scale-aware 
 """
 from __future__ import annotations
 
+import gc
 import os
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
@@ -317,8 +318,19 @@ class TrainEngine:
             torch.cuda.synchronize()
             self._graph = torch.cuda.CUDAGraph()
             count, opt = self.step_count, self.opt_steps
-            with torch.cuda.graph(self._graph):
-                self._captured = self._step_eager(*self._static, hyper=self._hyper_dev)
+            # No cyclic garbage collection while the stream captures.  An engine is a reference cycle (self._objective is a bound
+            # method), so a dead one -- with its CUDAGraph, its graph-pool tensors and its page-locked staging buffer -- waits for
+            # the collector, and a collection that fires inside the capture destroys them through API calls that a capturing
+            # thread may not make: the process aborts.  torch.cuda.graph() no longer collects on entry, so collect here.
+            gc.collect()
+            gc_was_on = gc.isenabled()
+            gc.disable()
+            try:
+                with torch.cuda.graph(self._graph):
+                    self._captured = self._step_eager(*self._static, hyper=self._hyper_dev)
+            finally:
+                if gc_was_on:
+                    gc.enable()
             self.step_count, self.opt_steps = count, opt          # capturing enqueued nothing: the replay below IS this step
         else:
             for dst, src in zip(self._static, inputs):

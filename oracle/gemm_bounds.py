@@ -40,6 +40,13 @@ polynomial's coefficients of +-1.4 leave a few ulp of 1.4), 1.13e-6 with the two
 re-measures both).  ERF_AS_ERR = 1.2e-6 -- eight times the "1.5e-7" that the comment in common.h quotes, still 2^-11 of a bf16
 half-ulp.  Beyond |z| = 12 the exponential underflows and the formula returns exactly +-1.
 The generic kernels call erff / __expf instead (a few ulp): inside the same constant.
+
+fp32 operands (Spec.in_ = "f32": csrc/gemm_f32.hip, the parity-mode product) and the mixed layouts (Spec.trans_b != Spec.trans).  The
+products of two fp32 values are no longer exact, but the exact-fp32 MFMA rounds a product once, TOGETHER with the sum it joins
+(acc = fma(a, b, acc)): K roundings per output, each relative to a partial sum that T bounds, which is what gamma_K |alpha| T already
+states.  No constant changes.  emulate() follows the kernel for these operands: one fma32() chain per output in ascending k (fma32 is
+an exact float32 fused multiply-add: the product is exact in float64, the float64 sum is corrected to round-to-odd by the TwoSum
+error term, and a round-to-odd float64 rounds to float32 as the exact value would -- 53 >= 24 + 2 bits).
 """
 from __future__ import annotations
 
@@ -82,6 +89,28 @@ def bf16_trunc(x: np.ndarray) -> np.ndarray:
 
 def bf16_to_f64(b: np.ndarray) -> np.ndarray:
     return (b.astype(np.uint32) << 16).view(np.float32).astype(np.float64)
+
+
+# ------------------------------------------------------------------------------------------ an exact float32 fused multiply-add
+def fma32(a, b, c) -> np.ndarray:
+    """fl32(a b + c) with ONE rounding, elementwise, for finite float32 operands whose result is a normal float32.  The product of
+    two float32 values is exact in float64 (48 bits).  s = fl64(p + c) and the TwoSum error term e give p + c = s + e exactly; where
+    e != 0 the sum is moved to the neighbour with an odd last bit (round to odd), and a float64 rounded to odd rounds to float32
+    exactly as the unrounded value does: the sticky bit survives, so no tie is invented and none is lost."""
+    a, b, c = (np.asarray(x, dtype=np.float32).astype(np.float64) for x in (a, b, c))
+    p = a * b
+    s = np.asarray(p + c)
+    t = s - p
+    e = (p - (s - t)) + (c - t)
+    even = (np.ascontiguousarray(s).view(np.int64) & 1) == 0
+    s = np.where((e != 0) & even, np.nextafter(s, np.where(e > 0, np.inf, -np.inf)), s)
+    return s.astype(np.float32)
+
+
+def fma32_double_rounded(a, b, c) -> np.ndarray:
+    """What fma32 must NOT be: the float64 sum rounded to float32 (two roundings)."""
+    a, b, c = (np.asarray(x, dtype=np.float32).astype(np.float64) for x in (a, b, c))
+    return (a * b + c).astype(np.float32)
 
 
 # ------------------------------------------------------------------------------------------ GELU in float64, and the constants
@@ -142,11 +171,13 @@ def _dgelu_eval_err(v):
 @dataclass(frozen=True)
 class Spec:
     """dinox_gemm_args without the pointers.  pad* = leading dimension minus width; gap* = elements between batch items beyond one
-    item's extent; off* = byte offset of the operand's first element from a 16-byte boundary."""
+    item's extent (negative: the items' extents overlap, as in the split-K form where item c starts K elements further along every
+    row of one wide matrix -- no ELEMENT belongs to two items); off* = byte offset of the operand's first element from a 16-byte
+    boundary."""
     M: int
     N: int
     K: int
-    trans: int = 0                      # 0: NT, 1: TN
+    trans: int = 0                      # 0: NT, 1: TN (transA; transB too unless trans_b is given)
     out: str = "bf16"                   # "bf16" | "f32": C and the side tensor
     epi: int = 0
     alpha: float = 1.0
@@ -167,6 +198,12 @@ class Spec:
     off_b: int = 0
     off_c: int = 0
     seed: int = 0
+    in_: str = "bf16"                   # "bf16" | "f32": A and B
+    trans_b: Optional[int] = None       # transB; None: equal to trans
+
+    @property
+    def tb(self) -> int:
+        return self.trans if self.trans_b is None else self.trans_b
 
     # shapes as stored
     @property
@@ -175,7 +212,7 @@ class Spec:
 
     @property
     def b_shape(self):
-        return (self.K, self.N) if self.trans else (self.N, self.K)
+        return (self.K, self.N) if self.tb else (self.N, self.K)
 
     @property
     def lda(self):
@@ -265,9 +302,10 @@ def build(s: Spec) -> Dict[str, Buf]:
     ar, ac = s.a_shape
     br, bc = s.b_shape
     out16 = s.out == "bf16"
+    in16 = s.in_ == "bf16"
     bufs = {
-        "A": _make(rng.standard_normal((s.batch, ar, ac)) * sc, True, s.batch, ar, ac, s.lda, s.stride_a, s.off_a, False),
-        "B": _make(rng.standard_normal((s.batch, br, bc)) * sc, True, s.batch, br, bc, s.ldb, s.stride_b, s.off_b, False),
+        "A": _make(rng.standard_normal((s.batch, ar, ac)) * sc, in16, s.batch, ar, ac, s.lda, s.stride_a, s.off_a, False),
+        "B": _make(rng.standard_normal((s.batch, br, bc)) * sc, in16, s.batch, br, bc, s.ldb, s.stride_b, s.off_b, False),
         "C": _make(rng.standard_normal((s.batch, s.M, s.N)), out16, s.batch, s.M, s.N, s.ldc, s.stride_c, s.off_c, True,
                    fill_live=bool(s.epi & ACCUM)),
     }
@@ -295,7 +333,9 @@ def is_output(s: Spec, name: str) -> bool:
 def _operands(s: Spec, bufs):
     A, B = bufs["A"].live(), bufs["B"].live()          # [batch][rows][cols] as stored
     if s.trans:
-        A, B = A.transpose(0, 2, 1), B.transpose(0, 2, 1)
+        A = A.transpose(0, 2, 1)
+    if s.tb:
+        B = B.transpose(0, 2, 1)
     return A, B                                        # [batch][M][K], [batch][N][K]
 
 
@@ -392,30 +432,63 @@ def _gelu_both_f32(x):
     return x * h, h + x * e * f(0.39894228040143268)
 
 
+def _gather(buf: Buf, rel: np.ndarray) -> np.ndarray:
+    """float64 values at element offsets `rel` from the operand's first element, as a kernel with a wrong index would read them: NaN
+    padding where it lands on padding, NaN too outside the allocation (the emulation does not fault)."""
+    idx = buf.origin + rel
+    ok = (idx >= 0) & (idx < buf.data.size)
+    v = buf.data[np.where(ok, idx, 0)]
+    v = bf16_to_f64(v) if buf.data.dtype == np.uint16 else v.astype(np.float64)
+    return np.where(ok, v, np.nan)
+
+
 def emulate(s: Spec, bufs: Dict[str, Buf], order: str = "seq", mutant: Optional[str] = None) -> Dict[str, np.ndarray]:
     """The kernels' documented arithmetic on the CPU: float32 accumulation of the exact bf16 products (order "seq": k ascending;
-    "blk32": blocks of 32 summed on their own, then added in order), float32 epilogue with the fast erf, bf16 rounding.  Works on the
+    "blk32": blocks of 32 summed on their own, then added in order), float32 epilogue with the fast erf, bf16 rounding.  With fp32
+    operands every step is acc = fma32(a, b, acc): order "seq" is then the chain that csrc/gemm_f32.hip documents.  Works on the
     raw buffers and returns the output arrays as a launch would leave them.  `mutant` plants one defect (MUTANTS)."""
     f = np.float32
     A, B = _operands(s, bufs)
+    if mutant == "trans_b_follows_a" and s.tb != s.trans:
+        n, k = np.arange(s.N).reshape(1, -1, 1), np.arange(s.K).reshape(1, 1, -1)
+        B = _gather(bufs["B"], np.arange(s.batch).reshape(-1, 1, 1) * s.stride_b + (n + k * s.ldb if s.trans else n * s.ldb + k))
+    if mutant == "batch_stride_as_extent" and s.batch > 1 and not s.share_a:
+        m, k = np.arange(s.M).reshape(1, -1, 1), np.arange(s.K).reshape(1, 1, -1)
+        A = _gather(bufs["A"], np.arange(s.batch).reshape(-1, 1, 1) * (s.a_shape[0] * s.lda) + (m + k * s.lda if s.trans else m * s.lda + k))
     A, B = A.astype(f), B.astype(f)
     if mutant == "batch1_uses_b0" and s.batch > 1:
         B = B.copy()
         B[1] = B[0]
-    K = s.K - 8 if mutant == "drop_last_8k" else s.K
+    ks = list(range(s.K))
+    if mutant == "drop_last_8k":
+        ks = ks[:-8]
+    if mutant == "odd_k_dropped" and s.K % 2:
+        ks = ks[:-1]
+    if mutant == "stale_last_slab" and s.K > 16:                  # the last 16-slab is never fetched: the one before it is multiplied twice
+        last = (s.K - 1) // 16 * 16
+        ks = ks[:last] + ks[last - 16:last]
+    fused = s.in_ == "f32"                                        # fp32 operands: the product is rounded once, with the sum
     acc = np.zeros((s.batch, s.M, s.N), dtype=f)
     part = np.zeros_like(acc)
     cs = np.zeros(s.M, dtype=f)
-    for k in range(K):
-        p = A[:, :, k, None] * B[:, None, :, k]
+    for i, k in enumerate(ks):
+        a, b = A[:, :, k, None], B[:, None, :, k]
         if order == "seq":
-            acc += p
+            acc = fma32(a, b, acc) if fused else acc + a * b
         else:
-            part += p
-            if k % 32 == 31 or k == K - 1:
+            part = fma32(a, b, part) if fused else part + a * b
+            if i % 32 == 31 or i == len(ks) - 1:
                 acc += part
                 part[...] = 0
         cs += A[0, :, k]
+    if mutant == "edge_row_map" and s.M % 32:                     # accumulator j of half h holds row (j & 3) + 8 (j >> 2) + 4 h of a 32-row
+        row0 = s.M - s.M % 32                                     # block; the defect stores it at (j >> 2) + 8 (j & 3) + 4 h
+        moved = acc.copy()
+        for l in range(32):
+            to = row0 + (l >> 3) + 8 * (l & 3) + (l & 4)
+            if to < s.M:
+                moved[:, to] = acc[:, row0 + l] if row0 + l < s.M else 0
+        acc = moved
     alpha = f(1.0) if mutant == "alpha_ignored" else f(s.alpha)
     v = acc * alpha
     if s.epi & BIAS:
@@ -458,6 +531,12 @@ def emulate(s: Spec, bufs: Dict[str, Buf], order: str = "seq", mutant: Optional[
 
 MUTANTS = ("drop_last_8k", "alpha_ignored", "bias_shift_last_strip", "accum_overwrites", "ldr_taken_as_n", "ldaux_taken_as_n",
            "batch1_uses_b0", "bf16_truncated", "canary_word")
+# defects of the kind csrc/gemm_f32.hip could have (tests/test_gemm_f32_contract_cpu.py): the last k of an odd K (a K-step of two that
+# does not guard its second half), the prefetch guard of the 128-tile kernel off by one slab, B read with A's layout flag, a
+# permuted accumulator-to-row map inside the last partial 32-row block, and the batch stride taken as rows x ld (what breaks the
+# split-K argument form, whose items overlap)
+F32_MUTANTS = ("odd_k_dropped", "stale_last_slab", "trans_b_follows_a", "edge_row_map", "batch_stride_as_extent")
+MUTANTS_ALL = MUTANTS + F32_MUTANTS
 
 
 # ------------------------------------------------------------------------------------------ the cases of the contract tests
@@ -593,3 +672,132 @@ def cpu_families():
     yield "tn-accum-colsum", Spec(40, 24, 1000, trans=1, out="f32", epi=ACCUM, colsum=True, seed=11, pad_a=16, pad_b=8)
     yield "tn-long-k", Spec(16, 24, 8192 + 40, trans=1, out="f32", seed=12, pad_a=8, pad_b=24)
     yield "misaligned", Spec(45, 24, 40, out="bf16", epi=BIAS | DGELU, aux=True, off_a=8, off_b=8, off_c=8, seed=13, **{**PADS, "pad_r": 5})
+
+
+# ------------------------------------------------------------------------------------------ the exact-fp32 kernels (csrc/gemm_f32.hip)
+LAYOUTS = ((0, 0), (0, 1), (1, 0), (1, 1))                          # (transA, transB); (0, 1) is the P V product of fp32 attention
+# gemm_f32 has no alignment rule: odd paddings, all different
+F32_PADS = dict(pad_a=3, pad_b=7, pad_c=5, pad_r=1, pad_x=9)
+F32_EPILOGUES = {
+    "plain": dict(),
+    "bias": dict(epi=BIAS),
+    "gelu_aux": dict(epi=BIAS | GELU, aux=True),
+    "gelu_auxgrad": dict(epi=BIAS | GELU | AUXGRAD, aux=True),
+    "dgelu": dict(epi=DGELU, aux=True),
+    "dgelu_auxgrad": dict(epi=DGELU | AUXGRAD, aux=True),
+    "residual": dict(epi=RESIDUAL),
+    "accum_bias": dict(epi=ACCUM | BIAS, alpha=-1.5),               # fp32 C only
+}
+
+
+def uses_big_tiles(s: Spec) -> bool:
+    """launch_gemm_f32's predicate: 128 x 128 tiles (gemm_f32_big) when both extents reach 128 and there is a tile per CU."""
+    return s.M >= 128 and s.N >= 128 and -(-s.M // 128) * -(-s.N // 128) * s.batch >= 256
+
+
+def _lay(ta: int, tb: int) -> dict:
+    return dict(trans=ta, trans_b=tb)
+
+
+def f32_layout_cases():
+    """All four layouts x both operand types x both output types at (77, 24, 44) and (65, 130, 17) -- one full tile plus one row,
+    three column tiles, K one past a slab -- every leading dimension padded, the epilogues cycling so that each meets at least two
+    layouts and both output types (tests/test_gemm_f32_contract_cpu.py counts them)."""
+    names = list(F32_EPILOGUES)
+    for si, (M, N, K) in enumerate(((77, 24, 44), (65, 130, 17))):
+        for li, (ta, tb) in enumerate(LAYOUTS):
+            for ii, in_ in enumerate(("f32", "bf16")):
+                n = li * 2 + ii
+                for out in ("f32", "bf16"):
+                    name = names[(n + 3 * si) % 8] if out == "f32" else names[(n + 3 * si) % 7]
+                    yield (f"{M}x{N}x{K}-{ta}{tb}-{in_}-{out}-{name}",
+                           Spec(M, N, K, out=out, in_=in_, seed=40 + 8 * si + n, **_lay(ta, tb), **F32_PADS, **F32_EPILOGUES[name]))
+
+
+def f32_k_edge_cases():
+    """K around the K-step of two and the 16-slab, on a tile ragged in M and N; and the degenerate extents."""
+    for K in (1, 2, 3, 15, 16, 17, 31, 32, 33):
+        for ta, tb in ((0, 0), (1, 0)):
+            yield f"33x40x{K}-{ta}{tb}", Spec(33, 40, K, out="f32", in_="f32", seed=60 + K, pad_a=3, pad_b=7, pad_c=5, **_lay(ta, tb))
+    for K in (1, 17):
+        for i, (M, N) in enumerate(((1, 1), (1, 70), (70, 1))):
+            ta, tb = LAYOUTS[(i + K) % 4]
+            yield f"{M}x{N}x{K}-{ta}{tb}", Spec(M, N, K, out="f32", in_="f32", seed=70 + K + i, pad_a=3, pad_b=7, pad_c=5, **_lay(ta, tb))
+
+
+def f32_big_cases():
+    """(name, on the 128-tile kernel?, spec).  Each case is written for one side of launch_gemm_f32's dispatch line and
+    uses_big_tiles() is asserted for it wherever it is used."""
+    base = Spec(129, 130, 37, batch=64, out="f32", pad_a=3, pad_b=7, pad_c=5)
+    variants = {
+        "own_b": dict(gap_a=2, gap_b=6),
+        "shared_b": dict(share_b=True, out="bf16", epi=BIAS | GELU, aux=True, pad_x=9),
+        "gap_c": dict(gap_c=11, epi=RESIDUAL, pad_r=1),
+    }
+    for li, (ta, tb) in enumerate(LAYOUTS):
+        for ii, in_ in enumerate(("f32", "bf16")):
+            for vi, (name, kw) in enumerate(variants.items()):
+                yield f"129x130x37b64-{ta}{tb}-{in_}-{name}", True, base.but(in_=in_, seed=80 + 6 * li + 3 * ii + vi, **_lay(ta, tb), **kw)
+    for ta, tb in ((0, 0), (0, 1)):
+        big = Spec(1930, 2050, 19, out="f32", in_="f32", pad_a=3, pad_b=7, pad_c=5, **_lay(ta, tb))
+        yield f"1930x2050x19-{ta}{tb}-bias_residual", True, big.but(epi=BIAS | RESIDUAL, pad_r=1, seed=110 + tb)
+        yield f"1930x2050x19-{ta}{tb}-accum", True, big.but(epi=ACCUM, seed=112 + tb)
+    yield "128x128x16b256-00", True, Spec(128, 128, 16, batch=256, out="f32", in_="f32", seed=114)
+    yield "128x128x16b256-11", True, Spec(128, 128, 16, batch=256, out="f32", in_="f32", seed=115, **_lay(1, 1))
+    yield "129x130x37b63-00-neighbour", False, base.but(batch=63, in_="f32", seed=116, gap_a=2, gap_b=6)
+    yield "129x130x37b63-01-neighbour", False, base.but(batch=63, in_="bf16", seed=117, gap_a=2, gap_b=6, **_lay(0, 1))
+
+
+def splitk_spec(M: int, N: int, kc: int, splits: int, **kw) -> Spec:
+    """ops.gemm_nt_f32_splitk's argument form: A [M][K_total] and B [N][K_total] contiguous, lda = ldb = K_total, item c = columns
+    c kc .. (c + 1) kc of every row (strideA = strideB = kc), batch = splits."""
+    kt = kc * splits
+    return Spec(M, N, kc, batch=splits, out="f32", in_="f32", pad_a=kt - kc, pad_b=kt - kc, gap_a=kc - M * kt, gap_b=kc - N * kt, **kw)
+
+
+def splitk_reference(A: np.ndarray, B: np.ndarray, splits: int, c_in: Optional[np.ndarray] = None):
+    """(float64 A B^T (+ c_in), bound) of a product whose reduction is cut into `splits` equal chunks (A [M][K], B [N][K] float64,
+    as ops.gemm_nt_f32_splitk and the split branch of ops.gemm run it): each chunk is an fma chain of kc = K / splits steps,
+    gamma_kc T_c; the parts, each at most (1 + gamma_kc) T_c in magnitude, meet in dinox_colsum over `splits` rows, at most
+    ceil(splits / 16) + 6 additions deep (tests/_colsum_emul.py), the last of them the addition to C.  One chunk: the chain, and two
+    roundings for alpha and ACCUM."""
+    K = A.shape[1]
+    assert K % splits == 0
+    kc = K // splits
+    T = np.abs(A) @ np.abs(B).T
+    c = np.zeros_like(T) if c_in is None else np.asarray(c_in, dtype=np.float64)
+    gk = kc * U32 / (1.0 - kc * U32)
+    d = math.ceil(splits / 16) + 6 if splits > 1 else 2
+    gd = d * U32 / (1.0 - d * U32)
+    return A @ B.T + c, gk * T + gd * ((1.0 + gk) * T + np.abs(c))
+
+
+def f32_overlapped_stride_cases():
+    yield "40x24-4x33", False, splitk_spec(40, 24, 33, 4, seed=120)
+    yield "129x130-64x18", True, splitk_spec(129, 130, 18, 64, seed=121)
+
+
+def f32_colsum_cases():
+    """dinox_gemm with colsum on fp32 operands (A stored [K][M]: dinox_colsum over it), with and without ACCUM."""
+    for ta, tb in ((1, 1), (1, 0)):
+        for acc in (0, ACCUM):
+            yield (f"76x20x44-{ta}{tb}-{'accum' if acc else 'overwrite'}",
+                   Spec(76, 20, 44, out="f32", in_="f32", epi=acc, colsum=True, seed=130 + 2 * tb + (acc > 0), pad_a=3, pad_b=7, pad_c=5,
+                        **_lay(ta, tb)))
+
+
+def f32_cpu_families():
+    """One representative of every gemm_f32 case family, at shapes the fma chain of the emulation finishes quickly."""
+    lay = dict(f32_layout_cases())
+    for n in ("77x24x44-00-f32-f32-plain", "77x24x44-00-bf16-bf16-bias", "77x24x44-01-f32-f32-gelu_aux", "77x24x44-10-f32-f32-dgelu",
+              "77x24x44-11-f32-bf16-residual", "65x130x17-00-f32-bf16-gelu_auxgrad", "65x130x17-01-f32-f32-dgelu_auxgrad",
+              "65x130x17-01-bf16-f32-residual", "65x130x17-10-f32-f32-accum_bias", "65x130x17-11-bf16-f32-gelu_aux"):
+        yield "layout-" + n, lay[n]
+    edge = dict(f32_k_edge_cases())
+    for n in ("33x40x1-00", "33x40x3-10", "33x40x17-00", "33x40x33-10", "1x1x17-01", "70x1x1-11"):
+        yield "kedge-" + n, edge[n]
+    yield "big-own-b", Spec(129, 130, 37, batch=3, out="f32", in_="f32", pad_a=3, pad_b=7, pad_c=5, gap_a=2, gap_b=6, seed=140, **_lay(0, 1))
+    yield "big-shared-b", Spec(129, 130, 37, batch=3, out="bf16", in_="bf16", epi=BIAS | GELU, aux=True, share_b=True, seed=141, **F32_PADS)
+    yield "overlapped", splitk_spec(40, 24, 33, 4, seed=120)
+    for n, s in f32_colsum_cases():
+        yield "colsum-" + n, s

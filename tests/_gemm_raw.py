@@ -18,7 +18,8 @@ FAKE = {"A": 0x100000, "B": 0x200000, "C": 0x300000, "bias": 0x400000, "residual
 def args(s: GB.Spec, ptr: dict, ws: int = 0) -> GemmArgs:
     """ptr: name -> address of the operand's FIRST element (the spec's byte offsets already applied)."""
     return GemmArgs(A=ptr["A"], B=ptr["B"], C=ptr["C"], M=s.M, N=s.N, K=s.K, lda=s.lda, ldb=s.ldb, ldc=s.ldc, batch=s.batch,
-                    strideA=s.stride_a, strideB=s.stride_b, strideC=s.stride_c, transA=s.trans, transB=s.trans, in_dtype=BF16,
+                    strideA=s.stride_a, strideB=s.stride_b, strideC=s.stride_c, transA=s.trans, transB=s.tb,
+                    in_dtype=BF16 if s.in_ == "bf16" else F32,
                     out_dtype=BF16 if s.out == "bf16" else F32, epilogue=s.epi, alpha=s.alpha,
                     bias=ptr["bias"] if s.epi & GB.BIAS else None, residual=ptr["residual"] if s.epi & GB.RESIDUAL else None, ldr=s.ldr,
                     aux=ptr["aux"] if s.aux else None, ldaux=s.ldaux, colsum=ptr["colsum"] if s.colsum else None, ws=ws or None)
@@ -82,14 +83,62 @@ def _torch_of(a: np.ndarray):
     return torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a)
 
 
-def run(s: GB.Spec, bufs: dict, use_ws: bool = False):
-    """One launch on cuda:0 from the buffers as built (they are not modified).  Returns (kernel name, {output name: raw array after
-    the launch}, workspace bytes used).  The workspace, when asked for and when dinox_gemm_ws_bytes grants one, is filled with NaN."""
-    import torch
+def _upload(bufs: dict):
     dev = {k: _torch_of(b.data).to("cuda") for k, b in bufs.items()}
     ptr = {k: dev[k].data_ptr() + bufs[k].origin * bufs[k].data.itemsize for k in bufs}
     for k in ("bias", "residual", "aux", "colsum"):
         ptr.setdefault(k, 0)
+    return dev, ptr
+
+
+def _download(s: GB.Spec, bufs: dict, dev: dict) -> dict:
+    after = {}
+    for k in GB.OUTPUTS:
+        if k in bufs and GB.is_output(s, k):
+            a = dev[k].cpu().numpy()
+            after[k] = a.view(np.uint16) if bufs[k].data.dtype == np.uint16 else a
+    return after
+
+
+def pieces(s: GB.Spec, by: str):
+    """The product of `s` cut into launches of their own: by = "item", one per batch item; by = "strip", one per 128 columns of N
+    (batch = 1).  Yields (spec of the piece -- shape and batch only, for the tile-form predicate --, batch item, first column)."""
+    if by == "item":
+        for b in range(s.batch):
+            yield s.but(batch=1), b, 0
+    else:
+        assert by == "strip" and s.batch == 1
+        for n0 in range(0, s.N, 128):
+            yield s.but(N=min(128, s.N - n0)), 0, n0
+
+
+def run_pieces(s: GB.Spec, bufs: dict, by: str):
+    """The same product as run(s, bufs), from the same buffers, as the launches of pieces(): every pointer is moved to the piece's
+    first element and nothing else changes (leading dimensions stay).  Returns {output name: raw array after all launches}."""
+    import torch
+    assert not s.colsum
+    dev, ptr = _upload(bufs)
+    ein, eout = (2 if s.in_ == "bf16" else 4), (2 if s.out == "bf16" else 4)
+    for sp, b, n0 in pieces(s, by):
+        p = dict(ptr)
+        p["A"] += b * s.stride_a * ein
+        p["B"] += (b * s.stride_b + n0 * (1 if s.tb else s.ldb)) * ein
+        p["C"] += (b * s.stride_c + n0) * eout
+        p["bias"] += n0 * 4
+        p["residual"] += (b * s.M * s.ldr + n0) * 4
+        p["aux"] += (b * s.M * s.ldaux + n0) * eout
+        g = args(s, p, 0)
+        g.N, g.batch = sp.N, 1
+        _lib.check(_lib.lib.dinox_gemm(C.byref(g), None), "dinox_gemm")
+    torch.cuda.synchronize()
+    return _download(s, bufs, dev)
+
+
+def run(s: GB.Spec, bufs: dict, use_ws: bool = False):
+    """One launch on cuda:0 from the buffers as built (they are not modified).  Returns (kernel name, {output name: raw array after
+    the launch}, workspace bytes used).  The workspace, when asked for and when dinox_gemm_ws_bytes grants one, is filled with NaN."""
+    import torch
+    dev, ptr = _upload(bufs)
     g = args(s, ptr, 0)
     need = int(_lib.lib.dinox_gemm_ws_bytes(C.byref(g))) if use_ws else 0
     ws = None
@@ -99,9 +148,4 @@ def run(s: GB.Spec, bufs: dict, use_ws: bool = False):
     name = _lib.lib.dinox_gemm_kernel_name(C.byref(g)).decode()
     _lib.check(_lib.lib.dinox_gemm(C.byref(g), None), "dinox_gemm")
     torch.cuda.synchronize()
-    after = {}
-    for k in GB.OUTPUTS:
-        if k in bufs and GB.is_output(s, k):
-            a = dev[k].cpu().numpy()
-            after[k] = a.view(np.uint16) if bufs[k].data.dtype == np.uint16 else a
-    return name, after, need
+    return name, _download(s, bufs, dev), need
