@@ -4,6 +4,8 @@ scripts/finetune_segmentation.py end to end.
 
 Shapes: (g, u) = (1, 4) every tap clamped, (2, 3) an odd factor, (3, 16) an interior patch and all four borders, (14, 16) the real geometry;
 C = 2, 5, 33, 64 cover the register widths 4, 8, 64 and a class count that fills none of them; z both 256-byte aligned and one float off.
+The widths 16 and 32, the class counts that fill a width exactly (C = 4, 8, 16, 32), the factors 1, 2, 8, 24, 32 and the byte label and
+prediction paths at u % 8 == 0 are in tests/test_seg_paths_gpu.py (case table: tests/_seg_paths_cases.py), against this module's oracle.
 Every (g, u, B, C) runs label x logit regimes with c0, the loss weights and the alignment cycling through them: all fifteen regime pairs at
 the three small geometries, two per (B, C) at (14, 16), which together are all fifteen."""
 import importlib.util
