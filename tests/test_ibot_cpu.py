@@ -102,6 +102,21 @@ def test_fp32_evaluation_of_the_oracle_stays_inside_the_bound(regime):
     assert abs(lo["loss"] - o["loss"]) <= b["loss"] + IO.CE_LOSS_RTOL * abs(o["loss"])
 
 
+@pytest.mark.parametrize("K", [2052, 4096, 4100, 1030, 8196])
+@pytest.mark.parametrize("regime", ["normal", "underflow", "onehot"])
+def test_fp32_evaluation_stays_inside_the_bound_at_every_row_length_the_gpu_runs(regime, K):
+    """The row lengths tests/test_ibot_gpu.py adds for ibot_ce_reg_kernel<4>, <8> with idle groups and the scalar kernel: the bound admits
+    correct fp32 arithmetic there before the GPU is asked (M = 5 as there)."""
+    M = 5
+    s, t, c = IO.dino_inputs(regime, M, M, K, seed=M + K)
+    w = np.random.default_rng(M * K).uniform(0.05, 1.0, M).astype(np.float32)
+    o, lo = IO.ibot_ce(s, t, c, w, 0.1, 0.04, 1.0 / 6, 0.5), IO.ibot_ce(s, t, c, w, 0.1, 0.04, 1.0 / 6, 0.5, dt=np.float32)
+    b = IO.bound_ibot(o)
+    assert np.all(np.abs(lo["row"] - o["row"]) <= b["row"] + IO.CE_LOSS_RTOL * np.abs(o["row"]))
+    assert np.all(np.abs(lo["ds"] - o["ds"]) <= b["ds"] + IO.CE_DS_RTOL * np.abs(o["ds"]).max(1, keepdims=True))
+    assert abs(lo["loss"] - o["loss"]) <= b["loss"] + IO.CE_LOSS_RTOL * abs(o["loss"])
+
+
 # ------------------------------------------------------------------------------------------ parser, engine, model
 def test_parser_flags_and_refusals(cli, monkeypatch):
     monkeypatch.delenv("DINOX_AUTOGRAD_TOP", raising=False)

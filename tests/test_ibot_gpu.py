@@ -66,9 +66,15 @@ def ce_case(regime, M, K):
 
 @pytest.mark.parametrize("offset", [0, 1], ids=["aligned", "offset"])
 @pytest.mark.parametrize("regime", ["normal", "underflow", "onehot"])
-@pytest.mark.parametrize("M,K", [(1, 8), (5, 8), (130, 8), (1, 1028), (5, 1028), (130, 1028), (1, 8192), (5, 8192), (130, 8192)])
+@pytest.mark.parametrize("M,K", [(1, 8), (5, 8), (130, 8), (1, 1028), (5, 1028), (130, 1028), (1, 8192), (5, 8192), (130, 8192),
+                                 (1, 2052), (5, 2052), (1, 4096), (5, 4096), (1, 4100), (5, 4100), (1, 1030), (5, 1030), (1, 8196), (5, 8196)])
 def test_ibot_ce_vs_float64(dx, M, K, regime, offset):
-    """Aligned operands with K % 4 == 0 and K <= 8192 run the register-resident kernel, operands one float off the scalar kernel."""
+    """Aligned operands with K % 4 == 0 and K <= 8192 run the register-resident kernel, operands one float off the scalar kernel.
+    K -> instantiation of the aligned run (K4 = K / 4 float4 groups, NV = ceil(K4 / 256) rounded up to 1, 2, 4, 8): 8 -> <1> with 254 idle
+    threads; 1028 -> <2>, ragged (K4 = 257); 2052 -> <4>, ragged (K4 = 513: the third and fourth group hold one float4 and none); 4096 ->
+    <4>, full; 4100 -> <8> with K4 = 1025: groups 5, 6 and 7 lie wholly past the row's end, hold -inf and drop out of the output pass;
+    8192 -> <8>, full; 1030 -> the scalar kernel on aligned rows (K % 4 != 0); 8196 -> the scalar kernel by size (K > 8192), aligned.
+    The offset run of every K is the scalar kernel by alignment."""
     ops, _ = dx
     s, t, c, w, o, b = ce_case(regime, M, K)
     sd, td, cd = dev_view(s, offset), dev_view(t, offset), dev_view(c, offset)
@@ -86,7 +92,7 @@ def test_ibot_ce_vs_float64(dx, M, K, regime, offset):
     assert none is None and np.array_equal(loss2.cpu().numpy(), loss) and np.array_equal(row2.cpu().numpy(), row)
 
 
-@pytest.mark.parametrize("K,offset", [(8192, 0), (1028, 0), (1028, 1)])
+@pytest.mark.parametrize("K,offset", [(8192, 0), (1028, 0), (1028, 1), (2052, 0), (8196, 0)])
 def test_ibot_ce_does_not_overflow_at_large_logits(dx, K, offset):
     """teacher_temp 0.04 and logits of +-60: (t - c) / tt reaches 1500 and exp of it leaves fp32 (and s / 0.1 = 600 does too); the
     max-shifted kernels stay finite and inside the same bounds."""

@@ -21,7 +21,7 @@ pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 MS = (1, 5, 130, 402)                  # 130: more than one 128-row chunk with a ragged tail
-DIMS = (8, 36, 384, 1152)              # 36: no multiple of 4 -> the scalar path
+DIMS = (8, 36, 384, 1152)              # all multiples of 4: the scalar widths, ragged second tiles and misaligned operands are tests/test_lora_paths_gpu.py
 RANKS = (1, 8, 16, 64)
 MODES = ("fp32", "bf16")
 RATIOS: dict = {}
